@@ -174,7 +174,7 @@ def test_bench_starts_its_own_ranks():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(util.ROOT, "bench.py"), "--gpus", "2", "--steps", "12", "--warmup", "2", "--envs", "8",
-                        "--no-dephase", "--event-steps", "4"], env=env, capture_output=True, text=True, timeout=600)
+                        "--no-dephase", "--event-steps", "4", "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout

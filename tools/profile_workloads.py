@@ -79,7 +79,7 @@ for spec in specs:
     NAMES = names_of(pack)
     key = "%s_d%d" % (w, depth) + ("_distinct%d" % distinct if distinct else "") + ("_keeprows" if keeprows else "")
     steps = {"cfg2": 300, "cfg3": 100, "cfg4": 100, "cfg5": 60}[w]
-    bargs = ["--no-cpu-baseline", "--no-extra-workloads", "--workload", w, "--tree-depth", str(depth), "--steps", str(steps), "--warmup", "20"]
+    bargs = ["--full", "--no-cpu-baseline", "--no-extra-workloads", "--workload", w, "--tree-depth", str(depth), "--steps", str(steps), "--warmup", "20"]
     if rebuild:
         bargs.append("--dm-rebuild")
     if distinct:

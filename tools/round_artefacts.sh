@@ -49,7 +49,7 @@ if [ -f ab_libs/libfl_timing.so ]; then
 fi
 echo "[artefacts] phase clocks done" ;;
 rest)
-python bench.py --detail $out/${tag}_bench_detail.json > $out/${tag}_bench_default.json 2> $out/bench_default.err || tail -3 $out/bench_default.err
+python bench.py --full --detail $out/${tag}_bench_detail.json > $out/${tag}_bench_default.json 2> $out/bench_default.err || tail -3 $out/bench_default.err
 python -c "
 import json,sys; d=json.load(open('$out/${tag}_bench_default.json')); print('headline %.2f M' % (d['value']/1e6), d['roofline'], {k: round(v['value']/1e6,1) for k,v in d.get('workloads',{}).items()}); print('line bytes', len(open('$out/${tag}_bench_default.json').read()))"
 python tools/bsweep.py --bs 256,512,1024,2048 --modes one_a_cu,two_a_cu,default,nofix --out $out/${tag}_cfg2_bsweep.json > $out/bsweep.log 2>&1 || tail -3 $out/bsweep.log
