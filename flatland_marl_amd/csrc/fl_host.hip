@@ -11,6 +11,7 @@
 #include "../../include/flatland_hip.h"
 #include "fl_internal.h"
 #include "fl_obs.h"
+#include "fl_global.h"
 
 static thread_local char g_err[512] = "";
 static void set_err(const char *fmt, ...) {
@@ -63,6 +64,7 @@ struct fl_batch {
     std::vector<int> h_tab;
     std::vector<uint8_t> h_need;
     FlObsScratch obs;
+    int n_cu;   // compute units of the device (fl_obs_global's launch shape), 0 = not queried yet
 };
 
 template <typename T>
@@ -963,6 +965,24 @@ int fl_obs_cutils_tree(fl_batch *h, int max_nodes, int pred_depth, float *attr_d
     int rc = fl_launch_obs_both(h->obs, h->d, max_nodes, pred_depth, attr_dev, forest_dev, adjacency_dev, node_order_dev,
                                 edge_order_dev, valid_actions_dev, props_dev, tree_max_depth, tree_pred_depth, tree_out_dev, h->stream);
     if (rc != FL_OK) { set_err("fl_obs_cutils_tree: no launch configuration: %d rail cells and %d agents per env do not fit the observation kernels' LDS (160 KiB a workgroup), or the sizes are out of range", h->d.Rcap, h->d.A); return rc; }
+    HIPCHK(hipGetLastError());
+    return FL_OK;
+}
+
+int fl_obs_global(fl_batch *h, int b0, int nb, int elem_bytes, void *rail_dev, void *agents_state_dev, void *targets_dev) {
+    NEED_COMMIT(h);
+    if (b0 < 0 || nb < 1 || b0 > h->B - nb) { set_err("fl_obs_global: env range [%d, %d + %d) is not inside [0, %d)", b0, b0, nb, h->B); return FL_ERR_ARG; }
+    if (elem_bytes != 4 && elem_bytes != 8) { set_err("fl_obs_global: elem_bytes must be 8 (float64) or 4 (float32), got %d", elem_bytes); return FL_ERR_ARG; }
+    if (!rail_dev && !agents_state_dev && !targets_dev) { set_err("fl_obs_global: every output buffer is NULL"); return FL_ERR_ARG; }
+    if (((uintptr_t)rail_dev | (uintptr_t)agents_state_dev | (uintptr_t)targets_dev) & 15u) {
+        set_err("fl_obs_global: the output buffers must be 16-byte aligned");
+        return FL_ERR_ARG;
+    }
+    if (h->n_cu == 0 && hipDeviceGetAttribute(&h->n_cu, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess) h->n_cu = 0;
+    if (fl_launch_obs_global(h->d, b0, nb, elem_bytes, h->n_cu, rail_dev, agents_state_dev, targets_dev, h->stream) != FL_OK) {
+        set_err("fl_obs_global: a %d x %d map needs more bands of cells than one launch holds", h->H, h->W);
+        return FL_ERR_ARG;
+    }
     HIPCHK(hipGetLastError());
     return FL_OK;
 }

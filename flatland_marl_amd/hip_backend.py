@@ -26,7 +26,7 @@ STATE_NAMES = ("row", "col", "dir", "state", "malf", "nmalf", "scount", "saved",
 # every symbol include/flatland_hip.h declares
 SYMBOLS = ("fl_last_error", "fl_version", "fl_device_count", "fl_create", "fl_destroy", "fl_set_stream", "fl_sync",
            "fl_load_env", "fl_reserve", "fl_commit", "fl_set_rng", "fl_get_rng", "fl_reset", "fl_reset_dev", "fl_step", "fl_step_synth", "fl_step_obs", "fl_check",
-           "fl_metrics", "fl_scores", "fl_info", "fl_obs_cutils", "fl_obs_cutils_policy", "fl_obs_cutils_handles", "fl_obs_cutils_tree", "fl_obs_tree", "fl_obs_tree_handles", "fl_obs_set_mode", "fl_policy_pack", "fl_get_state", "fl_get_state_aux", "fl_set_state", "fl_motion_check", "fl_distance_map", "fl_distance_map_rebuild", "fl_distance_map_rebuild_masked", "fl_positions_map",
+           "fl_metrics", "fl_scores", "fl_info", "fl_obs_cutils", "fl_obs_cutils_policy", "fl_obs_cutils_handles", "fl_obs_cutils_tree", "fl_obs_tree", "fl_obs_tree_handles", "fl_obs_global", "fl_obs_set_mode", "fl_policy_pack", "fl_get_state", "fl_get_state_aux", "fl_set_state", "fl_motion_check", "fl_distance_map", "fl_distance_map_rebuild", "fl_distance_map_rebuild_masked", "fl_positions_map",
            "fl_algorithmic_bytes_per_agent_step")
 
 _lib = None
@@ -92,6 +92,8 @@ def lib():
             L.fl_obs_cutils_policy.argtypes = [vp, i32, i32] + [vp] * 7
         if hasattr(L, "fl_obs_cutils_handles"):
             L.fl_obs_cutils_handles.argtypes = [vp, i32, i32, vp, i32] + [vp] * 7
+        if hasattr(L, "fl_obs_global"):
+            L.fl_obs_global.argtypes = [vp, i32, i32, i32, vp, vp, vp]
         if hasattr(L, "fl_obs_set_mode"):             # (an older build loaded through bench.py --lib for a same-box A/B run has none)
             L.fl_obs_set_mode.argtypes = [vp, i32]
         L.fl_step_obs.argtypes = [vp, vp, u32, u32, i32, vp, vp, vp, i32, i32, i32] + [vp] * 7 + [i32, i32, vp]
@@ -437,6 +439,43 @@ class BatchedRailEnv:
         _chk(lib().fl_obs_tree(self.h, max_depth, pred_depth, out.data_ptr()))
         return out
 
+    def _env_range(self, envs):
+        """None -> every env; a range / slice of consecutive envs or a (start, stop) pair -> (b0, nb)"""
+        if envs is None:
+            return 0, self.B
+        if isinstance(envs, (range, slice)):
+            start, stop, step = envs.indices(self.B) if isinstance(envs, slice) else (envs.start, envs.stop, envs.step)
+            if step != 1:
+                raise ValueError("obs_global: envs has to be a run of consecutive envs, got %r" % (envs,))
+        else:
+            start, stop = (int(v) for v in envs)
+        return int(start), int(stop) - int(start)
+
+    def obs_global(self, dtype=None, envs=None, rail=True):
+        """flatland.envs.observations.GlobalObsForRailEnv (observations.py:535-611) for every agent of the envs `envs` (None = all; a
+        range / slice of consecutive envs or a (start, stop) pair), one launch (fl_obs_global): (rail [nb,H,W,16] or None when
+        rail=False, agents_state [nb,A,H,W,5], targets [nb,A,H,W,2]) device tensors.  dtype torch.float64 (default: the reference's
+        values) or torch.float32 (the same values cast).  The buffers are cached per (dtype, range) and rewritten by every call: the
+        output is A times the map per env (4.8 GB in float64 for 1 024 envs of 80 agents on 35 x 30), so take big batches in ranges."""
+        t = self.torch
+        dtype = t.float64 if dtype is None else dtype
+        if dtype not in (t.float64, t.float32):
+            raise ValueError("obs_global: dtype has to be torch.float64 or torch.float32, got %r" % (dtype,))
+        b0, nb = self._env_range(envs)
+        if not (0 <= b0 and nb >= 1 and b0 + nb <= self.B):
+            raise ValueError("obs_global: env range [%d, %d) is not inside [0, %d)" % (b0, b0 + nb, self.B))
+        if not hasattr(self, "_glob"):
+            self._glob = {}
+        key = (dtype, b0, nb)
+        if key not in self._glob:
+            H, W, A, dev = self.H, self.W, self.A, self.device
+            self._glob[key] = (t.empty((nb, H, W, 16), dtype=dtype, device=dev), t.empty((nb, A, H, W, 5), dtype=dtype, device=dev),
+                               t.empty((nb, A, H, W, 2), dtype=dtype, device=dev))
+        r, ast, tgt = self._glob[key]
+        _chk(lib().fl_obs_global(self.h, b0, nb, 8 if dtype == t.float64 else 4, r.data_ptr() if rail else None, ast.data_ptr(),
+                                 tgt.data_ptr()))
+        return (r if rail else None), ast, tgt
+
     # ---- read-backs
     def state(self):
         st = np.zeros((self.B, self.A, STATE_COLS), dtype=np.int32)
@@ -600,6 +639,11 @@ class MixedBatch:
     def obs_policy(self):
         """the consumer's call per group (fl_obs_cutils_policy): the adjacency of group k is offset over ITS (env, agent) flattening"""
         return self._each(lambda g: g.obs_policy())
+
+    def obs_global(self, dtype=None, rail=True):
+        """GlobalObsForRailEnv per group (fl_obs_global): one (rail, agents_state, targets) triple per shape group, its env axis in the
+        group's batch order (pick(i, ...) gives env i's slices)"""
+        return self._each(lambda g: g.obs_global(dtype, None, rail))
 
     def state(self, i):
         g, b = self.where[i]

@@ -258,3 +258,36 @@ class TreeObsUpstream(_re.TreeObsUpstream):
 
     def get(self, handle=0):                     # (see rail_env.TreeObsUpstream.get: the agent's node of get_many(every handle))
         return self.get_many(list(range(len(self.env.agents))))[handle]
+
+
+class GlobalObsForRailEnv(_re.GlobalObsForRailEnv):
+    """`flatland.envs.observations.GlobalObsForRailEnv()` (observations.py:535-611) for any env object: {handle: (rail_obs,
+    agents_state, targets)} float64 numpy, one rail_obs array for every handle.  Given this library's own `RailEnv` it reads the env's
+    device-resident state directly (the base class); any other env is mirrored: reset() reads the static side (the reference builds
+    rail_obs there, :560-566), get_many() the agents' dynamic state."""
+
+    def __init__(self, *, device=0, verify_distance_map=False):
+        super().__init__()
+        self._bind = _EnvBinding(device, verify_distance_map)
+        self._native = False
+
+    def set_env(self, env):
+        self._native = isinstance(env, _re.RailEnv)
+        self.env = env
+
+    def _batch(self):
+        return self.env._batch if self._native else self._bind.batch
+
+    def reset(self):
+        if not self._native:
+            self._bind.load_static(self.env)
+        super().reset()
+
+    def get_many(self, handles=None):
+        if handles is None:
+            return {}
+        if not self._native:
+            if self._bind.batch is None:
+                raise RuntimeError("GlobalObsForRailEnv.get_many() before reset()")
+            self._bind.push_dynamic(self.env)
+        return super().get_many(handles)

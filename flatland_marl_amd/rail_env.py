@@ -324,6 +324,38 @@ class TreeObsUpstream(ObservationBuilder):
         return self.get_many(list(range(len(self.env.agents))))[handle]
 
 
+class GlobalObsForRailEnv(ObservationBuilder):
+    """flatland.envs.observations.GlobalObsForRailEnv (observations.py:535-611): get_many(handles) -> {handle: (rail_obs [H,W,16],
+    agents_state [H,W,5], targets [H,W,2])}, float64 numpy; rail_obs is ONE array for every handle, built at reset() (:560-566).
+    Computed by the GPU (fl_obs_global) for every agent in one launch; get_many(None) is {} as in the reference."""
+
+    checks_errors = True
+
+    def __init__(self):
+        super().__init__()
+        self.rail_obs = None
+
+    def _batch(self):
+        return self.env._batch
+
+    def reset(self):
+        r, _, _ = self._batch().obs_global(rail=True)
+        self._batch().check()
+        self.rail_obs = r[0].cpu().numpy()
+
+    def get_many(self, handles=None):
+        if handles is None:
+            return {}                 # core/env_observation_builder.py:52-55: no handles, no observations
+        handles = list(handles)
+        if not handles:
+            return {}
+        b = self._batch()
+        _, ast, tgt = b.obs_global(rail=False)
+        b.check()                     # the one synchronising error check of a step (RailEnv.step leaves it to the builder)
+        ast, tgt = ast[0].cpu().numpy(), tgt[0].cpu().numpy()
+        return {h: (self.rail_obs, ast[h], tgt[h]) for h in handles}
+
+
 class _FromDescription:
     """what `env.rail_generator` / `env.line_generator` are on an env made from a description or a file (the reference:
     rail_from_file / line_from_file closures, rail_generators.py:116-145, line_generators.py:168-206): hands the env's own rail /

@@ -22,6 +22,8 @@
  *   fl_obs_cutils_handles / fl_obs_tree_handles
  *                                         get_many(handles) with a handle list: the listed agents' predictions only, by list position
  *                                         (flatland_cutils/src/treeobs.cpp:50-62, 393-465; flatland/envs/observations.py:72-83, 337-366)
+ *   fl_obs_global                         flatland.envs.observations.GlobalObsForRailEnv.reset() + get_many()
+ *                                         (flatland/envs/observations.py:535-611)
  *   fl_step_obs                           RailEnv.step() incl. the observations it returns (rail_env.py:634 -> :660-666)
  *   fl_obs_cutils_tree                    both observation builders above in one launch
  *   fl_info                               RailEnv.get_info_dict / action_required (rail_env.py:243-258, 452-468),
@@ -210,6 +212,16 @@ int fl_obs_tree(fl_batch *h, int max_depth, int pred_depth, double *out_dev);
  * of 0 .. n_handles-1 (a listed handle >= len(handles) is an IndexError in the reference: FL_ERR_ARG).  The output holds the rows of ALL
  * agents (row i = agent i; the reference returns the listed handles' nodes: the caller picks them). */
 int fl_obs_tree_handles(fl_batch *h, int max_depth, int pred_depth, const int32_t *handles, int n_handles, double *out_dev);
+/* flatland.envs.observations.GlobalObsForRailEnv: reset() + get(handle) for every handle of the envs [b0, b0 + nb)
+ * (flatland/envs/observations.py:535-611, get_many: core/env_observation_builder.py:35-58), one launch, no host synchronisation.
+ * Device outputs, elem_bytes 8 = float64 (the reference's values) or 4 = float32 (the same values cast):
+ *   rail_dev         [nb][H][W][16]     channel k = bit 15 - k of the cell's transitions (:560-566; one array for every handle)
+ *   agents_state_dev [nb][A][H][W][5]   (:581-610)
+ *   targets_dev      [nb][A][H][W][2]   (:582, 587, 598)
+ * Any pointer may be NULL (that output is skipped), not all three; each has to be 16-byte aligned.  A bad range, element size or
+ * alignment is FL_ERR_ARG before anything is launched or written.  The output is A times the map per env: take big batches in
+ * env ranges. */
+int fl_obs_global(fl_batch *h, int b0, int nb, int elem_bytes, void *rail_dev, void *agents_state_dev, void *targets_dev);
 /* Opt-in modes of the observation launches of this handle (flags: OR of the values below, 0 = defaults).
  * FL_OBS_KEEP_TREE_ROWS: the caller promises that the upstream-tree output buffer handed to fl_obs_tree / fl_obs_cutils_tree /
  *   fl_step_obs is the buffer of the previous such call with the same max_depth, NOT modified in between.  The builder then stops
