@@ -27,7 +27,7 @@ STATE_NAMES = ("row", "col", "dir", "state", "malf", "nmalf", "scount", "saved",
 SYMBOLS = ("fl_last_error", "fl_version", "fl_device_count", "fl_create", "fl_destroy", "fl_set_stream", "fl_sync",
            "fl_load_env", "fl_reserve", "fl_commit", "fl_set_rng", "fl_get_rng", "fl_reset", "fl_reset_dev", "fl_step", "fl_step_synth", "fl_step_obs", "fl_check",
            "fl_metrics", "fl_scores", "fl_info", "fl_obs_cutils", "fl_obs_cutils_policy", "fl_obs_cutils_handles", "fl_obs_cutils_tree", "fl_obs_tree", "fl_obs_tree_handles", "fl_obs_global", "fl_obs_set_mode", "fl_policy_pack", "fl_get_state", "fl_get_state_aux", "fl_set_state", "fl_motion_check", "fl_distance_map", "fl_distance_map_rebuild", "fl_distance_map_rebuild_masked", "fl_positions_map",
-           "fl_algorithmic_bytes_per_agent_step")
+           "fl_algorithmic_bytes_per_agent_step", "fl_tree_lstm_workspace_bytes", "fl_tree_lstm")
 
 _lib = None
 
@@ -100,6 +100,10 @@ def lib():
         L.fl_obs_cutils_tree.argtypes = [vp, i32, i32] + [vp] * 7 + [i32, i32, vp]
         L.fl_info.argtypes = [vp, vp, vp, vp, vp]
         L.fl_policy_pack.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+        if hasattr(L, "fl_tree_lstm"):
+            L.fl_tree_lstm_workspace_bytes.argtypes = [i32, i32, i32]
+            L.fl_tree_lstm_workspace_bytes.restype = C.c_size_t
+            L.fl_tree_lstm.argtypes = [i32, i32] + [vp] * 12 + [i32, vp, vp, vp, vp, C.c_size_t, vp]
         L.fl_get_state.argtypes = [vp, vp, vp]
         L.fl_distance_map.argtypes = [vp, i32, C.POINTER(i32), vp, vp]
         L.fl_distance_map_rebuild.argtypes = [vp]
@@ -151,6 +155,32 @@ def policy_pack(adjacency, node_order, edge_order, adj_out, no_out, eo_out):
     s = torch.cuda.current_stream(adjacency.device).cuda_stream
     _chk(lib().fl_policy_pack(B, A, E, adjacency.data_ptr(), node_order.data_ptr(), edge_order.data_ptr(),
                               adj_out.data_ptr(), no_out.data_ptr(), eo_out.data_ptr(), C.c_void_p(s)))
+
+
+def tree_lstm(forest, adjacency, node_order, edge_order, weights, roots_only, h, c=None, status=None):
+    """TreeLSTM.forward (fl_tree_lstm) on torch's current stream of the inputs' device, with a workspace from torch's allocator.
+    forest f32 [..., N, 12], adjacency i64 [..., N-1, 3] (modified), node_order i64 [..., N], edge_order i64 [..., N-1], all
+    contiguous on one device; weights = (W_iou.weight, W_iou.bias, U_iou.weight, W_c.weight, W_c.bias, W_f.weight, W_f.bias,
+    U_f.weight), f32 contiguous; h (and c, if given) f32 [T*N, 128] or, roots_only, [T, 128]; status i32 [1] or None."""
+    import torch
+    N = forest.shape[-2]
+    T = forest.numel() // (N * 12)
+    L = lib()
+    if not hasattr(L, "fl_tree_lstm"):
+        raise FlatlandHipError(1, "the loaded library has no fl_tree_lstm (an older build loaded through --lib?)")
+    rows = (T if roots_only else T * N) * 128
+    for name, o in (("h", h), ("c", c)):
+        if o is not None and (o.dtype != torch.float32 or o.device != forest.device or not o.is_contiguous() or o.numel() < rows):
+            raise ValueError("tree_lstm: %s must be a contiguous float32 tensor of at least %d elements on %s" % (name, rows, forest.device))
+    nbytes = L.fl_tree_lstm_workspace_bytes(T, N, int(roots_only))
+    with torch.cuda.device(forest.device):
+        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=forest.device)
+        s = torch.cuda.current_stream(forest.device).cuda_stream
+        _chk(L.fl_tree_lstm(T, N, forest.data_ptr(), adjacency.data_ptr(), node_order.data_ptr(), edge_order.data_ptr(),
+                            *[w.data_ptr() for w in weights], int(roots_only), h.data_ptr(),
+                            None if c is None else c.data_ptr(), None if status is None else status.data_ptr(),
+                            ws.data_ptr(), ws.numel(), C.c_void_p(s)))
+    return h
 
 
 class BatchedRailEnv:

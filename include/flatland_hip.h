@@ -30,6 +30,8 @@
  *                                         evaluator scores (flatland/evaluators/service.py:875-879, 900-913)
  *   fl_policy_pack                        plfActor.get_feature + Network.modify_adjacency
  *                                         (solution/plfActor.py:48-74, solution/nn/net_tree.py:105-116)
+ *   fl_tree_lstm                          TreeLSTM.forward of the policy network, one launch for the whole batch
+ *                                         (solution/nn/TreeLSTM.py:33-154, called by solution/nn/net_tree.py:72-80)
  *   fl_get_state / fl_get_rng             EnvAgent attribute reads (agent_utils.py:57-88), np_random.get_state()
  *   fl_set_state / fl_get_state_aux       AgentsLoader's per-call read of a caller-owned env (flatland_cutils/src/loader.cpp:8-120,
  *                                         221-327), RailEnvPersister.set_full_state (flatland/envs/persistence.py:182-222)
@@ -43,6 +45,7 @@
  */
 #ifndef FLATLAND_HIP_H
 #define FLATLAND_HIP_H
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -244,6 +247,31 @@ int fl_info(fl_batch *h, uint8_t *action_required_dev, int32_t *malfunction_dev,
 int fl_policy_pack(int B, int A, int E, const int32_t *adjacency_dev, const int32_t *node_order_dev,
                    const int32_t *edge_order_dev, int64_t *adjacency_out_dev, int64_t *node_order_out_dev,
                    int64_t *edge_order_out_dev, void *hip_stream);
+
+/* Policy network's tree encoder, stateless (device pointers, enqueued on hip_stream, no host synchronisation, no allocation):
+ * TreeLSTM.forward (solution/nn/TreeLSTM.py:33-154) on n_trees trees of n_nodes nodes, in-features 12, hidden size 128 (the
+ * solution's FeatureParserConfig.node_sz / NetworkConfig.tree_embedding_sz; other sizes do not exist here).  Inputs as
+ * fl_obs_cutils_policy writes them: forest f32[T][N][12], adjacency i64[T][N-1][3] already modified (global node ids,
+ * every negative entry -2), node_order i64[T][N] (height, -2 = padding), edge_order i64[T][N-1] (the parent's height).
+ * Weights in torch's own layout ([out][in] row-major): W_iou [384][12] + b_iou [384], U_iou [384][384], W_c [128][384] + b_c [128],
+ * W_f [128][12] + b_f [128], U_f [128][128]; read as they are at every call (nothing is cached across calls).
+ * roots_only = 0: h_dev f32[T*N][128] gets h of every node (the reference's return value), c_dev (or NULL) the same shape for c;
+ * roots_only = 1: h_dev / c_dev f32[T][128] get node 0 of every tree (what Network.forward keeps, net_tree.py:77-80).
+ * Padding nodes have h = c = 0.  A node of height n > 0 takes the children of its three edges, in edge-list order; the reference
+ * pairs the i-th node of a level with the i-th triple of that level's edges over the whole batch, which is the same only when
+ * every such node has its three edges one after another in node order.  A tree that breaks this (or has an index outside itself,
+ * an edge_order other than its parent's node_order, a node_order outside {-2} u [0, N-1]) adds 1 to *status_dev (if not
+ * NULL; the caller zeroes it) and gets unspecified outputs.  workspace_dev holds h and c of the other nodes: at least
+ * fl_tree_lstm_workspace_bytes(n_trees, n_nodes, roots_only) bytes (T*N*512 B, twice that with roots_only).
+ * FL_ERR_ARG before any HIP call: n_trees <= 0, n_nodes outside [4, 64], (n_nodes - 1) % 3 != 0 (the reference fails there:
+ * its edge triples do not divide), a NULL input / weight / h / workspace, a float pointer not 16-byte aligned, an int64
+ * pointer not 8-byte aligned, a short workspace. */
+size_t fl_tree_lstm_workspace_bytes(int n_trees, int n_nodes, int roots_only);
+int fl_tree_lstm(int n_trees, int n_nodes, const float *forest_dev, const int64_t *adjacency_dev, const int64_t *node_order_dev,
+                 const int64_t *edge_order_dev, const float *w_iou_dev, const float *b_iou_dev, const float *u_iou_dev,
+                 const float *w_c_dev, const float *b_c_dev, const float *w_f_dev, const float *b_f_dev, const float *u_f_dev,
+                 int roots_only, float *h_dev, float *c_dev, int32_t *status_dev, void *workspace_dev, size_t workspace_bytes,
+                 void *hip_stream);
 
 /* Host read-backs (synchronising). state int32[B][A][FL_STATE_COLS]; elapsed int32[B]. */
 int fl_get_state(fl_batch *h, int32_t *state, int32_t *elapsed);
