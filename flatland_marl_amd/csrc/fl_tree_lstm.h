@@ -16,8 +16,8 @@
 // group's child table and buckets the group's nodes by height.  Then level by level, in tiles of 32 nodes: [x | h_k1 | h_k2 | h_k3]
 // is staged in LDS (row stride 420 floats, = 4 mod 32: the 16 lanes of a ds_read_b128 phase hit distinct banks), and wave w
 // computes hidden units 32w .. 32w+31 of the tile with f32-input MFMA (v_mfma_f32_32x32x2_f32, exact f32): i, o, u over
-// K = 12 + 384, W_f x once and U_f h_kj for the three children, then f_j * c_kj goes to LDS (over the staged tile) and W_c runs
-// over K = 384.  A wave's three iou accumulators hold the same hidden units, so the epilogue is in registers.  Weights are read
+// K = 384 + 12 (U h from zero, then W x: see the level loop), W_f x once and U_f h_kj for the three children, then f_j * c_kj
+// goes to LDS (over the staged tile) and W_c runs over K = 384.  A wave's three iou accumulators hold the same hidden units, so the epilogue is in registers.  Weights are read
 // in torch's [out][in] layout straight from global memory (L2): lane l of an MFMA step takes k = kc + 16 * (l >> 5) + s of
 // chunk kc, so every lane loads 64 contiguous bytes of one weight row a chunk.  h and c of every node go to the output buffers
 // or the workspace; the next level of the same workgroup reads them back after a barrier (workgroup-scope release / acquire).
@@ -263,11 +263,13 @@ __global__ void __launch_bounds__(FTL_THREADS) k_tree_lstm(FtlArgs p) {
             __syncthreads();
 
             const float *arow = &s_x[col * FTL_STRIDE];         // this lane's A row (MFMA row = lane & 31)
+            // U h first, from zero, W x on top of it: every MFMA step rounds at the size of the running sum, and W x can be far
+            // larger than U h (the 192 steps of U h on top of W x cost up to 4x the error of a plain float32 forward)
             ftl_f32x16 ai = {}, ao = {}, au = {};
-            ftl_wx(arow, p.w_iou, j0, M + j0, 2 * M + j0, col, ai, ao, au, 3, hh);
             if (n > 0)
                 ftl_gemm3<3 * FTL_M>(arow + FTL_F, p.u_iou + (size_t)(j0 + col) * 3 * M, p.u_iou + (size_t)(M + j0 + col) * 3 * M,
                                      p.u_iou + (size_t)(2 * M + j0 + col) * 3 * M, ai, ao, au, hh);
+            ftl_wx(arow, p.w_iou, j0, M + j0, 2 * M + j0, col, ai, ao, au, 3, hh);
             const float bi = p.b_iou[j0 + col], bo = p.b_iou[M + j0 + col], bu = p.b_iou[2 * M + j0 + col];
             float iu[16], og[16], cc[16];
 #pragma unroll
@@ -283,14 +285,14 @@ __global__ void __launch_bounds__(FTL_THREADS) k_tree_lstm(FtlArgs p) {
                 float fc[3][16];
 #pragma unroll
                 for (int j = 0; j < 3; j++) {
-                    ftl_f32x16 af = wfx;
+                    ftl_f32x16 af = {};                          // (U_f h from zero as well; W_f x is added once, below)
                     ftl_gemm1<FTL_M>(arow + FTL_F + j * M, p.u_f + (size_t)(j0 + col) * M, af, hh);
 #pragma unroll
                     for (int r = 0; r < 16; r++) {
                         const int row = (r & 3) + 8 * (r >> 2) + 4 * hh;
                         const int ch = s_rowch[row][j];
                         const float cv = ch >= 0 ? p.cbuf[(size_t)ch * M + j0 + col] : 0.f;
-                        fc[j][r] = ftl_sigmoid(af[r] + bf) * cv;
+                        fc[j][r] = ftl_sigmoid((af[r] + wfx[r]) + bf) * cv;
                     }
                 }
                 __syncthreads();                                // every wave is done with the staged tile

@@ -1,0 +1,448 @@
+"""fl_tree_lstm on synthetic forests (tests/tree_lstm_forests.py): the tree shapes the contract allows and no observation has, the
+group sizes and 32-row tiles the kernel's own machinery turns on, and the status word.
+
+CPU: the generator is valid and reproduces the inputs stored in tests/golden/synth_tree_lstm_*.npz bit for bit; the float64
+restatement matches the reference module's outputs stored there (tools/capture_tree_lstm.py ran the real module on these forests;
+it raised on none of them, which the test asserts, so no kind is left to the restatement alone).
+
+GPU: the kernel against the float64 restatement run on the device.  Tolerance: per case e32 = the error of the same restatement
+run in torch.float32 against its float64 run (max |dh|, and max |dc| / max(1, |c|)); the kernel passes when its error is at most
+R * e32.  R = 3, set on 2026-10-17 from tests/golden/synth_tree_lstm_errors.json (MI355X): twice the largest ratio recorded there
+(1.48), rounded up to an integer.  TREE_LSTM_SYNTH_ERRORS=<path> makes the GPU cases write their figures to <path> in that
+file's format.  The first measurement gave ratios up to 4.34 (observation features, weight scale 1): the kernel ran the 192 MFMA
+steps of U h on top of W x in one accumulator, so each step rounded at the size of W x; a float32 forward written that way on
+the CPU reproduced the kernel's error to three digits (4.56e-7 against 4.49e-7 in h), while v_mfma_f32_32x32x2_f32 itself
+matched an fmaf chain exactly and the level-0 cases (no U h) sat at ratio 1.00.  fl_tree_lstm.h now sums U h from zero and adds
+W x last; the figures in the file are from that kernel.
+"""
+import fnmatch
+import functools
+import glob
+import json
+import math
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from tests import tree_lstm_forests as tf
+from tests import tree_lstm_torch as tl
+from tests import util
+from tests.test_tree_lstm_golden import assert_close, golden_params
+
+R = 3
+ERRORS = os.path.join(util.GOLD, "synth_tree_lstm_errors.json")
+GOLDENS = sorted(glob.glob(os.path.join(util.GOLD, "synth_tree_lstm_*.npz")))
+NAMES = [os.path.basename(p)[len("synth_tree_lstm_"):-4] for p in GOLDENS]
+FX = "fixture:cfg2_uniform"
+DEV = "cuda:0"
+
+
+# ---------------------------------------------------------------------------------------------------------------- CPU
+def _violations(x):
+    return int(tl.triple_rule_violations(x[1], x[2], x[3]).sum())
+
+
+@pytest.mark.parametrize("N", [4, 7, 31, 34, 64])
+@pytest.mark.parametrize("kind", tf.KINDS)
+def test_generated_forests_are_valid(kind, N):
+    kw = dict(L=(0, 1, N - 1, N), m=tuple(range(tf.max_lvl1(N) + 1)), base="weird")
+    forest, adj, no, eo = x = tf.make(kind, 23, N, 5, **kw)
+    assert forest.shape == (1, 23, N, 12) and forest.dtype == torch.float32 and adj.shape == (1, 23, N - 1, 3)
+    assert no.shape == (1, 23, N) and eo.shape == (1, 23, N - 1) and {adj.dtype, no.dtype, eo.dtype} == {torch.int64}
+    assert _violations(x) == 0
+    assert all(torch.equal(a, b) for a, b in zip(x, tf.make(kind, 23, N, 5, **kw)))
+    assert not torch.equal(no, tf.make(kind, 23, N, 6, **kw)[2]) or kind in ("chain", "full", "flat", "lvl1")
+    real = eo.view(23, N - 1) != -2
+    assert ((adj[0][..., :2] == -2).all(-1) == ~real).all()
+    if kind == "mixpad":
+        assert (no[0, ::3] == -2).all() and (eo[0, ::3] == -2).all() and (no[0, 1::3, 0] >= 0).all()
+    else:
+        assert (no[0, :, 0] >= 0).all() or kind == "flat"
+    if kind == "flat":
+        assert not real.any() and (no[0] == 0).sum(-1).tolist() == [(0, 1, N - 1, N)[t % 4] for t in range(23)]
+    if kind == "lvl1":
+        assert (no[0] == 1).sum(-1).tolist() == [t % (tf.max_lvl1(N) + 1) for t in range(23)]
+
+
+def test_generated_shapes_reach_the_edges():
+    _, adj, no, eo = tf.make("chain", 3, 64, 1)
+    assert int(no.max()) == 21 and (no[0] >= 0).all() and ((no[0] == 21).sum(-1) == 1).all()     # 22 heights on one path
+    assert [int(tf.make("full", 1, N, 1)[2].ge(0).sum()) for N in (4, 13, 40, 31, 64)] == [4, 13, 40, 13, 40]
+    _, adj, no, eo = tf.make("gaps", 40, 64, 2)
+    tops = no[0].max(-1).values
+    assert int(tops.max()) == 63                                                                # the last label there is
+    heights = [sorted(set(v.tolist()) - {-2}) for v in no[0]]
+    assert any(h != list(range(len(h))) for h in heights)
+    _, adj, no, eo = tf.make("perm", 40, 31, 3)
+    n, e, a = no[0], eo[0], adj[0] - (torch.arange(40) * 31).view(40, 1, 1)
+    not_bfs = interleaved = False
+    for t in range(40):
+        real = e[t] != -2
+        if real.sum() >= 6:
+            kids = a[t][real, 1]
+            not_bfs |= bool((n[t][kids[:-1]] < n[t][kids[1:]]).any() or (kids[:-1] > kids[1:]).any())
+            lv = e[t][real]
+            interleaved |= len(torch.unique_consecutive(lv)) > len(torch.unique(lv)) or bool((~real[:int(real.sum())]).any())
+    assert not_bfs and interleaved
+    _, adj, no, eo = tf.make("weird", 60, 31, 4)
+    n, e, a = no[0], eo[0], adj[0] - (torch.arange(60) * 31).view(60, 1, 1)
+    self_child = pad_child = higher = shared = 0
+    for t in range(60):
+        real = e[t] != -2
+        p, c = a[t][real, 0], a[t][real, 1]
+        self_child += int((p == c).sum())
+        pad_child += int((n[t][c] == -2).sum())
+        higher += int(((n[t][c] >= n[t][p]) & (p != c)).sum())
+        shared += len(c) - len(torch.unique(c))
+    assert min(self_child, pad_child, higher, shared) > 0, (self_child, pad_child, higher, shared)
+
+
+def test_checker_counts_a_child_outside_the_tree_on_an_edge_of_order_0():
+    """include/flatland_hip.h: a tree with "an index outside itself" is counted; the kernel does so for every real edge"""
+    x = tf.make("full", 4, 31, 1)
+    assert _violations(x) == 0
+    adj, eo = x[1].clone(), x[3].clone()
+    eo[0, 2, 20] = 0
+    adj[0, 2, 20] = torch.tensor([2 * 31 + 5, 2 * 31 + 6, -2])            # a real edge of order 0, child inside: allowed
+    assert _violations((x[0], adj, x[2], eo)) == 0
+    adj[0, 2, 20, 1] = 2 * 31 - 1                                          # the previous tree's last node
+    assert tl.triple_rule_violations(adj, x[2], eo).view(-1).tolist() == [False, False, True, False]
+    adj[0, 2, 20, 1] = -2
+    assert tl.triple_rule_violations(adj, x[2], eo).view(-1).tolist() == [False, False, True, False]
+
+
+def test_synth_goldens_present():
+    kinds = {str(np.load(p)["kind"]) for p in GOLDENS}
+    assert kinds == set(tf.KINDS)
+    assert {int(np.load(p)["N"]) for p in GOLDENS} == {4, 31, 64}
+    for p in GOLDENS:
+        assert os.path.getsize(p) < 256 * 1024
+        assert not fnmatch.fnmatch(os.path.basename(p), "tree_lstm_*.npz")
+
+
+def stored_inputs(g):
+    return tf.to_policy(g["forest"], g["node_order"].astype(np.int64), g["edge_order"].astype(np.int64),
+                        g["adjacency"].astype(np.int64))
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_generator_reproduces_stored_inputs(name):
+    g = np.load(os.path.join(util.GOLD, "synth_tree_lstm_%s.npz" % name))
+    assert g["node_order"].dtype == g["edge_order"].dtype == g["adjacency"].dtype == np.int8
+    new = tf.make(str(g["kind"]), int(g["T"]), int(g["N"]), int(g["gen_seed"]), feat=str(g["feat"]), base=str(g["base"]),
+                  L=list(g["L"]) or None, m=list(g["m"]) or None)
+    for a, b in zip(new, stored_inputs(g)):
+        assert a.dtype == b.dtype and a.shape == b.shape and a.numpy().tobytes() == b.numpy().tobytes()
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_restatement_matches_reference_on_synthetic_forests(name):
+    g = np.load(os.path.join(util.GOLD, "synth_tree_lstm_%s.npz" % name))
+    assert str(g["exception"]) == ""            # the reference took every kind: each is pinned to it, none to the restatement alone
+    x = stored_inputs(g)
+    T, N = int(g["T"]), int(g["N"])
+    assert _violations(x) == 0
+    ids = list(g["tree_ids"])
+    pad = x[2].view(T, N) == -2
+    assert list(g["scales"]) == [1.0, 4.0]
+    for s, scale in enumerate(g["scales"]):
+        h, c = tl.tree_lstm(*x, golden_params(g, scale), with_c=True)
+        h, c = h.view(T, N, -1), c.view(T, N, -1)
+        assert_close(h[:, 0], c[:, 0], g["root_h"][s], g["root_c"][s])
+        assert_close(h[ids], c[ids], g["all_h"][s], g["all_c"][s])
+        assert (h[pad] == 0).all() and (c[pad] == 0).all()
+        assert (g["all_h"][s][pad[ids].numpy()] == 0).all() and (g["all_c"][s][pad[ids].numpy()] == 0).all()
+        assert (g["root_h"][s][pad[:, 0].numpy()] == 0).all()
+
+
+def test_R_follows_the_recorded_errors():
+    rec = json.load(open(ERRORS))
+    ratios = [c[k] for c in rec["cases"].values() for k in ("ratio_h", "ratio_c")]
+    assert R == math.ceil(2 * max(ratios)) and rec["R"] == R
+    for c in rec["cases"].values():
+        assert c["ratio_h"] == c["err_h"] / c["e32_h"] and c["ratio_c"] == c["err_c"] / c["e32_c"]
+    assert set(rec["cases"]) == {_case_id(*c, feat, scale) for c in CASES for feat, scale in _combos(c[1])}
+
+
+# ---------------------------------------------------------------------------------------------------------------- GPU
+def group_of(T, cu):
+    """ftl_group (fl_tree_lstm.h): trees a workgroup"""
+    want = 2 * (cu if cu > 0 else 256)
+    return max(1, min(16, (T + want - 1) // want))
+
+
+def _first(lo, mod, rem):
+    return next(T for T in range(lo + 1, lo + mod + 1) if T % mod == rem)
+
+
+def sizes(cu):
+    """T by what it does to the grouping on a device of cu compute units"""
+    W = 2 * cu
+    return {"g1": 37, "g2_tail1": _first(W, 2, 1), "g5_tail3": _first(4 * W, 5, 3), "g6_tail2": _first(5 * W, 6, 2),
+            "g7_tail1": _first(6 * W, 7, 1), "g16_full": 16 * W, "g16_tail1": _first(15 * W, 16, 1),
+            "g16_tail15": _first(15 * W, 16, 15)}
+
+
+def _cu():
+    return torch.cuda.get_device_properties(0).multi_processor_count
+
+
+TILE_EDGES = (31, 32, 33, 64, 65)
+# kind, size, N, extra arguments of the generator ("edges": L / m spread so that a group's level holds each of TILE_EDGES)
+CASES = [
+    ("rand", "g16_full", 64, {}), ("chain", "g16_tail1", 64, {}), ("perm", "g16_tail15", 64, {}),
+    ("weird", "g16_tail1", 31, {}), ("gaps", "g16_tail15", 31, {}), ("mixpad", "g16_full", 31, dict(base="weird")),
+    ("full", "g5_tail3", 4, {}), ("full", "g2_tail1", 13, {}), ("full", "g1", 40, {}),
+    ("rand", "g2_tail1", 34, {}), ("rand", "g1", 4, {}), ("chain", "g1", 64, {}), ("chain", "g6_tail2", 7, {}),
+    ("perm", "g6_tail2", 34, {}), ("perm", "g1", 31, {}), ("gaps", "g7_tail1", 64, {}), ("gaps", "g1", 34, {}),
+    ("weird", "g5_tail3", 7, {}), ("weird", "g1", 64, {}), ("weird", "g2_tail1", 4, {}),
+    ("mixpad", "g7_tail1", 7, dict(base="chain")), ("mixpad", "g1", 64, dict(base="gaps")),
+    ("flat", "g1", 64, dict(L=(31, 32, 33, 64))), ("flat", "g1", 34, dict(L=(31, 32, 33, 34, 0, 1))),
+    ("flat", "g2_tail1", 64, dict(L="edges")),
+    ("lvl1", "g6_tail2", 64, dict(m="edges")), ("lvl1", "g16_tail15", 31, dict(m="edges")), ("lvl1", "g1", 7, dict(m=(0, 1, 1))),
+]
+
+
+def _combos(size):
+    """(features, weight scale): all four, two of them at the largest sizes"""
+    return [("gauss", 4.0), (FX, 1.0)] if size.startswith("g16") else [("gauss", 1.0), ("gauss", 4.0), (FX, 1.0), (FX, 4.0)]
+
+
+def _case_id(kind, size, N, extra, feat, scale):
+    return "%s-%s-n%d-%s-x%d" % (kind + ("_" + extra["base"] if "base" in extra else ""), size, N, feat.split(":")[0], scale)
+
+
+@functools.lru_cache(maxsize=2)
+def _structure(kind, size, N, extra, cu):
+    T = sizes(cu)[size]
+    kw = dict(extra)
+    for k in ("L", "m"):
+        if kw.get(k) == "edges":
+            kw[k] = tuple(v for P in TILE_EDGES for v in tf.spread(P, group_of(T, cu)))
+    return tf.structure(kind, T, N, 7, **kw)
+
+
+GUARD = 16      # FTL_MAX_G: the most trees a workgroup could reach past the last one
+
+
+def _guarded(x):
+    """the four inputs on the device as views of buffers that go on for GUARD more trees: NaN features, no edges, and a
+    node_order of -1, which the kernel counts in the status word if it ever looks at one"""
+    T = x[2].shape[1]
+    out = []
+    for v, fill in zip(x, (float("nan"), -2, -1, -2)):
+        g = torch.full((1, GUARD) + tuple(v.shape[2:]), fill, dtype=v.dtype)
+        out.append(torch.cat([v.cpu(), g], 1).to(DEV)[:, :T])
+        assert out[-1].is_contiguous()
+    return out
+
+
+def _forest(kind, size, N, extra, feat, cu):
+    no, eo, adj = _structure(kind, size, N, tuple(sorted(extra.items())), cu)
+    x = tf.features(feat, no.shape[0], N, np.random.default_rng([7, 1, feat != "gauss"]))
+    return _guarded(tf.to_policy(x, no, eo, adj))
+
+
+def _weights(params):
+    from flatland_marl_amd.policy import PARAM_ORDER
+    return [params[k].to(DEV).contiguous() for k in PARAM_ORDER]
+
+
+def _launch(x, weights, roots_only, with_c, status):
+    """one fl_tree_lstm launch into NaN-filled outputs, which go on for GUARD more trees that must stay NaN"""
+    from flatland_marl_amd import hip_backend as hb
+    T, N = x[2].shape[1:]
+    rows, more = (T, GUARD) if roots_only else (T * N, GUARD * N)
+    hb_, cb_ = [torch.full((rows + more, 128), float("nan"), device=DEV) if k else None for k in (True, with_c)]
+    h, c = hb_[:rows], cb_[:rows] if with_c else None
+    hb.tree_lstm(*x, weights, roots_only, h, c, status)
+    assert torch.isnan(hb_[rows:]).all() and (not with_c or torch.isnan(cb_[rows:]).all()), "a write past the last tree"
+    return h, c
+
+
+def _errors(h, c, h64, c64):
+    return float((h.double() - h64).abs().max()), float(((c.double() - c64).abs() / c64.abs().clamp(min=1)).max())
+
+
+def _record(case, figs):
+    path = os.environ.get("TREE_LSTM_SYNTH_ERRORS")
+    if path:
+        rec = json.load(open(path)) if os.path.exists(path) else dict(device=torch.cuda.get_device_name(0), cases={})
+        rec["cases"][case] = figs
+        json.dump(rec, open(path, "w"), indent=1, sort_keys=True)
+
+
+@pytest.mark.gpu
+def test_sizes_cover_the_groupings():
+    """G = 1; G = 2 with a one-tree tail; 2 < G < 16 with 1, 2 and 3 waves in the last set-up pass (tb += 4), in full groups and
+    in tails; G = 16 with a full last group, a one-tree and a 15-tree tail -- on this device's CU count"""
+    cu = _cu()
+    got = {}
+    for name, T in sizes(cu).items():
+        G = group_of(T, cu)
+        got[name] = (G, T - (-(-T // G) - 1) * G)
+    assert got["g1"] == (1, 1) and got["g2_tail1"] == (2, 1) and got["g5_tail3"] == (5, 3) and got["g6_tail2"] == (6, 2)
+    assert got["g7_tail1"] == (7, 1) and got["g16_full"] == (16, 16) and got["g16_tail1"] == (16, 1) and got["g16_tail15"] == (16, 15)
+    mid = [v for v in got.values() if 2 < v[0] < 16]
+    assert {g % 4 for g, _ in mid} | {t % 4 for _, t in mid} >= {1, 2, 3}
+    assert max(sizes(cu).values()) == 32 * cu
+    used = {c[1] for c in CASES}
+    assert used == set(got)
+    assert {(s, N) for _, s, N, _ in CASES} >= {(s, N) for s in ("g16_full", "g16_tail1", "g16_tail15") for N in (31, 64)}
+    assert {N for _, s, N, _ in CASES if not s.startswith("g16")} >= {4, 7, 34}
+    assert {c[0] for c in CASES} == set(tf.KINDS)
+
+
+@pytest.mark.gpu
+def test_level_populations_sit_on_the_tile_edges():
+    """the flat and lvl1 cases put 31, 32, 33, 64 and 65 nodes on a level of one workgroup: at height 0 and above it"""
+    cu = _cu()
+    level0, above = set(), set()
+    for kind, size, N, extra in CASES:
+        if kind in ("flat", "lvl1"):
+            no = _structure(kind, size, N, tuple(sorted(extra.items())), cu)[0]
+            pops = tf.level_populations(torch.from_numpy(no), group_of(sizes(cu)[size], cu))
+            level0 |= {v for (_, n), v in pops.items() if n == 0}
+            above |= {v for (_, n), v in pops.items() if n >= 1}
+    assert level0 >= set(TILE_EDGES), sorted(level0)
+    assert above >= set(TILE_EDGES), sorted(above)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", [c + fs for c in CASES for fs in _combos(c[1])], ids=lambda c: _case_id(*c))
+def test_kernel_matches_the_restatement(case):
+    kind, size, N, extra, feat, scale = case
+    x = _forest(kind, size, N, extra, feat, _cu())
+    T = x[2].shape[1]
+    assert _violations([v[:, :300] for v in x]) == 0          # (the host checker walks tree by tree; status says it for all)
+    params = tl.seeded_params(11, scale)
+    w = _weights(params)
+    status = torch.zeros(1, dtype=torch.int32, device=DEV)
+    h, c = _launch(x, w, False, True, status)                 # every node, c given
+    h2, c2 = _launch(x, w, False, True, status)
+    hn, _ = _launch(x, w, False, False, status)               # every node, c in the workspace: the module's path
+    hr, cr = _launch(x, w, True, True, status)                # roots only
+    hq, _ = _launch(x, w, True, False, status)
+    assert int(status.item()) == 0
+    assert torch.equal(h, h2) and torch.equal(c, c2)
+    pad = (x[2] == -2).view(-1)
+    assert (h[pad] == 0).all() and (c[pad] == 0).all() and (hn[pad] == 0).all()
+    assert torch.equal(hr, h.view(T, N, 128)[:, 0]) and torch.equal(cr, c.view(T, N, 128)[:, 0])
+    assert torch.equal(hq, hr) and torch.equal(hn, h)
+    del h2, c2, hq
+    h64, c64 = tl.tree_lstm(*x, params, with_c=True)
+    h32, c32 = tl.tree_lstm(*x, params, dtype=torch.float32, with_c=True)
+    e32_h, e32_c = _errors(h32, c32, h64, c64)
+    del h32, c32
+    err_h, err_c = _errors(h, c, h64, c64)
+    figs = dict(err_h=err_h, e32_h=e32_h, ratio_h=err_h / e32_h, err_c=err_c, e32_c=e32_c, ratio_c=err_c / e32_c)
+    print(_case_id(*case), "T %d" % T, " ".join("%s %.3g" % kv for kv in figs.items()))
+    _record(_case_id(*case), figs)
+    assert err_h <= R * e32_h, figs
+    assert err_c <= R * e32_c, figs
+    e_h, e_c = _errors(hn, c, h64, c64)
+    assert e_h <= R * e32_h
+    e_h, e_c = _errors(hr, cr, h64.view(T, N, 128)[:, 0], c64.view(T, N, 128)[:, 0])
+    assert e_h <= R * e32_h and e_c <= R * e32_c
+
+
+# ---- bad trees: complete ternary trees of 13 nodes in N = 31 (node 0 of height 2, nodes 1-3 of height 1 with the edges 3-11,
+# leaves 4-12, padding nodes 13-30 and edges 12-29), one condition injected into the trees BAD
+def _no(v):
+    return lambda t, b, N, no, eo, adj: no[t].__setitem__(20, v(N))
+
+
+def _eo(v):
+    return lambda t, b, N, no, eo, adj: eo[t].__setitem__(4, v(N))
+
+
+def _adj(e, col, v):
+    return lambda t, b, N, no, eo, adj: adj[t, e].__setitem__(col, v(b, N))
+
+
+def _order0_child_outside(t, b, N, no, eo, adj):
+    eo[t, 15] = 0
+    adj[t, 15] = torch.tensor([b + 5, b - 1, -2])
+
+
+def _triple_padded(t, b, N, no, eo, adj):
+    eo[t, 4] = -2
+    adj[t, 4] = -2
+
+
+def _swapped(t, b, N, no, eo, adj):
+    adj[t, 3:6, 0] = b + 2
+    adj[t, 6:9, 0] = b + 1
+
+
+def _split(t, b, N, no, eo, adj):
+    adj[t, 5, 0] = b + 2
+    adj[t, 6, 0] = b + 1
+
+
+CONDITIONS = {
+    "node_order_minus_1": _no(lambda N: -1), "node_order_N": _no(lambda N: N), "node_order_far": _no(lambda N: 1 << 40),
+    "edge_order_minus_1": _eo(lambda N: -1), "edge_order_minus_3": _eo(lambda N: -3), "edge_order_N": _eo(lambda N: N),
+    "parent_in_previous_tree": _adj(4, 0, lambda b, N: b - 1), "parent_in_next_tree": _adj(4, 0, lambda b, N: b + N),
+    "parent_minus_2": _adj(4, 0, lambda b, N: -2),
+    "child_outside_order_1": _adj(4, 1, lambda b, N: b + N), "child_minus_2_order_2": _adj(1, 1, lambda b, N: -2),
+    "child_outside_order_0": _order0_child_outside,
+    "edge_order_not_the_parents": _eo(lambda N: 2), "triple_with_a_padding_edge": _triple_padded,
+    "triples_with_swapped_parents": _swapped, "triple_split_over_two_parents": _split,
+}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("cond", list(CONDITIONS))
+def test_bad_trees_are_counted_and_leave_the_others_alone(cond):
+    from flatland_marl_amd.policy import TreeLSTM, TreeLSTMViolation
+    cu, N = _cu(), 31
+    T = sizes(cu)["g5_tail3"]
+    G = group_of(T, cu)
+    BAD = [G + 2, G + 3, T - 1]                               # two in one full group, one in the tail group
+    assert G > 1 and BAD[0] // G == BAD[1] // G and T % G and BAD[2] // G == T // G
+    forest, adj, no, eo = [v[0].clone() for v in tf.make("full", T, N, 3)]
+    assert no[BAD[0]].tolist() == [2, 1, 1, 1] + [0] * 9 + [-2] * 18 and eo[BAD[0]].tolist() == [2] * 3 + [1] * 9 + [-2] * 18
+    assert (adj[BAD[0], :12, 0] - BAD[0] * N).tolist() == [0, 0, 0, 1, 1, 1, 2, 2, 2, 3, 3, 3]
+    clean = [forest[None], adj.clone()[None], no.clone()[None], eo.clone()[None]]
+    for t in BAD:
+        clean[1][0, t], clean[2][0, t], clean[3][0, t] = -2, -2, -2                   # all padding
+        CONDITIONS[cond](t, t * N, N, no, eo, adj)
+    no[BAD[2], 25] = N + 3                                     # a second violation in one of them
+    x = [forest[None], adj[None], no[None], eo[None]]
+    assert tl.triple_rule_violations(*x[1:]).view(-1).nonzero().flatten().tolist() == BAD
+    assert _violations(clean) == 0
+    x, clean = _guarded(x), _guarded(clean)
+    params = tl.seeded_params(11, 1.0)
+    w = _weights(params)
+    status = torch.zeros(1, dtype=torch.int32, device=DEV)
+    h, c = _launch(x, w, False, True, status)
+    assert int(status.item()) == len(BAD)
+    status.zero_()
+    hr, cr = _launch(x, w, True, True, status)
+    assert int(status.item()) == len(BAD)
+    status.zero_()
+    h0, c0 = _launch(clean, w, False, True, status)
+    hr0, cr0 = _launch(clean, w, True, True, status)
+    assert int(status.item()) == 0
+    others = torch.ones(T, dtype=torch.bool, device=DEV)
+    others[BAD] = False
+    assert not torch.isnan(h0).any() and not torch.isnan(c0).any()
+    for a, b in ((h, h0), (c, c0)):
+        assert torch.equal(a.view(T, N, 128)[others], b.view(T, N, 128)[others])
+    assert torch.equal(hr[others], hr0[others]) and torch.equal(cr[others], cr0[others])
+    assert torch.equal(hr0, h0.view(T, N, 128)[:, 0])
+    h64, c64 = tl.tree_lstm(*clean, params, with_c=True)
+    e32 = _errors(*tl.tree_lstm(*clean, params, dtype=torch.float32, with_c=True), h64, c64)
+    err = _errors(h0, c0, h64, c64)
+    assert err[0] <= R * e32[0] and err[1] <= R * e32[1], (err, e32)
+    m = TreeLSTM().to(DEV)
+    m.load_state_dict(params)
+    with torch.no_grad():
+        with pytest.raises(TreeLSTMViolation):
+            m(*x, check=True)
+        with pytest.raises(TreeLSTMViolation):
+            m.roots(*x, check=True)
+        assert torch.equal(m(*clean, check=True), h0)

@@ -17,7 +17,9 @@ import torch
 
 def triple_rule_violations(adjacency, node_order, edge_order):
     """trees [B, A] (bool) where a node of height n > 0 does not have its three edges one after another, in node order, inside
-    its own tree -- the condition under which the reference's batch-wide pairing of level nodes and edge triples is per tree"""
+    its own tree -- the condition under which the reference's batch-wide pairing of level nodes and edge triples is per tree;
+    also a node_order outside {-2} u [0, N-1], a real edge (of any order, 0 included) with its parent or child outside the tree,
+    or an edge_order other than the parent's node_order: what include/flatland_hip.h says fl_tree_lstm counts"""
     B, A, N = node_order.shape
     no = node_order.reshape(B * A, N).cpu()
     eo = edge_order.reshape(B * A, N - 1).cpu()
@@ -37,8 +39,10 @@ def triple_rule_violations(adjacency, node_order, edge_order):
                 break
         real = eo[t] != -2
         if not bad[t] and real.any():
-            p = adj[t][real, 0]
+            p, ch = adj[t][real, 0], adj[t][real, 1]
             if ((p < base) | (p >= base + N)).any() or not torch.equal(no[t][p - base], eo[t][real]):
+                bad[t] = True
+            elif ((ch < base) | (ch >= base + N)).any():      # "an index outside itself": on an edge of order 0 as well
                 bad[t] = True
     return bad.view(B, A)
 
