@@ -1,8 +1,8 @@
 // fl_obs.hip -- host side of the observation kernels: scratch allocation, the choice of what a launch keeps in LDS
 // (obs_pick_config; the carving itself is obs_layout_c in fl_obs_layout.h, shared with the kernels), the fixed launch classes
-// and the three launch entry points.  The kernels are in fl_obs_m0 ... m5.hip (one unit per MODE) and fl_obs_f1 ... f4.hip (one
-// per fixed launch class), all instantiating fl_obs_body.h and the phase-level headers it includes (fl_obs_ctx.h,
-// fl_obs_passb.h, fl_obs_trees.h).
+// and the three launch entry points.  The kernels are fl_obs_unit.hip, compiled once per unit of build.sh's list (one unit per
+// runtime-carving MODE, per launch class and per split kernel), each instantiating fl_obs_body.h and the phase-level headers it
+// includes (fl_obs_ctx.h, fl_obs_passb.h, fl_obs_trees.h); obs_launch below names them all.
 #include <algorithm>
 #include <stdio.h>
 #include <stdlib.h>
@@ -199,6 +199,11 @@ static bool exact_split_covers_most(const FlDev &d, ObsArgs &P, const ObsLayout 
     P.L = keep;
     return 2 * n >= d.B;
 }
+// the first class of K... (in this order) that holds the batch becomes P.fix
+template <int... K>
+static bool obs_take_exact(const FlDev &d, ObsArgs &P, const ObsOptions &o, ObsLayout &L) { return ((obs_fits_fixed<K>(d, P, o, L) && (P.fix = K) != 0) || ...); }
+template <int... K>
+static bool obs_take_bin(const FlDev &d, ObsArgs &P, const ObsOptions &o, ObsLayout &L) { return ((obs_fits_bin<K>(d, P, o, L) && (P.fix = K) != 0) || ...); }
 static void obs_take_fixed_class(const FlDev &d, ObsArgs &P, const ObsOptions &o, ObsLayout &L, bool allowed) {
     static const bool no_fix = getenv("FL_OBS_NO_FIX") != nullptr;   // diagnostic: the runtime carving for every batch
     // diagnostic: exact classes only (the launcher of rounds 4 and 5).  A bin class REPLACES the batch's own options, so the switches that shape those options
@@ -211,36 +216,13 @@ static void obs_take_fixed_class(const FlDev &d, ObsArgs &P, const ObsOptions &o
     P.fix = 0; P.split = 0;
     if (no_fix || !allowed) return;
     if (P.tw_t == 0) {   // the flatland_cutils builder alone: classes 6 .. 10 (the counterparts of 1 .. 5)
-        if (obs_fits_fixed<6>(d, P, o, L)) P.fix = 6;
-        else if (obs_fits_fixed<7>(d, P, o, L)) P.fix = 7;
-        else if (obs_fits_fixed<8>(d, P, o, L)) P.fix = 8;
-        else if (obs_fits_fixed<9>(d, P, o, L)) P.fix = 9;
-        else if (obs_fits_fixed<10>(d, P, o, L)) P.fix = 10;
-        else if (obs_fits_fixed<21>(d, P, o, L)) P.fix = 21;
-        else if (no_bins || !P.cutils_alone) return;   // (FL_OBS_NO_CUTILS_MERGE: the stand-alone kernel as it ran before round 6)
-        else if (obs_fits_bin<21>(d, P, o, L)) P.fix = 21;
-        else if (obs_fits_bin<17>(d, P, o, L)) P.fix = 17;
-        else if (obs_fits_bin<8>(d, P, o, L)) P.fix = 8;
-        else if (obs_fits_bin<18>(d, P, o, L)) P.fix = 18;
-        else if (obs_fits_bin<9>(d, P, o, L)) P.fix = 9;
-        else if (obs_fits_bin<19>(d, P, o, L)) P.fix = 19;
-        else if (obs_fits_bin<20>(d, P, o, L)) P.fix = 20;
+        if (obs_take_exact<6, 7, 8, 9, 10, 21>(d, P, o, L) || no_bins || !P.cutils_alone) return;   // (FL_OBS_NO_CUTILS_MERGE: the stand-alone kernel as it ran before round 6)
+        obs_take_bin<21, 17, 8, 18, 9, 19, 20>(d, P, o, L);
         return;
     }
-    if (obs_fits_fixed<1>(d, P, o, L)) P.fix = 1;
-    else if (obs_fits_fixed<2>(d, P, o, L)) P.fix = 2;
-    else if (obs_fits_fixed<3>(d, P, o, L)) P.fix = 3;
-    else if (obs_fits_fixed<4>(d, P, o, L)) P.fix = 4;
-    else if (obs_fits_fixed<5>(d, P, o, L)) P.fix = 5;
-    else if (no_bins) return;
-    else if (exact_split_covers_most<2>(d, P, L) || exact_split_covers_most<3>(d, P, L)) return;   // (obs_take_split_class takes it)
-    else if (obs_fits_bin<11>(d, P, o, L)) P.fix = 11;
-    else if (obs_fits_bin<12>(d, P, o, L)) P.fix = 12;
-    else if (obs_fits_bin<13>(d, P, o, L)) P.fix = 13;
-    else if (obs_fits_bin<15>(d, P, o, L)) P.fix = 15;
-    else if (obs_fits_bin<4>(d, P, o, L)) P.fix = 4;
-    else if (obs_fits_bin<14>(d, P, o, L)) P.fix = 14;
-    else if (obs_fits_bin<16>(d, P, o, L)) P.fix = 16;
+    if (obs_take_exact<1, 2, 3, 4, 5>(d, P, o, L) || no_bins) return;
+    if (exact_split_covers_most<2>(d, P, L) || exact_split_covers_most<3>(d, P, L)) return;   // (obs_take_split_class takes it)
+    obs_take_bin<11, 12, 13, 15, 4, 14, 16>(d, P, o, L);
 }
 
 // (ObsArgs::fix_allowed: this launch's configuration was chosen without the diagnostic overrides that rule the fixed launch classes out)
@@ -485,6 +467,29 @@ static void obs_verbose(const ObsArgs &P) {
 }
 static int obs_var(const ObsArgs &P) { return P.L.tab_lds ? 1 : P.L.wl_bytes == 0 ? 2 : 0; }
 
+// The kernel of a launch: the split kernel of (P.split, P.fix), the kernel of class P.fix, or else the runtime-carving kernel of the launch's
+// MODE; FL_ERR_ARG for a (split, class) pair that has no kernel.  The lists are build.sh's units.
+template <int FIX2, int... K>
+static int obs_launch_class(const FlDev &d, const FlObsScratch &u, const ObsArgs &P, hipStream_t s) {
+    int rc = FL_ERR_ARG;
+    (void)((P.fix == K && (rc = fl_obs_launch_class<K, FIX2>(d, u, P, s), true)) || ...);
+    return rc;
+}
+template <int... M>
+static int obs_launch_mode(int mode, const FlDev &d, const FlObsScratch &u, const ObsArgs &P, hipStream_t s) {
+    int rc = FL_ERR_ARG;
+    (void)((mode == M && (rc = fl_obs_launch_mode<M>(obs_var(P), d, u, P, s), true)) || ...);
+    return rc;
+}
+static int obs_launch(const FlDev &d, const FlObsScratch &u, const ObsArgs &P, hipStream_t s) {
+    if (P.split == 2) return P.fix == 4 ? fl_obs_launch_class<4, 14>(d, u, P, s) : P.fix == 9 ? fl_obs_launch_class<9, 19>(d, u, P, s) : FL_ERR_ARG;
+    if (P.split) return obs_launch_class<0, 2, 3, 4, 9>(d, u, P, s);
+    if (P.fix) return obs_launch_class<-1, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21>(d, u, P, s);
+    // one pass B (P.merged 1 / 2 / 3): MODE 3 / 4 / 5 for both builders, 6 / 7 / 8 for the flatland_cutils builder alone; else the builders of the launch
+    const int mode = P.merged ? (P.tw_t ? 2 : 5) + P.merged : P.tw_c == 0 ? 1 : P.tw_t ? 2 : 0;
+    return obs_launch_mode<0, 1, 2, 3, 4, 5, 6, 7, 8>(mode, d, u, P, s);
+}
+
 // node tables of the upstream builder: compact slots when no direction of a cell of the batch has more than two transitions
 static void obs_tree_args(const FlDev &d, ObsArgs &P, int max_depth, int tree_pred, double *tree_out) {
     P.max_depth = max_depth; P.tree_pred = tree_pred; P.tree_out = tree_out;
@@ -522,23 +527,7 @@ int fl_launch_obs_cutils(FlObsScratch &o, const FlDev &d, int max_nodes, int pre
     FlObsScratch u = o;
     if (P.merged == 1) u.order = nullptr;   // small envs, one round: workgroup k builds env k
     else u = fl_obs_env_order(o, d, s);
-    if (P.split == 2) return P.fix == 9 ? fl_obs_launch_s9b(d, u, P, s) : FL_ERR_ARG;
-    if (P.split) return P.fix == 9 ? fl_obs_launch_s9(d, u, P, s) : FL_ERR_ARG;
-    switch (P.fix) {
-    case 17: return fl_obs_launch_f17(d, u, P, s);
-    case 18: return fl_obs_launch_f18(d, u, P, s);
-    case 19: return fl_obs_launch_f19(d, u, P, s);
-    case 20: return fl_obs_launch_f20(d, u, P, s);
-    case 21: return fl_obs_launch_f21(d, u, P, s);
-    case 6: return fl_obs_launch_f6(d, u, P, s);
-    case 7: return fl_obs_launch_f7(d, u, P, s);
-    case 8: return fl_obs_launch_f8(d, u, P, s);
-    case 9: return fl_obs_launch_f9(d, u, P, s);
-    case 10: return fl_obs_launch_f10(d, u, P, s);
-    default: break;
-    }
-    return P.merged == 1 ? fl_obs_launch_m6(obs_var(P), d, u, P, s) : P.merged == 2 ? fl_obs_launch_m7(obs_var(P), d, u, P, s) :
-           P.merged == 3 ? fl_obs_launch_m8(obs_var(P), d, u, P, s) : fl_obs_launch_m0(obs_var(P), d, u, P, s);
+    return obs_launch(d, u, P, s);
 }
 
 int fl_launch_obs_both(FlObsScratch &o, const FlDev &d, int max_nodes, int pred_depth, float *attr, float *forest,
@@ -568,31 +557,7 @@ int fl_launch_obs_both(FlObsScratch &o, const FlDev &d, int max_nodes, int pred_
     FlObsScratch u = o;
     if (P.merged == 1) u.order = nullptr;   // small envs, one round: workgroup k builds env k
     else u = fl_obs_env_order(o, d, s);
-    if (P.split == 2) return P.fix == 4 ? fl_obs_launch_s4b(d, u, P, s) : FL_ERR_ARG;
-    if (P.split) {   // the class for the envs that fit it, the runtime carving for the others: one kernel, the choice per workgroup
-        switch (P.fix) {
-        case 2: return fl_obs_launch_s2(d, u, P, s);
-        case 3: return fl_obs_launch_s3(d, u, P, s);
-        case 4: return fl_obs_launch_s4(d, u, P, s);
-        default: return FL_ERR_ARG;
-        }
-    }
-    switch (P.fix) {   // a fixed launch class: its own kernel (MODE and VAR are the class's)
-    case 1: return fl_obs_launch_f1(d, u, P, s);
-    case 2: return fl_obs_launch_f2(d, u, P, s);
-    case 3: return fl_obs_launch_f3(d, u, P, s);
-    case 4: return fl_obs_launch_f4(d, u, P, s);
-    case 5: return fl_obs_launch_f5(d, u, P, s);
-    case 11: return fl_obs_launch_f11(d, u, P, s);
-    case 12: return fl_obs_launch_f12(d, u, P, s);
-    case 13: return fl_obs_launch_f13(d, u, P, s);
-    case 14: return fl_obs_launch_f14(d, u, P, s);
-    case 15: return fl_obs_launch_f15(d, u, P, s);
-    case 16: return fl_obs_launch_f16(d, u, P, s);
-    default: break;
-    }
-    return P.merged == 1 ? fl_obs_launch_m3(obs_var(P), d, u, P, s) : P.merged == 2 ? fl_obs_launch_m4(obs_var(P), d, u, P, s) :
-           P.merged == 3 ? fl_obs_launch_m5(obs_var(P), d, u, P, s) : fl_obs_launch_m2(obs_var(P), d, u, P, s);
+    return obs_launch(d, u, P, s);
 }
 
 int fl_launch_obs_tree(FlObsScratch &o, const FlDev &d, int max_depth, int pred_depth, double *out, hipStream_t s, const int16_t *label_dev) {
@@ -615,7 +580,7 @@ int fl_launch_obs_tree(FlObsScratch &o, const FlDev &d, int max_depth, int pred_
     o.last_fix = 0; o.last_split = 0; o.last_fit = 0;
     obs_verbose(P);
     obs_keep_verify(d, P, rowmask, s);
-    return fl_obs_launch_m1(obs_var(P), d, fl_obs_env_order(o, d, s), P, s);
+    return obs_launch(d, fl_obs_env_order(o, d, s), P, s);
 }
 
 // diagnostic: the configuration obs_pick_config chooses for the fused launch (cutils + upstream tree of max_depth):

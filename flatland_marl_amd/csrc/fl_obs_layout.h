@@ -438,45 +438,15 @@ struct ObsArgs {
                        // carving compiled in)
 };
 
-// kernel launchers, one translation unit per MODE (0 = flatland_cutils outputs, 1 = upstream dense tree, 2 / 3 = both in one launch);
-// var: see obs_body (1 = static tables in LDS, 2 = work lists in HBM scratch)
-int fl_obs_launch_m0(int var, const FlDev &d, const FlObsScratch &o, const ObsArgs &P, hipStream_t s);
-int fl_obs_launch_m1(int var, const FlDev &d, const FlObsScratch &o, const ObsArgs &P, hipStream_t s);
-int fl_obs_launch_m2(int var, const FlDev &d, const FlObsScratch &o, const ObsArgs &P, hipStream_t s);
-int fl_obs_launch_m3(int var, const FlDev &d, const FlObsScratch &o, const ObsArgs &P, hipStream_t s);   // both, one pass B, one round
-int fl_obs_launch_m4(int var, const FlDev &d, const FlObsScratch &o, const ObsArgs &P, hipStream_t s);   // both, one pass B per round of 32 agents
-int fl_obs_launch_m5(int var, const FlDev &d, const FlObsScratch &o, const ObsArgs &P, hipStream_t s);   // the same in rounds of 16 agents on 512 threads (two workgroups a CU)
-// the FIXED launch classes (P.fix = k: MODE and VAR are the class's, the LDS carving is compiled in)
-int fl_obs_launch_f1(const FlDev &d, const FlObsScratch &o, const ObsArgs &P, hipStream_t s);
-int fl_obs_launch_f2(const FlDev &d, const FlObsScratch &o, const ObsArgs &P, hipStream_t s);
-int fl_obs_launch_f3(const FlDev &d, const FlObsScratch &o, const ObsArgs &P, hipStream_t s);
-int fl_obs_launch_f4(const FlDev &d, const FlObsScratch &o, const ObsArgs &P, hipStream_t s);
-int fl_obs_launch_f5(const FlDev &d, const FlObsScratch &o, const ObsArgs &P, hipStream_t s);
-// the flatland_cutils builder alone: MODE 6 / 7 / 8 (runtime carving) and its classes 6 .. 10, class 9's split kernel
-int fl_obs_launch_m6(int var, const FlDev &d, const FlObsScratch &o, const ObsArgs &P, hipStream_t s);
-int fl_obs_launch_m7(int var, const FlDev &d, const FlObsScratch &o, const ObsArgs &P, hipStream_t s);
-int fl_obs_launch_m8(int var, const FlDev &d, const FlObsScratch &o, const ObsArgs &P, hipStream_t s);
-int fl_obs_launch_f6(const FlDev &d, const FlObsScratch &o, const ObsArgs &P, hipStream_t s);
-int fl_obs_launch_f7(const FlDev &d, const FlObsScratch &o, const ObsArgs &P, hipStream_t s);
-int fl_obs_launch_f8(const FlDev &d, const FlObsScratch &o, const ObsArgs &P, hipStream_t s);
-int fl_obs_launch_f9(const FlDev &d, const FlObsScratch &o, const ObsArgs &P, hipStream_t s);
-int fl_obs_launch_f10(const FlDev &d, const FlObsScratch &o, const ObsArgs &P, hipStream_t s);
-int fl_obs_launch_s9(const FlDev &d, const FlObsScratch &o, const ObsArgs &P, hipStream_t s);
-// bin classes (round 6) and the large-map split kernels whose second body is the larger bin class (P.split 2) instead of the runtime carving
-int fl_obs_launch_f11(const FlDev &d, const FlObsScratch &o, const ObsArgs &P, hipStream_t s);
-int fl_obs_launch_f12(const FlDev &d, const FlObsScratch &o, const ObsArgs &P, hipStream_t s);
-int fl_obs_launch_f13(const FlDev &d, const FlObsScratch &o, const ObsArgs &P, hipStream_t s);
-int fl_obs_launch_f14(const FlDev &d, const FlObsScratch &o, const ObsArgs &P, hipStream_t s);
-int fl_obs_launch_f15(const FlDev &d, const FlObsScratch &o, const ObsArgs &P, hipStream_t s);
-int fl_obs_launch_f18(const FlDev &d, const FlObsScratch &o, const ObsArgs &P, hipStream_t s);
-int fl_obs_launch_f16(const FlDev &d, const FlObsScratch &o, const ObsArgs &P, hipStream_t s);
-int fl_obs_launch_f20(const FlDev &d, const FlObsScratch &o, const ObsArgs &P, hipStream_t s);
-int fl_obs_launch_f21(const FlDev &d, const FlObsScratch &o, const ObsArgs &P, hipStream_t s);
-int fl_obs_launch_f17(const FlDev &d, const FlObsScratch &o, const ObsArgs &P, hipStream_t s);
-int fl_obs_launch_f19(const FlDev &d, const FlObsScratch &o, const ObsArgs &P, hipStream_t s);
-int fl_obs_launch_s4b(const FlDev &d, const FlObsScratch &o, const ObsArgs &P, hipStream_t s);
-int fl_obs_launch_s9b(const FlDev &d, const FlObsScratch &o, const ObsArgs &P, hipStream_t s);
-// the same classes for a batch with larger maps among its envs (P.split): per env the class's body or the runtime-carving one
-int fl_obs_launch_s2(const FlDev &d, const FlObsScratch &o, const ObsArgs &P, hipStream_t s);
-int fl_obs_launch_s3(const FlDev &d, const FlObsScratch &o, const ObsArgs &P, hipStream_t s);
-int fl_obs_launch_s4(const FlDev &d, const FlObsScratch &o, const ObsArgs &P, hipStream_t s);
+// kernel launchers: fl_obs_unit.hip defines the two templates and every unit of build.sh's list instantiates one of them (unit mk: MODE k;
+// fK: class K; sK / sKb: class K's split kernel), so naming a kernel that the build lacks leaves the library with an undefined symbol.
+// MODE: 0 = flatland_cutils outputs, 1 = upstream dense tree, 2 = both in one launch (two stages), 3 / 4 / 5 = both with one pass B (one
+// round / rounds of 32 agents / rounds of 16 agents on 512 threads, two workgroups a CU), 6 / 7 / 8 = MODE 3 / 4 / 5 with the
+// flatland_cutils builder alone; var: see obs_body (1 = static tables in LDS, 2 = work lists in HBM scratch)
+template <int MODE>
+int fl_obs_launch_mode(int var, const FlDev &d, const FlObsScratch &o, const ObsArgs &P, hipStream_t s);
+// a launch class (P.fix = FIX: MODE and VAR are the class's, the LDS carving is compiled in).  FIX2 >= 0: the class's SPLIT kernel for a batch
+// with larger maps among its envs -- per env the class's body or, when the env does not fit it, the runtime-carving one (FIX2 0, P.split 1)
+// or the larger bin class FIX2's (P.split 2)
+template <int FIX, int FIX2 = -1>
+int fl_obs_launch_class(const FlDev &d, const FlObsScratch &o, const ObsArgs &P, hipStream_t s);

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
-"""Static instruction mix of the kernels of one translation unit (device-only compile with the build's flags, disassembled):
-total / VALU / SALU / LDS / global instructions, v_readlane + v_writelane (= scalar-register spill traffic), registers and
-spills as the compiler reports them.  No GPU needed.
-    tools/kernel_asm_stats.py fl_obs_m3 [fl_obs_m4 ...]      (EXTRA_HIPCC_FLAGS is honoured)"""
+"""Static instruction mix of the kernels of one unit of csrc/build.sh's list (device-only compile with what `build.sh --compile-args UNIT`
+prints: the build's flags, the unit's defines and its source; disassembled): total / VALU / SALU / LDS / global instructions,
+v_readlane + v_writelane (= scalar-register spill traffic), registers and spills as the compiler reports them.  No GPU needed.
+    tools/kernel_asm_stats.py fl_obs_m3 [fl_obs_f6 fl_obs_s4b ...]      (EXTRA_HIPCC_FLAGS and FL_LSR_FLAGS are honoured)"""
 import collections
 import os
 import re
@@ -11,16 +11,14 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LLVM = "/opt/rocm/lib/llvm/bin"
-FLAGS = ["--offload-arch=gfx950", "--cuda-device-only", "-O3", "-std=c++17", "-ffp-contract=off", "-mllvm", "-disable-machine-licm",
-         "-mllvm", "-disable-lsr", "-mllvm", "-amdgpu-atomic-optimizer-strategy=None", "-Wno-unused-result"]
+BUILD = os.path.join(ROOT, "flatland_marl_amd", "csrc", "build.sh")
 
 
 def stats(unit, outdir="/tmp/asm"):
     os.makedirs(outdir, exist_ok=True)
     obj, elf = os.path.join(outdir, unit + ".o"), os.path.join(outdir, unit + ".elf")
-    extra = os.environ.get("EXTRA_HIPCC_FLAGS", "").split()
-    r = subprocess.run(["/opt/rocm/bin/hipcc"] + FLAGS + extra + ["-Rpass-analysis=kernel-resource-usage", "-c",
-                        os.path.join(ROOT, "flatland_marl_amd", "csrc", unit + ".hip"), "-o", obj], capture_output=True, text=True)
+    args = subprocess.check_output([BUILD, "--compile-args", unit], text=True).split()
+    r = subprocess.run(["/opt/rocm/bin/hipcc", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage"] + args + ["-c", "-o", obj], capture_output=True, text=True)
     if r.returncode:
         sys.exit(r.stderr[-3000:])
     res, cur = {}, None
