@@ -65,8 +65,16 @@ struct fl_batch {
     std::vector<int> h_tab;
     std::vector<uint8_t> h_need;
     FlObsScratch obs;
+    int last_obs_launch[FL_OBS_LAUNCH_WORDS];   // diagnostic: what the handle's last observation launch ran (fl_debug_last_obs_launch)
     int n_cu;   // compute units of the device (fl_obs_global's launch shape), 0 = not queried yet
 };
+
+// every observation launch of a handle goes through here: the handle keeps the record of what was launched (MODE -1: nothing was)
+static int obs_launched(fl_batch *h, int rc) {
+    fl_obs_last_launch(h->last_obs_launch);
+    if (rc != FL_OK) { memset(h->last_obs_launch, 0, sizeof h->last_obs_launch); h->last_obs_launch[0] = -1; }
+    return rc;
+}
 
 template <typename T>
 static int dev_alloc(fl_batch *h, T **p, size_t n) {
@@ -123,6 +131,7 @@ int fl_create(int B, int A, int H, int W, int device, fl_batch **out) {
     h->h_key.assign(B, 0); h->h_built.assign(B, 0); h->h_tab.assign(B, 0); h->h_need.assign(B, 0);
     h->need_dev = nullptr;
     memset(&h->obs, 0, sizeof h->obs);
+    h->last_obs_launch[0] = -1;   // (no observation launch yet)
     *out = h;
     return FL_OK;
 }
@@ -588,11 +597,11 @@ int fl_step_obs(fl_batch *h, const uint8_t *actions_dev, uint32_t seed, uint32_t
     HIPCHK(hipGetLastError());
     if (tree_max_depth > 3 || (tree_max_depth > 0 && max_nodes > 32)) return fl_obs_cutils_tree(h, max_nodes, pred_depth, attr_dev, forest_dev, adjacency_dev, node_order_dev, edge_order_dev,
                                                       valid_actions_dev, props_dev, tree_max_depth, tree_pred_depth, tree_out_dev);
-    const int rc = tree_max_depth > 0 ? fl_launch_obs_both(h->obs, h->d, max_nodes, pred_depth, attr_dev, forest_dev, adjacency_dev, node_order_dev,
+    const int rc = tree_max_depth > 0 ? obs_launched(h, fl_launch_obs_both(h->obs, h->d, max_nodes, pred_depth, attr_dev, forest_dev, adjacency_dev, node_order_dev,
                                                            edge_order_dev, valid_actions_dev, props_dev, tree_max_depth, tree_pred_depth,
-                                                           tree_out_dev, h->stream)
-                                      : fl_launch_obs_cutils(h->obs, h->d, max_nodes, pred_depth, attr_dev, forest_dev, adjacency_dev, node_order_dev,
-                                                             edge_order_dev, valid_actions_dev, props_dev, h->stream);
+                                                           tree_out_dev, h->stream))
+                                      : obs_launched(h, fl_launch_obs_cutils(h->obs, h->d, max_nodes, pred_depth, attr_dev, forest_dev, adjacency_dev, node_order_dev,
+                                                             edge_order_dev, valid_actions_dev, props_dev, h->stream));
     if (rc != FL_OK) { set_err("fl_step_obs: no launch configuration: %d rail cells and %d agents per env do not fit the observation kernels' LDS (160 KiB a workgroup), or the sizes are out of range", h->d.Rcap, h->d.A); return rc; }
     HIPCHK(hipGetLastError());
     return FL_OK;
@@ -937,8 +946,8 @@ int fl_obs_cutils(fl_batch *h, int max_nodes, int pred_depth, float *attr_dev, f
         set_err("fl_obs_cutils: null output buffer");
         return FL_ERR_ARG;
     }
-    int rc = fl_launch_obs_cutils(h->obs, h->d, max_nodes, pred_depth, attr_dev, forest_dev, adjacency_dev, node_order_dev,
-                                  edge_order_dev, valid_actions_dev, props_dev, h->stream);
+    int rc = obs_launched(h, fl_launch_obs_cutils(h->obs, h->d, max_nodes, pred_depth, attr_dev, forest_dev, adjacency_dev, node_order_dev,
+                                  edge_order_dev, valid_actions_dev, props_dev, h->stream));
     if (rc != FL_OK) { set_err("fl_obs_cutils: no launch configuration: %d rail cells and %d agents per env do not fit the observation kernels' LDS (160 KiB a workgroup), or the sizes are out of range", h->d.Rcap, h->d.A); return rc; }
     HIPCHK(hipGetLastError());
     return FL_OK;
@@ -955,9 +964,9 @@ int fl_obs_cutils_policy(fl_batch *h, int max_nodes, int pred_depth, float *attr
         set_err("fl_obs_cutils_policy: null output buffer");
         return FL_ERR_ARG;
     }
-    int rc = fl_launch_obs_cutils(h->obs, h->d, max_nodes, pred_depth, attr_dev, forest_dev, reinterpret_cast<int32_t *>(adjacency_dev),
+    int rc = obs_launched(h, fl_launch_obs_cutils(h->obs, h->d, max_nodes, pred_depth, attr_dev, forest_dev, reinterpret_cast<int32_t *>(adjacency_dev),
                                   reinterpret_cast<int32_t *>(node_order_dev), reinterpret_cast<int32_t *>(edge_order_dev), valid_actions_dev, props_dev,
-                                  h->stream, nullptr, 1);
+                                  h->stream, nullptr, 1));
     if (rc != FL_OK) { set_err("fl_obs_cutils_policy: no launch configuration: %d rail cells and %d agents per env do not fit the observation kernels' LDS (160 KiB a workgroup), or the sizes are out of range", h->d.Rcap, h->d.A); return rc; }
     HIPCHK(hipGetLastError());
     return FL_OK;
@@ -995,8 +1004,8 @@ int fl_obs_cutils_handles(fl_batch *h, int max_nodes, int pred_depth, const int3
     }
     HIPCHK(hipMemcpyAsync(h->obs.label, label.data(), (size_t)A * sizeof(int16_t), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));      // (the staging vector is a local)
-    int rc = fl_launch_obs_cutils(h->obs, h->d, max_nodes, pred_depth, attr_dev, forest_dev, adjacency_dev, node_order_dev,
-                                  edge_order_dev, valid_actions_dev, props_dev, h->stream, h->obs.label);
+    int rc = obs_launched(h, fl_launch_obs_cutils(h->obs, h->d, max_nodes, pred_depth, attr_dev, forest_dev, adjacency_dev, node_order_dev,
+                                  edge_order_dev, valid_actions_dev, props_dev, h->stream, h->obs.label));
     if (rc != FL_OK) { set_err("fl_obs_cutils_handles: no launch configuration"); return rc; }
     HIPCHK(hipGetLastError());
     return FL_OK;
@@ -1024,8 +1033,8 @@ int fl_obs_cutils_tree(fl_batch *h, int max_nodes, int pred_depth, float *attr_d
         int rc2 = fl_obs_cutils(h, max_nodes, pred_depth, attr_dev, forest_dev, adjacency_dev, node_order_dev, edge_order_dev, valid_actions_dev, props_dev);
         return rc2 != FL_OK ? rc2 : fl_obs_tree(h, tree_max_depth, tree_pred_depth, tree_out_dev);
     }
-    int rc = fl_launch_obs_both(h->obs, h->d, max_nodes, pred_depth, attr_dev, forest_dev, adjacency_dev, node_order_dev,
-                                edge_order_dev, valid_actions_dev, props_dev, tree_max_depth, tree_pred_depth, tree_out_dev, h->stream);
+    int rc = obs_launched(h, fl_launch_obs_both(h->obs, h->d, max_nodes, pred_depth, attr_dev, forest_dev, adjacency_dev, node_order_dev,
+                                edge_order_dev, valid_actions_dev, props_dev, tree_max_depth, tree_pred_depth, tree_out_dev, h->stream));
     if (rc != FL_OK) { set_err("fl_obs_cutils_tree: no launch configuration: %d rail cells and %d agents per env do not fit the observation kernels' LDS (160 KiB a workgroup), or the sizes are out of range", h->d.Rcap, h->d.A); return rc; }
     HIPCHK(hipGetLastError());
     return FL_OK;
@@ -1067,7 +1076,7 @@ int fl_obs_tree(fl_batch *h, int max_depth, int pred_depth, double *out_dev) {
         set_err("fl_obs_tree: max_depth 4 needs a grid on which no direction of a cell has more than two transitions (every Flatland rail cell type); this batch has %d", h->d.max_branch);
         return FL_ERR_ARG;
     }
-    int rc = fl_launch_obs_tree(h->obs, h->d, max_depth, pred_depth, out_dev, h->stream);
+    int rc = obs_launched(h, fl_launch_obs_tree(h->obs, h->d, max_depth, pred_depth, out_dev, h->stream));
     if (rc != FL_OK) { set_err("fl_obs_tree: no launch configuration: %d rail cells and %d agents per env do not fit the observation kernels' LDS (160 KiB a workgroup), or the sizes are out of range", h->d.Rcap, h->d.A); return rc; }
     HIPCHK(hipGetLastError());
     return FL_OK;
@@ -1103,7 +1112,7 @@ int fl_obs_tree_handles(fl_batch *h, int max_depth, int pred_depth, const int32_
     }
     HIPCHK(hipMemcpyAsync(h->obs.label, label.data(), (size_t)A * sizeof(int16_t), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));      // (the staging vector is a local)
-    int rc = fl_launch_obs_tree(h->obs, h->d, max_depth, pred_depth, out_dev, h->stream, h->obs.label);
+    int rc = obs_launched(h, fl_launch_obs_tree(h->obs, h->d, max_depth, pred_depth, out_dev, h->stream, h->obs.label));
     if (rc != FL_OK) { set_err("fl_obs_tree_handles: no launch configuration"); return rc; }
     HIPCHK(hipGetLastError());
     return FL_OK;
@@ -1133,6 +1142,15 @@ extern "C" int fl_debug_batch_is_wide(int B, int n_cu) { return obs_batch_is_wid
 extern "C" int fl_debug_last_obs_class(fl_batch *h, int *out3) {
     if (!h || !out3) return FL_ERR_ARG;
     out3[0] = h->obs.last_fix; out3[1] = h->obs.last_split; out3[2] = h->obs.last_fit;
+    return FL_OK;
+}
+
+// diagnostic (not part of the public header): what the handle's last observation launch ran, through any of fl_obs_cutils*, fl_obs_tree*, fl_obs_cutils_tree and
+// fl_step_obs -- FL_OBS_LAUNCH_WORDS ints as fl_obs.h lists them (kernel MODE / VAR / class / split, threads, LDS bytes, the accepted options, what the launcher
+// derived from them); MODE -1: no launch yet, or the last call found no configuration
+extern "C" int fl_debug_last_obs_launch(fl_batch *h, int *out, int n_out) {
+    if (!h || !out || n_out < FL_OBS_LAUNCH_WORDS) return FL_ERR_ARG;
+    memcpy(out, h->last_obs_launch, sizeof h->last_obs_launch);
     return FL_OK;
 }
 

@@ -51,3 +51,9 @@ int fl_launch_obs_tree(FlObsScratch &o, const FlDev &d, int max_depth, int pred_
 // more envs than CUs: the order in which the workgroups take the envs (longest previous launch first); returns the scratch the launch uses
 FlObsScratch fl_obs_env_order(FlObsScratch &o, const FlDev &d, hipStream_t s);
 int fl_obs_config_of_fused(const FlDev &d, int pred_depth, int max_depth, int tree_pred, int out[11], int wide = 0);  // diagnostic (wide: several envs per CU)
+// diagnostic: what the last observation launch made by the calling thread ran (obs_launch of fl_obs.hip fills it from the ObsArgs it launches):
+//   [0] MODE  [1] VAR  [2] launch class (0: runtime carving)  [3] split kind  [4] second class of a split-2 kernel  [5] threads  [6] dynamic LDS bytes
+//   [7..20] the ObsOptions the preference walk accepted: wl_bytes, tab, nh, tmask, dual, items, items_cap, snext, partial, bk_room, own_filter, fb, raw, wl_head
+//   [21] ObsArgs::bk  [22] tshift  [23] compact_t  [24] 1 = a handle subset (label set)
+#define FL_OBS_LAUNCH_WORDS 25
+void fl_obs_last_launch(int out[FL_OBS_LAUNCH_WORDS]);

@@ -380,7 +380,9 @@ static bool obs_pick_config(const FlDev &d, ObsArgs &P) {
             // 0.268 ms with the LDS lists against 0.261 with HBM lists behind a 16 KB LDS head.  Small maps (cfg3) keep the LDS lists.
             if (!up && P.merged == 2 && prefs[pk].wl >= 36 * 1024 && d.Rcap > OBS_ALONE_LDS_LISTS_RCAP) continue;
             o.fb = prefs[pk].fb && P.pred_depth + 1 > 64; o.wl_bytes = prefs[pk].wl; o.items = prefs[pk].items;
-            o.tab = force.tab == 1 && o.wl_bytes && nh_fit;   // diagnostic: the env's static tables in LDS too
+            // diagnostic: the env's static tables in LDS too -- but never for both builders in rounds of 16 agents (MODE 5 has no VAR 1 kernel:
+            // fl_obs_unit.hip), where FL_OBS_FORCE=tab=1 leaves the tables in HBM / L2
+            o.tab = force.tab == 1 && o.wl_bytes && nh_fit && !(P.merged == 3 && up);
             if ((o.fb && no_fb) || !ok(force.wl, o.wl_bytes) || !ok(force.items, o.items) || (o.items && d.A * 32 > OBS_ITEMS_LDS_CAP)) continue;
             // the own-path filter of the classify loop (a second set of time masks) before the full-size LDS copy of the items: on
             // sparse maps a third of the conflict entries are the walking agent's own prediction (cfg4: 34 %), and an env whose
@@ -439,6 +441,7 @@ static bool obs_pick_config(const FlDev &d, ObsArgs &P) {
                                 else if (force.tab == 1) continue;
                             } else if (force.tab == 1) continue;
                             g_last_options = o;
+                            g_last_options.tab = L.tab_lds;   // (the tables joined the carving above)
                             P.use_tmask = o.tmask; P.dual_index = o.dual;
                             P.bk = o.bk_room; P.bk_nb = OBS_BK_NB; P.bk_shift = OBS_BK_SHIFT;
                             // 2-step buckets where the traffic is and one catch-all bucket for late times (8-step buckets over the
@@ -481,12 +484,29 @@ static int obs_launch_mode(int mode, const FlDev &d, const FlObsScratch &u, cons
     (void)((mode == M && (rc = fl_obs_launch_mode<M>(obs_var(P), d, u, P, s), true)) || ...);
     return rc;
 }
+// diagnostic: what the last observation launch of this thread ran (fl_obs_last_launch; fl_host.hip keeps a copy per handle).  Filled here, from the
+// ObsArgs that are launched and the options the preference walk accepted for them -- host side only, no kernel argument carries it.
+static thread_local int g_last_launch[FL_OBS_LAUNCH_WORDS];
+template <int... K>
+static void obs_class_kernel(int fix, int &mode, int &var) { (void)((fix == K && (mode = obs_fixed_mode<K>(), var = obs_fixed_var<K>(), true)) || ...); }
+static void obs_record_launch(const ObsArgs &P, int mode) {
+    int var = obs_var(P);
+    if (P.fix) obs_class_kernel<1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21>(P.fix, mode, var);
+    const ObsOptions &q = g_last_options;
+    const int rec[FL_OBS_LAUNCH_WORDS] = {mode, var, P.fix, P.split, P.split == 2 ? (P.fix == 4 ? 14 : 19) : 0, P.L.nt, (int)P.L.total,
+                                          q.wl_bytes, q.tab, q.nh, q.tmask, q.dual, q.items, q.items_cap, q.snext, q.partial, q.bk_room, q.own_filter, q.fb, q.raw, q.wl_head,
+                                          P.bk, P.tshift, P.compact_t, P.label != nullptr};
+    memcpy(g_last_launch, rec, sizeof rec);
+}
+void fl_obs_last_launch(int out[FL_OBS_LAUNCH_WORDS]) { memcpy(out, g_last_launch, sizeof g_last_launch); }
+
 static int obs_launch(const FlDev &d, const FlObsScratch &u, const ObsArgs &P, hipStream_t s) {
+    // one pass B (P.merged 1 / 2 / 3): MODE 3 / 4 / 5 for both builders, 6 / 7 / 8 for the flatland_cutils builder alone; else the builders of the launch
+    const int mode = P.merged ? (P.tw_t ? 2 : 5) + P.merged : P.tw_c == 0 ? 1 : P.tw_t ? 2 : 0;
+    obs_record_launch(P, mode);
     if (P.split == 2) return P.fix == 4 ? fl_obs_launch_class<4, 14>(d, u, P, s) : P.fix == 9 ? fl_obs_launch_class<9, 19>(d, u, P, s) : FL_ERR_ARG;
     if (P.split) return obs_launch_class<0, 2, 3, 4, 9>(d, u, P, s);
     if (P.fix) return obs_launch_class<-1, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21>(d, u, P, s);
-    // one pass B (P.merged 1 / 2 / 3): MODE 3 / 4 / 5 for both builders, 6 / 7 / 8 for the flatland_cutils builder alone; else the builders of the launch
-    const int mode = P.merged ? (P.tw_t ? 2 : 5) + P.merged : P.tw_c == 0 ? 1 : P.tw_t ? 2 : 0;
     return obs_launch_mode<0, 1, 2, 3, 4, 5, 6, 7, 8>(mode, d, u, P, s);
 }
 
@@ -597,6 +617,7 @@ int fl_obs_config_of_fused(const FlDev &d, int pred_depth, int max_depth, int tr
         P.cutils_alone = getenv("FL_OBS_NO_CUTILS_MERGE") == nullptr;
     }
     if (!obs_pick_config(d, P)) return FL_ERR_ARG;
+    if (max_depth <= 0 && !P.merged && !P.fix) P.compact_t = 0;    // (as fl_launch_obs_cutils: the stand-alone kernel's own pass A)
     if (getenv("FL_OBS_VERBOSE")) {   // diagnostic: the carving of the LDS, array by array (enum L_* of fl_obs_layout.h)
         const ObsOptions &q = g_last_options;
         fprintf(stderr, "  options {nt %d, wl_bytes %d, tab %d, nh %d, tmask %d, dual %d, items %d, snext %d, partial %d, bk_room %d, own_filter %d, fb %d, raw %d, items_cap %d, wl_head %d}; "

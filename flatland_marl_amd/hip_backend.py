@@ -110,6 +110,8 @@ def lib():
         L.fl_positions_map.argtypes = [vp, i32, vp]
         if hasattr(L, "fl_debug_last_obs_class"):
             L.fl_debug_last_obs_class.argtypes = [vp, vp]       # diagnostic, not part of the public header
+        if hasattr(L, "fl_debug_last_obs_launch"):
+            L.fl_debug_last_obs_launch.argtypes = [vp, vp, i32]  # diagnostic, not part of the public header
         L.fl_algorithmic_bytes_per_agent_step.argtypes = [vp, i32, i32]
         L.fl_algorithmic_bytes_per_agent_step.restype = C.c_double
         _lib = L
@@ -577,6 +579,20 @@ class BatchedRailEnv:
         out = (C.c_int * 3)()
         _chk(lib().fl_debug_last_obs_class(self.h, out))
         return tuple(out)
+
+    LAUNCH_FIELDS = ("mode", "var", "fix", "split", "fix2", "nt", "lds", "wl_bytes", "tab", "nh", "tmask", "dual", "items", "items_cap", "snext",
+                     "partial", "bk_room", "own_filter", "fb", "raw", "wl_head", "bk", "tshift", "compact_t", "label")
+
+    def last_obs_launch(self):
+        """diagnostic: what the last observation launch of this handle ran, through any of obs_cutils / obs_policy / obs_both / obs_tree / step_obs
+        -- a dict of LAUNCH_FIELDS: the kernel (k_obs<mode, var> of launch class `fix`, 0 = the runtime carving; split 1 / 2 = the class's split
+        kernel, fix2 the second class of a split-2 kernel), threads and dynamic LDS bytes of the launch, the ObsOptions the launcher's preference
+        walk accepted (wl_bytes .. wl_head) and what it derived from them (bk, tshift, compact_t; label = a handle subset).  mode -1: no launch yet."""
+        if not hasattr(lib(), "fl_debug_last_obs_launch"):
+            raise FlatlandHipError(1, "the loaded library has no fl_debug_last_obs_launch (an older build loaded through --lib?)")
+        out = (C.c_int * len(self.LAUNCH_FIELDS))()
+        _chk(lib().fl_debug_last_obs_launch(self.h, out, len(out)))
+        return dict(zip(self.LAUNCH_FIELDS, out))
 
     def algorithmic_bytes_per_agent_step(self, with_cutils_obs=True, tree_depth=0):
         return float(lib().fl_algorithmic_bytes_per_agent_step(self.h, int(with_cutils_obs), int(tree_depth)))
