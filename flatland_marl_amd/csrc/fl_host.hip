@@ -65,24 +65,12 @@ struct fl_batch {
     std::vector<int> h_tab;
     std::vector<uint8_t> h_need;
     FlObsScratch obs;
-    int last_obs_launch[FL_OBS_LAUNCH_WORDS];   // diagnostic: what the handle's last observation launch ran (fl_debug_last_obs_launch)
-    int n_cu;   // compute units of the device (fl_obs_global's launch shape), 0 = not queried yet
+    int last_obs_launch[FL_OBS_LAUNCH_WORDS];   // diagnostic: what the handle's last observation launch ran, written by the fl_launch_obs_* it calls (fl_debug_last_obs_launch)
 };
-
-// every observation launch of a handle goes through here: the handle keeps the record of what was launched (MODE -1: nothing was)
-static int obs_launched(fl_batch *h, int rc) {
-    fl_obs_last_launch(h->last_obs_launch);
-    if (rc != FL_OK) { memset(h->last_obs_launch, 0, sizeof h->last_obs_launch); h->last_obs_launch[0] = -1; }
-    return rc;
-}
 
 template <typename T>
 static int dev_alloc(fl_batch *h, T **p, size_t n) {
-    void *q = nullptr;
-    HIPCHK(hipMalloc(&q, n * sizeof(T) + 16));
-    HIPCHK(hipMemsetAsync(q, 0, n * sizeof(T) + 16, h->stream));
-    h->allocs.push_back(q);
-    *p = (T *)q;
+    HIPCHK(fl_alloc_zeroed(p, n, h->stream, h->allocs));
     return FL_OK;
 }
 #define DALLOC(ptr, n)                                   \
@@ -407,6 +395,21 @@ static int share_tables(fl_batch *h) {
     return FL_OK;
 }
 
+// the chain of table kernels for the envs of mask_dev (u8[B]; through_tab: the OWNERS of the masked envs' tables, fl_launch_env_list)
+static int launch_table_kernels(fl_batch *h, const uint8_t *mask_dev, bool through_tab) {
+    fl_launch_env_list(h->d, mask_dev, h->stream, through_tab);
+    HIPCHK(hipGetLastError());
+    fl_launch_distance_maps(h->d, mask_dev, h->stream);
+    HIPCHK(hipGetLastError());
+    fl_launch_segments(h->d, mask_dev, h->stream);
+    HIPCHK(hipGetLastError());
+    fl_launch_nexthop(h->d, mask_dev, h->stream);
+    HIPCHK(hipGetLastError());
+    fl_launch_hop8(h->d, mask_dev, h->stream);
+    HIPCHK(hipGetLastError());
+    return FL_OK;
+}
+
 int fl_commit(fl_batch *h) {
     if (!h) return FL_ERR_ARG;
     for (int b = 0; b < h->B; b++)
@@ -491,15 +494,10 @@ int fl_commit(fl_batch *h) {
         int rc_t = share_tables(h);
         if (rc_t != FL_OK) return rc_t;
     }
-    fl_launch_env_list(d, h->need_dev, h->stream);
-    fl_launch_distance_maps(d, h->need_dev, h->stream);
-    HIPCHK(hipGetLastError());
-    fl_launch_segments(d, h->need_dev, h->stream);
-    HIPCHK(hipGetLastError());
-    fl_launch_nexthop(d, h->need_dev, h->stream);
-    HIPCHK(hipGetLastError());
-    fl_launch_hop8(d, h->need_dev, h->stream);
-    HIPCHK(hipGetLastError());
+    {
+        int rc_k = launch_table_kernels(h, h->need_dev, false);
+        if (rc_k != FL_OK) return rc_k;
+    }
     fl_launch_reset(d, mask, 1, h->stream);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -569,42 +567,109 @@ int fl_step_synth(fl_batch *h, uint32_t seed, uint32_t stream_base, int kind, in
     return FL_OK;
 }
 
+// ---- the observation entry points (fl_step_obs, fl_obs_cutils, fl_obs_cutils_policy, fl_obs_cutils_handles, fl_obs_cutils_tree, fl_obs_tree,
+// fl_obs_tree_handles) share one host path: obs_check_request, obs_handle_list for a handle list, then one of the obs_run_* below.  `who` is
+// the entry point's name, the prefix of every message.
+struct ObsTreeRequest {
+    int min_depth, max_depth, pred_depth;
+    double *out;
+    bool compact_switch;   // refuse depth 4 under FL_OBS_NO_COMPACT here (the call launches something else before fl_launch_obs_tree would refuse it)
+};
+// Every argument check of an observation request, in the order all entry points have them: sizes, then pointers, then the depth-4 condition.
+// c: the flatland_cutils part (with max_nodes and pred_depth; null: none), t: the upstream tree's (null: none; depth 0 where min_depth allows
+// it: no tree in this call).  With both parts the tree's predicted path has to be a prefix of the cutils one.
+static int obs_check_request(const fl_batch *h, const char *who, const FlObsCutilsOut *c, int max_nodes, int pred_depth, const ObsTreeRequest *t) {
+    if (c && (max_nodes < 4 || max_nodes > FL_OBS_MAX_NODES || pred_depth < 1 || pred_depth > FL_OBS_MAX_PRED)) {
+        set_err("%s: max_nodes must be in [4,%d] and pred_depth in [1,%d]", who, FL_OBS_MAX_NODES, FL_OBS_MAX_PRED);
+        return FL_ERR_ARG;
+    }
+    const bool tree = t && t->max_depth != 0;
+    if (t) {
+        const bool pred_ok = !tree || (c ? t->pred_depth >= 0 && t->pred_depth <= pred_depth : t->pred_depth <= FL_OBS_MAX_PRED);
+        if (t->max_depth < t->min_depth || t->max_depth > FL_MAX_TREE_DEPTH || !pred_ok) {
+            if (c) set_err("%s: max_depth must be in [%d,%d] and 0 <= tree_pred_depth <= pred_depth", who, t->min_depth, FL_MAX_TREE_DEPTH);
+            else set_err("%s: max_depth must be in [%d,%d], pred_depth <= %d", who, t->min_depth, FL_MAX_TREE_DEPTH, FL_OBS_MAX_PRED);
+            return FL_ERR_ARG;
+        }
+    }
+    if ((c && (!c->attr || !c->forest || !c->adjacency || !c->node_order || !c->edge_order || !c->valid)) || (tree && !t->out)) {   // (props may be null)
+        set_err("%s: null output buffer", who);
+        return FL_ERR_ARG;
+    }
+    // every argument error is raised BEFORE anything is launched: a depth-4 tree needs compact node tables (fl_launch_obs_tree's own check, which in
+    // a call with a step or a cutils launch would fire after the envs have advanced a step and the cutils launch has set its sticky deadlock bits)
+    if (tree && t->max_depth > 3 && (h->d.max_branch > 2 || (t->compact_switch && fl_obs_no_compact()))) {
+        set_err("%s: max_depth 4 needs a grid on which no direction of a cell has more than two transitions (every Flatland rail cell type)%s; this batch has %d "
+                "(nothing was launched: the envs have not advanced)", who, t->compact_switch ? " and the compact node tables" : "", h->d.max_branch);
+        return FL_ERR_ARG;
+    }
+    return FL_OK;
+}
+
+// get_many(handles): the list has to be a permutation of 0 .. n_handles-1 (`reference`: what the reference builder does with any other list).
+// *label_dev: the agents' list positions, staged on the device for the launch (FlObsScratch::label) -- null when the list is every agent in
+// order, or when the call does not `use_list` (no predictor: no conflict test), which is the launch without a list.
+static int obs_handle_list(fl_batch *h, const char *who, const int32_t *handles, int n_handles, const char *reference, bool use_list, const int16_t **label_dev) {
+    const int A = h->A;
+    *label_dev = nullptr;
+    if (!handles || n_handles < 1 || n_handles > A) { set_err("%s: 1 <= n_handles <= %d agents", who, A); return FL_ERR_ARG; }
+    std::vector<int16_t> label(A, (int16_t)-1);
+    bool identity = n_handles == A;
+    for (int j = 0; j < n_handles; j++) {
+        const int a = handles[j];
+        if (a < 0 || a >= n_handles || label[a] >= 0) {
+            set_err("%s: handles has to be a permutation of 0 .. %d (handle %d at position %d): %s", who, n_handles - 1, a, j, reference);
+            return FL_ERR_ARG;
+        }
+        label[a] = (int16_t)j;
+        identity = identity && a == j;
+    }
+    if (identity || !use_list) return FL_OK;
+    HIPCHK(hipMemcpyAsync(h->obs.label, label.data(), (size_t)A * sizeof(int16_t), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));      // (the staging vector is a local)
+    *label_dev = h->obs.label;
+    return FL_OK;
+}
+
+// the tail of every observation launch: rc is what the fl_launch_obs_* returned (it has written the handle's record, MODE -1 when nothing ran)
+static int obs_launched(fl_batch *h, const char *who, int rc) {
+    if (rc != FL_OK) {
+        set_err("%s: no launch configuration: %d rail cells and %d agents per env do not fit the observation kernels' LDS (160 KiB a workgroup), or the sizes are out of range", who, h->d.Rcap, h->d.A);
+        return rc;
+    }
+    HIPCHK(hipGetLastError());
+    return FL_OK;
+}
+// the launches of a checked request
+static int obs_run_cutils(fl_batch *h, const char *who, int max_nodes, int pred_depth, const FlObsCutilsOut &out, const int16_t *label_dev = nullptr, int out64 = 0) {
+    return obs_launched(h, who, fl_launch_obs_cutils(h->obs, h->d, max_nodes, pred_depth, out, h->stream, h->last_obs_launch, label_dev, out64));
+}
+static int obs_run_tree(fl_batch *h, const char *who, const ObsTreeRequest &t, const int16_t *label_dev = nullptr) {
+    return obs_launched(h, who, fl_launch_obs_tree(h->obs, h->d, t.max_depth, t.pred_depth, t.out, h->stream, h->last_obs_launch, label_dev));
+}
+static int obs_run_both(fl_batch *h, const char *who, int max_nodes, int pred_depth, const FlObsCutilsOut &out, const ObsTreeRequest &t) {
+    if (t.max_depth > 3 || max_nodes > 32) {   // beyond the fused kernels' node tables: the two builders one after the other (same outputs)
+        const int rc = obs_run_cutils(h, who, max_nodes, pred_depth, out);
+        return rc != FL_OK ? rc : obs_run_tree(h, who, t);
+    }
+    return obs_launched(h, who, fl_launch_obs_both(h->obs, h->d, max_nodes, pred_depth, out, t.max_depth, t.pred_depth, t.out, h->stream, h->last_obs_launch));
+}
+
 int fl_step_obs(fl_batch *h, const uint8_t *actions_dev, uint32_t seed, uint32_t stream_base, int kind, int32_t *rewards_dev,
                 uint8_t *dones_dev, uint8_t *done_all_dev, int flags, int max_nodes, int pred_depth, float *attr_dev,
                 float *forest_dev, int32_t *adjacency_dev, int32_t *node_order_dev, int32_t *edge_order_dev,
                 uint8_t *valid_actions_dev, double *props_dev, int tree_max_depth, int tree_pred_depth, double *tree_out_dev) {
     NEED_COMMIT(h);
     if (!rewards_dev || !dones_dev || !done_all_dev || kind < 0 || kind > 2) { set_err("fl_step_obs: bad step argument"); return FL_ERR_ARG; }
-    if (max_nodes < 4 || max_nodes > FL_OBS_MAX_NODES || pred_depth < 1 || pred_depth > FL_OBS_MAX_PRED || tree_max_depth < 0 ||
-        tree_max_depth > FL_MAX_TREE_DEPTH || (tree_max_depth > 0 && (tree_pred_depth < 0 || tree_pred_depth > pred_depth || !tree_out_dev))) {
-        set_err("fl_step_obs: max_nodes in [4,%d], pred_depth in [1,%d], tree depth in [0,%d], 0 <= tree_pred_depth <= pred_depth",
-                FL_OBS_MAX_NODES, FL_OBS_MAX_PRED, FL_MAX_TREE_DEPTH);
-        return FL_ERR_ARG;
-    }
-    if (!attr_dev || !forest_dev || !adjacency_dev || !node_order_dev || !edge_order_dev || !valid_actions_dev) {
-        set_err("fl_step_obs: null output buffer");
-        return FL_ERR_ARG;
-    }
-    // every argument error is raised BEFORE anything is launched: a depth-4 tree needs compact node tables (fl_obs_tree's own check,
-    // which would otherwise fire after the envs have advanced a step and the cutils launch has set its sticky deadlock bits)
-    if (tree_max_depth > 3 && (h->d.max_branch > 2 || getenv("FL_OBS_NO_COMPACT") != nullptr)) {
-        set_err("fl_step_obs: max_depth 4 needs a grid on which no direction of a cell has more than two transitions (every Flatland rail cell type) and the compact node tables; this batch has %d (nothing was launched: the envs have not advanced)", h->d.max_branch);
-        return FL_ERR_ARG;
-    }
+    const FlObsCutilsOut out = {attr_dev, forest_dev, adjacency_dev, node_order_dev, edge_order_dev, valid_actions_dev, props_dev};
+    const ObsTreeRequest tree = {0, tree_max_depth, tree_pred_depth, tree_out_dev, true};
+    const int rc = obs_check_request(h, "fl_step_obs", &out, max_nodes, pred_depth, &tree);
+    if (rc != FL_OK) return rc;
     // TWO launches (k_step, then the observation kernel) back to back on the handle's stream behind this one call.  A single fused launch was
     // measured and is slower: the step wants one lane per agent and few wavefronts, the builders 16 wavefronts, and the second launch's dispatch overlaps the first.
     fl_launch_step(h->d, actions_dev, seed, stream_base, kind, rewards_dev, dones_dev, done_all_dev, flags, h->stream);
     HIPCHK(hipGetLastError());
-    if (tree_max_depth > 3 || (tree_max_depth > 0 && max_nodes > 32)) return fl_obs_cutils_tree(h, max_nodes, pred_depth, attr_dev, forest_dev, adjacency_dev, node_order_dev, edge_order_dev,
-                                                      valid_actions_dev, props_dev, tree_max_depth, tree_pred_depth, tree_out_dev);
-    const int rc = tree_max_depth > 0 ? obs_launched(h, fl_launch_obs_both(h->obs, h->d, max_nodes, pred_depth, attr_dev, forest_dev, adjacency_dev, node_order_dev,
-                                                           edge_order_dev, valid_actions_dev, props_dev, tree_max_depth, tree_pred_depth,
-                                                           tree_out_dev, h->stream))
-                                      : obs_launched(h, fl_launch_obs_cutils(h->obs, h->d, max_nodes, pred_depth, attr_dev, forest_dev, adjacency_dev, node_order_dev,
-                                                             edge_order_dev, valid_actions_dev, props_dev, h->stream));
-    if (rc != FL_OK) { set_err("fl_step_obs: no launch configuration: %d rail cells and %d agents per env do not fit the observation kernels' LDS (160 KiB a workgroup), or the sizes are out of range", h->d.Rcap, h->d.A); return rc; }
-    HIPCHK(hipGetLastError());
-    return FL_OK;
+    return tree_max_depth > 0 ? obs_run_both(h, "fl_step_obs", max_nodes, pred_depth, out, tree) : obs_run_cutils(h, "fl_step_obs", max_nodes, pred_depth, out);
 }
 
 int fl_check(fl_batch *h) {
@@ -898,16 +963,7 @@ static int rebuild_tables(fl_batch *h, const uint8_t *mask_dev) {
         for (int b = 0; b < h->B; b++) h->h_need[b] = h->h_tab[b] == b;
         HIPCHK(hipMemcpyAsync(h->need_dev, h->h_need.data(), h->B, hipMemcpyHostToDevice, h->stream));
     }
-    fl_launch_env_list(h->d, mask_dev ? mask_dev : h->need_dev, h->stream, mask_dev != nullptr);
-    mask_dev = mask_dev ? mask_dev : h->need_dev;
-    fl_launch_distance_maps(h->d, mask_dev, h->stream);
-    HIPCHK(hipGetLastError());
-    fl_launch_segments(h->d, mask_dev, h->stream);
-    HIPCHK(hipGetLastError());
-    fl_launch_nexthop(h->d, mask_dev, h->stream);
-    fl_launch_hop8(h->d, mask_dev, h->stream);
-    HIPCHK(hipGetLastError());
-    return FL_OK;
+    return launch_table_kernels(h, mask_dev ? mask_dev : h->need_dev, mask_dev != nullptr);
 }
 
 int fl_distance_map_rebuild(fl_batch *h) {
@@ -938,106 +994,43 @@ int fl_positions_map(fl_batch *h, int b, int32_t *out) {
 int fl_obs_cutils(fl_batch *h, int max_nodes, int pred_depth, float *attr_dev, float *forest_dev, int32_t *adjacency_dev,
                   int32_t *node_order_dev, int32_t *edge_order_dev, uint8_t *valid_actions_dev, double *props_dev) {
     NEED_COMMIT(h);
-    if (max_nodes < 4 || max_nodes > FL_OBS_MAX_NODES || pred_depth < 1 || pred_depth > FL_OBS_MAX_PRED) {
-        set_err("fl_obs_cutils: max_nodes must be in [4,%d] and pred_depth in [1,%d]", FL_OBS_MAX_NODES, FL_OBS_MAX_PRED);
-        return FL_ERR_ARG;
-    }
-    if (!attr_dev || !forest_dev || !adjacency_dev || !node_order_dev || !edge_order_dev || !valid_actions_dev) {
-        set_err("fl_obs_cutils: null output buffer");
-        return FL_ERR_ARG;
-    }
-    int rc = obs_launched(h, fl_launch_obs_cutils(h->obs, h->d, max_nodes, pred_depth, attr_dev, forest_dev, adjacency_dev, node_order_dev,
-                                  edge_order_dev, valid_actions_dev, props_dev, h->stream));
-    if (rc != FL_OK) { set_err("fl_obs_cutils: no launch configuration: %d rail cells and %d agents per env do not fit the observation kernels' LDS (160 KiB a workgroup), or the sizes are out of range", h->d.Rcap, h->d.A); return rc; }
-    HIPCHK(hipGetLastError());
-    return FL_OK;
+    const FlObsCutilsOut out = {attr_dev, forest_dev, adjacency_dev, node_order_dev, edge_order_dev, valid_actions_dev, props_dev};
+    const int rc = obs_check_request(h, "fl_obs_cutils", &out, max_nodes, pred_depth, nullptr);
+    return rc != FL_OK ? rc : obs_run_cutils(h, "fl_obs_cutils", max_nodes, pred_depth, out);
 }
 
 int fl_obs_cutils_policy(fl_batch *h, int max_nodes, int pred_depth, float *attr_dev, float *forest_dev, int64_t *adjacency_dev,
                          int64_t *node_order_dev, int64_t *edge_order_dev, uint8_t *valid_actions_dev, double *props_dev) {
     NEED_COMMIT(h);
-    if (max_nodes < 4 || max_nodes > FL_OBS_MAX_NODES || pred_depth < 1 || pred_depth > FL_OBS_MAX_PRED) {
-        set_err("fl_obs_cutils_policy: max_nodes must be in [4,%d] and pred_depth in [1,%d]", FL_OBS_MAX_NODES, FL_OBS_MAX_PRED);
-        return FL_ERR_ARG;
-    }
-    if (!attr_dev || !forest_dev || !adjacency_dev || !node_order_dev || !edge_order_dev || !valid_actions_dev) {
-        set_err("fl_obs_cutils_policy: null output buffer");
-        return FL_ERR_ARG;
-    }
-    int rc = obs_launched(h, fl_launch_obs_cutils(h->obs, h->d, max_nodes, pred_depth, attr_dev, forest_dev, reinterpret_cast<int32_t *>(adjacency_dev),
-                                  reinterpret_cast<int32_t *>(node_order_dev), reinterpret_cast<int32_t *>(edge_order_dev), valid_actions_dev, props_dev,
-                                  h->stream, nullptr, 1));
-    if (rc != FL_OK) { set_err("fl_obs_cutils_policy: no launch configuration: %d rail cells and %d agents per env do not fit the observation kernels' LDS (160 KiB a workgroup), or the sizes are out of range", h->d.Rcap, h->d.A); return rc; }
-    HIPCHK(hipGetLastError());
-    return FL_OK;
+    const FlObsCutilsOut out = {attr_dev, forest_dev, reinterpret_cast<int32_t *>(adjacency_dev), reinterpret_cast<int32_t *>(node_order_dev),
+                                reinterpret_cast<int32_t *>(edge_order_dev), valid_actions_dev, props_dev};
+    const int rc = obs_check_request(h, "fl_obs_cutils_policy", &out, max_nodes, pred_depth, nullptr);
+    return rc != FL_OK ? rc : obs_run_cutils(h, "fl_obs_cutils_policy", max_nodes, pred_depth, out, nullptr, 1);
 }
 
 int fl_obs_cutils_handles(fl_batch *h, int max_nodes, int pred_depth, const int32_t *handles, int n_handles, float *attr_dev,
                           float *forest_dev, int32_t *adjacency_dev, int32_t *node_order_dev, int32_t *edge_order_dev,
                           uint8_t *valid_actions_dev, double *props_dev) {
     NEED_COMMIT(h);
-    const int A = h->A;
-    if (!handles || n_handles < 1 || n_handles > A) { set_err("fl_obs_cutils_handles: 1 <= n_handles <= %d agents", A); return FL_ERR_ARG; }
     // the reference's conflict test erases position `agent.handle` from a list of len(handles) entries (tool.h:428-434): a listed
     // handle >= len(handles) is undefined behaviour there; what remains are the permutations of 0 .. n-1
-    std::vector<int16_t> label(A, (int16_t)-1);
-    bool identity = n_handles == A;
-    for (int j = 0; j < n_handles; j++) {
-        const int a = handles[j];
-        if (a < 0 || a >= n_handles || label[a] >= 0) {
-            set_err("fl_obs_cutils_handles: handles has to be a permutation of 0 .. %d (handle %d at position %d): the reference's get_many is undefined for any other strict subset "
-                    "(treeobs.cpp:393-401 erases list position `handle`)", n_handles - 1, a, j);
-            return FL_ERR_ARG;
-        }
-        label[a] = (int16_t)j;
-        identity = identity && a == j;
-    }
-    if (identity)
-        return fl_obs_cutils(h, max_nodes, pred_depth, attr_dev, forest_dev, adjacency_dev, node_order_dev, edge_order_dev, valid_actions_dev, props_dev);
-    if (max_nodes < 4 || max_nodes > FL_OBS_MAX_NODES || pred_depth < 1 || pred_depth > FL_OBS_MAX_PRED) {
-        set_err("fl_obs_cutils_handles: max_nodes must be in [4,%d] and pred_depth in [1,%d]", FL_OBS_MAX_NODES, FL_OBS_MAX_PRED);
-        return FL_ERR_ARG;
-    }
-    if (!attr_dev || !forest_dev || !adjacency_dev || !node_order_dev || !edge_order_dev || !valid_actions_dev) {
-        set_err("fl_obs_cutils_handles: null output buffer");
-        return FL_ERR_ARG;
-    }
-    HIPCHK(hipMemcpyAsync(h->obs.label, label.data(), (size_t)A * sizeof(int16_t), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));      // (the staging vector is a local)
-    int rc = obs_launched(h, fl_launch_obs_cutils(h->obs, h->d, max_nodes, pred_depth, attr_dev, forest_dev, adjacency_dev, node_order_dev,
-                                  edge_order_dev, valid_actions_dev, props_dev, h->stream, h->obs.label));
-    if (rc != FL_OK) { set_err("fl_obs_cutils_handles: no launch configuration"); return rc; }
-    HIPCHK(hipGetLastError());
-    return FL_OK;
+    const int16_t *label_dev;
+    int rc = obs_handle_list(h, "fl_obs_cutils_handles", handles, n_handles, "the reference's get_many is undefined for any other strict subset "
+                             "(treeobs.cpp:393-401 erases list position `handle`)", true, &label_dev);
+    if (rc != FL_OK) return rc;
+    const FlObsCutilsOut out = {attr_dev, forest_dev, adjacency_dev, node_order_dev, edge_order_dev, valid_actions_dev, props_dev};
+    rc = obs_check_request(h, "fl_obs_cutils_handles", &out, max_nodes, pred_depth, nullptr);
+    return rc != FL_OK ? rc : obs_run_cutils(h, "fl_obs_cutils_handles", max_nodes, pred_depth, out, label_dev);
 }
 
 int fl_obs_cutils_tree(fl_batch *h, int max_nodes, int pred_depth, float *attr_dev, float *forest_dev, int32_t *adjacency_dev,
                        int32_t *node_order_dev, int32_t *edge_order_dev, uint8_t *valid_actions_dev, double *props_dev,
                        int tree_max_depth, int tree_pred_depth, double *tree_out_dev) {
     NEED_COMMIT(h);
-    if (max_nodes < 4 || max_nodes > FL_OBS_MAX_NODES || pred_depth < 1 || pred_depth > FL_OBS_MAX_PRED || tree_max_depth < 1 ||
-        tree_max_depth > FL_MAX_TREE_DEPTH || tree_pred_depth < 0 || tree_pred_depth > pred_depth) {
-        set_err("fl_obs_cutils_tree: max_nodes in [4,%d], pred_depth in [1,%d], tree depth in [1,%d], 0 <= tree_pred_depth <= pred_depth",
-                FL_OBS_MAX_NODES, FL_OBS_MAX_PRED, FL_MAX_TREE_DEPTH);
-        return FL_ERR_ARG;
-    }
-    if (!attr_dev || !forest_dev || !adjacency_dev || !node_order_dev || !edge_order_dev || !valid_actions_dev || !tree_out_dev) {
-        set_err("fl_obs_cutils_tree: null output buffer");
-        return FL_ERR_ARG;
-    }
-    if (tree_max_depth > 3 && (h->d.max_branch > 2 || getenv("FL_OBS_NO_COMPACT") != nullptr)) {   // (before the cutils launch sets its sticky deadlock bits)
-        set_err("fl_obs_cutils_tree: max_depth 4 needs a grid on which no direction of a cell has more than two transitions (every Flatland rail cell type) and the compact node tables; this batch has %d", h->d.max_branch);
-        return FL_ERR_ARG;
-    }
-    if (tree_max_depth > 3 || max_nodes > 32) {   // beyond the fused kernels' node tables: the two builders one after the other (same outputs)
-        int rc2 = fl_obs_cutils(h, max_nodes, pred_depth, attr_dev, forest_dev, adjacency_dev, node_order_dev, edge_order_dev, valid_actions_dev, props_dev);
-        return rc2 != FL_OK ? rc2 : fl_obs_tree(h, tree_max_depth, tree_pred_depth, tree_out_dev);
-    }
-    int rc = obs_launched(h, fl_launch_obs_both(h->obs, h->d, max_nodes, pred_depth, attr_dev, forest_dev, adjacency_dev, node_order_dev,
-                                edge_order_dev, valid_actions_dev, props_dev, tree_max_depth, tree_pred_depth, tree_out_dev, h->stream));
-    if (rc != FL_OK) { set_err("fl_obs_cutils_tree: no launch configuration: %d rail cells and %d agents per env do not fit the observation kernels' LDS (160 KiB a workgroup), or the sizes are out of range", h->d.Rcap, h->d.A); return rc; }
-    HIPCHK(hipGetLastError());
-    return FL_OK;
+    const FlObsCutilsOut out = {attr_dev, forest_dev, adjacency_dev, node_order_dev, edge_order_dev, valid_actions_dev, props_dev};
+    const ObsTreeRequest tree = {1, tree_max_depth, tree_pred_depth, tree_out_dev, true};   // (depth 4: before the cutils launch sets its sticky deadlock bits)
+    const int rc = obs_check_request(h, "fl_obs_cutils_tree", &out, max_nodes, pred_depth, &tree);
+    return rc != FL_OK ? rc : obs_run_both(h, "fl_obs_cutils_tree", max_nodes, pred_depth, out, tree);
 }
 
 int fl_obs_global(fl_batch *h, int b0, int nb, int elem_bytes, void *rail_dev, void *agents_state_dev, void *targets_dev) {
@@ -1049,8 +1042,7 @@ int fl_obs_global(fl_batch *h, int b0, int nb, int elem_bytes, void *rail_dev, v
         set_err("fl_obs_global: the output buffers must be 16-byte aligned");
         return FL_ERR_ARG;
     }
-    if (h->n_cu == 0 && hipDeviceGetAttribute(&h->n_cu, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess) h->n_cu = 0;
-    if (fl_launch_obs_global(h->d, b0, nb, elem_bytes, h->n_cu, rail_dev, agents_state_dev, targets_dev, h->stream) != FL_OK) {
+    if (fl_launch_obs_global(h->d, b0, nb, elem_bytes, h->obs.n_cu, rail_dev, agents_state_dev, targets_dev, h->stream) != FL_OK) {
         set_err("fl_obs_global: a %d x %d map needs more bands of cells than one launch holds", h->H, h->W);
         return FL_ERR_ARG;
     }
@@ -1068,54 +1060,23 @@ int fl_obs_set_mode(fl_batch *h, int flags) {
 
 int fl_obs_tree(fl_batch *h, int max_depth, int pred_depth, double *out_dev) {
     NEED_COMMIT(h);
-    if (max_depth < 1 || max_depth > FL_MAX_TREE_DEPTH || pred_depth > FL_OBS_MAX_PRED || !out_dev) {
-        set_err("fl_obs_tree: max_depth must be in [1,%d], pred_depth <= %d", FL_MAX_TREE_DEPTH, FL_OBS_MAX_PRED);
-        return FL_ERR_ARG;
-    }
-    if (max_depth > 3 && h->d.max_branch > 2) {
-        set_err("fl_obs_tree: max_depth 4 needs a grid on which no direction of a cell has more than two transitions (every Flatland rail cell type); this batch has %d", h->d.max_branch);
-        return FL_ERR_ARG;
-    }
-    int rc = obs_launched(h, fl_launch_obs_tree(h->obs, h->d, max_depth, pred_depth, out_dev, h->stream));
-    if (rc != FL_OK) { set_err("fl_obs_tree: no launch configuration: %d rail cells and %d agents per env do not fit the observation kernels' LDS (160 KiB a workgroup), or the sizes are out of range", h->d.Rcap, h->d.A); return rc; }
-    HIPCHK(hipGetLastError());
-    return FL_OK;
+    const ObsTreeRequest tree = {1, max_depth, pred_depth, out_dev, false};
+    const int rc = obs_check_request(h, "fl_obs_tree", nullptr, 0, 0, &tree);
+    return rc != FL_OK ? rc : obs_run_tree(h, "fl_obs_tree", tree);
 }
 
 int fl_obs_tree_handles(fl_batch *h, int max_depth, int pred_depth, const int32_t *handles, int n_handles, double *out_dev) {
     NEED_COMMIT(h);
-    const int A = h->A;
-    if (!handles || n_handles < 1 || n_handles > A) { set_err("fl_obs_tree_handles: 1 <= n_handles <= %d agents", A); return FL_ERR_ARG; }
     // the reference's conflict test deletes position `handle` from the arrays of the listed handles' predictions and reads
     // env.agents[position].state (observations.py:337-366): a listed handle >= len(handles) is an IndexError there; what remains are
     // the permutations of 0 .. n-1
-    std::vector<int16_t> label(A, (int16_t)-1);
-    bool identity = n_handles == A;
-    for (int j = 0; j < n_handles; j++) {
-        const int a = handles[j];
-        if (a < 0 || a >= n_handles || label[a] >= 0) {
-            set_err("fl_obs_tree_handles: handles has to be a permutation of 0 .. %d (handle %d at position %d): the reference's get_many raises IndexError for a handle >= len(handles) "
-                    "(observations.py:337 deletes list position `handle`)", n_handles - 1, a, j);
-            return FL_ERR_ARG;
-        }
-        label[a] = (int16_t)j;
-        identity = identity && a == j;
-    }
-    if (identity || pred_depth < 0) return fl_obs_tree(h, max_depth, pred_depth, out_dev);   // (no predictor: no conflict test, the list does not matter)
-    if (max_depth < 1 || max_depth > FL_MAX_TREE_DEPTH || pred_depth > FL_OBS_MAX_PRED || !out_dev) {
-        set_err("fl_obs_tree_handles: max_depth must be in [1,%d], pred_depth <= %d", FL_MAX_TREE_DEPTH, FL_OBS_MAX_PRED);
-        return FL_ERR_ARG;
-    }
-    if (max_depth > 3 && h->d.max_branch > 2) {
-        set_err("fl_obs_tree_handles: max_depth 4 needs a grid on which no direction of a cell has more than two transitions; this batch has %d", h->d.max_branch);
-        return FL_ERR_ARG;
-    }
-    HIPCHK(hipMemcpyAsync(h->obs.label, label.data(), (size_t)A * sizeof(int16_t), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));      // (the staging vector is a local)
-    int rc = obs_launched(h, fl_launch_obs_tree(h->obs, h->d, max_depth, pred_depth, out_dev, h->stream, h->obs.label));
-    if (rc != FL_OK) { set_err("fl_obs_tree_handles: no launch configuration"); return rc; }
-    HIPCHK(hipGetLastError());
-    return FL_OK;
+    const int16_t *label_dev;
+    int rc = obs_handle_list(h, "fl_obs_tree_handles", handles, n_handles, "the reference's get_many raises IndexError for a handle >= len(handles) "
+                             "(observations.py:337 deletes list position `handle`)", pred_depth >= 0, &label_dev);   // (no predictor: no conflict test, the list does not matter)
+    if (rc != FL_OK) return rc;
+    const ObsTreeRequest tree = {1, max_depth, pred_depth, out_dev, false};
+    rc = obs_check_request(h, "fl_obs_tree_handles", nullptr, 0, 0, &tree);
+    return rc != FL_OK ? rc : obs_run_tree(h, "fl_obs_tree_handles", tree, label_dev);
 }
 
 // diagnostic (not part of the public header): copy the per-env phase clocks of a -DFL_OBS_TIMING build
@@ -1156,24 +1117,22 @@ extern "C" int fl_debug_last_obs_launch(fl_batch *h, int *out, int n_out) {
 
 // diagnostic (not part of the public header), no GPU needed: the same for a batch of the given sizes -- agents, rail-cell and
 // unique-target capacities, maps taller than wide (compact prediction keys), most transitions of a (cell, direction)
-extern "C" int fl_debug_obs_config_of(int A, int Rcap, int Ucap, int tall, int max_branch, int pred_depth, int max_depth, int tree_pred,
-                                      int *out11) {
+static int obs_config_of(int A, int Rcap, int Ucap, int tall, int max_branch, int pred_depth, int max_depth, int tree_pred, int *out11, int wide) {
     FlDev d;
     memset(&d, 0, sizeof d);
     d.A = A; d.Rcap = Rcap; d.Ucap = Ucap; d.max_branch = max_branch;
     static uint16_t dummy_key;
     d.rkey = tall ? &dummy_key : nullptr;
-    return fl_obs_config_of_fused(d, pred_depth, max_depth, tree_pred, out11);
+    return fl_obs_config_of_fused(d, pred_depth, max_depth, tree_pred, out11, wide);
+}
+extern "C" int fl_debug_obs_config_of(int A, int Rcap, int Ucap, int tall, int max_branch, int pred_depth, int max_depth, int tree_pred,
+                                      int *out11) {
+    return obs_config_of(A, Rcap, Ucap, tall, max_branch, pred_depth, max_depth, tree_pred, out11, 0);
 }
 // ... of a WIDE batch (several envs per CU)
 extern "C" int fl_debug_obs_config_of_wide(int A, int Rcap, int Ucap, int tall, int max_branch, int pred_depth, int max_depth, int tree_pred,
                                            int *out11) {
-    FlDev d;
-    memset(&d, 0, sizeof d);
-    d.A = A; d.Rcap = Rcap; d.Ucap = Ucap; d.max_branch = max_branch;
-    static uint16_t dummy_key;
-    d.rkey = tall ? &dummy_key : nullptr;
-    return fl_obs_config_of_fused(d, pred_depth, max_depth, tree_pred, out11, 1);
+    return obs_config_of(A, Rcap, Ucap, tall, max_branch, pred_depth, max_depth, tree_pred, out11, 1);
 }
 
 double fl_algorithmic_bytes_per_agent_step(fl_batch *h, int with_cutils_obs, int tree_depth) {

@@ -18,6 +18,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 #define FL_INF16 0xFFFFu
 
 #define FL_R_NONE 0xFFFFu  /* no rail cell / no such state (u16 tables) */
@@ -153,6 +155,19 @@ __host__ __device__ inline uint32_t synth_action(uint32_t seed, uint32_t b, uint
     if (kind == 2) return h;  // shortest-path following: the step kernel derives the action from the agent's state (fl_step_body.h)
     uint32_t r = h % 100u;
     return r >= 95 ? 0u : r >= 90 ? 4u : r >= 85 ? 3u : r >= 80 ? 1u : 2u;
+}
+
+// host side: a device array of n elements plus `slack` bytes, zeroed on stream s and registered in `allocs` (what the handle frees).
+// Everything a handle allocates comes from here: its behaviour must not depend on what a freed allocation of an earlier handle left
+// in the memory it got.
+template <typename T>
+static inline hipError_t fl_alloc_zeroed(T **p, size_t n, hipStream_t s, std::vector<void *> &allocs, size_t slack = 16) {
+    void *q = nullptr;
+    hipError_t e = hipMalloc(&q, n * sizeof(T) + slack);
+    if (e != hipSuccess) return e;
+    allocs.push_back(q);
+    *p = (T *)q;
+    return hipMemsetAsync(q, 0, n * sizeof(T) + slack, s);
 }
 
 // kernel launchers (defined in the .hip files).  mask_dev: u8[B] or nullptr (= every env): only the envs with a non-zero

@@ -40,20 +40,31 @@ struct FlObsScratch {
                                          // served only the envs that fit it, and how many envs took the class's body
 };
 
-int fl_obs_alloc(FlObsScratch &o, const FlDev &d, hipStream_t s, std::vector<void *> &allocs);
-int fl_launch_obs_cutils(FlObsScratch &o, const FlDev &d, int max_nodes, int pred_depth, float *attr, float *forest,
-                         int32_t *adjacency, int32_t *node_order, int32_t *edge_order, uint8_t *valid, double *props,
-                         hipStream_t s, const int16_t *label_dev = nullptr, int out64 = 0);   // out64: adjacency / node_order / edge_order are int64 policy tensors
-int fl_launch_obs_both(FlObsScratch &o, const FlDev &d, int max_nodes, int pred_depth, float *attr, float *forest,
-                       int32_t *adjacency, int32_t *node_order, int32_t *edge_order, uint8_t *valid, double *props,
-                       int max_depth, int tree_pred, double *tree_out, hipStream_t s);
-int fl_launch_obs_tree(FlObsScratch &o, const FlDev &d, int max_depth, int pred_depth, double *out, hipStream_t s, const int16_t *label_dev = nullptr);
-// more envs than CUs: the order in which the workgroups take the envs (longest previous launch first); returns the scratch the launch uses
-FlObsScratch fl_obs_env_order(FlObsScratch &o, const FlDev &d, hipStream_t s);
-int fl_obs_config_of_fused(const FlDev &d, int pred_depth, int max_depth, int tree_pred, int out[11], int wide = 0);  // diagnostic (wide: several envs per CU)
-// diagnostic: what the last observation launch made by the calling thread ran (obs_launch of fl_obs.hip fills it from the ObsArgs it launches):
+// the seven output tensors of the flatland_cutils builder (device pointers; props may be null)
+struct FlObsCutilsOut {
+    float *attr, *forest;
+    int32_t *adjacency, *node_order, *edge_order;
+    uint8_t *valid;
+    double *props;
+};
+
+// What an observation launch ran: every fl_launch_obs_* below fills the caller's `record` (the handle's own array: fl_batch::last_obs_launch,
+// fl_debug_last_obs_launch) from the ObsArgs it launches and the options the preference walk accepted for them -- host side only, no kernel
+// argument carries it.  MODE -1, the rest zero: the call returned an error and launched nothing.
 //   [0] MODE  [1] VAR  [2] launch class (0: runtime carving)  [3] split kind  [4] second class of a split-2 kernel  [5] threads  [6] dynamic LDS bytes
 //   [7..20] the ObsOptions the preference walk accepted: wl_bytes, tab, nh, tmask, dual, items, items_cap, snext, partial, bk_room, own_filter, fb, raw, wl_head
 //   [21] ObsArgs::bk  [22] tshift  [23] compact_t  [24] 1 = a handle subset (label set)
 #define FL_OBS_LAUNCH_WORDS 25
-void fl_obs_last_launch(int out[FL_OBS_LAUNCH_WORDS]);
+
+int fl_obs_alloc(FlObsScratch &o, const FlDev &d, hipStream_t s, std::vector<void *> &allocs);
+// out64: adjacency / node_order / edge_order are int64 policy tensors
+int fl_launch_obs_cutils(FlObsScratch &o, const FlDev &d, int max_nodes, int pred_depth, const FlObsCutilsOut &out, hipStream_t s,
+                         int record[FL_OBS_LAUNCH_WORDS], const int16_t *label_dev = nullptr, int out64 = 0);
+int fl_launch_obs_both(FlObsScratch &o, const FlDev &d, int max_nodes, int pred_depth, const FlObsCutilsOut &out, int max_depth, int tree_pred,
+                       double *tree_out, hipStream_t s, int record[FL_OBS_LAUNCH_WORDS]);
+int fl_launch_obs_tree(FlObsScratch &o, const FlDev &d, int max_depth, int pred_depth, double *out, hipStream_t s, int record[FL_OBS_LAUNCH_WORDS],
+                       const int16_t *label_dev = nullptr);
+// more envs than CUs: the order in which the workgroups take the envs (longest previous launch first); returns the scratch the launch uses
+FlObsScratch fl_obs_env_order(FlObsScratch &o, const FlDev &d, hipStream_t s);
+int fl_obs_config_of_fused(const FlDev &d, int pred_depth, int max_depth, int tree_pred, int out[11], int wide = 0);  // diagnostic (wide: several envs per CU)
+bool fl_obs_no_compact();   // FL_OBS_NO_COMPACT (diagnostic): DFS-slot node tables for the upstream trees of every grid -- no depth 4

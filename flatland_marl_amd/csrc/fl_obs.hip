@@ -14,42 +14,31 @@
 int fl_obs_alloc(FlObsScratch &o, const FlDev &d, hipStream_t s, std::vector<void *> &allocs) {
     o.pred_cap = OBS_PRED_CAP;
     o.items_cap = (size_t)d.A * (o.pred_cap + 2 * OBS_FB_NB + 2);  // bucketed lists: an item sits in every time bucket it touches
-    const size_t BA = (size_t)d.B * d.A;
-    void *p = nullptr;
-    if (hipMalloc(&p, BA * o.pred_cap * 2) != hipSuccess) return FL_ERR_HIP;
-    o.path = (uint16_t *)p; allocs.push_back(p);
-    if (hipMalloc(&p, (size_t)d.B * o.items_cap * 4 + 64) != hipSuccess) return FL_ERR_HIP;   // (+ 64: conflict_flags reads up to seven words behind a list)
-    o.cell_items = (uint32_t *)p; allocs.push_back(p);
-    if (hipMalloc(&p, (size_t)d.B * 64 * 8) != hipSuccess) return FL_ERR_HIP;
-    o.dbg = (long long *)p; allocs.push_back(p);
-    if (hipMalloc(&p, (size_t)d.B * (d.Rcap + 1) * OBS_BK_NB * 2 + 16) != hipSuccess) return FL_ERR_HIP;
-    o.bk_rel = (uint16_t *)p; allocs.push_back(p);
     o.wl_cap = OBS_WL_HBM_ENTRIES;
-    if (hipMalloc(&p, (size_t)d.B * o.wl_cap * 8) != hipSuccess) return FL_ERR_HIP;
-    o.wl = (uint2 *)p; allocs.push_back(p);
-    if (hipMalloc(&p, (size_t)d.A * sizeof(int16_t) + 16) != hipSuccess) return FL_ERR_HIP;
-    o.label = (int16_t *)p; allocs.push_back(p);
-    if (hipMalloc(&p, BA * sizeof(uint4)) != hipSuccess) return FL_ERR_HIP;
-    o.rowmask = (uint4 *)p; allocs.push_back(p);
-    if (hipMemsetAsync(o.rowmask, 0, BA * sizeof(uint4), s) != hipSuccess) return FL_ERR_HIP;
-    o.rows_out = nullptr; o.rows_depth = 0; o.keep_rows = 0;
-    if (hipMalloc(&p, (size_t)d.B * 4) != hipSuccess) return FL_ERR_HIP;
-    o.cost = (uint32_t *)p; allocs.push_back(p);
-    if (hipMemsetAsync(o.cost, 0, (size_t)d.B * 4, s) != hipSuccess) return FL_ERR_HIP;
+    const size_t B = (size_t)d.B, BA = B * d.A;
     // every scratch array starts out zeroed: what a kernel reads of them it has written before in the same launch, but a handle's
     // behaviour must not depend on what a freed allocation of an earlier handle left in the memory it got
-    if (hipMemsetAsync(o.path, 0, BA * o.pred_cap * 2, s) != hipSuccess || hipMemsetAsync(o.cell_items, 0, (size_t)d.B * o.items_cap * 4, s) != hipSuccess ||
-        hipMemsetAsync(o.dbg, 0, (size_t)d.B * 64 * 8, s) != hipSuccess || hipMemsetAsync(o.bk_rel, 0, (size_t)d.B * (d.Rcap + 1) * OBS_BK_NB * 2 + 16, s) != hipSuccess ||
-        hipMemsetAsync(o.wl, 0, (size_t)d.B * o.wl_cap * 8, s) != hipSuccess) return FL_ERR_HIP;
-    if (hipMalloc(&p, (size_t)d.B * 4) != hipSuccess) return FL_ERR_HIP;
-    o.order = (int *)p; allocs.push_back(p);
-    if (hipMemsetAsync(o.order, 0, (size_t)d.B * 4, s) != hipSuccess) return FL_ERR_HIP;
+    if (fl_alloc_zeroed(&o.path, BA * o.pred_cap, s, allocs) != hipSuccess ||
+        fl_alloc_zeroed(&o.cell_items, B * o.items_cap, s, allocs, 64) != hipSuccess ||   // (64: conflict_flags reads up to seven words behind a list)
+        fl_alloc_zeroed(&o.dbg, B * 64, s, allocs) != hipSuccess || fl_alloc_zeroed(&o.bk_rel, B * (d.Rcap + 1) * OBS_BK_NB, s, allocs) != hipSuccess ||
+        fl_alloc_zeroed(&o.wl, B * o.wl_cap, s, allocs) != hipSuccess || fl_alloc_zeroed(&o.label, (size_t)d.A, s, allocs) != hipSuccess ||
+        fl_alloc_zeroed(&o.rowmask, BA, s, allocs) != hipSuccess || fl_alloc_zeroed(&o.cost, B, s, allocs) != hipSuccess ||
+        fl_alloc_zeroed(&o.order, B, s, allocs) != hipSuccess) return FL_ERR_HIP;
+    o.rows_out = nullptr; o.rows_depth = 0; o.keep_rows = 0;
     int dev = 0, n_cu = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return FL_ERR_HIP;
     o.n_cu = n_cu;
     o.order_age = 0;
     return FL_OK;
 }
+
+// Diagnostic switches that more than one function reads: one accessor each, read once per process.
+bool fl_obs_no_compact() { static const bool v = getenv("FL_OBS_NO_COMPACT") != nullptr; return v; }
+static bool obs_no_fix() { static const bool v = getenv("FL_OBS_NO_FIX") != nullptr; return v; }                    // the runtime carving for every batch
+static bool obs_no_split() { static const bool v = getenv("FL_OBS_NO_SPLIT") != nullptr; return v; }                // no split kernels
+static bool obs_no_cutils_merge() { static const bool v = getenv("FL_OBS_NO_CUTILS_MERGE") != nullptr; return v; }  // the builder alone on the stand-alone kernel, as before round 6
+static bool obs_verbose_on() { static const bool v = getenv("FL_OBS_VERBOSE") != nullptr; return v; }               // print the configuration obs_pick_config chose
+static bool obs_no_wl_head() { static const bool v = getenv("FL_OBS_NO_WL_HEAD") != nullptr; return v; }            // HBM work lists without their LDS head (rules out the classes that have one)
 
 // The launch is one workgroup per env and a CU holds one workgroup: with more envs than CUs the launch ends when the last CU has
 // worked through its envs, and the envs differ (agents on the map, traffic around them) -- mean 187 us, slowest 315 us at cfg4.
@@ -132,10 +121,6 @@ static ObsLayout obs_layout(const FlDev &d, const ObsArgs &P, const ObsOptions &
 // A FIXED launch class (compile-time carving, ObsFixed<k> in fl_obs_layout.h) is taken when the batch fits the class's capacities
 // and the configuration just chosen for it has the class's options and shape; L becomes the class's carving (what the kernel has
 // compiled in) with the next-hop tables, last in the carving, at the batch's size.
-static bool obs_no_wl_head() {
-    static const bool v = getenv("FL_OBS_NO_WL_HEAD") != nullptr;   // diagnostic: HBM work lists without their LDS head (rules out the classes that have one)
-    return v;
-}
 template <int FIX>
 static bool obs_fits_fixed(const FlDev &d, const ObsArgs &P, const ObsOptions &o, ObsLayout &L) {
     using F = ObsFixed<FIX>;
@@ -191,8 +176,7 @@ static bool obs_fits_bin(const FlDev &d, ObsArgs &P, const ObsOptions &own, ObsL
 // whole batch when at least half the envs fit the exact class
 template <int FIX>
 static bool exact_split_covers_most(const FlDev &d, ObsArgs &P, const ObsLayout &L) {
-    static const bool no_split = getenv("FL_OBS_NO_SPLIT") != nullptr;
-    if (no_split || !P.h_R) return false;
+    if (obs_no_split() || !P.h_R) return false;
     const ObsLayout keep = P.L;
     P.L = L;
     const int n = obs_split_fits<FIX>(d, P, P.h_R);
@@ -205,7 +189,6 @@ static bool obs_take_exact(const FlDev &d, ObsArgs &P, const ObsOptions &o, ObsL
 template <int... K>
 static bool obs_take_bin(const FlDev &d, ObsArgs &P, const ObsOptions &o, ObsLayout &L) { return ((obs_fits_bin<K>(d, P, o, L) && (P.fix = K) != 0) || ...); }
 static void obs_take_fixed_class(const FlDev &d, ObsArgs &P, const ObsOptions &o, ObsLayout &L, bool allowed) {
-    static const bool no_fix = getenv("FL_OBS_NO_FIX") != nullptr;   // diagnostic: the runtime carving for every batch
     // diagnostic: exact classes only (the launcher of rounds 4 and 5).  A bin class REPLACES the batch's own options, so the switches that shape those options
     // (what a same-box experiment wants to measure) rule the bins out as well; an exact class only ever matches options it dominates.
     static const bool no_bins = [] {
@@ -214,7 +197,7 @@ static void obs_take_fixed_class(const FlDev &d, ObsArgs &P, const ObsOptions &o
         return false;
     }();
     P.fix = 0; P.split = 0;
-    if (no_fix || !allowed) return;
+    if (obs_no_fix() || !allowed) return;
     if (P.tw_t == 0) {   // the flatland_cutils builder alone: classes 6 .. 10 (the counterparts of 1 .. 5)
         if (obs_take_exact<6, 7, 8, 9, 10, 21>(d, P, o, L) || no_bins || !P.cutils_alone) return;   // (FL_OBS_NO_CUTILS_MERGE: the stand-alone kernel as it ran before round 6)
         obs_take_bin<21, 17, 8, 18, 9, 19, 20>(d, P, o, L);
@@ -248,8 +231,7 @@ static int obs_split_fits(const FlDev &d, const ObsArgs &P, const int *h_R) {
     return n;
 }
 static int obs_take_split_class(const FlDev &d, ObsArgs &P, const int *h_R) {
-    static const bool no_fix = getenv("FL_OBS_NO_FIX") != nullptr, no_split = getenv("FL_OBS_NO_SPLIT") != nullptr;   // diagnostic
-    if (no_fix || no_split || !P.fix_allowed) return 0;
+    if (obs_no_fix() || obs_no_split() || !P.fix_allowed) return 0;
     if (P.fix == 14 || P.fix == 19) {
         // the larger large-map bin (no LDS successor table) was taken because of the batch's largest map: the envs that fit the smaller class
         // (with the table) run ITS body, the others the bin's -- one kernel, every env on a compile-time carving (split 2)
@@ -276,10 +258,9 @@ static int obs_take_split_class(const FlDev &d, ObsArgs &P, const int *h_R) {
     return n;
 }
 
-static thread_local ObsOptions g_last_options;   // diagnostic (FL_OBS_VERBOSE): the options of the last configuration obs_pick_config chose
-
-// Choose what lives in LDS so that the workgroup fits 160 KiB.
-static bool obs_pick_config(const FlDev &d, ObsArgs &P) {
+// Choose what lives in LDS so that the workgroup fits 160 KiB.  `accepted`: the options of the configuration chosen (what the launch's
+// record and FL_OBS_VERBOSE report), untouched when nothing fits.
+static bool obs_pick_config(const FlDev &d, ObsArgs &P, ObsOptions &accepted) {
     // diagnostic overrides (experiments on the LDS / occupancy trade-off): FL_OBS_NT, FL_OBS_LDS_LIMIT (bytes), FL_OBS_NO_TAB
     static const int force_nt = getenv("FL_OBS_NT") ? atoi(getenv("FL_OBS_NT")) : 0;
     static const size_t lds_limit = getenv("FL_OBS_LDS_LIMIT") ? (size_t)atol(getenv("FL_OBS_LDS_LIMIT")) : (size_t)160 * 1024;
@@ -364,7 +345,7 @@ static bool obs_pick_config(const FlDev &d, ObsArgs &P) {
         const int n_prefs = P.merged == 1 ? (int)(sizeof one_round / sizeof one_round[0]) : P.merged == 3 ? (d.A <= 32 ? (int)(sizeof rounds16_small / sizeof rounds16_small[0]) : (int)(sizeof rounds16 / sizeof rounds16[0])) : (int)(sizeof rounds / sizeof rounds[0]);
         // what a configuration of this branch sets in P (and the fixed launch class that has exactly these options, if the batch fits one)
         auto accept = [&](const ObsOptions &oo, ObsLayout L) {
-            g_last_options = oo;
+            accepted = oo;
             P.use_tmask = 1; P.dual_index = up ? 1 : 0;
             P.bk = oo.fb ? 2 : 0; P.bk_nb = OBS_FB_NB; P.bk_shift = OBS_FB_SHIFT;
             P.wl_occ_div = d.A <= 32 ? OBS_WL_OCC_DIV : 3;
@@ -440,8 +421,8 @@ static bool obs_pick_config(const FlDev &d, ObsArgs &P) {
                                 if (Lt.total <= lds_limit) L = Lt;
                                 else if (force.tab == 1) continue;
                             } else if (force.tab == 1) continue;
-                            g_last_options = o;
-                            g_last_options.tab = L.tab_lds;   // (the tables joined the carving above)
+                            accepted = o;
+                            accepted.tab = L.tab_lds;   // (the tables joined the carving above)
                             P.use_tmask = o.tmask; P.dual_index = o.dual;
                             P.bk = o.bk_room; P.bk_nb = OBS_BK_NB; P.bk_shift = OBS_BK_SHIFT;
                             // 2-step buckets where the traffic is and one catch-all bucket for late times (8-step buckets over the
@@ -459,16 +440,17 @@ static bool obs_pick_config(const FlDev &d, ObsArgs &P) {
 }
 
 static void obs_verbose(const ObsArgs &P) {
-    static const bool verbose = getenv("FL_OBS_VERBOSE") != nullptr;  // diagnostic: the configuration obs_pick_config chose
     static int printed = 0;
     const ObsLayout &L = P.L;
-    if (verbose && printed < 4) {
+    if (obs_verbose_on() && printed < 4) {
         printed++;
         fprintf(stderr, "[fl_obs] fixed launch class %d%s, %d threads, %u B LDS: static tables in LDS %d, next-hop in LDS %d, successor table %d, work lists %d B, time masks %d, second index %d, items in LDS %d, one pass B for both builders %d, compact upstream trees %d, bucketed index %d\n",
                 P.fix, P.split ? " (split: the envs that fit it)" : "", L.nt, L.total, L.tab_lds, L.off[L_NH] != L_ABSENT, L.off[L_SNEXT] != L_ABSENT, L.wl_bytes, P.use_tmask, P.dual_index, L.off[L_ITEMS] != L_ABSENT, P.merged, P.compact_t, P.bk);
     }
 }
 static int obs_var(const ObsArgs &P) { return P.L.tab_lds ? 1 : P.L.wl_bytes == 0 ? 2 : 0; }
+// one pass B (P.merged 1 / 2 / 3): MODE 3 / 4 / 5 for both builders, 6 / 7 / 8 for the flatland_cutils builder alone; else the builders of the launch
+static int obs_mode(const ObsArgs &P) { return P.merged ? (P.tw_t ? 2 : 5) + P.merged : P.tw_c == 0 ? 1 : P.tw_t ? 2 : 0; }
 
 // The kernel of a launch: the split kernel of (P.split, P.fix), the kernel of class P.fix, or else the runtime-carving kernel of the launch's
 // MODE; FL_ERR_ARG for a (split, class) pair that has no kernel.  The lists are build.sh's units.
@@ -484,105 +466,119 @@ static int obs_launch_mode(int mode, const FlDev &d, const FlObsScratch &u, cons
     (void)((mode == M && (rc = fl_obs_launch_mode<M>(obs_var(P), d, u, P, s), true)) || ...);
     return rc;
 }
-// diagnostic: what the last observation launch of this thread ran (fl_obs_last_launch; fl_host.hip keeps a copy per handle).  Filled here, from the
-// ObsArgs that are launched and the options the preference walk accepted for them -- host side only, no kernel argument carries it.
-static thread_local int g_last_launch[FL_OBS_LAUNCH_WORDS];
-template <int... K>
-static void obs_class_kernel(int fix, int &mode, int &var) { (void)((fix == K && (mode = obs_fixed_mode<K>(), var = obs_fixed_var<K>(), true)) || ...); }
-static void obs_record_launch(const ObsArgs &P, int mode) {
-    int var = obs_var(P);
-    if (P.fix) obs_class_kernel<1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21>(P.fix, mode, var);
-    const ObsOptions &q = g_last_options;
-    const int rec[FL_OBS_LAUNCH_WORDS] = {mode, var, P.fix, P.split, P.split == 2 ? (P.fix == 4 ? 14 : 19) : 0, P.L.nt, (int)P.L.total,
-                                          q.wl_bytes, q.tab, q.nh, q.tmask, q.dual, q.items, q.items_cap, q.snext, q.partial, q.bk_room, q.own_filter, q.fb, q.raw, q.wl_head,
-                                          P.bk, P.tshift, P.compact_t, P.label != nullptr};
-    memcpy(g_last_launch, rec, sizeof rec);
-}
-void fl_obs_last_launch(int out[FL_OBS_LAUNCH_WORDS]) { memcpy(out, g_last_launch, sizeof g_last_launch); }
-
 static int obs_launch(const FlDev &d, const FlObsScratch &u, const ObsArgs &P, hipStream_t s) {
-    // one pass B (P.merged 1 / 2 / 3): MODE 3 / 4 / 5 for both builders, 6 / 7 / 8 for the flatland_cutils builder alone; else the builders of the launch
-    const int mode = P.merged ? (P.tw_t ? 2 : 5) + P.merged : P.tw_c == 0 ? 1 : P.tw_t ? 2 : 0;
-    obs_record_launch(P, mode);
     if (P.split == 2) return P.fix == 4 ? fl_obs_launch_class<4, 14>(d, u, P, s) : P.fix == 9 ? fl_obs_launch_class<9, 19>(d, u, P, s) : FL_ERR_ARG;
     if (P.split) return obs_launch_class<0, 2, 3, 4, 9>(d, u, P, s);
     if (P.fix) return obs_launch_class<-1, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21>(d, u, P, s);
-    return obs_launch_mode<0, 1, 2, 3, 4, 5, 6, 7, 8>(mode, d, u, P, s);
+    return obs_launch_mode<0, 1, 2, 3, 4, 5, 6, 7, 8>(obs_mode(P), d, u, P, s);
+}
+// the record of a launch (fl_obs.h lists the words): the ObsArgs that were launched and the options `q` the preference walk accepted for them
+template <int... K>
+static void obs_class_kernel(int fix, int &mode, int &var) { (void)((fix == K && (mode = obs_fixed_mode<K>(), var = obs_fixed_var<K>(), true)) || ...); }
+static void obs_record_launch(const ObsArgs &P, const ObsOptions &q, int record[FL_OBS_LAUNCH_WORDS]) {
+    int mode = obs_mode(P), var = obs_var(P);
+    if (P.fix) obs_class_kernel<1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21>(P.fix, mode, var);
+    const int rec[FL_OBS_LAUNCH_WORDS] = {mode, var, P.fix, P.split, P.split == 2 ? (P.fix == 4 ? 14 : 19) : 0, P.L.nt, (int)P.L.total,
+                                          q.wl_bytes, q.tab, q.nh, q.tmask, q.dual, q.items, q.items_cap, q.snext, q.partial, q.bk_room, q.own_filter, q.fb, q.raw, q.wl_head,
+                                          P.bk, P.tshift, P.compact_t, P.label != nullptr};
+    memcpy(record, rec, sizeof rec);
 }
 
+// ---- what a launch asks for: the two builders' sides of the ObsArgs (the launches below and the diagnostic fl_obs_config_of_fused)
+static void obs_cutils_args(ObsArgs &P, int max_nodes, int pred_depth, int wide) {
+    P.max_nodes = max_nodes; P.pred_depth = pred_depth; P.wide = wide;
+    P.tw_c = N_WORDS_C * (max_nodes > OBS_CAP_C ? 64 : OBS_CAP_C);   // (more than 32 nodes: 64-slot tables, one tree a wavefront -- the builder alone only)
+}
+// The builder alone -- what the reference's solution launches (solution/eval_env.py:15-17) -- runs on the one-pass kernels' machinery
+// (MODE 6 / 7 / 8 = MODE 3 / 4 / 5 without the upstream builder; classes 6 .. 10) wherever those apply: 16-lane pass A teams need grids
+// whose cells have at most two transitions a direction (every Flatland rail cell type).  FL_OBS_NO_CUTILS_MERGE: the stand-alone kernel.
+static void obs_alone_args(const FlDev &d, ObsArgs &P) {
+    P.compact_t = d.max_branch <= 2 && !fl_obs_no_compact();
+    P.cutils_alone = !obs_no_cutils_merge();
+}
 // node tables of the upstream builder: compact slots when no direction of a cell of the batch has more than two transitions
 static void obs_tree_args(const FlDev &d, ObsArgs &P, int max_depth, int tree_pred, double *tree_out) {
     P.max_depth = max_depth; P.tree_pred = tree_pred; P.tree_out = tree_out;
     int n = 0, p = 1;
     for (int k = 0; k <= max_depth; k++) { n += p; p *= 4; }
     P.n_tree_nodes = n;
-    static const bool no_compact = getenv("FL_OBS_NO_COMPACT") != nullptr;
-    P.compact_t = d.max_branch <= 2 && !no_compact;
+    P.compact_t = d.max_branch <= 2 && !fl_obs_no_compact();
     if (P.compact_t && max_depth >= 4) { P.tw_t = N_WORDS_T * 32; P.tpw_t = 2; }   // depth 4: 30 compact slots on a 32-lane team (the stand-alone tree launch)
     else if (P.compact_t) { P.tw_t = N_WORDS_T * OBS_CAP_T_COMPACT; P.tpw_t = 4; }
     else { P.tw_t = max_depth <= 2 ? N_WORDS_T * 32 : N_WORDS_T * 88; P.tpw_t = max_depth <= 2 ? 2 : 1; }
 }
-int fl_launch_obs_cutils(FlObsScratch &o, const FlDev &d, int max_nodes, int pred_depth, float *attr, float *forest,
-                         int32_t *adjacency, int32_t *node_order, int32_t *edge_order, uint8_t *valid, double *props,
-                         hipStream_t s, const int16_t *label_dev, int out64) {
-    if (d.A > 1024 || pred_depth + 2 > o.pred_cap || pred_depth > 510 || max_nodes > FL_OBS_MAX_NODES) return FL_ERR_ARG;
-    ObsArgs P = {};
-    P.label = label_dev;
-    P.out64 = out64;
-    P.max_nodes = max_nodes; P.pred_depth = pred_depth; P.attr = attr; P.forest = forest; P.adjacency = adjacency;
-    P.node_order = node_order; P.edge_order = edge_order; P.valid = valid; P.props = props; P.dbg = o.dbg;
-    P.tw_c = N_WORDS_C * (max_nodes > OBS_CAP_C ? 64 : OBS_CAP_C);   // (more than 32 nodes: 64-slot tables, one tree a wavefront)
-    // The builder alone -- what the reference's solution launches (solution/eval_env.py:15-17) -- runs on the one-pass kernels' machinery
-    // (MODE 6 / 7 / 8 = MODE 3 / 4 / 5 without the upstream builder; classes 6 .. 10) wherever those apply: 16-lane pass A teams need grids
-    // whose cells have at most two transitions a direction (every Flatland rail cell type).  FL_OBS_NO_CUTILS_MERGE: the stand-alone kernel.
-    static const bool no_compact = getenv("FL_OBS_NO_COMPACT") != nullptr, no_alone = getenv("FL_OBS_NO_CUTILS_MERGE") != nullptr;
-    P.compact_t = d.max_branch <= 2 && !no_compact;
-    P.cutils_alone = !no_alone;
-    P.wide = obs_batch_is_wide(d.B, o.n_cu);
-    if (!obs_pick_config(d, P)) return FL_ERR_ARG;
-    const int n_split = P.label ? 0 : obs_take_split_class(d, P, o.h_R);
-    if (!P.merged && !P.fix) P.compact_t = 0;    // (the stand-alone kernel's own pass A: teams of 32 lanes)
-    o.last_fix = P.fix; o.last_split = P.split; o.last_fit = P.split ? n_split : P.fix ? d.B : 0;
-    obs_verbose(P);
-    FlObsScratch u = o;
-    if (P.merged == 1) u.order = nullptr;   // small envs, one round: workgroup k builds env k
-    else u = fl_obs_env_order(o, d, s);
-    return obs_launch(d, u, P, s);
+static void obs_out_args(ObsArgs &P, const FlObsScratch &o, const FlObsCutilsOut &out) {
+    P.attr = out.attr; P.forest = out.forest; P.adjacency = out.adjacency; P.node_order = out.node_order; P.edge_order = out.edge_order;
+    P.valid = out.valid; P.props = out.props; P.dbg = o.dbg;
+}
+// The configuration of a request: the preference walk, then the split class (h_R: the envs' rail cells, null: no split).  Returns how many envs
+// run a launch class's body (all of them, those that fit a split class, or 0: the runtime carving), -1: no configuration fits.
+static int obs_configure(const FlDev &d, ObsArgs &P, ObsOptions &accepted, const int *h_R) {
+    if (!obs_pick_config(d, P, accepted)) return -1;
+    const int n_split = h_R ? obs_take_split_class(d, P, h_R) : 0;
+    if (P.tw_t == 0 && !P.merged && !P.fix) P.compact_t = 0;    // (the builder alone on the stand-alone kernel: its own pass A, teams of 32 lanes)
+    return P.split ? n_split : P.fix ? d.B : 0;
 }
 
-int fl_launch_obs_both(FlObsScratch &o, const FlDev &d, int max_nodes, int pred_depth, float *attr, float *forest,
-                       int32_t *adjacency, int32_t *node_order, int32_t *edge_order, uint8_t *valid, double *props,
-                       int max_depth, int tree_pred, double *tree_out, hipStream_t s) {
-    if (d.A > 1024 || pred_depth + 2 > o.pred_cap || pred_depth > 510 || max_nodes > OBS_CAP_C) return FL_ERR_ARG;   // (the fused kernels: 32-lane teams)
-    if (max_depth > 3 || tree_pred > pred_depth || tree_pred < 0) return FL_ERR_ARG;  // the upstream path must be a prefix
-    ObsArgs P = {};
-    P.max_nodes = max_nodes; P.pred_depth = pred_depth; P.attr = attr; P.forest = forest; P.adjacency = adjacency;
-    P.node_order = node_order; P.edge_order = edge_order; P.valid = valid; P.props = props; P.dbg = o.dbg;
-    P.tw_c = N_WORDS_C * OBS_CAP_C;
-    obs_tree_args(d, P, max_depth, tree_pred, tree_out);
-    P.wide = obs_batch_is_wide(d.B, o.n_cu);
-    P.keep_mode = o.keep_rows;
-    P.h_R = o.h_R;
-    if (!obs_pick_config(d, P)) return FL_ERR_ARG;
+// ---- the three launches: obs_begin, their own limits and arguments, obs_run
+// voids the record (MODE -1: nothing ran -- what every failing return leaves) and checks the limits every launch has
+static bool obs_begin(const FlObsScratch &o, const FlDev &d, int pred_depth, int record[FL_OBS_LAUNCH_WORDS]) {
+    memset(record, 0, FL_OBS_LAUNCH_WORDS * sizeof record[0]);
+    record[0] = -1;
+    return d.A <= 1024 && pred_depth + 2 <= o.pred_cap && pred_depth <= 510;
+}
+static int obs_run(FlObsScratch &o, const FlDev &d, ObsArgs &P, const int *h_R, hipStream_t s, int record[FL_OBS_LAUNCH_WORDS]) {
+    ObsOptions accepted = {};
+    const int n_fit = obs_configure(d, P, accepted, h_R);
+    if (n_fit < 0) return FL_ERR_ARG;
+    o.last_fix = P.fix; o.last_split = P.split; o.last_fit = n_fit;
     // FL_OBS_KEEP_TREE_ROWS: the row masks of the previous launch describe this very buffer at this depth -> no pre-fill of the slab
-    P.keep_rows = o.keep_rows && o.rows_out == tree_out && o.rows_depth == max_depth;
-    o.rows_out = tree_out; o.rows_depth = max_depth;
     uint4 *const rowmask = o.rowmask;
-    if (!o.keep_rows) o.rowmask = nullptr;   // (mode off: the kernels keep no row masks; restored below -- `u` is a copy of o)
     struct Restore { FlObsScratch &o; uint4 *m; ~Restore() { o.rowmask = m; } } restore{o, rowmask};
-    const int n_split = obs_take_split_class(d, P, o.h_R);
-    o.last_fix = P.fix; o.last_split = P.split; o.last_fit = P.split ? n_split : P.fix ? d.B : 0;
+    if (P.tw_t) {
+        P.keep_rows = o.keep_rows && o.rows_out == P.tree_out && o.rows_depth == P.max_depth;
+        o.rows_out = P.tree_out; o.rows_depth = P.max_depth;
+        // mode off, or more rows than the masks' 96 bits (the tree launch alone goes beyond depth 3): the kernels keep no row masks (restored on return -- `u` is a copy of o)
+        if (!o.keep_rows || P.max_depth > 3) { o.rowmask = nullptr; P.keep_rows = 0; o.rows_out = nullptr; }
+    }
     obs_verbose(P);
     obs_keep_verify(d, P, rowmask, s);
     FlObsScratch u = o;
     if (P.merged == 1) u.order = nullptr;   // small envs, one round: workgroup k builds env k
     else u = fl_obs_env_order(o, d, s);
-    return obs_launch(d, u, P, s);
+    const int rc = obs_launch(d, u, P, s);
+    if (rc == FL_OK) obs_record_launch(P, accepted, record);
+    return rc;
 }
 
-int fl_launch_obs_tree(FlObsScratch &o, const FlDev &d, int max_depth, int pred_depth, double *out, hipStream_t s, const int16_t *label_dev) {
-    if (d.A > 1024 || pred_depth + 2 > o.pred_cap || pred_depth > 510) return FL_ERR_ARG;
-    if (max_depth > FL_MAX_TREE_DEPTH) return FL_ERR_ARG;
+int fl_launch_obs_cutils(FlObsScratch &o, const FlDev &d, int max_nodes, int pred_depth, const FlObsCutilsOut &out, hipStream_t s,
+                         int record[FL_OBS_LAUNCH_WORDS], const int16_t *label_dev, int out64) {
+    if (!obs_begin(o, d, pred_depth, record) || max_nodes > FL_OBS_MAX_NODES) return FL_ERR_ARG;
+    ObsArgs P = {};
+    P.label = label_dev;
+    P.out64 = out64;
+    obs_out_args(P, o, out);
+    obs_cutils_args(P, max_nodes, pred_depth, obs_batch_is_wide(d.B, o.n_cu));
+    obs_alone_args(d, P);
+    return obs_run(o, d, P, P.label ? nullptr : o.h_R, s, record);   // (a handle subset: no split class)
+}
+
+int fl_launch_obs_both(FlObsScratch &o, const FlDev &d, int max_nodes, int pred_depth, const FlObsCutilsOut &out, int max_depth, int tree_pred,
+                       double *tree_out, hipStream_t s, int record[FL_OBS_LAUNCH_WORDS]) {
+    if (!obs_begin(o, d, pred_depth, record) || max_nodes > OBS_CAP_C) return FL_ERR_ARG;   // (the fused kernels: 32-lane teams)
+    if (max_depth > 3 || tree_pred > pred_depth || tree_pred < 0) return FL_ERR_ARG;  // the upstream path must be a prefix
+    ObsArgs P = {};
+    obs_out_args(P, o, out);
+    obs_cutils_args(P, max_nodes, pred_depth, obs_batch_is_wide(d.B, o.n_cu));
+    obs_tree_args(d, P, max_depth, tree_pred, tree_out);
+    P.keep_mode = o.keep_rows;
+    P.h_R = o.h_R;
+    return obs_run(o, d, P, o.h_R, s, record);
+}
+
+int fl_launch_obs_tree(FlObsScratch &o, const FlDev &d, int max_depth, int pred_depth, double *out, hipStream_t s, int record[FL_OBS_LAUNCH_WORDS],
+                       const int16_t *label_dev) {
+    if (!obs_begin(o, d, pred_depth, record) || max_depth > FL_MAX_TREE_DEPTH) return FL_ERR_ARG;
     // depth 4: compact node tables only (level L of the tree has at most 2^L nodes when no direction of a cell has more than two
     // transitions -- every Flatland rail cell type): 30 slots; the DFS-slot tables of other grids stop at depth 3 (85 slots)
     if (max_depth > 3 && d.max_branch > 2) return FL_ERR_ARG;
@@ -591,35 +587,19 @@ int fl_launch_obs_tree(FlObsScratch &o, const FlDev &d, int max_depth, int pred_
     P.label = label_dev;
     obs_tree_args(d, P, max_depth, pred_depth, out);
     if (max_depth > 3 && !P.compact_t) return FL_ERR_ARG;   // (FL_OBS_NO_COMPACT)
-    if (!obs_pick_config(d, P)) return FL_ERR_ARG;
-    P.keep_rows = o.keep_rows && o.rows_out == out && o.rows_depth == max_depth;
-    o.rows_out = out; o.rows_depth = max_depth;
-    uint4 *const rowmask = o.rowmask;
-    if (!o.keep_rows || max_depth > 3) { o.rowmask = nullptr; P.keep_rows = 0; o.rows_out = nullptr; }   // (mode off, or more rows than the masks' 96 bits: no row masks)
-    struct Restore { FlObsScratch &o; uint4 *m; ~Restore() { o.rowmask = m; } } restore{o, rowmask};
-    o.last_fix = 0; o.last_split = 0; o.last_fit = 0;
-    obs_verbose(P);
-    obs_keep_verify(d, P, rowmask, s);
-    return obs_launch(d, fl_obs_env_order(o, d, s), P, s);
+    return obs_run(o, d, P, nullptr, s, record);   // (no split class has the upstream builder alone)
 }
 
 // diagnostic: the configuration obs_pick_config chooses for the fused launch (cutils + upstream tree of max_depth):
 // threads, LDS bytes, static tables in LDS, next-hop in LDS, work-list bytes, time masks, second index, items in LDS
 int fl_obs_config_of_fused(const FlDev &d, int pred_depth, int max_depth, int tree_pred, int out[11], int wide) {
     ObsArgs P = {};
-    P.wide = wide;
-    P.pred_depth = pred_depth;
-    P.max_nodes = 31;   // (the solution's tree size; the fixed launch classes are for exactly that)
-    P.tw_c = N_WORDS_C * OBS_CAP_C;
+    obs_cutils_args(P, 31, pred_depth, wide);   // (the solution's tree size; the fixed launch classes are for exactly that)
     if (max_depth > 0) obs_tree_args(d, P, max_depth, tree_pred, nullptr);
-    else {   // max_depth 0: the flatland_cutils builder alone (fl_launch_obs_cutils)
-        P.compact_t = d.max_branch <= 2 && getenv("FL_OBS_NO_COMPACT") == nullptr;
-        P.cutils_alone = getenv("FL_OBS_NO_CUTILS_MERGE") == nullptr;
-    }
-    if (!obs_pick_config(d, P)) return FL_ERR_ARG;
-    if (max_depth <= 0 && !P.merged && !P.fix) P.compact_t = 0;    // (as fl_launch_obs_cutils: the stand-alone kernel's own pass A)
-    if (getenv("FL_OBS_VERBOSE")) {   // diagnostic: the carving of the LDS, array by array (enum L_* of fl_obs_layout.h)
-        const ObsOptions &q = g_last_options;
+    else obs_alone_args(d, P);   // max_depth 0: the flatland_cutils builder alone (fl_launch_obs_cutils)
+    ObsOptions q = {};
+    if (obs_configure(d, P, q, nullptr) < 0) return FL_ERR_ARG;
+    if (obs_verbose_on()) {   // diagnostic: the carving of the LDS, array by array (enum L_* of fl_obs_layout.h)
         fprintf(stderr, "  options {nt %d, wl_bytes %d, tab %d, nh %d, tmask %d, dual %d, items %d, snext %d, partial %d, bk_room %d, own_filter %d, fb %d, raw %d, items_cap %d, wl_head %d}; "
                         "shape {merged %d, tw_c %d, tw_t %d, tpw_t %d, tree_pred %d}; bk %d tshift %d wl_occ_div %d\n",
                 q.nt, q.wl_bytes, q.tab, q.nh, q.tmask, q.dual, q.items, q.snext, q.partial, q.bk_room, q.own_filter, q.fb, q.raw, q.items_cap, q.wl_head,
@@ -640,4 +620,3 @@ int fl_obs_config_of_fused(const FlDev &d, int pred_depth, int max_depth, int tr
     out[8] = P.merged; out[9] = P.compact_t; out[10] = P.fix;   // fixed launch class (compile-time LDS carving), 0 = none
     return FL_OK;
 }
-

@@ -109,5 +109,30 @@ def test_row_matches_the_oracle_and_runs_the_kernel_it_names(row_id):
     assert ("DONE %s" % row_id) in child.stdout.splitlines()
 
 
+@pytest.mark.gpu
+def test_each_handle_reports_its_own_last_launch():
+    """two handles of different shapes (cfg1 and cfg2 size) in one process: a launch of one leaves the other's record alone"""
+    from flatland_marl_amd.hip_backend import BatchedRailEnv
+    e1 = BatchedRailEnv([util.static_of(util.load("cfg1_uniform"))])
+    e2 = BatchedRailEnv([util.static_of(util.load("cfg2_uniform"))] * 2)
+    assert (e1.B, e1.A) != (e2.B, e2.A)
+    assert e1.last_obs_launch()["mode"] == -1 and e2.last_obs_launch()["mode"] == -1
+    e1.step_synth(SEED, 0, 0, auto_reset=False)
+    e2.step_synth(SEED, 0, 0, auto_reset=False)
+    e1.obs_tree(2, 30)
+    r1 = e1.last_obs_launch()
+    assert r1["mode"] == 1 and e2.last_obs_launch()["mode"] == -1
+    e2.obs_cutils()
+    r2 = e2.last_obs_launch()
+    assert r2["mode"] not in (-1, 1) and r2 != r1
+    assert e1.last_obs_launch() == r1                    # ... after the other handle has launched
+    e1.obs_both(2, 30)
+    r1b = e1.last_obs_launch()
+    assert r1b["mode"] not in (-1, 1) and r1b != r1 and e2.last_obs_launch() == r2
+    e2.obs_tree(3, 30)
+    assert e2.last_obs_launch()["mode"] == 1 and e1.last_obs_launch() == r1b
+    e1.check(); e2.check()
+
+
 if __name__ == "__main__":
     _run(cases.BY_ID[sys.argv[1]])

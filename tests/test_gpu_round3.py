@@ -229,6 +229,7 @@ def test_capacities_are_checked_before_anything_is_allocated():
     env.check()
     with pytest.raises(FlatlandHipError, match="FL_ERR_ARG.*observation kernels' LDS"):   # ... the observation index of 10 000 cells does not fit
         env.obs_both(3, 30)
+    assert env.last_obs_launch()["mode"] == -1       # the launcher found no configuration: the handle's record says that nothing ran
     env = BatchedRailEnv([util.static_of(fx)], reserve=(8, 5000))
     env.step_synth(1, 0, 0, auto_reset=False)
     env.obs_both(3, 30)
