@@ -23,11 +23,59 @@ AUX_COLS = 4
 STATE_NAMES = ("row", "col", "dir", "state", "malf", "nmalf", "scount", "saved", "arrival",
                "old_row", "old_col", "old_dir")
 
-# every symbol include/flatland_hip.h declares
-SYMBOLS = ("fl_last_error", "fl_version", "fl_device_count", "fl_create", "fl_destroy", "fl_set_stream", "fl_sync",
-           "fl_load_env", "fl_reserve", "fl_commit", "fl_set_rng", "fl_get_rng", "fl_reset", "fl_reset_dev", "fl_step", "fl_step_synth", "fl_step_obs", "fl_check",
-           "fl_metrics", "fl_scores", "fl_info", "fl_obs_cutils", "fl_obs_cutils_policy", "fl_obs_cutils_handles", "fl_obs_cutils_tree", "fl_obs_tree", "fl_obs_tree_handles", "fl_obs_global", "fl_obs_set_mode", "fl_policy_pack", "fl_get_state", "fl_get_state_aux", "fl_set_state", "fl_motion_check", "fl_distance_map", "fl_distance_map_rebuild", "fl_distance_map_rebuild_masked", "fl_positions_map",
-           "fl_algorithmic_bytes_per_agent_step", "fl_tree_lstm_workspace_bytes", "fl_tree_lstm")
+vp, i32, u32, u64 = C.c_void_p, C.c_int, C.c_uint32, C.c_uint64
+_cutils7 = [vp] * 7        # attr, forest, adjacency, node_order, edge_order, valid_actions, props
+_tree3 = [i32, i32, vp]    # tree_max_depth, tree_pred_depth, tree_out
+# name -> (argtypes, restype) of every function include/flatland_hip.h declares, in the header's order
+_ABI = {
+    "fl_last_error": ([], C.c_char_p),
+    "fl_version": ([], i32),
+    "fl_device_count": ([], i32),
+    "fl_create": ([i32, i32, i32, i32, i32, C.POINTER(vp)], i32),
+    "fl_destroy": ([vp], None),
+    "fl_set_stream": ([vp, vp], i32),
+    "fl_sync": ([vp], i32),
+    "fl_load_env": ([vp, i32] + [vp] * 7 + [i32, u64, i32, i32, vp, i32], i32),
+    "fl_reserve": ([vp, i32, i32], i32),
+    "fl_commit": ([vp], i32),
+    "fl_set_rng": ([vp, vp, vp], i32),
+    "fl_get_rng": ([vp, vp, vp], i32),
+    "fl_reset": ([vp, vp, i32], i32),
+    "fl_reset_dev": ([vp, vp, i32], i32),
+    "fl_step": ([vp, vp, vp, vp, vp, i32], i32),
+    "fl_step_synth": ([vp, u32, u32, i32, vp, vp, vp, i32], i32),
+    "fl_step_obs": ([vp, vp, u32, u32, i32, vp, vp, vp, i32, i32, i32] + _cutils7 + _tree3, i32),
+    "fl_obs_cutils_tree": ([vp, i32, i32] + _cutils7 + _tree3, i32),
+    "fl_metrics": ([vp, vp, i32], i32),
+    "fl_scores": ([vp, vp, i32], i32),
+    "fl_check": ([vp], i32),
+    "fl_obs_cutils": ([vp, i32, i32] + _cutils7, i32),
+    "fl_obs_cutils_handles": ([vp, i32, i32, vp, i32] + _cutils7, i32),
+    "fl_obs_cutils_policy": ([vp, i32, i32] + _cutils7, i32),
+    "fl_obs_tree": ([vp, i32, i32, vp], i32),
+    "fl_obs_tree_handles": ([vp, i32, i32, vp, i32, vp], i32),
+    "fl_obs_global": ([vp, i32, i32, i32, vp, vp, vp], i32),
+    "fl_obs_set_mode": ([vp, i32], i32),
+    "fl_info": ([vp, vp, vp, vp, vp], i32),
+    "fl_policy_pack": ([i32, i32, i32] + [vp] * 7, i32),
+    "fl_tree_lstm_workspace_bytes": ([i32, i32, i32], C.c_size_t),
+    "fl_tree_lstm": ([i32, i32] + [vp] * 12 + [i32, vp, vp, vp, vp, C.c_size_t, vp], i32),
+    "fl_get_state": ([vp, vp, vp], i32),
+    "fl_get_state_aux": ([vp, vp], i32),
+    "fl_set_state": ([vp, vp, vp, vp, vp], i32),
+    "fl_motion_check": ([i32, i32, vp, vp, vp, vp], i32),
+    "fl_distance_map": ([vp, i32, C.POINTER(i32), vp, vp], i32),
+    "fl_distance_map_rebuild": ([vp], i32),
+    "fl_distance_map_rebuild_masked": ([vp, vp], i32),
+    "fl_positions_map": ([vp, i32, vp], i32),
+    "fl_algorithmic_bytes_per_agent_step": ([vp, i32, i32], C.c_double),
+}
+# diagnostics the library exports beside the public header
+_DEBUG_ABI = {
+    "fl_debug_last_obs_class": ([vp, vp], i32),
+    "fl_debug_last_obs_launch": ([vp, vp, i32], i32),
+}
+SYMBOLS = tuple(_ABI)      # every symbol include/flatland_hip.h declares
 
 _lib = None
 
@@ -61,61 +109,20 @@ def lib():
         # otherwise torch.cuda finds no device once the library below has pulled in the system runtime
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
-        vp, i32, u32, u64 = C.c_void_p, C.c_int, C.c_uint32, C.c_uint64
-        L.fl_last_error.restype = C.c_char_p
-        L.fl_create.argtypes = [i32, i32, i32, i32, i32, C.POINTER(vp)]
-        L.fl_destroy.argtypes = [vp]
-        L.fl_destroy.restype = None
-        L.fl_set_stream.argtypes = [vp, vp]
-        L.fl_sync.argtypes = [vp]
-        L.fl_load_env.argtypes = [vp, i32] + [vp] * 7 + [i32, u64, i32, i32, vp, i32]
-        L.fl_commit.argtypes = [vp]
-        L.fl_reserve.argtypes = [vp, i32, i32]
-        L.fl_distance_map_rebuild_masked.argtypes = [vp, vp]
-        L.fl_set_rng.argtypes = [vp, vp, vp]
-        L.fl_get_rng.argtypes = [vp, vp, vp]
-        L.fl_reset.argtypes = [vp, vp, i32]
-        L.fl_reset_dev.argtypes = [vp, vp, i32]
-        L.fl_get_state_aux.argtypes = [vp, vp]
-        L.fl_set_state.argtypes = [vp, vp, vp, vp, vp]
-        L.fl_motion_check.argtypes = [i32, i32, vp, vp, vp, vp]
-        L.fl_step.argtypes = [vp, vp, vp, vp, vp, i32]
-        L.fl_step_synth.argtypes = [vp, u32, u32, i32, vp, vp, vp, i32]
-        L.fl_check.argtypes = [vp]
-        L.fl_metrics.argtypes = [vp, vp, i32]
-        L.fl_scores.argtypes = [vp, vp, i32]
-        L.fl_obs_cutils.argtypes = [vp, i32, i32] + [vp] * 7
-        L.fl_obs_tree.argtypes = [vp, i32, i32, vp]
-        if hasattr(L, "fl_obs_tree_handles"):
-            L.fl_obs_tree_handles.argtypes = [vp, i32, i32, vp, i32, vp]
-        if hasattr(L, "fl_obs_cutils_policy"):
-            L.fl_obs_cutils_policy.argtypes = [vp, i32, i32] + [vp] * 7
-        if hasattr(L, "fl_obs_cutils_handles"):
-            L.fl_obs_cutils_handles.argtypes = [vp, i32, i32, vp, i32] + [vp] * 7
-        if hasattr(L, "fl_obs_global"):
-            L.fl_obs_global.argtypes = [vp, i32, i32, i32, vp, vp, vp]
-        if hasattr(L, "fl_obs_set_mode"):             # (an older build loaded through bench.py --lib for a same-box A/B run has none)
-            L.fl_obs_set_mode.argtypes = [vp, i32]
-        L.fl_step_obs.argtypes = [vp, vp, u32, u32, i32, vp, vp, vp, i32, i32, i32] + [vp] * 7 + [i32, i32, vp]
-        L.fl_obs_cutils_tree.argtypes = [vp, i32, i32] + [vp] * 7 + [i32, i32, vp]
-        L.fl_info.argtypes = [vp, vp, vp, vp, vp]
-        L.fl_policy_pack.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
-        if hasattr(L, "fl_tree_lstm"):
-            L.fl_tree_lstm_workspace_bytes.argtypes = [i32, i32, i32]
-            L.fl_tree_lstm_workspace_bytes.restype = C.c_size_t
-            L.fl_tree_lstm.argtypes = [i32, i32] + [vp] * 12 + [i32, vp, vp, vp, vp, C.c_size_t, vp]
-        L.fl_get_state.argtypes = [vp, vp, vp]
-        L.fl_distance_map.argtypes = [vp, i32, C.POINTER(i32), vp, vp]
-        L.fl_distance_map_rebuild.argtypes = [vp]
-        L.fl_positions_map.argtypes = [vp, i32, vp]
-        if hasattr(L, "fl_debug_last_obs_class"):
-            L.fl_debug_last_obs_class.argtypes = [vp, vp]       # diagnostic, not part of the public header
-        if hasattr(L, "fl_debug_last_obs_launch"):
-            L.fl_debug_last_obs_launch.argtypes = [vp, vp, i32]  # diagnostic, not part of the public header
-        L.fl_algorithmic_bytes_per_agent_step.argtypes = [vp, i32, i32]
-        L.fl_algorithmic_bytes_per_agent_step.restype = C.c_double
+        for name, (args, res) in {**_ABI, **_DEBUG_ABI}.items():
+            fn = getattr(L, name, None)        # (a library from bench.py --lib or a tool's LIB_PATH may predate the newer ones)
+            if fn is not None:
+                fn.argtypes, fn.restype = args, res
         _lib = L
     return _lib
+
+
+def _sym(name):
+    """entry point `name` of the loaded library -- which may be an older build that does not have it yet"""
+    fn = getattr(lib(), name, None)
+    if fn is None:
+        raise FlatlandHipError(1, "the loaded library has no %s (an older build loaded through --lib?)" % name)
+    return fn
 
 
 def _chk(rc):
@@ -167,21 +174,19 @@ def tree_lstm(forest, adjacency, node_order, edge_order, weights, roots_only, h,
     import torch
     N = forest.shape[-2]
     T = forest.numel() // (N * 12)
-    L = lib()
-    if not hasattr(L, "fl_tree_lstm"):
-        raise FlatlandHipError(1, "the loaded library has no fl_tree_lstm (an older build loaded through --lib?)")
+    fn = _sym("fl_tree_lstm")
     rows = (T if roots_only else T * N) * 128
     for name, o in (("h", h), ("c", c)):
         if o is not None and (o.dtype != torch.float32 or o.device != forest.device or not o.is_contiguous() or o.numel() < rows):
             raise ValueError("tree_lstm: %s must be a contiguous float32 tensor of at least %d elements on %s" % (name, rows, forest.device))
-    nbytes = L.fl_tree_lstm_workspace_bytes(T, N, int(roots_only))
+    nbytes = lib().fl_tree_lstm_workspace_bytes(T, N, int(roots_only))
     with torch.cuda.device(forest.device):
         ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=forest.device)
         s = torch.cuda.current_stream(forest.device).cuda_stream
-        _chk(L.fl_tree_lstm(T, N, forest.data_ptr(), adjacency.data_ptr(), node_order.data_ptr(), edge_order.data_ptr(),
-                            *[w.data_ptr() for w in weights], int(roots_only), h.data_ptr(),
-                            None if c is None else c.data_ptr(), None if status is None else status.data_ptr(),
-                            ws.data_ptr(), ws.numel(), C.c_void_p(s)))
+        _chk(fn(T, N, forest.data_ptr(), adjacency.data_ptr(), node_order.data_ptr(), edge_order.data_ptr(),
+                *[w.data_ptr() for w in weights], int(roots_only), h.data_ptr(),
+                None if c is None else c.data_ptr(), None if status is None else status.data_ptr(),
+                ws.data_ptr(), ws.numel(), C.c_void_p(s)))
     return h
 
 
@@ -222,8 +227,10 @@ class BatchedRailEnv:
         self.rewards = torch.zeros((B, A), dtype=torch.int32, device=self.device)
         self.dones = torch.zeros((B, A), dtype=torch.uint8, device=self.device)
         self.done_all = torch.zeros((B,), dtype=torch.uint8, device=self.device)
-        self._obs = None
-        self._tree = {}
+        self._obs = None                      # the cutils output tensors (made at the first use, dropped when max_nodes changes)
+        self._tree = {}                       # (depth,) -> the upstream-tree tensor of that depth
+        self._info = self._metrics = self._scores = self._pol = self._pol64 = None     # output tensors, made at the first use
+        self._glob = {}                       # (dtype, b0, nb) -> obs_global's three tensors
         self.use_torch_stream()
 
     def _load(self, b, e):
@@ -280,11 +287,7 @@ class BatchedRailEnv:
     def step(self, actions, auto_reset=False, filter_required=False):
         """actions: uint8 tensor [B, A] on the device (255 = agent not in the action dict).
         filter_required: ignore the actions of agents without action_required (eval_env.parse_actions)."""
-        t = self.torch
-        if not (isinstance(actions, t.Tensor) and actions.is_cuda):
-            actions = t.as_tensor(np.ascontiguousarray(actions, dtype=np.uint8)).to(self.device)
-        actions = actions.contiguous()
-        assert actions.dtype == t.uint8 and actions.shape == (self.B, self.A)
+        actions = self._actions(actions)
         _chk(lib().fl_step(self.h, actions.data_ptr(), self.rewards.data_ptr(), self.dones.data_ptr(),
                            self.done_all.data_ptr(), int(bool(auto_reset)) | (2 if filter_required else 0)))
         return self.rewards, self.dones, self.done_all
@@ -292,7 +295,7 @@ class BatchedRailEnv:
     def info(self):
         """get_info_dict as device tensors + evaluator scores of each env's last finished episode."""
         t = self.torch
-        if not hasattr(self, "_info"):
+        if self._info is None:
             B, A = self.B, self.A
             self._info = dict(action_required=t.zeros((B, A), dtype=t.uint8, device=self.device),
                               malfunction=t.zeros((B, A), dtype=t.int32, device=self.device),
@@ -308,29 +311,14 @@ class BatchedRailEnv:
         """RailEnv.step() as the reference defines it: the tick AND the observations of the new state, one launch.
         actions None: the on-device synthetic stream (seed, stream_base, kind).  Returns (rewards, dones, done_all,
         cutils observation dict, upstream tree tensor or None)."""
-        t = self.torch
-        ap = None
         if actions is not None:
-            if not (isinstance(actions, t.Tensor) and actions.is_cuda):
-                actions = t.as_tensor(np.ascontiguousarray(actions, dtype=np.uint8)).to(self.device)
-            actions = actions.contiguous()
-            assert actions.dtype == t.uint8 and actions.shape == (self.B, self.A)
-            ap = actions.data_ptr()
+            actions = self._actions(actions)
         o = self._obs_buffers()
-        tree = None
-        if tree_depth > 0:
-            key = (tree_depth,)
-            if key not in self._tree:
-                n = (4 ** (tree_depth + 1) - 1) // 3
-                self._tree[key] = t.zeros((self.B, self.A, n, 12), dtype=t.float64, device=self.device)
-            tree = self._tree[key]
-        _chk(lib().fl_step_obs(self.h, ap, int(seed), int(stream_base), int(kind), self.rewards.data_ptr(),
-                               self.dones.data_ptr(), self.done_all.data_ptr(),
+        tree = self._tree_buffer(tree_depth) if tree_depth > 0 else None
+        _chk(lib().fl_step_obs(self.h, None if actions is None else actions.data_ptr(), int(seed), int(stream_base), int(kind),
+                               self.rewards.data_ptr(), self.dones.data_ptr(), self.done_all.data_ptr(),
                                int(bool(auto_reset)) | (2 if filter_required else 0), self.max_nodes, self.pred_depth,
-                               o["agent_attr"].data_ptr(), o["forest"].data_ptr(), o["adjacency"].data_ptr(),
-                               o["node_order"].data_ptr(), o["edge_order"].data_ptr(), o["valid_actions"].data_ptr(),
-                               o["props"].data_ptr(), int(tree_depth), int(tree_pred),
-                               tree.data_ptr() if tree is not None else None))
+                               *self._cutils_ptrs(o), int(tree_depth), int(tree_pred), None if tree is None else tree.data_ptr()))
         return self.rewards, self.dones, self.done_all, o, tree
 
     def step_synth(self, seed, stream_base=0, kind=0, auto_reset=True):
@@ -340,7 +328,7 @@ class BatchedRailEnv:
 
     def metrics(self, reset=False):
         """int64[4] device tensor: (sum terminal rewards, arrived agents, agent-steps, finished episodes)."""
-        if not hasattr(self, "_metrics"):
+        if self._metrics is None:
             self._metrics = self.torch.zeros(4, dtype=self.torch.int64, device=self.device)
         _chk(lib().fl_metrics(self.h, self._metrics.data_ptr(), int(reset)))
         return self._metrics
@@ -350,7 +338,7 @@ class BatchedRailEnv:
         since the counters were reset -- the evaluator's mean_normalized_reward / mean_percentage_complete as sums
         (flatland/evaluators/service.py:875-879, 900-913).  The episode count is the scores' own counter, reset with the sums
         (independent of metrics(reset=True))."""
-        if not hasattr(self, "_scores"):
+        if self._scores is None:
             self._scores = self.torch.zeros(3, dtype=self.torch.float64, device=self.device)
         _chk(lib().fl_scores(self.h, self._scores.data_ptr(), int(reset)))
         return self._scores
@@ -376,36 +364,48 @@ class BatchedRailEnv:
                 props=t.zeros((B, A, 3), dtype=t.float64, device=dev))
         return self._obs
 
+    @staticmethod
+    def _cutils_ptrs(o, index=None):
+        """the seven flatland_cutils outputs as the C-ABI orders them; index: (adjacency, node_order, edge_order) tensors that take
+        the place of o's (obs_policy's int64 ones)"""
+        adj, no, eo = index if index is not None else (o["adjacency"], o["node_order"], o["edge_order"])
+        return (o["agent_attr"].data_ptr(), o["forest"].data_ptr(), adj.data_ptr(), no.data_ptr(), eo.data_ptr(),
+                o["valid_actions"].data_ptr(), o["props"].data_ptr())
+
+    def _tree_buffer(self, depth):
+        """the upstream-tree tensor of a depth: one object per depth, handed out by every call (see keep_tree_rows)"""
+        key = (depth,)
+        if key not in self._tree:
+            n = (4 ** (depth + 1) - 1) // 3
+            self._tree[key] = self.torch.zeros((self.B, self.A, n, 12), dtype=self.torch.float64, device=self.device)
+        return self._tree[key]
+
+    def _actions(self, actions):
+        """a host array or a device tensor -> contiguous uint8 [B, A] on the device"""
+        t = self.torch
+        if not (isinstance(actions, t.Tensor) and actions.is_cuda):
+            actions = t.as_tensor(np.ascontiguousarray(actions, dtype=np.uint8)).to(self.device)
+        actions = actions.contiguous()
+        assert actions.dtype == t.uint8 and actions.shape == (self.B, self.A)
+        return actions
+
     def obs_cutils(self, handles=None):
         """flatland_cutils.TreeObsForRailEnv.get_many + get_properties for every agent of every env.  handles: get_many(handles)
         with a strict subset (a permutation of 0 .. n-1, the same list for every env; fl_obs_cutils_handles): the tensors still
         hold every agent's rows, the trees computed against the predictions of the listed agents only."""
         o = self._obs_buffers()
         if handles is not None:
-            if not hasattr(lib(), "fl_obs_cutils_handles"):
-                raise FlatlandHipError(1, "the loaded library has no fl_obs_cutils_handles (an older build loaded through --lib?)")
             hs = np.ascontiguousarray(handles, dtype=np.int32)
-            _chk(lib().fl_obs_cutils_handles(self.h, self.max_nodes, self.pred_depth, _p(hs), len(hs), o["agent_attr"].data_ptr(),
-                                             o["forest"].data_ptr(), o["adjacency"].data_ptr(), o["node_order"].data_ptr(),
-                                             o["edge_order"].data_ptr(), o["valid_actions"].data_ptr(), o["props"].data_ptr()))
-            return o
-        _chk(lib().fl_obs_cutils(self.h, self.max_nodes, self.pred_depth, o["agent_attr"].data_ptr(),
-                                 o["forest"].data_ptr(), o["adjacency"].data_ptr(), o["node_order"].data_ptr(),
-                                 o["edge_order"].data_ptr(), o["valid_actions"].data_ptr(), o["props"].data_ptr()))
+            _chk(_sym("fl_obs_cutils_handles")(self.h, self.max_nodes, self.pred_depth, _p(hs), len(hs), *self._cutils_ptrs(o)))
+        else:
+            _chk(lib().fl_obs_cutils(self.h, self.max_nodes, self.pred_depth, *self._cutils_ptrs(o)))
         return o
 
     def obs_both(self, max_depth=2, pred_depth=30):
         """obs_cutils() and obs_tree(max_depth, pred_depth) in one launch; returns (cutils dict, tree tensor)."""
         o = self._obs_buffers()
-        n = (4 ** (max_depth + 1) - 1) // 3
-        key = (max_depth,)
-        if key not in self._tree:
-            self._tree[key] = self.torch.zeros((self.B, self.A, n, 12), dtype=self.torch.float64, device=self.device)
-        out = self._tree[key]
-        _chk(lib().fl_obs_cutils_tree(self.h, self.max_nodes, self.pred_depth, o["agent_attr"].data_ptr(),
-                                      o["forest"].data_ptr(), o["adjacency"].data_ptr(), o["node_order"].data_ptr(),
-                                      o["edge_order"].data_ptr(), o["valid_actions"].data_ptr(), o["props"].data_ptr(),
-                                      max_depth, pred_depth, out.data_ptr()))
+        out = self._tree_buffer(max_depth)
+        _chk(lib().fl_obs_cutils_tree(self.h, self.max_nodes, self.pred_depth, *self._cutils_ptrs(o), max_depth, pred_depth, out.data_ptr()))
         return o, out
 
     def keep_tree_rows(self, on=True):
@@ -414,9 +414,7 @@ class BatchedRailEnv:
         HAZARD: obs_tree / obs_both / step_obs hand out that very tensor; an in-place op on it (replacing -inf before a network, say) breaks
         the promise silently -- clone it first.  FL_OBS_KEEP_VERIFY=1 (environment, diagnostic) checks the promise before every such launch
         and latches an error for check() when a constant row is no longer -inf or a real row is."""
-        if not hasattr(lib(), "fl_obs_set_mode"):
-            raise FlatlandHipError(1, "the loaded library has no fl_obs_set_mode (an older build loaded through --lib?)")
-        _chk(lib().fl_obs_set_mode(self.h, 1 if on else 0))
+        _chk(_sym("fl_obs_set_mode")(self.h, 1 if on else 0))
 
     def policy_inputs(self, obs=None):
         """(agents_attr f32[B,A,83], forest f32[B,A,N,12], adjacency i64[B,A,N-1,3], node_order i64[B,A,N],
@@ -425,7 +423,7 @@ class BatchedRailEnv:
         t = self.torch
         o = obs if obs is not None else self.obs_cutils()
         B, A, E = o["adjacency"].shape[:3]
-        if not hasattr(self, "_pol") or self._pol[2].shape[-1] != E:
+        if self._pol is None or self._pol[2].shape[-1] != E:
             self._pol = (t.empty((B, A, E, 3), dtype=t.int64, device=self.device),
                          t.empty((B, A, E + 1), dtype=t.int64, device=self.device),
                          t.empty((B, A, E), dtype=t.int64, device=self.device))
@@ -441,34 +439,23 @@ class BatchedRailEnv:
         t = self.torch
         o = self._obs_buffers()
         B, A, N = self.B, self.A, self.max_nodes
-        if not hasattr(self, "_pol64") or self._pol64[1].shape[-1] != N:       # (max_nodes may be set anew by a builder's set_env)
+        if self._pol64 is None or self._pol64[1].shape[-1] != N:       # (max_nodes may be set anew by a builder's set_env)
             self._pol64 = (t.empty((B, A, N - 1, 3), dtype=t.int64, device=self.device), t.empty((B, A, N), dtype=t.int64, device=self.device),
                            t.empty((B, A, N - 1), dtype=t.int64, device=self.device))
         adj, no, eo = self._pol64
-        L = lib()
-        if not hasattr(L, "fl_obs_cutils_policy"):
-            raise FlatlandHipError(1, "the loaded library has no fl_obs_cutils_policy (an older build loaded through --lib?)")
-        _chk(L.fl_obs_cutils_policy(self.h, self.max_nodes, self.pred_depth, o["agent_attr"].data_ptr(), o["forest"].data_ptr(), adj.data_ptr(),
-                                    no.data_ptr(), eo.data_ptr(), o["valid_actions"].data_ptr(), o["props"].data_ptr()))
+        _chk(_sym("fl_obs_cutils_policy")(self.h, self.max_nodes, self.pred_depth, *self._cutils_ptrs(o, self._pol64)))
         return o["agent_attr"], o["forest"], adj, no, eo
 
     def obs_tree(self, max_depth=2, pred_depth=30, handles=None):
         """upstream TreeObsForRailEnv(max_depth, ShortestPathPredictorForRailEnv(pred_depth)) as a dense tensor.  handles: get_many(handles)
         with a list (a permutation of 0 .. n-1, the same for every env; fl_obs_tree_handles): every agent's rows, the trees computed against
         the predictions of the listed agents only, by list position (observations.py:72-83, 337-366)."""
-        n = (4 ** (max_depth + 1) - 1) // 3
-        key = (max_depth,)
-        if key not in self._tree:
-            self._tree[key] = self.torch.zeros((self.B, self.A, n, 12), dtype=self.torch.float64, device=self.device)
-        out = self._tree[key]
+        out = self._tree_buffer(max_depth)
         if handles is not None:
-            L = lib()
-            if not hasattr(L, "fl_obs_tree_handles"):
-                raise FlatlandHipError(1, "the loaded library has no fl_obs_tree_handles (an older build loaded through --lib?)")
             hs = np.ascontiguousarray(handles, dtype=np.int32)
-            _chk(L.fl_obs_tree_handles(self.h, max_depth, pred_depth, _p(hs), len(hs), out.data_ptr()))
-            return out
-        _chk(lib().fl_obs_tree(self.h, max_depth, pred_depth, out.data_ptr()))
+            _chk(_sym("fl_obs_tree_handles")(self.h, max_depth, pred_depth, _p(hs), len(hs), out.data_ptr()))
+        else:
+            _chk(lib().fl_obs_tree(self.h, max_depth, pred_depth, out.data_ptr()))
         return out
 
     def _env_range(self, envs):
@@ -496,8 +483,6 @@ class BatchedRailEnv:
         b0, nb = self._env_range(envs)
         if not (0 <= b0 and nb >= 1 and b0 + nb <= self.B):
             raise ValueError("obs_global: env range [%d, %d) is not inside [0, %d)" % (b0, b0 + nb, self.B))
-        if not hasattr(self, "_glob"):
-            self._glob = {}
         key = (dtype, b0, nb)
         if key not in self._glob:
             H, W, A, dev = self.H, self.W, self.A, self.device
@@ -525,7 +510,6 @@ class BatchedRailEnv:
         """inject the dynamic agent state (fl_set_state): state int32[B, A, 12] as state() returns it."""
         state = np.ascontiguousarray(state, dtype=np.int32)
         assert state.shape == (self.B, self.A, STATE_COLS)
-        keep = [state]
         if aux is not None:
             aux = np.ascontiguousarray(aux, dtype=np.int32)
             assert aux.shape == (self.B, self.A, AUX_COLS)
@@ -535,7 +519,6 @@ class BatchedRailEnv:
         if done_all is not None:
             done_all = np.ascontiguousarray(done_all, dtype=np.uint8)
             assert done_all.shape == (self.B,)
-        keep += [aux, elapsed, done_all]
         _chk(lib().fl_set_state(self.h, _p(state), None if aux is None else _p(aux), None if elapsed is None else _p(elapsed),
                                 None if done_all is None else _p(done_all)))
 
@@ -577,7 +560,7 @@ class BatchedRailEnv:
         """diagnostic: (fixed launch class, split, envs on the class's body) of the last obs_both / step_obs launch -- class 0 = the
         runtime-carving kernel; split 1 = the class served only the envs that fit it, the others ran the runtime-carving body"""
         out = (C.c_int * 3)()
-        _chk(lib().fl_debug_last_obs_class(self.h, out))
+        _chk(_sym("fl_debug_last_obs_class")(self.h, out))
         return tuple(out)
 
     LAUNCH_FIELDS = ("mode", "var", "fix", "split", "fix2", "nt", "lds", "wl_bytes", "tab", "nh", "tmask", "dual", "items", "items_cap", "snext",
@@ -588,10 +571,8 @@ class BatchedRailEnv:
         -- a dict of LAUNCH_FIELDS: the kernel (k_obs<mode, var> of launch class `fix`, 0 = the runtime carving; split 1 / 2 = the class's split
         kernel, fix2 the second class of a split-2 kernel), threads and dynamic LDS bytes of the launch, the ObsOptions the launcher's preference
         walk accepted (wl_bytes .. wl_head) and what it derived from them (bk, tshift, compact_t; label = a handle subset).  mode -1: no launch yet."""
-        if not hasattr(lib(), "fl_debug_last_obs_launch"):
-            raise FlatlandHipError(1, "the loaded library has no fl_debug_last_obs_launch (an older build loaded through --lib?)")
         out = (C.c_int * len(self.LAUNCH_FIELDS))()
-        _chk(lib().fl_debug_last_obs_launch(self.h, out, len(out)))
+        _chk(_sym("fl_debug_last_obs_launch")(self.h, out, len(out)))
         return dict(zip(self.LAUNCH_FIELDS, out))
 
     def algorithmic_bytes_per_agent_step(self, with_cutils_obs=True, tree_depth=0):

@@ -10,12 +10,14 @@ into the reference's dicts / lists.  reset(regenerate_rail=True, regenerate_sche
 description a reference env has after reset() (RailEnv.from_static, flatland_marl_amd.from_reference_env).
 """
 import collections
+import time
 from enum import IntEnum
 
 import numpy as np
 
 from . import generators
 from .hip_backend import BatchedRailEnv, EpisodeDoneError, FlatlandHipError
+from .reference_bridge import static_of_env, agents_static_of_env, dynamic_state_of_env, AGENT_STATIC_KEYS
 
 # flatland.envs.malfunction_generators.MalfunctionParameters / ParamMalfunctionGen (malfunction_generators.py:19-53)
 MalfunctionParameters = collections.namedtuple("MalfunctionParameters", ["malfunction_rate", "min_duration", "max_duration"])
@@ -137,8 +139,17 @@ class _Rail:
         self.height, self.width = self.grid.shape
 
 
+def distance_map_of(batch, b=0):
+    """DistanceMap.get() (flatland/envs/distance_map.py:27-45) of env b of a batch: float64 [A, H, W, 4], inf = unreachable -- the
+    device keeps one u16 map per unique target (0xFFFF = unreachable) and every agent's target slot"""
+    dm, slot = batch.distance_map(b)
+    full = dm[slot].astype(np.float64)
+    full[dm[slot] == 0xFFFF] = np.inf
+    return full
+
+
 class _DistanceMap:
-    """DistanceMap.get() (flatland/envs/distance_map.py:27-45): float64 [A, H, W, 4], inf = unreachable."""
+    """env.distance_map of this library's RailEnv: get() computed once per map"""
 
     def __init__(self, env):
         self._env = env
@@ -146,10 +157,7 @@ class _DistanceMap:
 
     def get(self):
         if self._cache is None:
-            dm, slot = self._env._batch.distance_map(0)
-            full = dm[slot].astype(np.float64)
-            full[dm[slot] == 0xFFFF] = np.inf
-            self._cache = full
+            self._cache = distance_map_of(self._env._batch)
         return self._cache
 
 
@@ -203,33 +211,219 @@ def upstream_handle_list(handles, n_agents, has_predictor=True):
     return h
 
 
-class TreeObsForRailEnv(ObservationBuilder):
-    """Drop-in for flatland_cutils.TreeObsForRailEnv(max_nodes, max_pred_depth) (treeobs.h:133-169)."""
-    checks_errors = True
+# ---- where a builder's B = 1 batch comes from and how it is kept current: this library's own RailEnv (_OwnBatch) or any other env
+# object (_EnvBinding).  The builders below hold everything else once.
+class _Source:
+    computes_at_reset = False     # True: the cutils builder's reset() runs one AgentsLoader::update itself (treeobs.cpp:22-28)
+    profile = None                # a dict: seconds per stage of the calls, accumulated (tools/plugin_latency.py)
+    dead = None                   # the DeadlockChecker's sticky flags as of the last call (deadlock_checker.cpp:3-9)
 
-    def __init__(self, max_nodes=31, max_pred_depth=500):
+    def clock(self):
+        return time.perf_counter() if self.profile is not None else 0.0
+
+    def lap(self, key, t0, sync=False):
+        """profiling only: seconds since t0 into stage `key` (sync: after the handle's stream has drained)"""
+        if self.profile is None:
+            return t0
+        if sync:
+            self.batch.sync()
+        t1 = time.perf_counter()
+        self.profile[key] = self.profile.get(key, 0.0) + (t1 - t0)
+        return t1
+
+
+class _OwnBatch(_Source):
+    """this library's own RailEnv: the env's device-resident batch IS the state, nothing is read or pushed per call (the sticky
+    deadlock flags live in it too)"""
+
+    def __init__(self, env):
+        self.env = env
+
+    @property
+    def batch(self):
+        return self.env._batch        # (a new object with every map the env adopts)
+
+    def configure(self, max_nodes, pred_depth):
+        b = self.batch
+        if b is not None:             # (before the env's first reset() there is nothing to configure yet: reset() binds again)
+            b.max_nodes, b.pred_depth = max_nodes, pred_depth
+            b._obs = None
+
+    def load_static(self, env, max_nodes=31, pred_depth=500):
+        pass
+
+    def current(self, env, what):
+        return self.batch
+
+    def pred_depth(self, builder):
+        return builder.pred_depth
+
+    def properties(self, env):
+        cfg = {"curr_step": env._elapsed_steps, "n_agents": env.get_num_agents(), "max_timesteps": env._max_episode_steps,
+               "height": env.height, "width": env.width}
+        return (cfg, [a.earliest_departure for a in env.agents], [a.latest_arrival for a in env.agents],
+                [a.speed_counter.speed for a in env.agents])
+
+
+def _agents_signature(st):
+    return tuple(np.asarray(st[k]).tobytes() for k in AGENT_STATIC_KEYS)
+
+
+def _static_signature(st):
+    g = np.asarray(st["grid"])
+    return (g.shape, g.tobytes()) + _agents_signature(st)
+
+
+class _EnvBinding(_Source):
+    """a caller-owned env mirrored into a B = 1 batch on the device: the static side is read at reset() (load_static), the agents'
+    dynamic state before every launch (push_dynamic), duck-typed -- see flatland_marl_amd/plugin.py"""
+    make_batch = BatchedRailEnv          # (tests of the host-side extraction substitute a recorder: there is no CPU compute path)
+    computes_at_reset = True
+
+    def __init__(self, device, verify_distance_map):
+        self.device = device
+        self.verify = verify_distance_map
+        self.batch = None
+        self.sig = None
+        self.static = None
+        self.dead = None
+        self.elapsed = 0
+        self.agents_sig = None    # the agents' line / timetable as of the last static read (compared on every call)
+        self.profile = None
+
+    def configure(self, max_nodes, pred_depth):
+        pass                      # (set_env reads nothing, treeobs.cpp:17-21 -- a reference RailEnv has no rail yet: load_static does it)
+
+    def load_static(self, env, max_nodes=31, pred_depth=500):
+        st = static_of_env(env)
+        sig = _static_signature(st)
+        if sig != self.sig:
+            H, W = st["grid"].shape
+            b = self.batch
+            if b is not None and (b.H, b.W, b.A) == (H, W, len(st["init_dir"])):
+                try:
+                    b.replace_env(0, st)          # same shape: into the live handle (fl_load_env + fl_commit)
+                except FlatlandHipError as e:
+                    if e.code != 6:               # FL_ERR_CAPACITY: more rail cells / targets than the first map -> new handle
+                        raise
+                    b = None
+            else:
+                b = None
+            if b is None:
+                if self.batch is not None:
+                    self.batch.close()
+                b = self.make_batch([st], device=self.device, max_nodes=max_nodes, pred_depth=pred_depth)
+            self.batch, self.sig, self.static = b, sig, st
+            if self.verify:
+                self.verify_distance_map(env)
+        self.agents_sig = _agents_signature(st)
+        if self.batch.max_nodes != max_nodes:
+            self.batch._obs = None
+        self.batch.max_nodes, self.batch.pred_depth = max_nodes, pred_depth
+        self.dead = np.zeros(self.batch.A, dtype=np.int32)
+        return st
+
+    def verify_distance_map(self, env):
+        ours = distance_map_of(self.batch)
+        theirs = np.asarray(env.distance_map.get(), dtype=np.float64)
+        if theirs.shape != ours.shape or not np.array_equal(ours, theirs):
+            raise ValueError("env.distance_map is not the distance map of env.rail.grid towards the agents' targets "
+                             "(distance_map.py:57-160): a caller-supplied distance map is not supported")
+
+    def push_dynamic(self, env):
+        """Agent::Agent for every agent (loader.cpp:8-120); the line and timetable are re-read too, like the reference does on
+        every call (loader.cpp:19-73), and a change of them reloads the static side.  The rail is the reference's RailLoader: read
+        at reset() only (loader.cpp:329-333) -- nothing here is proportional to the map."""
+        t0 = self.clock()
+        if _agents_signature(agents_static_of_env(env)) != self.agents_sig:
+            dead = self.dead
+            self.load_static(env, self.batch.max_nodes, self.batch.pred_depth)
+            if dead is not None and len(dead) == len(self.dead):
+                self.dead = dead                 # the checker object lives until reset() (loader.cpp:186-199)
+        state, aux, elapsed = dynamic_state_of_env(env)
+        aux[:, 2] = self.dead
+        self.elapsed = elapsed
+        t0 = self.lap("extract_python", t0)
+        self.batch.set_state(state[None], aux[None], np.array([elapsed], dtype=np.int32))
+        self.lap("fl_set_state", t0)
+
+    def current(self, env, what):
+        if self.batch is None:
+            raise RuntimeError("%s before reset()" % what)
+        self.push_dynamic(env)
+        return self.batch
+
+    def pred_depth(self, builder):
+        """the predictor is the caller's object too: read again at every call"""
+        return builder.pred_depth if builder.predictor is None else int(builder.predictor.max_depth)
+
+    def properties(self, env):
+        st = self.static
+        H, W = st["grid"].shape
+        cfg = {"curr_step": int(self.elapsed), "n_agents": len(st["init_dir"]), "max_timesteps": int(st["T"]),
+               "height": int(getattr(env, "height", H)), "width": int(getattr(env, "width", W))}
+        return cfg, st["earliest"], st["latest"], st["speed"]
+
+
+class _DeviceObs(ObservationBuilder):
+    """what the three builders share: the binding for a caller-owned env, and the choice of the source when the env is set"""
+    checks_errors = True          # (RailEnv.step leaves the one synchronising error check of a step to the builder)
+
+    def __init__(self, device=0, verify_distance_map=False):
         super().__init__()
-        self.max_nodes, self.max_pred_depth = max_nodes, max_pred_depth
-        self._last = None
+        self._bind = _EnvBinding(device, verify_distance_map)
+        self._src = self._bind
 
     def set_env(self, env):
         self.env = env
-        if env._batch is not None:            # (before the env's first reset() there is nothing to configure yet: reset() binds again)
-            env._batch.max_nodes, env._batch.pred_depth = self.max_nodes, self.max_pred_depth
-            env._batch._obs = None
+        self._src = _OwnBatch(env) if isinstance(env, RailEnv) else self._bind
 
-    def get_many(self, handles):
-        """-> (agent_attr [A][83], (nodes [A][N][12], adjacency [A][N-1][3], node_order [A][N], edge_order [A][N-1]))
-        as nested lists, like the pybind11 STL casters return them (treeobs.h:160-161)."""
-        h = list(handles)
-        o = self.env._batch.obs_cutils(cutils_handle_list(h, self.env.get_num_agents()))
-        self.env._batch.check()       # the one synchronising error check of a step (RailEnv.step leaves it to the builder)
+
+class TreeObsForRailEnv(_DeviceObs):
+    """Drop-in for flatland_cutils.TreeObsForRailEnv(max_nodes, max_pred_depth) (treeobs.h:133-169), for any env object."""
+
+    def __init__(self, max_nodes=31, max_pred_depth=500, *, device=0, verify_distance_map=False):
+        super().__init__(device, verify_distance_map)
+        self.max_nodes, self.max_pred_depth = int(max_nodes), int(max_pred_depth)
+        self._last = None
+
+    def set_env(self, env):                      # treeobs.cpp:17-21: keeps the object
+        super().set_env(env)
+        self._src.configure(self.max_nodes, self.max_pred_depth)
+
+    def reset(self):                             # treeobs.cpp:22-28
+        self._src.load_static(self.env, self.max_nodes, self.max_pred_depth)
+        if self._src.computes_at_reset:
+            self._compute()                      # the checker sees the state at reset, and get_properties() is valid straight after it
+
+    def _compute(self, handles=None):
+        s = self._src
+        b = s.current(self.env, "TreeObsForRailEnv.get_many()")
+        t0 = s.clock()
+        # a strict subset: the reference's conflict test then sees the listed agents' predictions only, by list position
+        # (treeobs.cpp:50-62) -- fl_obs_cutils_handles; lists the reference has no defined behaviour for raise ValueError
+        o = b.obs_cutils(None if handles is None else cutils_handle_list(handles, b.A))
+        b.check()                                # (synchronises: the kernel has run)
+        t0 = s.lap("kernel", t0)
         self._last = {k: v[0].cpu().numpy() for k, v in o.items()}
-        L = self._last
-        # (the attribute rows of ALL agents, the trees of the listed ones in list order: feature_parser.cpp:100-118, treeobs.cpp:93-101)
-        return (L["agent_attr"].tolist(),
-                (L["forest"][h].tolist(), L["adjacency"][h].tolist(), L["node_order"][h].tolist(),
-                 L["edge_order"][h].tolist()))
+        s.dead = self._last["props"][:, 1].astype(np.int32)
+        s.lap("read_back", t0)
+        return self._last
+
+    def get_many(self, handles, as_arrays=False):
+        """-> (agent_attr [A][83], (nodes [n][N][12], adjacency [n][N-1][3], node_order [n][N], edge_order [n][N-1])) as nested
+        lists, what the pybind11 STL casters return (treeobs.h:160-161, treeobs.cpp:30-108); as_arrays=True: the same five as
+        numpy arrays (float32 / int32), without the conversion to Python lists."""
+        h = list(handles)
+        L = self._compute(h)
+        # the attribute rows of ALL agents (feature_parser.cpp:100-118), the trees of the listed ones in list order (treeobs.cpp:93-101)
+        trees = tuple(L[k][h] for k in ("forest", "adjacency", "node_order", "edge_order"))
+        if as_arrays:
+            return L["agent_attr"], trees
+        t0 = self._src.clock()
+        out = (L["agent_attr"].tolist(), tuple(a.tolist() for a in trees))
+        self._src.lap("tolist", t0)
+        return out
 
     def get(self, handle=0):
         """ONE agent's observation as RailEnv would see it: its row of get_many(every handle) (the pybind11 class has no get();
@@ -238,16 +432,21 @@ class TreeObsForRailEnv(ObservationBuilder):
         return attr[handle], (nodes[handle], adj[handle], node_order[handle], edge_order[handle])
 
     def get_properties(self):
-        """treeobs.cpp:612-640"""
-        e, L = self.env, self._last
-        cfg = {"curr_step": e._elapsed_steps, "n_agents": e.get_num_agents(), "max_timesteps": e._max_episode_steps,
-               "height": e.height, "width": e.width}
+        """treeobs.cpp:612-640: the values of the last get_many() / reset()"""
+        L = self._last
+        if L is None:
+            raise RuntimeError("TreeObsForRailEnv.get_properties() before get_many()")
+        cfg, earliest, latest, speed = self._src.properties(self.env)
         props = {"dist_target": L["props"][:, 0].tolist(), "deadlocked": L["props"][:, 1].tolist(),
                  "ready_not_depart": L["props"][:, 2].tolist(),
-                 "earliest_departure": [float(a.earliest_departure) for a in e.agents],
-                 "latest_arrival": [float(a.latest_arrival) for a in e.agents],
-                 "speed": [float(np.float32(a.speed_counter.speed)) for a in e.agents]}
+                 "earliest_departure": [float(v) for v in earliest],
+                 "latest_arrival": [float(v) for v in latest],
+                 "speed": [float(np.float32(v)) for v in speed]}
         return cfg, props, L["valid_actions"].astype(bool).tolist()
+
+    def last_arrays(self):
+        """the tensors of the last call, for callers that want arrays instead of nested lists"""
+        return self._last
 
 
 NODE_FIELDS = ("dist_own_target_encountered", "dist_other_target_encountered", "dist_other_agent_encountered",
@@ -290,32 +489,47 @@ def dense_from_nodes(node, max_depth):
     return np.array(rows, dtype=np.float64)
 
 
-class TreeObsUpstream(ObservationBuilder):
+class TreeObsUpstream(_DeviceObs):
     """flatland.envs.observations.TreeObsForRailEnv(max_depth, ShortestPathPredictorForRailEnv(pred_depth))
-    (observations.py:34-532).  get_many() returns what the reference returns: {handle: Node}, nested namedtuples with a
-    `childs` dict ('L', 'F', 'R', 'B' -> Node or -inf).  get_many_dense() / the batched tensor API keep the dense form the
-    kernel writes: float64 [N(max_depth), 12] per agent in DFS pre-order (node, L, F, R, B), missing subtree = -inf."""
+    (observations.py:34-532), for any env object.  get_many() returns what the reference returns: {handle: Node}, nested namedtuples
+    with a `childs` dict ('L', 'F', 'R', 'B' -> Node or -inf).  get_many_dense() / the batched tensor API keep the dense form the
+    kernel writes: float64 [N(max_depth), 12] per agent in DFS pre-order (node, L, F, R, B), missing subtree = -inf.
+    predictor: anything with `max_depth` (the shortest-path predictor, predictions.py:91-180, is part of the kernel); without one the
+    conflict prediction runs pred_depth deep, pred_depth < 0: not at all (observations.py:72)."""
 
-    checks_errors = True
     FIELDS = NODE_FIELDS
     tree_explored_actions_char = ["L", "F", "R", "B"]     # observations.py:41
 
-    def __init__(self, max_depth=2, pred_depth=30, predictor=None):
-        super().__init__()
-        self.max_depth = max_depth
+    def __init__(self, max_depth=2, pred_depth=30, predictor=None, *, device=0, verify_distance_map=False):
+        super().__init__(device, verify_distance_map)
+        self.max_depth = int(max_depth)
+        self.predictor = predictor
         self.pred_depth = pred_depth if predictor is None else getattr(predictor, "max_depth", pred_depth)
         self.observation_dim = 11                         # observations.py:46
 
+    def set_env(self, env):                      # observations.py:524-527
+        super().set_env(env)
+        if self.predictor is not None and hasattr(self.predictor, "set_env"):
+            self.predictor.set_env(env)
+
+    def reset(self):                             # observations.py:57-58: the targets' lookup = the static side
+        self._src.load_static(self.env)
+
     def get_many_dense(self, handles=None):
-        handles = list(range(self.env.get_num_agents())) if handles is None else list(handles)
-        t = self.env._batch.obs_tree(self.max_depth, self.pred_depth, upstream_handle_list(handles, self.env.get_num_agents(), self.pred_depth >= 0) if handles else None)
-        self.env._batch.check()
+        """{handle: float64 [N(max_depth), 12]}; the dense form is this library's own: None = every agent"""
+        s = self._src
+        b = s.current(self.env, "TreeObsForRailEnv.get_many()")
+        pred = s.pred_depth(self)
+        hs = list(range(b.A)) if handles is None else list(handles)
+        # a handle list: the reference's semantics (the listed agents' predictions only, by list position: observations.py:72-83, 337-366)
+        t = b.obs_tree(self.max_depth, pred, upstream_handle_list(hs, b.A, pred >= 0) if hs else None)
+        b.check()
         arr = t[0].cpu().numpy()
-        return {h: arr[h] for h in handles}
+        return {h: arr[h] for h in hs}
 
     def get_many(self, handles=None):
         if handles is None:
-            return {}                 # observations.py:66-67: None -> no handles, no observations (get_many_dense(None): every agent)
+            return {}                 # observations.py:66-67: None -> no handles, no observations
         return {h: nodes_from_dense(a, self.max_depth) for h, a in self.get_many_dense(handles).items()}
 
     def get(self, handle=0):
@@ -324,34 +538,31 @@ class TreeObsUpstream(ObservationBuilder):
         return self.get_many(list(range(len(self.env.agents))))[handle]
 
 
-class GlobalObsForRailEnv(ObservationBuilder):
-    """flatland.envs.observations.GlobalObsForRailEnv (observations.py:535-611): get_many(handles) -> {handle: (rail_obs [H,W,16],
-    agents_state [H,W,5], targets [H,W,2])}, float64 numpy; rail_obs is ONE array for every handle, built at reset() (:560-566).
-    Computed by the GPU (fl_obs_global) for every agent in one launch; get_many(None) is {} as in the reference."""
+class GlobalObsForRailEnv(_DeviceObs):
+    """flatland.envs.observations.GlobalObsForRailEnv (observations.py:535-611), for any env object: get_many(handles) -> {handle:
+    (rail_obs [H,W,16], agents_state [H,W,5], targets [H,W,2])}, float64 numpy; rail_obs is ONE array for every handle, built at
+    reset() (:560-566).  Computed by the GPU (fl_obs_global) for every agent in one launch; get_many(None) is {} as in the reference."""
 
-    checks_errors = True
-
-    def __init__(self):
-        super().__init__()
+    def __init__(self, *, device=0, verify_distance_map=False):
+        super().__init__(device, verify_distance_map)
         self.rail_obs = None
 
-    def _batch(self):
-        return self.env._batch
-
     def reset(self):
-        r, _, _ = self._batch().obs_global(rail=True)
-        self._batch().check()
+        self._src.load_static(self.env)
+        b = self._src.batch
+        r, _, _ = b.obs_global(rail=True)
+        b.check()
         self.rail_obs = r[0].cpu().numpy()
 
     def get_many(self, handles=None):
         if handles is None:
             return {}                 # core/env_observation_builder.py:52-55: no handles, no observations
+        b = self._src.current(self.env, "GlobalObsForRailEnv.get_many()")
         handles = list(handles)
         if not handles:
             return {}
-        b = self._batch()
         _, ast, tgt = b.obs_global(rail=False)
-        b.check()                     # the one synchronising error check of a step (RailEnv.step leaves it to the builder)
+        b.check()
         ast, tgt = ast[0].cpu().numpy(), tgt[0].cpu().numpy()
         return {h: (self.rail_obs, ast[h], tgt[h]) for h in handles}
 

@@ -130,3 +130,42 @@ def test_verify_distance_map_accepts_the_reference_map_and_refuses_another():
     b.set_env(env2)
     with pytest.raises(ValueError, match="distance map"):
         b.reset()
+
+
+def _equal(a, b):
+    """element for element, through the dicts / tuples / lists / Nodes / arrays the builders return"""
+    if isinstance(a, np.ndarray) or isinstance(b, np.ndarray):
+        return type(a) is type(b) and a.dtype == b.dtype and a.shape == b.shape and bool(np.array_equal(a, b))
+    if isinstance(a, dict):
+        return isinstance(b, dict) and a.keys() == b.keys() and all(_equal(a[k], b[k]) for k in a)
+    if isinstance(a, (list, tuple)):
+        return type(a) is type(b) and len(a) == len(b) and all(_equal(x, y) for x, y in zip(a, b))
+    return type(a) is type(b) and a == b
+
+
+@pytest.mark.parametrize("kind", ["cutils", "upstream", "global"])
+def test_both_sources_one_builder_same_answer(kind):
+    """the same builder class on this library's own RailEnv (the env's device-resident state, read in place) and on a caller-owned env
+    object (mirrored per call): the first 40 steps of a golden episode with malfunctions, one stepped with the golden actions, the
+    other replaying the golden states -- get_many(every handle) of the two is equal element for element after every step"""
+    from flatland_marl_amd import plugin
+    from flatland_marl_amd.rail_env import RailEnv
+    make = {"cutils": lambda: plugin.TreeObsForRailEnv(31, 500),
+            "upstream": lambda: plugin.TreeObsUpstream(2, util._NS(max_depth=30)),
+            "global": lambda: plugin.GlobalObsForRailEnv()}[kind]
+    fx = util.load("cfg1_spfollow")
+    own, mirrored = make(), make()
+    env = RailEnv.from_static(util.static_of(fx), obs_builder_object=own)
+    env.reset(regenerate_rail=False, regenerate_schedule=False)
+    duck = util.DuckEnv(fx)
+    mirrored.set_env(duck)
+    mirrored.reset()
+    handles = list(range(env.get_num_agents()))
+    assert len(handles) == duck.get_num_agents() and fx["s_malf"][:40].max() > 0
+    for t, row in enumerate(util.actions_of(fx)[:40], start=1):
+        env.step({i: int(a) for i, a in enumerate(row) if a != 255})
+        duck.goto(t)
+        a, b = own.get_many(handles), mirrored.get_many(handles)
+        assert len(a) > 0 and _equal(a, b), f"{kind}: get_many differs after step {t}"
+        if kind == "cutils":
+            assert _equal(own.get_properties(), mirrored.get_properties()), f"get_properties differs after step {t}"
