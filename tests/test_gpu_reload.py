@@ -116,15 +116,24 @@ def test_replacement_without_reserve_is_limited_to_the_first_commit_sizes():
 
 def test_masked_rebuild_touches_only_the_masked_envs_and_reset_takes_a_device_mask():
     import torch
+    from oracle import orc
+    from flatland_marl_amd import synth
     fx = util.load("cfg4_fwd_head")
     st = util.static_of(fx)
     env = _env([st, st, st])
-    for _ in range(30):
+    oracles = [orc.OracleEnv(st) for _ in range(3)]
+    for t in range(30):
         env.step_synth(3, 0, 1, auto_reset=True)
+        for b, oe in enumerate(oracles):
+            oe.step(synth.forward_biased_actions(3, b, t, env.A))
     mask = torch.tensor([0, 1, 0], dtype=torch.uint8, device="cuda")
     env.rebuild_distance_maps(mask)
     for b in range(3):
         _same(env.distance_map(b)[0], fx["dm_u16"], f"env {b} distance map")
+    # the same map before and after says little about a rebuild: the tables the observations read (segments, next-hop, hop8) are rebuilt with
+    # it, and the observations of all three envs are still the oracle's (a rebuild from scratch, at a size where the work is spread over a
+    # looping grid: tests/test_gpu_handmaps.py)
+    _compare(env, oracles, "after the masked rebuild")
     s0 = env.state()[0].copy()
     env.reset(mask)                               # device mask: only env 1 starts over
     s1, el = env.state()

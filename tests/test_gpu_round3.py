@@ -217,7 +217,9 @@ def test_capacities_are_checked_before_anything_is_allocated():
     table, visited bitmaps and queues in LDS: about 10 900 rail cells); an env that does not fit a live batch's capacities is
     FL_ERR_CAPACITY at fl_load_env (tests/test_gpu_reload.py).  The kernel-side FL_ERR_CAPACITY latches (BFS ring, 16-bit
     distances of a tree walk) cannot be reached below those limits: a BFS level of a map of 10 900 cells has at most ~1 000
-    states (ring of 4 096), a 31-node tree walks at most 4 laps of the longest possible loop (43 600 < 65 535)."""
+    states (ring of 4 096; the widest levels a grid can have are a full mesh's, about eight states per cell of its side --
+    tests/golden/handmap_mesh33.npz has levels of 260 at 33 x 33, which tests/test_gpu_handmaps.py runs through the kernel),
+    a 31-node tree walks at most 4 laps of the longest possible loop (43 600 < 65 535)."""
     from flatland_marl_amd.hip_backend import BatchedRailEnv, FlatlandHipError
     fx = util.load("cfg1_uniform")
     with pytest.raises(FlatlandHipError, match="FL_ERR_ARG.*distance-map kernel's LDS"):
