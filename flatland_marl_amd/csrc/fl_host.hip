@@ -21,6 +21,12 @@ static void set_err(const char *fmt, ...) {
     vsnprintf(g_err, sizeof g_err, fmt, ap);
     va_end(ap);
 }
+void fl_set_error(const char *fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof g_err, fmt, ap);
+    va_end(ap);
+}
 const char *fl_last_error(void) { return g_err; }
 int fl_version(void) { return 100; }
 int fl_device_count(void) {

@@ -1,0 +1,447 @@
+// fl_policy_head.h -- the policy network after its tree encoder (solution/nn/net_tree.py:82-103) and the actor's choice of an
+// action (solution/plfActor.py:30-46) for a whole batch, float32, gfx950.  Included by fl_policy_head.hip, which holds the entry
+// points fl_policy_head / fl_policy_head_workspace_bytes (include/flatland_policy.h).
+//
+// Rows = the B*A (env, agent) pairs, flattened.  Everything but the attention is independent per row, so a workgroup (4 waves)
+// takes a tile of 32 consecutive rows -- which may straddle envs -- and keeps a whole chain of layers in LDS:
+//   k_ph_embed          attr MLP (83 -> 256 -> 256 -> 256 -> 128, GELU each) -> embedding [attr | tree] (256) -> q, k, v of block 1
+//   k_ph_attn           softmax(q k^T / 8) v of one block: a workgroup per (env, tile of 32 queries), a wave per head
+//   k_ph_block<false>   out_proj -> att_mlp = GELU(Linear [input | attention]) = the next block's input -> its q, k, v
+//   k_ph_block<true>    out_proj -> att_mlp -> actor_net and critic_net on [embedding | att_mlp] -> logits, a row's critic value,
+//                       the action
+//   k_ph_value          mean of the critic values over the agents of an env, in a fixed order
+// = embed, (attn, block) x 3 and value: 8 launches on one stream (7 without value).
+//
+// Products are f32-input MFMA (v_mfma_f32_32x32x2_f32, exact f32) as in fl_tree_lstm.h: a wave computes a block of 32 rows x
+// 32 output features, lane l holds the A operand of row l & 31 and the weight row of feature l & 31, step s of a 32-wide chunk
+// kc takes k = kc + 16 * (l >> 5) + s, so a lane reads 64 contiguous bytes of its weight row (torch's [out][in] layout, straight
+// from global memory / L2) and of its LDS row a chunk (row stride 260 floats = 4 mod 32: conflict-free ds_read_b128).  Every sum
+// starts from zero and takes the bias last.  A layer's results stay in registers until every wave has read the layer's input,
+// so a layer may write over its own input.
+#pragma once
+#include "fl_internal.h"
+
+void fl_set_error(const char *fmt, ...) __attribute__((format(printf, 1, 2)));   // fl_host.hip: the message of fl_last_error
+
+#define FPH_ATTR 83
+#define FPH_ATTR_PAD 96             // K of the first layer in LDS, zero filled
+#define FPH_H 128                   // hidden_sz = tree_embedding_sz
+#define FPH_E 256                   // embedding
+#define FPH_HEADS 4
+#define FPH_D 64                    // head size
+#define FPH_ACT 5
+#define FPH_THREADS 256
+#define FPH_ROWS 32
+#define FPH_STRIDE 260
+#define FPH_PSTRIDE 36              // a wave's tile of attention probabilities: 32 x 32, row stride 36
+#define FPH_NPARAMS 38
+#define FPH_MAX_A 1024
+#define FPH_ROW_FLOATS (4 * FPH_E + 3 * FPH_E + 1)   // workspace floats a row: embedding, two block outputs, attention, q k v, value
+
+typedef float fph_f32x16 __attribute__((ext_vector_type(16)));
+
+// parameter indices: the Network's state_dict without tree_lstm.*, in state_dict order
+enum {
+    FPH_P_ATTR = 0,                 // attr_embedding.{0,2,4,6}.{weight,bias}
+    FPH_P_BLOCK = 8,                // transformer.i: attention.in_proj_weight, in_proj_bias, out_proj.weight, out_proj.bias, att_mlp.0.weight, .bias
+    FPH_P_ACTOR = 26,               // actor_net.{0,2,4}.{weight,bias}
+    FPH_P_CRITIC = 32,              // critic_net.{0,2,4}.{weight,bias}
+};
+
+struct FphArgs {
+    int B, A, R;                    // R = B * A rows
+    int select;                     // 0 none, 1 soft, 2 hard
+    double u;
+    const float *attr, *tree;
+    const float *p[FPH_NPARAMS];
+    const unsigned char *valid;
+    float *logits, *value;
+    unsigned char *actions;
+    float *emb, *xa, *xb, *ao, *qkv, *val;     // workspace: [R][256] x 4, [R][768], [R]
+};
+
+__device__ __forceinline__ fph_f32x16 fph_mfma(float a, float b, fph_f32x16 c) {
+    return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
+}
+
+__device__ __forceinline__ float fph_gelu(float x) { return (x * 0.5f) * (1.0f + erff(x * 0.70710678118654752440f)); }
+
+// row of an accumulator register: lane l holds rows (r & 3) + 8 * (r >> 2) + 4 * (l >> 5), r = 0 .. 15, of column l & 31
+__device__ __forceinline__ int fph_row(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }
+
+// acc[b] += X[row][k] * W[j[b]][woff + k] over k in [0, K), K a multiple of 32: xrow = this lane's LDS row, w[b] = its weight row
+template <int NB>
+__device__ __forceinline__ void fph_mm(const float *xrow, int K, const float *const (&w)[NB], fph_f32x16 (&acc)[NB], int hh) {
+#pragma unroll 1
+    for (int kc = 0; kc < K; kc += 32) {
+        float a[16], b[NB][16];
+        const int o = kc + 16 * hh;
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const float4 av = ((const float4 *)(xrow + o))[q];
+            a[4 * q] = av.x; a[4 * q + 1] = av.y; a[4 * q + 2] = av.z; a[4 * q + 3] = av.w;
+#pragma unroll
+            for (int n = 0; n < NB; n++) {
+                const float4 bv = ((const float4 *)(w[n] + o))[q];
+                b[n][4 * q] = bv.x; b[n][4 * q + 1] = bv.y; b[n][4 * q + 2] = bv.z; b[n][4 * q + 3] = bv.w;
+            }
+        }
+#pragma unroll
+        for (int s = 0; s < 16; s++)
+#pragma unroll
+            for (int n = 0; n < NB; n++) acc[n] = fph_mfma(a[s], b[n][s], acc[n]);
+    }
+}
+
+// the first layer: weight rows of 83 floats (no 16-byte alignment), X zero filled up to 96
+__device__ __forceinline__ void fph_mm_attr(const float *xrow, const float *w0, const float *w1, fph_f32x16 &c0, fph_f32x16 &c1, int hh) {
+#pragma unroll 1
+    for (int kc = 0; kc < FPH_ATTR_PAD; kc += 32) {
+        const int o = kc + 16 * hh;
+#pragma unroll
+        for (int s = 0; s < 16; s++) {
+            const int k = o + s;
+            const float a = xrow[k];
+            const float b0 = k < FPH_ATTR ? w0[k] : 0.f, b1 = k < FPH_ATTR ? w1[k] : 0.f;
+            c0 = fph_mfma(a, b0, c0);
+            c1 = fph_mfma(a, b1, c1);
+        }
+    }
+}
+
+// (acc + bias) [GELU] of one 32 x 32 block -> LDS columns c0 .. c0 + 31
+template <bool GELU>
+__device__ __forceinline__ void fph_to_lds(const fph_f32x16 &acc, float bias, float *dst, int c0, int col, int hh) {
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const float v = acc[r] + bias;
+        dst[fph_row(r, hh) * FPH_STRIDE + c0 + col] = GELU ? fph_gelu(v) : v;
+    }
+}
+
+// rows [0, rows) x 64 float4 of an LDS tile <-> global rows of ld floats (rows past `rows` read as zero)
+__device__ __forceinline__ void fph_load_tile(float *dst, int c0, const float *src, int ld, int nq, int rows, int tid) {
+    for (int i = tid; i < FPH_ROWS * nq; i += FPH_THREADS) {
+        const int r = i / nq, q = i % nq;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (r < rows) v = ((const float4 *)(src + (size_t)r * ld))[q];
+        *(float4 *)&dst[r * FPH_STRIDE + c0 + 4 * q] = v;
+    }
+}
+
+__device__ __forceinline__ void fph_store_tile(const float *src, float *dst, int rows, int tid) {
+    for (int i = tid; i < FPH_ROWS * (FPH_E / 4); i += FPH_THREADS) {
+        const int r = i / (FPH_E / 4), q = i % (FPH_E / 4);
+        if (r < rows) ((float4 *)(dst + (size_t)r * FPH_E))[q] = *(const float4 *)&src[r * FPH_STRIDE + 4 * q];
+    }
+}
+
+// q, k, v of the next block: [rows][768] = X[32][256] in_proj^T + bias, straight to global memory (6 blocks a wave, in pairs)
+__device__ __forceinline__ void fph_qkv(const float *x, const float *w, const float *bias, float *out, int rows, int wave, int col, int hh) {
+#pragma unroll 1
+    for (int pr = 0; pr < 3; pr++) {
+        const int j0 = 32 * (6 * wave + 2 * pr), j1 = j0 + 32;
+        const float *const ws[2] = {w + (size_t)(j0 + col) * FPH_E, w + (size_t)(j1 + col) * FPH_E};
+        fph_f32x16 acc[2] = {};
+        fph_mm<2>(x + col * FPH_STRIDE, FPH_E, ws, acc, hh);
+        const float b0 = bias[j0 + col], b1 = bias[j1 + col];
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            const int row = fph_row(r, hh);
+            if (row < rows) {
+                out[(size_t)row * (3 * FPH_E) + j0 + col] = acc[0][r] + b0;
+                out[(size_t)row * (3 * FPH_E) + j1 + col] = acc[1][r] + b1;
+            }
+        }
+    }
+}
+
+// Y[32][256] = [GELU](X0[32][K0] | X1[32][K1]) W^T + bias: the wave's two blocks, left in registers (bias and GELU applied by fph_to_lds)
+__device__ __forceinline__ void fph_layer256(const float *x0, int K0, const float *x1, int K1, const float *w, fph_f32x16 (&acc)[2],
+                                             int wave, int col, int hh) {
+    const int ld = K0 + K1, j0 = 64 * wave, j1 = j0 + 32;
+    const float *const ws[2] = {w + (size_t)(j0 + col) * ld, w + (size_t)(j1 + col) * ld};
+    fph_mm<2>(x0 + col * FPH_STRIDE, K0, ws, acc, hh);
+    if (K1) {
+        const float *const ws1[2] = {ws[0] + K0, ws[1] + K0};
+        fph_mm<2>(x1 + col * FPH_STRIDE, K1, ws1, acc, hh);
+    }
+}
+
+// a 512 -> 256 -> 128 -> n_out head (actor_net / critic_net) on [e | y]: the result of rows x n_out (n_out <= 32) in wave 0's acc
+// registers, bias added; h is scratch.  Every wave calls it (barriers inside).
+__device__ __forceinline__ void fph_head(const float *e, const float *y, float *h, const float *const *p, int n_out, fph_f32x16 &out,
+                                         int wave, int col, int hh) {
+    {
+        fph_f32x16 acc[2] = {};
+        fph_layer256(e, FPH_E, y, FPH_E, p[0], acc, wave, col, hh);
+        __syncthreads();                                         // (h may still be read by the head before this one)
+        fph_to_lds<true>(acc[0], p[1][64 * wave + col], h, 64 * wave, col, hh);
+        fph_to_lds<true>(acc[1], p[1][64 * wave + 32 + col], h, 64 * wave + 32, col, hh);
+    }
+    __syncthreads();
+    {
+        const float *const ws[1] = {p[2] + (size_t)(32 * wave + col) * FPH_E};
+        fph_f32x16 acc[1] = {};
+        fph_mm<1>(h + col * FPH_STRIDE, FPH_E, ws, acc, hh);
+        __syncthreads();
+        fph_to_lds<true>(acc[0], p[3][32 * wave + col], h, 32 * wave, col, hh);
+    }
+    __syncthreads();
+    if (wave == 0) {
+        const int j = min(col, n_out - 1);                       // (columns past n_out repeat the last feature and are dropped)
+        const float *const ws[1] = {p[4] + (size_t)j * FPH_H};
+        fph_f32x16 acc[1] = {};
+        fph_mm<1>(h + col * FPH_STRIDE, FPH_H, ws, acc, hh);
+        const float b = p[5][j];
+#pragma unroll
+        for (int r = 0; r < 16; r++) out[r] = acc[0][r] + b;
+    }
+}
+
+// Actor._choose_action (plfActor.py:30-46) on one agent's logits and valid-action mask.  The softmax over the valid logits in
+// float32, as numpy computes it on a float32 array (max, exp, a sum from the left, the division).  soft: np.random.choice with
+// the draw u: the float64 cumulative sum of p divided by its last element, searchsorted(u, side="right").  hard: the first
+// largest p.  No valid action: 0.
+__device__ __forceinline__ int fph_choose(const float *lg, const unsigned char *valid, int select, double u) {
+    int idx[FPH_ACT], n = 0;
+    float x[FPH_ACT];
+    for (int a = 0; a < FPH_ACT; a++)
+        if (valid[a]) { idx[n] = a; x[n] = lg[a]; n++; }
+    if (n == 0) return 0;
+    float m = x[0];
+    for (int i = 1; i < n; i++) m = fmaxf(m, x[i]);
+    float e[FPH_ACT], s = 0.f;
+    for (int i = 0; i < n; i++) { e[i] = expf(x[i] - m); s = i ? s + e[i] : e[i]; }
+    float pr[FPH_ACT];
+    for (int i = 0; i < n; i++) pr[i] = e[i] / s;
+    if (select == 2) {
+        int best = 0;
+        for (int i = 1; i < n; i++) if (pr[i] > pr[best]) best = i;
+        return idx[best];
+    }
+    double cdf[FPH_ACT], c = 0.0;
+    for (int i = 0; i < n; i++) { c = i ? c + (double)pr[i] : (double)pr[i]; cdf[i] = c; }
+    int k = 0;
+    for (int i = 0; i < n; i++) k += (cdf[i] / c) <= u;
+    return idx[min(k, n - 1)];
+}
+
+// ---- attr MLP, embedding, q k v of the first block
+__global__ void __launch_bounds__(FPH_THREADS) k_ph_embed(FphArgs p) {
+    extern __shared__ __attribute__((aligned(16))) float s_f[];
+    float *b0 = s_f, *b1 = s_f + FPH_ROWS * FPH_STRIDE;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, hh = lane >> 5;
+    const int row0 = blockIdx.x * FPH_ROWS, rows = min(FPH_ROWS, p.R - row0);
+
+    for (int i = tid; i < FPH_ROWS * FPH_ATTR_PAD; i += FPH_THREADS) {
+        const int r = i / FPH_ATTR_PAD, c = i % FPH_ATTR_PAD;
+        b0[r * FPH_STRIDE + c] = (r < rows && c < FPH_ATTR) ? p.attr[(size_t)(row0 + r) * FPH_ATTR + c] : 0.f;
+    }
+    __syncthreads();
+    const float *const *w = p.p + FPH_P_ATTR;
+    {
+        fph_f32x16 acc[2] = {};
+        fph_mm_attr(b0 + col * FPH_STRIDE, w[0] + (size_t)(64 * wave + col) * FPH_ATTR, w[0] + (size_t)(64 * wave + 32 + col) * FPH_ATTR,
+                    acc[0], acc[1], hh);
+        fph_to_lds<true>(acc[0], w[1][64 * wave + col], b1, 64 * wave, col, hh);
+        fph_to_lds<true>(acc[1], w[1][64 * wave + 32 + col], b1, 64 * wave + 32, col, hh);
+    }
+    __syncthreads();
+    for (int l = 1; l <= 2; l++) {                               // 256 -> 256 twice: b1 -> b0 -> b1
+        float *src = l == 1 ? b1 : b0, *dst = l == 1 ? b0 : b1;
+        fph_f32x16 acc[2] = {};
+        fph_layer256(src, FPH_E, nullptr, 0, w[2 * l], acc, wave, col, hh);
+        fph_to_lds<true>(acc[0], w[2 * l + 1][64 * wave + col], dst, 64 * wave, col, hh);
+        fph_to_lds<true>(acc[1], w[2 * l + 1][64 * wave + 32 + col], dst, 64 * wave + 32, col, hh);
+        __syncthreads();
+    }
+    {                                                            // 256 -> 128: b1 -> b0[:, :128]; the tree embedding beside it
+        const float *const ws[1] = {w[6] + (size_t)(32 * wave + col) * FPH_E};
+        fph_f32x16 acc[1] = {};
+        fph_mm<1>(b1 + col * FPH_STRIDE, FPH_E, ws, acc, hh);
+        fph_to_lds<true>(acc[0], w[7][32 * wave + col], b0, 32 * wave, col, hh);
+        fph_load_tile(b0, FPH_H, p.tree + (size_t)row0 * FPH_H, FPH_H, FPH_H / 4, rows, tid);
+    }
+    __syncthreads();
+    fph_store_tile(b0, p.emb + (size_t)row0 * FPH_E, rows, tid);
+    fph_qkv(b0, p.p[FPH_P_BLOCK], p.p[FPH_P_BLOCK + 1], p.qkv + (size_t)row0 * (3 * FPH_E), rows, wave, col, hh);
+}
+
+// ---- attention of one block: workgroup = (env, tile of 32 queries), wave = head.  Two passes over the keys in chunks of 32: the
+// row maxima of q k^T, then p = exp((s - max) / 8) (the scale 1/8 is a power of two: where it is applied does not change the
+// rounding), its row sums and p v; the quotient last.  Keys past the env's last agent take no part.
+__global__ void __launch_bounds__(FPH_THREADS) k_ph_attn(FphArgs p) {
+    __shared__ __attribute__((aligned(16))) float s_p[FPH_HEADS][FPH_ROWS * FPH_PSTRIDE];
+    const int tid = threadIdx.x, lane = tid & 63, head = tid >> 6, col = lane & 31, hh = lane >> 5;
+    const int A = p.A, tiles = (A + FPH_ROWS - 1) / FPH_ROWS;
+    const int env = blockIdx.x / tiles, q0 = (blockIdx.x % tiles) * FPH_ROWS;
+    const size_t base = (size_t)env * A;
+    const float *qkv = p.qkv + base * (3 * FPH_E);
+    float *sp = s_p[head];
+
+    float qa[2][16];                                             // this lane's A operand: q of row q0 + col (the last one repeated past the env)
+    {
+        const float *qrow = qkv + (size_t)min(q0 + col, A - 1) * (3 * FPH_E) + head * FPH_D;
+#pragma unroll
+        for (int c = 0; c < 2; c++)
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                const float4 v = ((const float4 *)(qrow + 32 * c + 16 * hh))[q];
+                qa[c][4 * q] = v.x; qa[c][4 * q + 1] = v.y; qa[c][4 * q + 2] = v.z; qa[c][4 * q + 3] = v.w;
+            }
+    }
+    float mx[16], sum[16];
+#pragma unroll
+    for (int r = 0; r < 16; r++) { mx[r] = -INFINITY; sum[r] = 0.f; }
+    fph_f32x16 o0 = {}, o1 = {};
+
+#pragma unroll 1
+    for (int pass = 0; pass < 2; pass++) {
+#pragma unroll 1
+        for (int k0 = 0; k0 < A; k0 += 32) {
+            const bool live = k0 + col < A;                       // this lane's key (score column)
+            const float *krow = qkv + (size_t)min(k0 + col, A - 1) * (3 * FPH_E) + FPH_E + head * FPH_D;
+            fph_f32x16 s = {};
+#pragma unroll
+            for (int c = 0; c < 2; c++) {
+                float kb[16];
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+                    const float4 v = ((const float4 *)(krow + 32 * c + 16 * hh))[q];
+                    kb[4 * q] = v.x; kb[4 * q + 1] = v.y; kb[4 * q + 2] = v.z; kb[4 * q + 3] = v.w;
+                }
+#pragma unroll
+                for (int t = 0; t < 16; t++) s = fph_mfma(qa[c][t], kb[t], s);
+            }
+            if (pass == 0) {
+                if (live) {
+#pragma unroll
+                    for (int r = 0; r < 16; r++) mx[r] = fmaxf(mx[r], s[r]);
+                }
+                continue;
+            }
+            __syncthreads();                                     // the previous chunk's probabilities have been read
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const float e = live ? expf((s[r] - mx[r]) * 0.125f) : 0.f;
+                sum[r] += e;
+                sp[fph_row(r, hh) * FPH_PSTRIDE + col] = e;
+            }
+            __syncthreads();
+            float pa[16];
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                const float4 v = ((const float4 *)(sp + col * FPH_PSTRIDE + 16 * hh))[q];
+                pa[4 * q] = v.x; pa[4 * q + 1] = v.y; pa[4 * q + 2] = v.z; pa[4 * q + 3] = v.w;
+            }
+#pragma unroll
+            for (int t = 0; t < 16; t++) {
+                const int key = k0 + 16 * hh + t;
+                float v0 = 0.f, v1 = 0.f;
+                if (key < A) {
+                    const float *vrow = qkv + (size_t)key * (3 * FPH_E) + 2 * FPH_E + head * FPH_D;
+                    v0 = vrow[col]; v1 = vrow[32 + col];
+                }
+                o0 = fph_mfma(pa[t], v0, o0);
+                o1 = fph_mfma(pa[t], v1, o1);
+            }
+        }
+        // a row's maximum / sum over the 32 lanes that hold its columns (a butterfly: every lane ends with the same value)
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            float v = pass == 0 ? mx[r] : sum[r];
+#pragma unroll
+            for (int d = 1; d < 32; d <<= 1) {
+                const float w = __shfl_xor(v, d, 64);
+                v = pass == 0 ? fmaxf(v, w) : v + w;
+            }
+            if (pass == 0) mx[r] = v; else sum[r] = v;
+        }
+    }
+    float *out = p.ao + base * FPH_E + head * FPH_D;
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const int qi = q0 + fph_row(r, hh);
+        if (qi < A) {
+            out[(size_t)qi * FPH_E + col] = o0[r] / sum[r];
+            out[(size_t)qi * FPH_E + 32 + col] = o1[r] / sum[r];
+        }
+    }
+}
+
+// ---- the rest of a block per row tile; LAST: the heads and the action instead of the next block's q k v
+template <bool LAST>
+__global__ void __launch_bounds__(FPH_THREADS) k_ph_block(FphArgs p, int blk, const float *xin, float *xout) {
+    extern __shared__ __attribute__((aligned(16))) float s_f[];
+    __shared__ float s_lg[FPH_ROWS][FPH_ACT + 1];
+    float *bx = s_f, *ba = s_f + FPH_ROWS * FPH_STRIDE, *bh = s_f + 2 * FPH_ROWS * FPH_STRIDE;     // (bh: LAST only)
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, hh = lane >> 5;
+    const int row0 = blockIdx.x * FPH_ROWS, rows = min(FPH_ROWS, p.R - row0);
+    const float *const *w = p.p + FPH_P_BLOCK + 6 * blk;
+
+    fph_load_tile(bx, 0, xin + (size_t)row0 * FPH_E, FPH_E, FPH_E / 4, rows, tid);
+    fph_load_tile(ba, 0, p.ao + (size_t)row0 * FPH_E, FPH_E, FPH_E / 4, rows, tid);
+    __syncthreads();
+    {                                                            // out_proj, over the attention output
+        fph_f32x16 acc[2] = {};
+        fph_layer256(ba, FPH_E, nullptr, 0, w[2], acc, wave, col, hh);
+        __syncthreads();
+        fph_to_lds<false>(acc[0], w[3][64 * wave + col], ba, 64 * wave, col, hh);
+        fph_to_lds<false>(acc[1], w[3][64 * wave + 32 + col], ba, 64 * wave + 32, col, hh);
+    }
+    __syncthreads();
+    {                                                            // att_mlp on [input | attention], over the input
+        fph_f32x16 acc[2] = {};
+        fph_layer256(bx, FPH_E, ba, FPH_E, w[4], acc, wave, col, hh);
+        __syncthreads();
+        fph_to_lds<true>(acc[0], w[5][64 * wave + col], bx, 64 * wave, col, hh);
+        fph_to_lds<true>(acc[1], w[5][64 * wave + 32 + col], bx, 64 * wave + 32, col, hh);
+    }
+    __syncthreads();
+    if (!LAST) {
+        fph_store_tile(bx, xout + (size_t)row0 * FPH_E, rows, tid);
+        fph_qkv(bx, w[6], w[7], p.qkv + (size_t)row0 * (3 * FPH_E), rows, wave, col, hh);
+        return;
+    }
+    fph_load_tile(ba, 0, p.emb + (size_t)row0 * FPH_E, FPH_E, FPH_E / 4, rows, tid);
+    __syncthreads();
+    fph_f32x16 out = {};
+    fph_head(ba, bx, bh, p.p + FPH_P_ACTOR, FPH_ACT, out, wave, col, hh);
+    if (wave == 0 && col < FPH_ACT) {
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            const int row = fph_row(r, hh);
+            s_lg[row][col] = out[r];
+            if (row < rows) p.logits[(size_t)(row0 + row) * FPH_ACT + col] = out[r];
+        }
+    }
+    if (p.value) {
+        fph_head(ba, bx, bh, p.p + FPH_P_CRITIC, 1, out, wave, col, hh);
+        if (wave == 0 && col == 0) {
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const int row = fph_row(r, hh);
+                if (row < rows) p.val[row0 + row] = out[r];
+            }
+        }
+    }
+    __syncthreads();
+    if (p.select && tid < rows)
+        p.actions[row0 + tid] = (unsigned char)fph_choose(s_lg[tid], p.valid + (size_t)(row0 + tid) * FPH_ACT, p.select, p.u);
+}
+
+// ---- value[env] = mean of the env's critic values: a wave per env, lane l sums agents l, l + 64, ... in order, then a butterfly
+__global__ void __launch_bounds__(64) k_ph_value(FphArgs p) {
+    const int env = blockIdx.x, lane = threadIdx.x;
+    const float *v = p.val + (size_t)env * p.A;
+    float s = 0.f;
+    for (int a = lane; a < p.A; a += 64) s += v[a];
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) s += __shfl_xor(s, d, 64);
+    if (lane == 0) p.value[env] = s / (float)p.A;
+}
+
+#define FPH_LDS_EMBED (2 * FPH_ROWS * FPH_STRIDE * sizeof(float))
+#define FPH_LDS_BLOCK (2 * FPH_ROWS * FPH_STRIDE * sizeof(float))
+#define FPH_LDS_LAST (3 * FPH_ROWS * FPH_STRIDE * sizeof(float))

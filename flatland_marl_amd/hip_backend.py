@@ -75,7 +75,16 @@ _DEBUG_ABI = {
     "fl_debug_last_obs_class": ([vp, vp], i32),
     "fl_debug_last_obs_launch": ([vp, vp, i32], i32),
 }
+# name -> (argtypes, restype) of every function include/flatland_policy.h declares, in the header's order
+_POLICY_ABI = {
+    "fl_policy_head_workspace_bytes": ([i32, i32], C.c_size_t),
+    "fl_policy_head": ([i32, i32, vp, vp, C.POINTER(vp), vp, i32, C.c_double, vp, vp, vp, vp, C.c_size_t, vp], i32),
+}
 SYMBOLS = tuple(_ABI)      # every symbol include/flatland_hip.h declares
+POLICY_SYMBOLS = tuple(_POLICY_ABI)      # ... and include/flatland_policy.h
+POLICY_HEAD_NPARAMS = 38
+POLICY_SELECT = {None: 0, "soft": 1, "hard": 2}
+POLICY_U_REFERENCE = 0.3745401188473625      # numpy.random.RandomState(42).random_sample(): the reference seeds before every draw
 
 _lib = None
 
@@ -109,7 +118,7 @@ def lib():
         # otherwise torch.cuda finds no device once the library below has pulled in the system runtime
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
-        for name, (args, res) in {**_ABI, **_DEBUG_ABI}.items():
+        for name, (args, res) in {**_ABI, **_DEBUG_ABI, **_POLICY_ABI}.items():
             fn = getattr(L, name, None)        # (a library from bench.py --lib or a tool's LIB_PATH may predate the newer ones)
             if fn is not None:
                 fn.argtypes, fn.restype = args, res
@@ -188,6 +197,35 @@ def tree_lstm(forest, adjacency, node_order, edge_order, weights, roots_only, h,
                 None if c is None else c.data_ptr(), None if status is None else status.data_ptr(),
                 ws.data_ptr(), ws.numel(), C.c_void_p(s)))
     return h
+
+
+def policy_head(agents_attr, tree_embedding, params, logits, value=None, valid_actions=None, actions=None, mode=None, u=None):
+    """The policy network after its tree encoder and the actor's choice (fl_policy_head) on torch's current stream of the inputs'
+    device, with a workspace from torch's allocator.  agents_attr f32 [B, A, 83], tree_embedding f32 [B, A, 128]; params = the 38
+    tensors of include/flatland_policy.h in its order, f32 contiguous; logits f32 [B, A, 5]; value f32 [B] or None (the critic is
+    not run); mode None / "soft" / "hard" with valid_actions u8 [B, A, 5] and actions u8 [B, A]; u None = the reference's constant."""
+    import torch
+    B, A = agents_attr.shape[:2]
+    fn = _sym("fl_policy_head")
+    if mode not in POLICY_SELECT:
+        raise ValueError("policy_head: mode must be None, 'soft' or 'hard', got %r" % (mode,))
+    if len(params) != POLICY_HEAD_NPARAMS:
+        raise ValueError("policy_head: %d parameters, %d expected" % (len(params), POLICY_HEAD_NPARAMS))
+    dev = agents_attr.device
+    for name, o, dt, n in (("logits", logits, torch.float32, B * A * 5), ("value", value, torch.float32, B),
+                           ("valid_actions", valid_actions, torch.uint8, B * A * 5), ("actions", actions, torch.uint8, B * A)):
+        if o is not None and (o.dtype != dt or o.device != dev or not o.is_contiguous() or o.numel() < n):
+            raise ValueError("policy_head: %s must be a contiguous %s tensor of at least %d elements on %s" % (name, dt, n, dev))
+    ptrs = (vp * POLICY_HEAD_NPARAMS)(*[w.data_ptr() for w in params])
+    nbytes = _sym("fl_policy_head_workspace_bytes")(B, A)
+    opt = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    with torch.cuda.device(dev):
+        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+        s = torch.cuda.current_stream(dev).cuda_stream
+        _chk(fn(B, A, agents_attr.data_ptr(), tree_embedding.data_ptr(), ptrs, opt(valid_actions), POLICY_SELECT[mode],
+                POLICY_U_REFERENCE if u is None else float(u), logits.data_ptr(), opt(value), opt(actions), ws.data_ptr(),
+                ws.numel(), C.c_void_p(s)))
+    return logits
 
 
 class BatchedRailEnv:
@@ -363,6 +401,11 @@ class BatchedRailEnv:
                 valid_actions=t.zeros((B, A, 5), dtype=t.uint8, device=dev),
                 props=t.zeros((B, A, 3), dtype=t.float64, device=dev))
         return self._obs
+
+    def obs_outputs(self):
+        """the flatland_cutils output tensors as the last observation call left them (obs_policy() returns five of the policy's
+        inputs; valid_actions u8 [B, A, 5] and props are here), without a launch"""
+        return self._obs_buffers()
 
     @staticmethod
     def _cutils_ptrs(o, index=None):

@@ -1,4 +1,6 @@
-"""The policy network's tree encoder on the GPU: TreeLSTM (solution/nn/TreeLSTM.py) as one HIP launch (fl_tree_lstm).
+"""The policy network on the GPU: TreeLSTM (solution/nn/TreeLSTM.py) as one HIP launch (fl_tree_lstm), and Network
+(solution/nn/net_tree.py) with everything after the tree encoder -- attribute MLP, three attention blocks over the agents of an
+env, actor and critic heads -- and the actor's choice of an action (solution/plfActor.py:30-46) as fl_policy_head.
 
 `TreeLSTM` has the reference module's submodules, parameter names and shapes, so a reference checkpoint loads unchanged, and it
 takes the tensors BatchedRailEnv.obs_policy() returns (adjacency already modified) as they are.  The kernel reads the live
@@ -6,6 +8,7 @@ parameter tensors at every call: after load_state_dict or an in-place update the
 only: the output comes through an autograd.Function whose backward raises NotImplementedError.
 
 Swap it into the reference's Network:  net.tree_lstm = TreeLSTM.from_module(net.tree_lstm)
+or take the whole network:              net = Network.from_module(net)
 """
 import torch
 import torch.nn as nn
@@ -123,3 +126,200 @@ class TreeLSTM(nn.Module):
         """h of node 0 of every tree, [B, A, 128]: what Network.forward keeps (net_tree.py:77-80), without the other nodes' output"""
         B, A = forest.shape[:2]
         return self._run(forest, adjacency, node_order, edge_order, True, check).view(B, A, OUT_FEATURES)
+
+
+# ---------------------------------------------------------------------------------------------------------------- Network
+AGENT_ATTR = 83       # FeatureParserConfig.agent_attr
+HIDDEN = 128          # NetworkConfig.hidden_sz
+EMBED = HIDDEN + OUT_FEATURES
+HEADS = 4
+ACTIONS = 5           # FeatureParserConfig.action_sz
+U_REFERENCE = hip_backend.POLICY_U_REFERENCE
+# the state_dict without tree_lstm.*, in state_dict order: the parameter list of fl_policy_head (include/flatland_policy.h)
+HEAD_PARAM_ORDER = tuple(
+    ["attr_embedding.%d.%s" % (i, k) for i in (0, 2, 4, 6) for k in ("weight", "bias")]
+    + ["transformer.%d.%s" % (i, k) for i in range(3)
+       for k in ("attention.in_proj_weight", "attention.in_proj_bias", "attention.out_proj.weight", "attention.out_proj.bias",
+                 "att_mlp.0.weight", "att_mlp.0.bias")]
+    + ["%s.%d.%s" % (n, i, k) for n in ("actor_net", "critic_net") for i in (0, 2, 4) for k in ("weight", "bias")])
+
+
+class Transformer(nn.Module):
+    """one attention block: MultiheadAttention over the agents of an env (sequence = agents, batch = envs), then
+    att_mlp = GELU(Linear([input | attention output])); no residual, no layer norm"""
+
+    def __init__(self, embed_dim, num_heads):
+        super().__init__()
+        self.attention = nn.MultiheadAttention(embed_dim, num_heads)
+        self.att_mlp = nn.Sequential(nn.Linear(2 * embed_dim, embed_dim), nn.GELU())
+
+    def forward(self, x):
+        seq = x.transpose(0, 1)                      # [A, B, E]
+        out, _ = self.attention(seq, seq, seq, need_weights=False)
+        return self.att_mlp(torch.cat([x, out.transpose(0, 1)], dim=-1))
+
+
+def _mlp(sizes, last_act):
+    layers = []
+    for i in range(len(sizes) - 1):
+        layers.append(nn.Linear(sizes[i], sizes[i + 1]))
+        if last_act or i < len(sizes) - 2:
+            layers.append(nn.GELU())
+    return nn.Sequential(*layers)
+
+
+class _Head(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, agents_attr, tree_embedding, valid_actions, mode, u, with_value, *weights):
+        B, A = agents_attr.shape[:2]
+        dev = agents_attr.device
+        logits = torch.empty((B, A, ACTIONS), dtype=torch.float32, device=dev)
+        value = torch.empty((B,), dtype=torch.float32, device=dev) if with_value else None
+        actions = torch.empty((B, A), dtype=torch.uint8, device=dev) if mode is not None else None
+        hip_backend.policy_head(agents_attr, tree_embedding, weights, logits, value, valid_actions, actions, mode, u)
+        out = (logits,) + ((value,) if with_value else ()) + ((actions,) if actions is not None else ())
+        if actions is not None:
+            ctx.mark_non_differentiable(actions)
+        return out
+
+    @staticmethod
+    def backward(ctx, *grads):
+        raise NotImplementedError("Network (fl_policy_head) is inference only: no backward; forward_torch is the path with autograd")
+
+
+class Network(nn.Module):
+    """The reference's Network (solution/nn/net_tree.py:32-103) with its submodule names and shapes, so load_state_dict of a
+    reference checkpoint works unchanged; tree_lstm is this file's TreeLSTM, everything after it runs as fl_policy_head."""
+
+    def __init__(self):
+        super().__init__()
+        self.tree_lstm = TreeLSTM(IN_FEATURES, OUT_FEATURES)
+        self.attr_embedding = _mlp((AGENT_ATTR, 2 * HIDDEN, 2 * HIDDEN, 2 * HIDDEN, HIDDEN), True)
+        self.transformer = nn.Sequential(*[Transformer(EMBED, HEADS) for _ in range(3)])
+        self.actor_net = _mlp((2 * EMBED, 2 * HIDDEN, HIDDEN, ACTIONS), False)
+        self.critic_net = _mlp((2 * EMBED, 2 * HIDDEN, HIDDEN, 1), False)
+
+    @classmethod
+    def from_module(cls, m):
+        """a Network that shares m's parameters (m: the reference's Network or one of these)"""
+        obj = cls.__new__(cls)
+        nn.Module.__init__(obj)
+        obj.tree_lstm = TreeLSTM.from_module(m.tree_lstm)
+        obj.attr_embedding = m.attr_embedding
+        blocks = []
+        for b in m.transformer:
+            t = Transformer.__new__(Transformer)
+            nn.Module.__init__(t)
+            t.attention, t.att_mlp = b.attention, b.att_mlp
+            blocks.append(t)
+        obj.transformer = nn.Sequential(*blocks)
+        obj.actor_net, obj.critic_net = m.actor_net, m.critic_net
+        obj._head_weights(None)                      # the names and shapes are the ones the kernels take
+        return obj
+
+    def _head_weights(self, device):
+        sd = dict(self.named_parameters())
+        ref = Network._shapes()
+        ws = []
+        for name in HEAD_PARAM_ORDER:
+            if name not in sd or tuple(sd[name].shape) != ref[name]:
+                raise ValueError("Network: parameter %s must have shape %s (got %s)"
+                                 % (name, ref[name], tuple(sd[name].shape) if name in sd else None))
+            w = sd[name]
+            if device is not None and (w.dtype != torch.float32 or w.device != device or not w.is_contiguous()):
+                raise TypeError("Network: parameter %s must be a contiguous float32 tensor on %s (got %s on %s%s)"
+                                % (name, device, w.dtype, w.device, "" if w.is_contiguous() else ", not contiguous"))
+            ws.append(w)
+        return ws
+
+    @staticmethod
+    def _shapes():
+        E, H = EMBED, HIDDEN
+        out = {}
+        for i, (o, k) in zip((0, 2, 4, 6), ((2 * H, AGENT_ATTR), (2 * H, 2 * H), (2 * H, 2 * H), (H, 2 * H))):
+            out["attr_embedding.%d.weight" % i], out["attr_embedding.%d.bias" % i] = tuple((o, k)), tuple((o,))
+        for i in range(3):
+            t = "transformer.%d." % i
+            out[t + "attention.in_proj_weight"], out[t + "attention.in_proj_bias"] = tuple((3 * E, E)), tuple((3 * E,))
+            out[t + "attention.out_proj.weight"], out[t + "attention.out_proj.bias"] = tuple((E, E)), tuple((E,))
+            out[t + "att_mlp.0.weight"], out[t + "att_mlp.0.bias"] = tuple((E, 2 * E)), tuple((E,))
+        for n, last in (("actor_net", ACTIONS), ("critic_net", 1)):
+            for i, (o, k) in zip((0, 2, 4), ((2 * H, 2 * E), (H, 2 * H), (last, H))):
+                out["%s.%d.weight" % (n, i)], out["%s.%d.bias" % (n, i)] = tuple((o, k)), tuple((o,))
+        return out
+
+    @staticmethod
+    def _check_head_inputs(agents_attr, tree_embedding, valid_actions):
+        for name, x, dt in (("agents_attr", agents_attr, torch.float32), ("tree_embedding", tree_embedding, torch.float32),
+                            ("valid_actions", valid_actions, torch.uint8)):
+            if x is None and name == "valid_actions":
+                continue
+            if not isinstance(x, torch.Tensor):
+                raise TypeError("Network: %s must be a tensor" % name)
+            if x.dtype != dt:
+                raise TypeError("Network: %s must be %s, got %s" % (name, dt, x.dtype))
+            if x.device.type != "cuda":
+                raise TypeError("Network: %s must be on a GPU, got %s" % (name, x.device))
+            if x.device != agents_attr.device:
+                raise TypeError("Network: %s is on %s, agents_attr on %s" % (name, x.device, agents_attr.device))
+            if not x.is_contiguous():
+                raise ValueError("Network: %s must be contiguous" % name)
+        if agents_attr.dim() != 3 or agents_attr.shape[2] != AGENT_ATTR:
+            raise ValueError("Network: agents_attr must be [B, A, %d], got %s" % (AGENT_ATTR, tuple(agents_attr.shape)))
+        B, A = agents_attr.shape[:2]
+        if tuple(tree_embedding.shape) != (B, A, OUT_FEATURES):
+            raise ValueError("Network: tree_embedding must be %s, got %s" % ((B, A, OUT_FEATURES), tuple(tree_embedding.shape)))
+        if valid_actions is not None and tuple(valid_actions.shape) != (B, A, ACTIONS):
+            raise ValueError("Network: valid_actions must be %s, got %s" % ((B, A, ACTIONS), tuple(valid_actions.shape)))
+        if B == 0 or A == 0:
+            raise ValueError("Network: no agents")
+        if A > 1024:
+            raise ValueError("Network: %d agents an env, at most 1024" % A)
+
+    def head(self, agents_attr, tree_embedding, valid_actions=None, mode=None, u=None, value=True):
+        """Everything after the tree encoder (fl_policy_head) on agents_attr f32 [B, A, 83] and tree_embedding f32 [B, A, 128] (what
+        TreeLSTM.roots returns): ([logits [B, A, 5]], value [B]) as forward returns them (value=False: the critic is not run, value is
+        None); with mode "soft" / "hard" and valid_actions u8 [B, A, 5] the actions u8 [B, A] come as a third item.  u: the uniform
+        draw of "soft", None = the reference's constant (it seeds numpy with 42 before every draw)."""
+        if mode not in (None, "soft", "hard"):
+            raise ValueError("Network: mode must be None, 'soft' or 'hard', got %r" % (mode,))
+        if mode is not None and valid_actions is None:
+            raise ValueError("Network: mode %r needs valid_actions" % mode)
+        if u is not None and not 0.0 <= float(u) < 1.0:
+            raise ValueError("Network: u must be in [0, 1), got %r" % (u,))
+        self._check_head_inputs(agents_attr, tree_embedding, valid_actions if mode is not None else None)
+        ws = self._head_weights(agents_attr.device)
+        out = list(_Head.apply(agents_attr, tree_embedding, valid_actions if mode is not None else None, mode, u, bool(value), *ws))
+        logits = out.pop(0)
+        val = out.pop(0) if value else None
+        return ([logits], val) + ((out.pop(0),) if mode is not None else ())
+
+    def forward(self, agents_attr, forest, adjacency, node_order, edge_order):
+        """([logits [B, A, 5]], value [B]) as the reference's forward returns them.  The inputs are the tensors of
+        BatchedRailEnv.obs_policy(): the adjacency is ALREADY MODIFIED (global node ids, negatives -2) -- the reference's forward
+        modifies it itself (net_tree.py:75, 105-116), this one does not."""
+        tree = self.tree_lstm.roots(forest, adjacency, node_order, edge_order)
+        return self.head(agents_attr, tree)
+
+    def act(self, agents_attr, forest, adjacency, node_order, edge_order, valid_actions, mode="soft", u=None):
+        """the actions u8 [B, A] of Actor._choose_action per agent, on the device and ready for BatchedRailEnv.step(actions,
+        filter_required=True); the inputs as for forward (adjacency already modified), valid_actions u8 [B, A, 5]"""
+        if mode not in ("soft", "hard"):
+            raise ValueError("Network.act: mode must be 'soft' or 'hard', got %r" % (mode,))
+        with torch.no_grad():
+            tree = self.tree_lstm.roots(forest, adjacency, node_order, edge_order)
+            return self.head(agents_attr, tree, valid_actions, mode, u, value=False)[2]
+
+    def head_torch(self, agents_attr, tree_embedding):
+        """head() through torch's eager ops on the same parameters, with autograd: ([logits], value)"""
+        embedding = torch.cat([self.attr_embedding(agents_attr), tree_embedding], dim=2)
+        both = torch.cat([embedding, self.transformer(embedding)], dim=-1)
+        return [self.actor_net(both)], self.critic_net(both).mean(1).view(-1)
+
+    def forward_torch(self, agents_attr, forest, adjacency, node_order, edge_order):
+        """forward() with everything after the tree encoder in torch's eager ops: the path with autograd (for the head's
+        parameters; the tree encoder is fl_tree_lstm here as well, which has no backward, so its output enters as a constant).
+        The adjacency is already modified, as for forward."""
+        with torch.no_grad():
+            tree = self.tree_lstm.roots(forest, adjacency, node_order, edge_order)
+        return self.head_torch(agents_attr, tree)
