@@ -109,6 +109,106 @@ def head(agents_attr, tree_embedding, params, dtype=torch.float64, with_probs=Fa
     return (logits, value, probs) if with_probs else (logits, value)
 
 
+# ---------------------------------------------------------------------------------------------------------------- stage by stage
+# The same network cut at the places where fl_policy_head leaves an intermediate in its workspace ("the workspace layout
+# the tests pin"), so that a test can compute each stage from the kernel's own previous stage.  Every function takes and returns
+# [B, A, .] tensors of one dtype and uses head()'s own ops in head()'s order: chained in float64 they give head()'s bits
+# (tests/test_policy_head_stages.py).  mm = the matrix product: torch.matmul, or matmul_seq for a float32 sum in a fixed order.
+# rec = None or a dict of lists that takes the arguments of every erf ("erf") and exp ("exp") on the way.
+def matmul_seq(a, b):
+    """a @ b with the products summed strictly from the left: every product and every sum rounded on its own (no FMA)"""
+    acc = a[..., :, 0:1] * b[..., 0:1, :]
+    for k in range(1, a.shape[-1]):
+        acc = acc + a[..., :, k:k + 1] * b[..., k:k + 1, :]
+    return acc
+
+
+def stage_params(params, device, dtype=torch.float64):
+    return {k: v.detach().to(device=device, dtype=dtype) for k, v in params.items() if not k.startswith("tree_lstm.")}
+
+
+def _gelu(x, rec):
+    if rec is not None:
+        rec["erf"].append(x / math.sqrt(2.0))
+    return gelu(x)
+
+
+def _lin(x, p, name, mm, weight="weight", bias="bias"):
+    return mm(x, p[name + weight].T) + p[name + bias]
+
+
+def stage_attr(attr, p, mm=torch.matmul, rec=None):
+    """emb[..., :128]: the four layers of attr_embedding, GELU after each"""
+    x = attr
+    for i in (0, 2, 4, 6):
+        x = _gelu(_lin(x, p, "attr_embedding.%d." % i, mm), rec)
+    return x
+
+
+def stage_qkv(y, p, blk, mm=torch.matmul):
+    """[B, A, 768]: q | k | v of block blk from its input"""
+    return _lin(y, p, "transformer.%d.attention." % blk, mm, "in_proj_weight", "in_proj_bias")
+
+
+def stage_attention(qkv, mm=torch.matmul, rec=None, with_probs=False):
+    """[B, A, 256]: softmax(q k^T / 8) v of the four heads side by side, before out_proj"""
+    B, A = qkv.shape[:2]
+    q, k, v = (qkv[..., 256 * j:256 * (j + 1)].reshape(B, A, 4, 64).permute(0, 2, 1, 3) for j in range(3))
+    s = mm(q, k.transpose(-1, -2)) / 8.0
+    s = s - s.max(dim=-1, keepdim=True).values
+    if rec is not None:
+        rec["exp"].append(s)
+    e = torch.exp(s)
+    den = e.sum(dim=-1, keepdim=True) if mm is torch.matmul else mm(e, torch.ones_like(e[..., :1, :]).transpose(-1, -2))
+    pr = e / den
+    ao = mm(pr, v).permute(0, 2, 1, 3).reshape(B, A, 256)
+    return (ao, pr) if with_probs else ao
+
+
+def stage_block(y, ao, p, blk, mm=torch.matmul, rec=None):
+    """the block's output = the next block's input: GELU(att_mlp([y | out_proj(ao)]))"""
+    t = "transformer.%d." % blk
+    o = _lin(ao, p, t + "attention.out_proj.", mm)
+    return _gelu(_lin(torch.cat([y, o], dim=-1), p, t + "att_mlp.0.", mm), rec)
+
+
+def stage_heads(emb, y, p, mm=torch.matmul, rec=None):
+    """(logits [B, A, 5], val [B, A]): actor_net and critic_net on [emb | y]"""
+    both = torch.cat([emb, y], dim=-1)
+
+    def mlp(name):
+        h = _gelu(_lin(both, p, name + ".0.", mm), rec)
+        return _lin(_gelu(_lin(h, p, name + ".2.", mm), rec), p, name + ".4.", mm)
+    return mlp("actor_net"), mlp("critic_net")[..., 0]
+
+
+def stage_tail(emb, xb, ao, p, mm=torch.matmul, rec=None):
+    """what k_ph_block<true> computes from the workspace: block 2 after its attention, then the heads"""
+    return stage_heads(emb, stage_block(xb, ao, p, 2, mm, rec), p, mm, rec)
+
+
+def stage_value(val):
+    """[B]: the mean of the agents' critic values"""
+    return val.unsqueeze(-1).mean(dim=1).reshape(-1)
+
+
+def stages(agents_attr, tree_embedding, params, dtype=torch.float64, mm=torch.matmul, rec=None):
+    """every stage chained from the inputs, in the workspace's names: emb, xa, xb, ao and qkv (block 2's; ao0, ao1, qkv0, qkv1 the
+    earlier blocks'), val, and the outputs logits and value"""
+    p = stage_params(params, agents_attr.device, dtype)
+    out = {}
+    out["emb"] = y = torch.cat([stage_attr(agents_attr.to(dtype), p, mm, rec), tree_embedding.to(dtype)], dim=-1)
+    for blk in range(3):
+        out["qkv%d" % blk] = stage_qkv(y, p, blk, mm)
+        out["ao%d" % blk] = stage_attention(out["qkv%d" % blk], mm, rec)
+        if blk < 2:
+            out[("xa", "xb")[blk]] = y = stage_block(y, out["ao%d" % blk], p, blk, mm, rec)
+    out["qkv"], out["ao"] = out["qkv2"], out["ao2"]
+    out["logits"], out["val"] = stage_tail(out["emb"], out["xb"], out["ao"], p, mm, rec)
+    out["value"] = stage_value(out["val"])
+    return out
+
+
 def _probabilities(logits, valid):
     """the valid actions of one agent and their float32 softmax, as numpy computes it on a float32 array"""
     idx = np.flatnonzero(valid)

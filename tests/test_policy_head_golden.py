@@ -114,6 +114,7 @@ def test_workspace_bytes():
     (dict(select=1, valid=None, actions=FAKE), "needs valid_actions"), (dict(select=2, valid=FAKE, actions=None), "needs valid_actions"),
     (dict(u=1.0), "u must be"), (dict(u=-0.1), "u must be"), (dict(u=float("nan")), "u must be"),
     (dict(ws=1000), "workspace of 1000 bytes"), (dict(A=1024, ws=2 * 1024 * 7172 - 16), "workspace"),
+    (dict(B=3000, A=1024), "bad sizes"),        # 3 072 000 rows, above INT32_MAX / 768 = 2 796 202
 ])
 def test_refusals(kw, words):
     rc, msg = call(**kw)
@@ -125,7 +126,8 @@ def test_a_good_call_passes_the_checks():
     """the same fake pointers with nothing wrong get past every check: without a GPU the first HIP call fails (FL_ERR_HIP)"""
     if hb.lib().fl_device_count() > 0:
         return
-    for kw in (dict(), dict(value=None), dict(select=1, valid=FAKE, actions=FAKE, u=0.0), dict(A=1024), dict(A=1)):
+    for kw in (dict(), dict(value=None), dict(select=1, valid=FAKE, actions=FAKE, u=0.0), dict(A=1024), dict(A=1),
+               dict(B=2730, A=1024)):        # 2 795 520 rows: the largest multiple of 1024 at or under INT32_MAX / 768
         rc, msg = call(**kw)
         assert rc == 2, (kw, rc, msg)
 
