@@ -8,13 +8,17 @@
 //                            malfunction_down_counter / speed of every agent not DONE that has a position; ch4 0, += 1 at the
 //                            initial_position of every agent not DONE in an off-map state, the handle included (:568-611)
 //   targets      [H][W][2]   ch0 1 at the handle's own target (also when DONE), ch1 1 at the target of every agent not DONE
-// On-map positions are unique (MotionCheck), so every handle's two arrays are ONE per-env slab -- ch0 all -1, ch1..ch4 and the
-// targets' ch1 as above, targets' ch0 all 0 -- with three single-cell patches: ch0 at the virtual position, ch1 back to -1 at the
-// handle's own position, the targets' ch0 at its own target.
+// On-map positions are NOT unique: an agent whose malfunction ends off the map and that is told to stop is put on its
+// initial_position without MotionCheck being asked (rail_env.py:599-601), onto whoever stands there.  The reference walks the agents in
+// handle order and the last writer wins, so ch1..ch3 of a cell come from the HIGHEST handle on it, all three from that one agent.
+// Every handle's two arrays are still ONE per-env slab -- ch0 all -1, ch1..ch4 and the targets' ch1 as above, targets' ch0 all 0 --
+// with three single-cell patches: ch0 at the virtual position; ch1 of the handle's own cell when it is the highest handle there: -1,
+// or the direction of the highest OTHER handle on that cell; the targets' ch0 at its own target.
 //
 // Kernel: one workgroup per (env, band of cells, group of agents).  A band is a run of consecutive cells (row-major, so every
-// agent's band is one contiguous run of the output) sized to the LDS budget; the workgroup builds the band's slab in LDS (the ch4
-// counts with LDS atomics), then streams it once per agent of its group with the patches applied on the way -- 16-byte
+// agent's band is one contiguous run of the output) sized to the LDS budget; the workgroup builds the band's slab in LDS (the highest
+// handle of a cell with an LDS atomicMax, the ch4 counts with LDS float adds of 1, exact), then streams it once per agent of its group
+// with the patches applied on the way -- 16-byte
 // stores (plain: measured faster than non-temporal ones here, FLG_NT), scalar ones only where an agent's run starts or ends
 // inside a 16-byte word.  The rail channels of a band are
 // written by its group-0 workgroup.  Pure HBM write traffic: nothing is read back, the reads are the env's agents (A x 28 B) and
@@ -48,8 +52,9 @@ template <> struct flg_vec<float> { typedef float type __attribute__((ext_vector
 template <> struct flg_vec<double> { typedef double type __attribute__((ext_vector_type(2))); };
 
 // Elements [seg0 + i * stride, + n) of out for the agents i = 0 .. na-1 of the group: slab[0 .. n) with slab[ka[i]] = va[i] and
-// slab[kb[i]] = vb (ka / kb < 0: no patch; va == nullptr: the ka patch writes vb too).  out is 16-byte aligned; one lane writes one aligned 16-byte word.
-template <typename T>
+// slab[kb[i]] = vb (ka / kb < 0: no patch; va == nullptr: the ka patch writes vb too).  KBV: kb[i] holds index * 8 + value + 1 with its
+// own value -1 .. 3 instead of vb.  out is 16-byte aligned; one lane writes one aligned 16-byte word.
+template <typename T, bool KBV>
 __device__ __forceinline__ void flg_stream(T *__restrict__ out, size_t seg0, size_t stride, int na, int n, const T *slab,
                                            const int *ka, const T *va, const int *kb, T vb) {
     typedef typename flg_vec<T>::type VT;
@@ -61,14 +66,16 @@ __device__ __forceinline__ void flg_stream(T *__restrict__ out, size_t seg0, siz
         const size_t gw = s / V + j;                       // aligned word of out
         const long long k0 = (long long)(gw * V) - (long long)s;   // local index of its first element (< 0 at a run's head)
         if (k0 >= n) continue;
-        const int pa = ka[i], pb = kb[i];
+        const int pa = ka[i], kbi = kb[i];
+        const int pb = KBV ? kbi >> 3 : kbi;          // (-1 stays -1)
         const T xa = va != nullptr ? va[i] : vb;
+        const T xb = KBV ? (T)((kbi & 7) - 1) : vb;
         if (k0 >= 0 && k0 + V <= n) {
             VT v;
 #pragma unroll
             for (int e = 0; e < V; e++) {
                 const int k = (int)k0 + e;
-                v[e] = k == pa ? xa : k == pb ? vb : slab[k];
+                v[e] = k == pa ? xa : k == pb ? xb : slab[k];
             }
             flg_store(v, reinterpret_cast<VT *>(out + gw * V));
         } else {
@@ -76,7 +83,7 @@ __device__ __forceinline__ void flg_stream(T *__restrict__ out, size_t seg0, siz
             for (int e = 0; e < V; e++) {
                 const long long k = k0 + e;
                 if (k < 0 || k >= n) continue;
-                const T x = k == pa ? xa : k == pb ? vb : slab[k];
+                const T x = k == pa ? xa : k == pb ? xb : slab[k];
                 flg_store(x, out + gw * V + e);
             }
         }
@@ -96,10 +103,11 @@ __global__ void __launch_bounds__(FLG_THREADS) k_obs_global(FlDev d, int b0, int
     T *s_as = reinterpret_cast<T *>(flg_lds);     // [cb][5]
     T *s_tg = s_as + (size_t)cb * 5;               // [cb][2]
     T *s_dir = s_tg + (size_t)cb * 2;              // [ga] the agents' directions (ch0 patch value)
-    uint32_t *s_cnt = reinterpret_cast<uint32_t *>(s_dir + ga);   // [cb] ch4 counts
-    int *s_k0 = reinterpret_cast<int *>(s_cnt + cb);              // [ga] ch0 patch (local element index, -1 = none)
-    int *s_k1 = s_k0 + ga;                                         // [ga] ch1 back to -1
+    int *s_top = reinterpret_cast<int *>(s_dir + ga);             // [cb] 1 + the highest handle that stands on the cell (0: none)
+    int *s_k0 = s_top + cb;                                        // [ga] ch0 patch (local element index, -1 = none)
+    int *s_k1 = s_k0 + ga;                                         // [ga] ch1 patch: index * 8 + value + 1 (flg_stream KBV), -1 = none
     int *s_kt = s_k1 + ga;                                         // [ga] targets' ch0
+    __shared__ int s_stacked;                                      // some cell of the band holds more than one train
     const int tid = threadIdx.x;
 
     // rail channels of the band (observations.py:560-566): group 0 only; 16 elements a cell -> whole aligned words
@@ -119,45 +127,71 @@ __global__ void __launch_bounds__(FLG_THREADS) k_obs_global(FlDev d, int b0, int
     }
     if (ast == nullptr && tgt == nullptr) return;
 
-    for (int i = tid; i < nc * 5; i += FLG_THREADS) s_as[i] = (T)-1;
+    for (int i = tid; i < nc * 5; i += FLG_THREADS) s_as[i] = (i % 5) == 4 ? (T)0 : (T)-1;
     for (int i = tid; i < nc * 2; i += FLG_THREADS) s_tg[i] = (T)0;
-    for (int i = tid; i < nc; i += FLG_THREADS) s_cnt[i] = 0;
+    for (int i = tid; i < nc; i += FLG_THREADS) s_top[i] = 0;
+    if (tid == 0) s_stacked = 0;
     __syncthreads();
 
-    // the env-wide part (:592-610) and the group's patches
+    // the env-wide part (:592-610), first half: the targets, the ch4 counts, every cell's highest handle; the group's ch0 / target patches
     const size_t g0 = (size_t)b * A;
+    uint32_t pk_r = 0;                  // the lane's first agent (a = tid: every agent when A <= 256) stays in registers for the second half
+    int pos_r = -1;
+    T malf_r = (T)0, speed_r = (T)0;
     for (int a = tid; a < A; a += FLG_THREADS) {
-        const uint32_t pk = d.pk[g0 + a], st = PK_STATE(pk), dir = PK_DIR(pk);
+        const uint32_t pk = d.pk[g0 + a], st = PK_STATE(pk);
         const int pos = d.pos[g0 + a], ip = d.init_pos[g0 + a], tg = d.target[g0 + a];
         const int lp = pos - c0, li = ip - c0, lt = tg - c0;
-        const bool has_pos = st != ST_DONE && pos >= 0;
+        if (a == tid) { pk_r = pk; pos_r = pos; }
         if (st != ST_DONE) {
             if (lt >= 0 && lt < nc) s_tg[lt * 2 + 1] = (T)1;
-            if (has_pos && lp >= 0 && lp < nc) {
-                s_as[lp * 5 + 1] = (T)dir;
-                s_as[lp * 5 + 2] = (T)(d.malf[g0 + a] & 0xFFFFu);
-                s_as[lp * 5 + 3] = (T)d.speed[g0 + a];
+            if (pos >= 0 && lp >= 0 && lp < nc) {
+                if (atomicMax(&s_top[lp], a + 1) != 0) s_stacked = 1;
+                if (a == tid) { malf_r = (T)(d.malf[g0 + a] & 0xFFFFu); speed_r = (T)d.speed[g0 + a]; }
             }
-            if (is_off_map(st) && li >= 0 && li < nc) atomicAdd(&s_cnt[li], 1u);
+            if (is_off_map(st) && li >= 0 && li < nc) atomicAdd(&s_as[li * 5 + 4], (T)1);
         }
         const int i = a - a0;
         if (i >= 0 && i < na) {
             const int lv = (is_off_map(st) ? ip : st == ST_DONE ? tg : pos) - c0;     // the virtual position (:572-579)
             s_k0[i] = lv >= 0 && lv < nc ? lv * 5 : -1;
-            s_k1[i] = has_pos && lp >= 0 && lp < nc ? lp * 5 + 1 : -1;
             s_kt[i] = lt >= 0 && lt < nc ? lt * 2 : -1;
-            s_dir[i] = (T)dir;
+            s_dir[i] = (T)PK_DIR(pk);
         }
     }
     __syncthreads();
-    for (int i = tid; i < nc; i += FLG_THREADS) s_as[i * 5 + 4] = (T)s_cnt[i];
+    // second half: a cell's ch1..ch3 from its highest handle (the reference's last writer); the ch1 patch of a group agent that IS the
+    // highest handle of its cell -- what the handles below it left there: nothing, unless the band holds a stack
+    const bool stacked = s_stacked != 0;
+    for (int a = tid; a < A; a += FLG_THREADS) {
+        const bool kept = a == tid;
+        const uint32_t pk = kept ? pk_r : d.pk[g0 + a];
+        const int pos = kept ? pos_r : d.pos[g0 + a], lp = pos - c0;
+        const bool here = PK_STATE(pk) != ST_DONE && pos >= 0 && lp >= 0 && lp < nc;
+        const bool top = here && s_top[lp] == a + 1;
+        if (top) {
+            s_as[lp * 5 + 1] = (T)PK_DIR(pk);
+            s_as[lp * 5 + 2] = kept ? malf_r : (T)(d.malf[g0 + a] & 0xFFFFu);
+            s_as[lp * 5 + 3] = kept ? speed_r : (T)d.speed[g0 + a];
+        }
+        const int i = a - a0;
+        if (i >= 0 && i < na) {
+            int v = -1;
+            if (top && stacked)
+                for (int j = a - 1; j >= 0; j--) {     // the highest OTHER handle on the cell
+                    const uint32_t pj = d.pk[g0 + j];
+                    if (d.pos[g0 + j] == pos && PK_STATE(pj) != ST_DONE) { v = (int)PK_DIR(pj); break; }
+                }
+            s_k1[i] = top ? (lp * 5 + 1) * 8 + v + 1 : -1;
+        }
+    }
     __syncthreads();
 
     const size_t first = (size_t)bl * A + a0;     // the group's first agent in the range's [nb][A] order
     if (ast != nullptr)
-        flg_stream<T>(ast, first * HW * 5 + (size_t)c0 * 5, (size_t)HW * 5, na, nc * 5, s_as, s_k0, s_dir, s_k1, (T)-1);
+        flg_stream<T, true>(ast, first * HW * 5 + (size_t)c0 * 5, (size_t)HW * 5, na, nc * 5, s_as, s_k0, s_dir, s_k1, (T)-1);
     if (tgt != nullptr)
-        flg_stream<T>(tgt, first * HW * 2 + (size_t)c0 * 2, (size_t)HW * 2, na, nc * 2, s_tg, s_kt, nullptr, s_kt, (T)1);
+        flg_stream<T, false>(tgt, first * HW * 2 + (size_t)c0 * 2, (size_t)HW * 2, na, nc * 2, s_tg, s_kt, nullptr, s_kt, (T)1);
 }
 
 static inline size_t flg_lds_bytes(int cb, int ga, int eb) { return (size_t)cb * (7 * eb + 4) + (size_t)ga * (eb + 12); }

@@ -20,6 +20,9 @@ N, E, S, W = 0 .. 3), init_pos i32[A, 2], init_dir i32[A], target i32[A, 2], ear
                        three ways on per direction
   mesh33        33x33  the same mesh: 4 356 states (more than the BFS ring holds), levels of up to 260 states
 
+full_grid(H, W) is the mesh on any H x W: rail on every cell, the border included.  GLOBAL_STATES (end of the file): constructed agent states
+for GlobalObsForRailEnv on full5x7 and the crossing, captured by oracle/refharness/capture_global_states.py.
+
 Adding a map: write a builder that returns such a dict, list it in MAPS, add its capture to oracle/refharness/capture_handmaps.py (run there,
 where the reference lies), and add the condition the map exists for to tests/test_handmaps.py::test_each_fixture_reaches_the_path_it_exists_for.
 """
@@ -137,15 +140,20 @@ def crossing_u5():
     return _map(_crossing_grid(), [a + t for a, t in zip(CROSSING_AGENTS, targets)], earliest=[8, 0, 0, 5, 30])
 
 
-def mesh_grid(n):
-    g = np.zeros((n, n), dtype=np.uint16)
-    for r in range(n):
-        for c in range(n):
+def full_grid(H, Wd):
+    """rail on EVERY cell, the border included: left, forward and right wherever the neighbour is inside the grid"""
+    g = np.zeros((H, Wd), dtype=np.uint16)
+    for r in range(H):
+        for c in range(Wd):
             for d in range(4):
                 for m in ((d + 3) % 4, d, (d + 1) % 4):
-                    if 0 <= r + DR[m] < n and 0 <= c + DC[m] < n:
+                    if 0 <= r + DR[m] < H and 0 <= c + DC[m] < Wd:
                         g[r, c] |= way(d, m)
     return g
+
+
+def mesh_grid(n):
+    return full_grid(n, n)
 
 
 def mesh12():
@@ -236,3 +244,79 @@ def level_sizes(dm_slab):
     """sizes of the BFS levels of one target's distance map u16[H, W, 4]: count of states per finite distance"""
     v = np.asarray(dm_slab).ravel()
     return np.bincount(v[v != 0xFFFF].astype(np.int64))
+
+
+# ---- constructed agent states for GlobalObsForRailEnv (oracle/refharness/capture_global_states.py -> tests/golden/global_states_<map>.npz)
+# What a played episode reaches only by luck: trains that SHARE a cell (an agent whose malfunction ends off the map and that is told to stop
+# is put on its initial_position without MotionCheck), such a stack on a DONE agent's target or on the start cell of waiting agents, many
+# agents of all three off-map states on one start cell, the two corner cells.  A state is one row per agent: (state, row, col, direction,
+# malfunction_down_counter); row = col = -1 off the map and when DONE.
+WAITING, READY, MALF_OFF, MOVING, STOPPED, MALF, DONE = range(7)
+
+
+def state_rows(spec):
+    """i32[A, 12] agent rows in the order of tests/util.STATE_NAMES from (state, row, col, direction, malfunction) per agent"""
+    rows = np.full((len(spec), 12), -1, dtype=np.int32)
+    for i, (kind, r, c, d, malf) in enumerate(spec):
+        assert (r >= 0) == (MOVING <= kind <= MALF), spec[i]
+        rows[i, 0:8] = (r, c, d, kind, malf, int(malf > 0), 0, 0)
+        rows[i, 8] = 7 if kind == DONE else -1
+    return rows
+
+
+def _off(kind, d=0, malf=0):
+    return (kind, -1, -1, d, malf)
+
+
+def full5x7_states():
+    """8 agents on a 5 x 7 grid with rail everywhere; agents 0 .. 4 start on ONE cell, agents 5 and 6 on the two corners"""
+    m = _map(full_grid(5, 7), [(2, 3, E, 4, 6), (2, 3, S, 0, 0), (2, 3, W, 3, 1), (2, 3, N, 3, 1), (2, 3, E, 1, 2),
+                               (0, 0, E, 4, 6), (4, 6, W, 0, 0), (1, 5, S, 2, 3)])
+    m["speed"] = np.array([1.0, 1 / 2, 1 / 3, 1 / 4, 1 / 5, 1 / 2, 1 / 3, 1.0])
+    states = [
+        # a stack of two (handles 1 and 4) on the start cell of the off-map agents 0, 2 and 3: ch0 at the virtual position over a ch4 count
+        [_off(WAITING, E), (STOPPED, 2, 3, E, 0), _off(READY, W), _off(MALF_OFF, N, 3), (MALF, 2, 3, W, 5), (MOVING, 1, 1, S, 0),
+         _off(WAITING, W), (MOVING, 3, 4, N, 0)],
+        # a stack of three (2, 5, 7), every direction, counter and speed different; trains on both corner cells
+        [(MOVING, 0, 0, S, 0), _off(WAITING, S), (STOPPED, 3, 3, N, 0), _off(READY, N), _off(MALF_OFF, E, 4), (MALF, 3, 3, E, 7),
+         (MOVING, 4, 6, N, 0), (MOVING, 3, 3, S, 1)],
+        # five agents off the map on one start cell, in all three off-map states; off-map agents on the corners
+        [_off(WAITING, E), _off(READY, S), _off(MALF_OFF, W, 2), _off(WAITING, N), _off(READY, E), _off(READY, E), _off(MALF_OFF, W, 6),
+         (MOVING, 1, 5, S, 0)],
+        # DONE agents: 2's target (3, 1) under the stack of 0 and 5 and also 3's target; 1's target (0, 0) under train 7
+        [(MOVING, 3, 1, W, 0), _off(DONE, N), _off(DONE, W), (STOPPED, 2, 2, W, 0), (MALF, 1, 2, N, 9), (STOPPED, 3, 1, S, 2),
+         (STOPPED, 4, 6, E, 0), (MOVING, 0, 0, N, 0)],
+        # everybody but the last handle DONE
+        [_off(DONE, E), _off(DONE, S), _off(DONE, W), _off(DONE, N), _off(DONE, E), _off(DONE, S), _off(DONE, W), (MOVING, 2, 3, S, 0)],
+        # two stacks at once, on the two corners, one of them on its lower handle's own start cell
+        [(MOVING, 4, 6, E, 0), _off(WAITING, S), _off(READY, W), (MOVING, 2, 3, N, 0), _off(MALF_OFF, E, 1), (STOPPED, 0, 0, W, 0),
+         (MALF, 4, 6, S, 3), (MOVING, 0, 0, S, 8)],
+    ]
+    return m, np.stack([state_rows(s) for s in states])
+
+
+def crossing_states():
+    """the five agents of crossing_u5 (a sparse rail: most cells hold none)"""
+    m = crossing_u5()
+    m["speed"] = np.array([1.0, 1 / 2, 1 / 3, 1 / 4, 1 / 5])
+    states = [
+        [_off(WAITING, E), _off(WAITING, S), _off(WAITING, W), _off(WAITING, N), _off(WAITING, N)],
+        # a stack of two on the diamond crossing, which is agent 1's target; agent 4 DONE with train 0 on its target
+        [(MOVING, 6, 4, N, 0), (MALF, 4, 4, S, 4), _off(MALF_OFF, W, 2), (MOVING, 4, 4, E, 0), _off(DONE, N)],
+        # a stack of three on the start cell of agent 2, which is ready to depart; observed from below, from inside and from the top
+        [(STOPPED, 4, 7, E, 2), (MOVING, 4, 7, W, 0), _off(READY, W), _off(DONE, N), (MALF, 4, 7, N, 6)],
+        # the highest handle of the stack is the only other train: the lowest one sees it, a handle elsewhere sees it too
+        [(MOVING, 4, 2, W, 0), (STOPPED, 2, 4, S, 0), (STOPPED, 4, 2, E, 1), _off(WAITING, N), (MOVING, 5, 6, S, 0)],
+    ]
+    return m, np.stack([state_rows(s) for s in states])
+
+
+GLOBAL_STATES = {"full5x7": full5x7_states, "crossing": crossing_states}
+
+
+def global_static(m):
+    """the static description BatchedRailEnv / tests/global_obs_np.py take, from a map dict that has speeds (no malfunctions, a long episode)"""
+    A = len(m["init_dir"])
+    return dict(grid=m["grid"], init_pos=m["init_pos"], init_dir=m["init_dir"], target=m["target"], speed=np.asarray(m["speed"], dtype=np.float64),
+                earliest=m["earliest"], latest=np.asarray(m["earliest"]) + 200, T=400, malf_rate=0.0, malf_min=0, malf_max=0,
+                mt_key=np.arange(624, dtype=np.uint32), mt_pos=624)
