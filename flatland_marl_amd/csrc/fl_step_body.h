@@ -1,5 +1,5 @@
-// fl_step_body.h -- RailEnv.step() of one env as a device function (used by k_step and by the fused step + observation
-// kernels of fl_obs.hip).  See fl_step.hip for the reference map.
+// fl_step_body.h -- RailEnv.step() of one env as a device function, used by k_step alone: the fused step + observation entry
+// point (fl_step_obs) launches k_step and then the observation kernels.  See fl_step.hip for the reference map.
 #pragma once
 #include "fl_internal.h"
 #include "../../include/flatland_hip.h"
