@@ -80,8 +80,14 @@ _POLICY_ABI = {
     "fl_policy_head_workspace_bytes": ([i32, i32], C.c_size_t),
     "fl_policy_head": ([i32, i32, vp, vp, C.POINTER(vp), vp, i32, C.c_double, vp, vp, vp, vp, C.c_size_t, vp], i32),
 }
+# name -> (argtypes, restype) of every function include/flatland_train.h declares, in the header's order
+_TRAIN_ABI = {
+    "fl_tree_lstm_backward_workspace_bytes": ([i32, i32], C.c_size_t),
+    "fl_tree_lstm_backward": ([i32, i32] + [vp] * 15 + [i32] + [vp] * 7 + [C.c_size_t, vp], i32),
+}
 SYMBOLS = tuple(_ABI)      # every symbol include/flatland_hip.h declares
 POLICY_SYMBOLS = tuple(_POLICY_ABI)      # ... and include/flatland_policy.h
+TRAIN_SYMBOLS = tuple(_TRAIN_ABI)      # ... and include/flatland_train.h
 POLICY_HEAD_NPARAMS = 38
 POLICY_SELECT = {None: 0, "soft": 1, "hard": 2}
 POLICY_U_REFERENCE = 0.3745401188473625      # numpy.random.RandomState(42).random_sample(): the reference seeds before every draw
@@ -118,7 +124,7 @@ def lib():
         # otherwise torch.cuda finds no device once the library below has pulled in the system runtime
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
-        for name, (args, res) in {**_ABI, **_DEBUG_ABI, **_POLICY_ABI}.items():
+        for name, (args, res) in {**_ABI, **_DEBUG_ABI, **_POLICY_ABI, **_TRAIN_ABI}.items():
             fn = getattr(L, name, None)        # (a library from bench.py --lib or a tool's LIB_PATH may predate the newer ones)
             if fn is not None:
                 fn.argtypes, fn.restype = args, res
@@ -197,6 +203,43 @@ def tree_lstm(forest, adjacency, node_order, edge_order, weights, roots_only, h,
                 None if c is None else c.data_ptr(), None if status is None else status.data_ptr(),
                 ws.data_ptr(), ws.numel(), C.c_void_p(s)))
     return h
+
+
+def tree_lstm_backward(forest, adjacency, node_order, edge_order, weights, h, c, grad_h, roots_only, da, dc, dg, q, child,
+                       status=None):
+    """The tree-ordered part of TreeLSTM's gradient (fl_tree_lstm_backward, include/flatland_train.h) on torch's current stream of
+    the inputs' device, with a workspace from torch's allocator.  Inputs and weights as for tree_lstm; h, c f32 [T*N, 128] of every
+    node from the forward; grad_h f32 [T*N, 128] or, roots_only, [T, 128].  Outputs, per node: da f32 [T*N, 384], dc f32
+    [T*N, 128], dg f32 [T*N, 3, 128], q f32 [T*N, 384], child i32 [T*N, 3]; status i32 [1] or None.  No parameter gradient is
+    written: policy.tree_lstm_param_grads forms them from these rows."""
+    import torch
+    N = forest.shape[-2]
+    T = forest.numel() // (N * 12)
+    fn = _sym("fl_tree_lstm_backward")
+    dev = forest.device
+    if len(weights) != 8:
+        raise ValueError("tree_lstm_backward: %d weights, 8 expected" % len(weights))
+    for name, o, dt in [("forest", forest, torch.float32), ("adjacency", adjacency, torch.int64), ("node_order", node_order, torch.int64),
+                        ("edge_order", edge_order, torch.int64)] + [("weight %d" % i, w, torch.float32) for i, w in enumerate(weights)]:
+        if o.dtype != dt or o.device != dev or not o.is_contiguous():
+            raise ValueError("tree_lstm_backward: %s must be a contiguous %s tensor on %s" % (name, dt, dev))
+    if adjacency.numel() != T * (N - 1) * 3 or node_order.numel() != T * N or edge_order.numel() != T * (N - 1):
+        raise ValueError("tree_lstm_backward: index tensors of %d trees x %d nodes are expected" % (T, N))
+    for name, o, dt, n in (("h", h, torch.float32, T * N * 128), ("c", c, torch.float32, T * N * 128),
+                           ("grad_h", grad_h, torch.float32, (T if roots_only else T * N) * 128),
+                           ("da", da, torch.float32, T * N * 384), ("dc", dc, torch.float32, T * N * 128),
+                           ("dg", dg, torch.float32, T * N * 384), ("q", q, torch.float32, T * N * 384),
+                           ("child", child, torch.int32, T * N * 3)):
+        if o.dtype != dt or o.device != dev or not o.is_contiguous() or o.numel() < n:
+            raise ValueError("tree_lstm_backward: %s must be a contiguous %s tensor of at least %d elements on %s" % (name, dt, n, dev))
+    nbytes = _sym("fl_tree_lstm_backward_workspace_bytes")(T, N)
+    with torch.cuda.device(dev):
+        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+        s = torch.cuda.current_stream(dev).cuda_stream
+        _chk(fn(T, N, forest.data_ptr(), adjacency.data_ptr(), node_order.data_ptr(), edge_order.data_ptr(),
+                *[w.data_ptr() for w in weights], h.data_ptr(), c.data_ptr(), grad_h.data_ptr(), int(roots_only),
+                da.data_ptr(), dc.data_ptr(), dg.data_ptr(), q.data_ptr(), child.data_ptr(),
+                None if status is None else status.data_ptr(), ws.data_ptr(), ws.numel(), C.c_void_p(s)))
 
 
 def policy_head(agents_attr, tree_embedding, params, logits, value=None, valid_actions=None, actions=None, mode=None, u=None):

@@ -4,8 +4,14 @@ env, actor and critic heads -- and the actor's choice of an action (solution/plf
 
 `TreeLSTM` has the reference module's submodules, parameter names and shapes, so a reference checkpoint loads unchanged, and it
 takes the tensors BatchedRailEnv.obs_policy() returns (adjacency already modified) as they are.  The kernel reads the live
-parameter tensors at every call: after load_state_dict or an in-place update the next forward uses the new values.  Inference
-only: the output comes through an autograd.Function whose backward raises NotImplementedError.
+parameter tensors at every call: after load_state_dict or an in-place update the next forward uses the new values.
+
+By default the encoder is inference only: the output comes through an autograd.Function whose backward raises NotImplementedError.
+TreeLSTM(trainable=True) (or m.trainable = True) makes forward / roots differentiable with respect to the eight parameters: the
+forward is the same kernel (every node, c kept), the backward is fl_tree_lstm_backward (include/flatland_train.h) for everything
+that follows the tree order, then the parameter gradients as float32 matrix products over all nodes, in chunks of
+BACKWARD_CHUNK_TREES trees added in order.  Two backward passes on the same inputs give the same bits.  The forest gets no
+gradient.  The head (fl_policy_head) is still inference only; Network.forward_torch is its path with autograd.
 
 Swap it into the reference's Network:  net.tree_lstm = TreeLSTM.from_module(net.tree_lstm)
 or take the whole network:              net = Network.from_module(net)
@@ -24,6 +30,94 @@ class TreeLSTMViolation(ValueError):
     """check=True found trees that break the reference's grouping (their outputs are unspecified)."""
 
 
+BACKWARD_CHUNK_TREES = 4096      # trees a fl_tree_lstm_backward launch: its per-node buffers and workspace are 8.2 KB a node
+REDUCE_BLOCK = 256               # nodes a float32 partial product of a parameter gradient
+
+
+def _tn(a, b):
+    """a^T b over the rows, [n, p] x [n, q] -> [p, q], summed in a fixed order: whole blocks of REDUCE_BLOCK rows as one batched
+    float32 product, the partial products added in float64, then the ragged rest.  Short blocks and the float64 sum keep the
+    rounding of a sum over 10^5 nodes at that of one block: one long float32 product over all rows measured up to 3.6x the error
+    of torch's own float32 autograd, which sums level by level"""
+    n = a.shape[0]
+    main = n - n % REDUCE_BLOCK
+    out = None
+    if main:
+        out = torch.bmm(a[:main].view(-1, REDUCE_BLOCK, a.shape[1]).transpose(1, 2),
+                        b[:main].view(-1, REDUCE_BLOCK, b.shape[1])).sum(0, dtype=torch.float64)
+    if main < n:
+        rest = torch.matmul(a[main:].t(), b[main:]).double()
+        out = rest if out is None else out + rest
+    return out.to(a.dtype)
+
+
+def _colsum(a):
+    """the sum over the rows, accumulated in float64"""
+    return a.sum(0, dtype=torch.float64).to(a.dtype)
+
+
+def tree_lstm_param_grads(x, node_order, h, da, dc, dg, q, child):
+    """the eight parameter gradients, in PARAM_ORDER, from fl_tree_lstm_backward's per-node rows (include/flatland_train.h): x f32
+    [n, 12], node_order i64 [n], h f32 [n, 128], da [n, 384], dc [n, 128], dg [n, 3, 128], q [n, 384], child i32 [n, 3] (ids into
+    these very rows, -1 = read as zero)"""
+    n = x.shape[0]
+    zero = x.new_zeros(())
+    x = torch.where((node_order >= 0).view(n, 1), x, zero)                   # (a padding node's features must not matter: 0 * nan)
+    hk = torch.where((child >= 0).view(n, 3, 1), h[child.clamp(min=0).long()], zero)
+    dgs = dg.sum(1)
+    return (_tn(da, x), _colsum(da), _tn(da, hk.view(n, 3 * OUT_FEATURES)), _tn(dc, q),
+            _colsum(torch.where((node_order >= 1).view(n, 1), dc, zero)), _tn(dgs, x), _colsum(dgs),
+            _tn(dg.reshape(3 * n, OUT_FEATURES), hk.view(3 * n, OUT_FEATURES)))
+
+
+class _TrainForward(torch.autograd.Function):
+    """fl_tree_lstm on every node with c kept, fl_tree_lstm_backward + the parameter products behind it"""
+
+    @staticmethod
+    def forward(ctx, forest, adjacency, node_order, edge_order, roots_only, status, *weights):
+        B, A, N = forest.shape[:3]
+        T = B * A
+        h = torch.empty((T * N, OUT_FEATURES), dtype=torch.float32, device=forest.device)
+        c = torch.empty_like(h)
+        hip_backend.tree_lstm(forest, adjacency, node_order, edge_order, weights, False, h, c, status=status)
+        ctx.roots_only = roots_only
+        ctx.save_for_backward(forest, adjacency, node_order, edge_order, h, c, *weights)
+        return h.view(T, N, OUT_FEATURES)[:, 0].contiguous() if roots_only else h
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        forest, adjacency, node_order, edge_order, h, c = ctx.saved_tensors[:6]
+        weights = ctx.saved_tensors[6:]
+        B, A, N = forest.shape[:3]
+        T, M, dev = B * A, OUT_FEATURES, forest.device
+        grad = grad.to(torch.float32).contiguous().view(T if ctx.roots_only else T * N, M)
+        x, adj = forest.view(T, N, IN_FEATURES), adjacency.view(T, N - 1, 3)
+        no, eo = node_order.view(T, N), edge_order.view(T, N - 1)
+        hv, cv, gv = h.view(T, N, M), c.view(T, N, M), grad.view(T, -1, M)
+        total = None
+        for t0 in range(0, T, BACKWARD_CHUNK_TREES):
+            t1 = min(T, t0 + BACKWARD_CHUNK_TREES)
+            n = (t1 - t0) * N
+            a = adj[t0:t1]
+            if t0:                                                # node ids count from the chunk's first tree
+                shift = torch.zeros(3, dtype=torch.int64, device=dev)
+                shift[:2] = t0 * N
+                a = torch.where(a >= 0, a - shift, a)
+            da = torch.empty((n, 3 * M), dtype=torch.float32, device=dev)
+            dc = torch.empty((n, M), dtype=torch.float32, device=dev)
+            dg = torch.empty((n, 3, M), dtype=torch.float32, device=dev)
+            q = torch.empty((n, 3 * M), dtype=torch.float32, device=dev)
+            child = torch.empty((n, 3), dtype=torch.int32, device=dev)
+            hc = hv[t0:t1].reshape(n, M)
+            hip_backend.tree_lstm_backward(x[t0:t1], a, no[t0:t1], eo[t0:t1], weights, hc, cv[t0:t1].reshape(n, M),
+                                           gv[t0:t1].reshape(-1, M), ctx.roots_only, da, dc, dg, q, child)
+            part = tree_lstm_param_grads(x[t0:t1].reshape(n, IN_FEATURES), no[t0:t1].reshape(n), hc, da, dc, dg, q, child)
+            total = part if total is None else tuple(u + v for u, v in zip(total, part))
+        need = ctx.needs_input_grad[6:]
+        return (None,) * 6 + tuple(g if k else None for g, k in zip(total, need))
+
+
 class _Forward(torch.autograd.Function):
     @staticmethod
     def forward(ctx, forest, adjacency, node_order, edge_order, roots_only, status, *weights):
@@ -40,10 +134,13 @@ class _Forward(torch.autograd.Function):
 
 class TreeLSTM(nn.Module):
     """TreeLSTM(in_features=12, out_features=128) on fl_tree_lstm; forward(forest, adjacency, node_order, edge_order) returns
-    h of every node, [B*A*N, 128] f32, as the reference does; roots(...) returns node 0 of every tree, [B, A, 128]."""
+    h of every node, [B*A*N, 128] f32, as the reference does; roots(...) returns node 0 of every tree, [B, A, 128].
+    trainable (a plain attribute, settable): False = inference only, backward raises; True = with grad mode on, forward and roots
+    are differentiable with respect to the parameters (fl_tree_lstm_backward), their values the same bits as the inference path's."""
 
-    def __init__(self, in_features=IN_FEATURES, out_features=OUT_FEATURES):
+    def __init__(self, in_features=IN_FEATURES, out_features=OUT_FEATURES, trainable=False):
         super().__init__()
+        self.trainable = bool(trainable)
         if (in_features, out_features) != (IN_FEATURES, OUT_FEATURES):
             raise ValueError("TreeLSTM: only in_features=%d, out_features=%d exist here, got %d, %d"
                              % (IN_FEATURES, OUT_FEATURES, in_features, out_features))
@@ -56,7 +153,7 @@ class TreeLSTM(nn.Module):
         self.U_f = nn.Linear(out_features, out_features, bias=False)
 
     @classmethod
-    def from_module(cls, m):
+    def from_module(cls, m, trainable=False):
         """a TreeLSTM that shares m's parameters (m: the reference's TreeLSTM or one of these)"""
         if (m.in_features, m.out_features) != (IN_FEATURES, OUT_FEATURES):
             raise ValueError("TreeLSTM.from_module: only in_features=%d, out_features=%d exist here, got %d, %d"
@@ -64,6 +161,7 @@ class TreeLSTM(nn.Module):
         obj = cls.__new__(cls)
         nn.Module.__init__(obj)
         obj.in_features, obj.out_features = m.in_features, m.out_features
+        obj.trainable = bool(trainable)
         for name in ("W_iou", "U_iou", "W_c", "W_f", "U_f"):
             setattr(obj, name, getattr(m, name))
         return obj
@@ -110,7 +208,11 @@ class TreeLSTM(nn.Module):
         self._check_inputs(forest, adjacency, node_order, edge_order)
         ws = self._weights(forest.device)
         status = torch.zeros(1, dtype=torch.int32, device=forest.device) if check else None
-        out = _Forward.apply(forest, adjacency, node_order, edge_order, roots_only, status, *ws)
+        train = self.trainable and torch.is_grad_enabled()
+        if train and forest.requires_grad:
+            raise ValueError("TreeLSTM: the forest gets no gradient (fl_tree_lstm_backward differentiates with respect to the "
+                             "parameters only): detach it")
+        out = (_TrainForward if train else _Forward).apply(forest, adjacency, node_order, edge_order, roots_only, status, *ws)
         if check:
             bad = int(status.item())
             if bad:
@@ -204,7 +306,7 @@ class Network(nn.Module):
         """a Network that shares m's parameters (m: the reference's Network or one of these)"""
         obj = cls.__new__(cls)
         nn.Module.__init__(obj)
-        obj.tree_lstm = TreeLSTM.from_module(m.tree_lstm)
+        obj.tree_lstm = TreeLSTM.from_module(m.tree_lstm, trainable=getattr(m.tree_lstm, "trainable", False))
         obj.attr_embedding = m.attr_embedding
         blocks = []
         for b in m.transformer:
@@ -317,9 +419,13 @@ class Network(nn.Module):
         return [self.actor_net(both)], self.critic_net(both).mean(1).view(-1)
 
     def forward_torch(self, agents_attr, forest, adjacency, node_order, edge_order):
-        """forward() with everything after the tree encoder in torch's eager ops: the path with autograd (for the head's
-        parameters; the tree encoder is fl_tree_lstm here as well, which has no backward, so its output enters as a constant).
-        The adjacency is already modified, as for forward."""
-        with torch.no_grad():
+        """forward() with everything after the tree encoder in torch's eager ops: the path with autograd.  The tree encoder is
+        fl_tree_lstm here as well: with tree_lstm.trainable set its parameters get gradients too (fl_tree_lstm_backward), so one
+        call trains the whole network; without it its output enters as a constant.  The adjacency is already modified, as for
+        forward."""
+        if self.tree_lstm.trainable:
             tree = self.tree_lstm.roots(forest, adjacency, node_order, edge_order)
+        else:
+            with torch.no_grad():
+                tree = self.tree_lstm.roots(forest, adjacency, node_order, edge_order)
         return self.head_torch(agents_attr, tree)
