@@ -261,6 +261,62 @@ void orc_get_state(const OrcEnv *e, int32_t *out) {
     }
 }
 
+/* start the env from a dynamic state: rows as orc_get_state writes them, aux (may be NULL) as fl_get_state_aux does -- previous_state
+ * (-1 = None), the in_malfunction signal of the last step, the deadlock flag, done.  The checks are fl_set_state's. */
+int orc_set_state(OrcEnv *e, const int32_t *state, const int32_t *aux, int elapsed, int done_all) {
+    int i;
+    if (!state) { orc_set_error("orc_set_state: null state"); return ORC_ERR_ARG; }
+    if (elapsed < 0) { orc_set_error("orc_set_state: negative elapsed steps"); return ORC_ERR_ARG; }
+    for (i = 0; i < e->A; i++) {
+        const int32_t *o = state + (size_t)i * ORC_STATE_COLS;
+        const int r = o[0], c = o[1], dir = o[2], st = o[3], mf = o[4], nmf = o[5], sc = o[6], sv = o[7], orow = o[9], ocol = o[10], od = o[11];
+        const int on = r >= 0;
+        if ((on && (r >= e->H || c < 0 || c >= e->W)) || dir < 0 || dir > 3 || st < ST_WAITING || st > ST_DONE || mf < 0 || mf > 0xFFFF ||
+            nmf < 0 || nmf > 0xFFFF || sc < 0 || sc > 63 || sv < 0 || sv > 3 || od < -1 || od > 3 ||
+            (orow >= 0 && (orow >= e->H || ocol < 0 || ocol >= e->W))) {
+            orc_set_error("orc_set_state: agent %d: value out of range", i);
+            return ORC_ERR_ARG;
+        }
+        if ((orc_is_on_map(st) && !on) || (st <= ST_MALF_OFF && on)) {       /* state_position_sync_check (step_utils/env_utils.py:45-52) */
+            orc_set_error("orc_set_state: agent %d: state %d does not match position", i, st);
+            return ORC_ERR_SYNC;
+        }
+        if ((on && orc_cell(e, r, c) == 0) || (orow >= 0 && orc_cell(e, orow, ocol) == 0)) {
+            orc_set_error("orc_set_state: agent %d: position (%d, %d) / old position (%d, %d) is not a rail cell", i, r, c, orow, ocol);
+            return ORC_ERR_SYNC;
+        }
+        if (aux) {
+            const int32_t *x = aux + (size_t)i * ORC_AUX_COLS;
+            if (x[0] < -1 || x[0] > ST_DONE || (x[1] | x[2] | x[3]) < 0 || x[1] > 1 || x[2] > 1 || x[3] > 1) {
+                orc_set_error("orc_set_state: agent %d: aux value out of range", i);
+                return ORC_ERR_ARG;
+            }
+        }
+    }
+    for (i = 0; i < e->A; i++) {
+        const int32_t *o = state + (size_t)i * ORC_STATE_COLS;
+        e->r[i] = o[0] < 0 ? -1 : o[0]; e->c[i] = o[0] < 0 ? -1 : o[1]; e->dir[i] = o[2]; e->state[i] = o[3];
+        e->malf[i] = o[4]; e->nmalf[i] = o[5]; e->scount[i] = o[6]; e->saved[i] = o[7]; e->arrival[i] = o[8];
+        e->old_r[i] = o[9] < 0 ? -1 : o[9]; e->old_c[i] = o[9] < 0 ? -1 : o[10]; e->old_dir[i] = o[11];
+        e->prev_state[i] = -1; e->sig_in_malf[i] = (uint8_t)(o[4] > 0); e->deadlocked[i] = 0; e->done[i] = (uint8_t)(o[3] == ST_DONE);
+        if (aux) {
+            const int32_t *x = aux + (size_t)i * ORC_AUX_COLS;
+            e->prev_state[i] = x[0]; e->sig_in_malf[i] = (uint8_t)x[1]; e->deadlocked[i] = (uint8_t)x[2]; e->done[i] = (uint8_t)x[3];
+        }
+    }
+    e->t = elapsed;
+    e->done_all = done_all ? 1 : 0;
+    return ORC_OK;
+}
+
+void orc_get_state_aux(const OrcEnv *e, int32_t *out) {
+    int i;
+    for (i = 0; i < e->A; i++) {
+        int32_t *o = out + (size_t)i * ORC_AUX_COLS;
+        o[0] = e->prev_state[i]; o[1] = e->sig_in_malf[i]; o[2] = e->deadlocked[i]; o[3] = e->done[i];
+    }
+}
+
 /* ------------------------------------------------------------------ MotionCheck (envs/agent_chains.py)
  * The reference builds a networkx DiGraph whose NODES are cells (off-map agents get a private virtual node,
  * :28-32) and whose edges are cur->next.  Restated on node ids without a graph library:

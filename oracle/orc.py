@@ -11,6 +11,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB = os.path.join(HERE, "libfl_oracle.so")
 STATE_COLS = 12
+AUX_COLS = 4
 STATE_NAMES = ("row", "col", "dir", "state", "malf", "nmalf", "scount", "saved", "arrival",
                "old_row", "old_col", "old_dir")
 _lib = None
@@ -38,6 +39,8 @@ def lib():
         _lib.orc_step.argtypes = [C.c_void_p] + [C.c_void_p] * 4
         _lib.orc_get_state.argtypes = [C.c_void_p, C.c_void_p]
         _lib.orc_elapsed.argtypes = [C.c_void_p]
+        _lib.orc_set_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+        _lib.orc_get_state_aux.argtypes = [C.c_void_p, C.c_void_p]
         _lib.orc_last_error.restype = C.c_char_p
         _lib.orc_num_targets.argtypes = [C.c_void_p]
         _lib.orc_get_distance_map.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
@@ -119,6 +122,27 @@ class OracleEnv:
         out = np.zeros((self.A, STATE_COLS), dtype=np.int32)
         lib().orc_get_state(self.h, _p(out))
         return out
+
+    def state_aux(self):
+        """int32[A, 4]: previous_state (-1 = None), in_malfunction signal of the last step, deadlocked, done"""
+        out = np.zeros((self.A, AUX_COLS), dtype=np.int32)
+        lib().orc_get_state_aux(self.h, _p(out))
+        return out
+
+    def elapsed(self):
+        return int(lib().orc_elapsed(self.h))
+
+    def set_state(self, state, aux=None, elapsed=0, done_all=False):
+        """start from a dynamic state (orc_set_state): state int32[A, 12] as state() returns it, aux int32[A, 4] as state_aux() does;
+        refused with fl_set_state's own checks"""
+        state = np.ascontiguousarray(state, dtype=np.int32)
+        assert state.shape == (self.A, STATE_COLS)
+        if aux is not None:
+            aux = np.ascontiguousarray(aux, dtype=np.int32)
+            assert aux.shape == (self.A, AUX_COLS)
+        rc = lib().orc_set_state(self.h, _p(state), None if aux is None else _p(aux), int(elapsed), int(bool(done_all)))
+        if rc != 0:
+            raise ValueError(lib().orc_last_error().decode())
 
     def distance_map(self):
         U = lib().orc_num_targets(self.h)

@@ -20,6 +20,9 @@ N, E, S, W = 0 .. 3), init_pos i32[A, 2], init_dir i32[A], target i32[A, 2], ear
                        three ways on per direction
   mesh33        33x33  the same mesh: 4 356 states (more than the BFS ring holds), levels of up to 260 states
 
+  yard          8x9    (STEP_MAPS, not in MAPS: no recorded episode) two lines joined by a stem that enters a symmetric switch from below and
+                       leaves at a facing simple switch, four dead ends, a stub nobody reaches: the rail of tests/step_state_cases.py
+
 full_grid(H, W) is the mesh on any H x W: rail on every cell, the border included.  GLOBAL_STATES (end of the file): constructed agent states
 for GlobalObsForRailEnv on full5x7 and the crossing, captured by oracle/refharness/capture_global_states.py.
 
@@ -210,6 +213,29 @@ def defined_attr(fx, t):
         if r >= 0 and not known_cell_type(fx["grid"][r, c]):
             ok[i, ROAD_TYPE_COLS] = False
     return ok
+
+
+# ---- the maps of tests/step_state_cases.py (constructed states of RailEnv.step(); oracle/refharness/capture_step_states.py)
+SYM_SWITCH = 0x5202                  # Flatland's symmetrical switch, stem to the south: a northbound train chooses west or east, never ahead
+YARD_SYM, YARD_SWITCH = (1, 3), (4, 3)
+
+
+def yard():
+    """8 x 9: two lines with dead ends joined by a stem.  The stem enters a SYMMETRIC switch from below (FORWARD has no transition there and
+    becomes STOP_MOVING); it leaves the bottom line at a simple switch that eastbound trains face (LEFT and FORWARD valid, RIGHT not); a
+    stub of three cells in row 6 is a component of its own (a target nobody reaches: shortest path of length 0)"""
+    g = np.zeros((8, 9), dtype=np.uint16)
+    g[1, 0], g[1, 1:6], g[1, 6] = DEAD_E, HORZ, DEAD_W
+    g[YARD_SYM] = SYM_SWITCH
+    g[2:4, 3] = VERT
+    g[4, 0], g[4, 1:7], g[4, 7] = DEAD_E, HORZ, DEAD_W
+    g[YARD_SWITCH] = rotated(0x9220, 1)      # eastbound: east or north; southbound (off the stem): west; westbound: west
+    g[6, 0], g[6, 1], g[6, 2] = DEAD_E, HORZ, DEAD_W
+    assert g[YARD_SWITCH] == ways((E, E), (E, N), (S, W), (W, W))
+    return _map(g, [(4, 1, E, 4, 6), (4, 5, W, 4, 0), (3, 3, N, 1, 6), (1, 5, W, 1, 0), (4, 1, E, 6, 1)], earliest=[2, 2, 2, 2, 2])
+
+
+STEP_MAPS = {"yard": yard, "crossing": crossing_u5}      # five agents each: they share a batch when padded onto one canvas
 
 
 # ---- plain numpy measurements of a map or a fixture (what tests/test_handmaps.py asserts the fixtures reach)
