@@ -38,6 +38,7 @@ static bool obs_no_fix() { static const bool v = getenv("FL_OBS_NO_FIX") != null
 static bool obs_no_split() { static const bool v = getenv("FL_OBS_NO_SPLIT") != nullptr; return v; }                // no split kernels
 static bool obs_no_cutils_merge() { static const bool v = getenv("FL_OBS_NO_CUTILS_MERGE") != nullptr; return v; }  // the builder alone on the stand-alone kernel, as before round 6
 static bool obs_verbose_on() { static const bool v = getenv("FL_OBS_VERBOSE") != nullptr; return v; }               // print the configuration obs_pick_config chose
+static bool obs_no_cf_dirs() { static const bool v = getenv("FL_OBS_NO_CF_DIRS") != nullptr; return v; }            // classify loop: file every query, whatever the directions of the key's items
 static bool obs_no_wl_head() { static const bool v = getenv("FL_OBS_NO_WL_HEAD") != nullptr; return v; }            // HBM work lists without their LDS head (rules out the classes that have one)
 
 // The launch is one workgroup per env and a CU holds one workgroup: with more envs than CUs the launch ends when the last CU has
@@ -541,6 +542,7 @@ static int obs_run(FlObsScratch &o, const FlDev &d, ObsArgs &P, const int *h_R, 
         // mode off, or more rows than the masks' 96 bits (the tree launch alone goes beyond depth 3): the kernels keep no row masks (restored on return -- `u` is a copy of o)
         if (!o.keep_rows || P.max_depth > 3) { o.rowmask = nullptr; P.keep_rows = 0; o.rows_out = nullptr; }
     }
+    P.no_cf_dirs = obs_no_cf_dirs();
     obs_verbose(P);
     obs_keep_verify(d, P, rowmask, s);
     FlObsScratch u = o;
@@ -606,7 +608,7 @@ int fl_obs_config_of_fused(const FlDev &d, int pred_depth, int max_depth, int tr
                 P.merged, P.tw_c, P.tw_t, P.tpw_t, P.tree_pred, P.bk, P.tshift, P.wl_occ_div);
         static const char *names[L_COUNT] = {"cellw", "nbr", "snext", "rkey", "slot_agent", "slot_ready", "cell_target", "a_speed", "a_vpos", "a_pos", "a_tslot",
             "a_target", "a_malf", "a_tpc", "a_tq", "a_tq2", "a_raw", "rtype", "a_lp", "a_n", "a_srank", "a_dir", "a_state", "a_free", "a_dead", "misc", "team_meta", "node_tables",
-            "csr", "items", "wl", "partial", "tmask", "tmask2", "nh", "csr2", "tmaskb", "tmaskb2", "items2", "a_lp2", "a_tpc2", "bkrel", "seg", "dm", "hop8"};
+            "csr", "items", "wl", "partial", "tmask", "tmask2", "nh", "csr2", "tmaskb", "tmaskb2", "items2", "a_lp2", "a_tpc2", "bkrel", "seg", "dm", "hop8", "cmask", "cmaskb"};
         for (int k = 0; k < L_COUNT; k++) {
             if (P.L.off[k] == L_ABSENT) continue;
             unsigned next = P.L.total;

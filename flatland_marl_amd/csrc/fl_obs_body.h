@@ -117,6 +117,15 @@ __device__ __forceinline__ void obs_body(const FlDev &d, const FlObsScratch &S, 
     unsigned long long *tmaskb = LDS_OPT(unsigned long long, L_TMASKB);
     unsigned long long *tmask_m2 = LDS_OPT(unsigned long long, L_TMASK2), *tmaskb_m2 = LDS_OPT(unsigned long long, L_TMASKB2);  // own-path filter
     uint32_t *items2 = LDS_OPT(uint32_t, L_ITEMS2);
+    // direction filter of the classify loop (ObsCtx::cmask): filled with the index below.  (A -DFL_OBS_COUNTS build fills and tests the masks
+    // under FL_OBS_NO_CF_DIRS too and only counts what they would reject.)
+#ifdef FL_OBS_COUNTS
+    const bool cf_off = false;
+#else
+    const bool cf_off = P.no_cf_dirs != 0;
+#endif
+    unsigned long long *cmask = cf_off ? nullptr : LDS_OPT(unsigned long long, L_CMASK);
+    uint32_t *cmaskb = (cf_off || P.tree_pred + 1 > 32) ? nullptr : LDS_OPT(uint32_t, L_CMASKB);
     uint16_t *a_lp2 = LDS_OPT(uint16_t, L_A_LP2);
     uint16_t *a_tpc2 = LDS_OPT(uint16_t, L_A_TPC2);
     double *a_tq2 = LDS_OPT(double, L_A_TQ2);
@@ -304,6 +313,10 @@ __device__ __forceinline__ void obs_body(const FlDev &d, const FlObsScratch &S, 
     X.n_cu = ROUND; X.round_base = 0;
     X.u_csr_end = csr2; X.u_items = items2; X.u_tmask = tmaskb; X.a_tq2 = a_tq2;
     X.tmask_m2 = merged ? tmask_m2 : nullptr; X.u_tmask_m2 = tmaskb_m2;
+    X.cmask = cmask; X.u_cmask = cmaskb;
+#ifdef FL_OBS_COUNTS
+    X.cf_count_only = P.no_cf_dirs != 0;
+#endif
     X.path = S.path + (size_t)b * A * OBS_PRED_CAP; X.pred_cap = OBS_PRED_CAP;
     X.a_lp = a_lp; X.a_lp2 = a_lp2; X.a_tpc2 = a_tpc2;
     X.u_Tn = P.tree_pred + 1; X.u_tshift = X.u_Tn <= 64 ? 0 : P.tshift;
@@ -577,9 +590,11 @@ __device__ __forceinline__ void obs_body(const FlDev &d, const FlObsScratch &S, 
             for (int k = tid; k <= K; k += nt) csr[k] = 0;
             if (tid == 0) misc[11] = 0;
             if (X.tmask) for (int k = tid; k <= K; k += nt) { tmask[k] = 0ull; if (X.tmask_m2) tmask_m2[k] = 0ull; }
+            if (cmask) for (int k = tid; k < NS; k += nt) cmask[k] = 0ull;
             if (bk) for (int k = tid; k < (bk_lds ? K * bk_w / 2 : ((K + 1) * bk_nb + 1) / 2); k += nt) bkc[k] = 0u;
         }
         if (dual) for (int k = tid; k <= K; k += nt) { csr2[k] = 0; if (p_use_tmask) tmaskb[k] = 0ull; if (X.tmask_m2) tmaskb_m2[k] = 0ull; }
+        if (dual && cmaskb) for (int k = tid; k < NS; k += nt) cmaskb[k] = 0u;
         if (STAGE != 2 && tid < 64) { team_meta[64 + tid] = 1; team_meta[192 + tid] = 1; }   // (trees the hoisted pass A below does not build: the root alone)
         __syncthreads();
         const int pred_depth = my_pred_depth;
@@ -1058,6 +1073,12 @@ __device__ __forceinline__ void obs_body(const FlDev &d, const FlObsScratch &S, 
                     } else {
                         atomicOr(&tmask[key], bits);
                     }
+                    if (cmask) {  // ... and the walking directions for which it can satisfy the conflict condition
+                        const uint32_t dirs = cf_dirs_of(cw_bits(X, (int)(w >> 2)), cf_against(w & 3u) | cf_against(dnext) | cf_against(dprev), a_state[i] == ST_DONE);
+#pragma unroll
+                        for (uint32_t dw = 0; dw < 4; dw++)
+                            if ((dirs >> dw) & 1u) atomicOr(&cmask[((uint32_t)key << 2) | dw], bits);
+                    }
                 }
                 const uint32_t item = IT_MAKE(lab ? (int)lab[i] : i, tlo, to_end, span, dprev, dnext, w & 3u);
                 if (bk) {  // csr[key] stays the START of the key's list; the bucket's running offset is bumped
@@ -1085,6 +1106,12 @@ __device__ __forceinline__ void obs_body(const FlDev &d, const FlObsScratch &S, 
                             if (seen & bits) atomicOr(&tmaskb_m2[key], seen & bits);
                         } else {
                             atomicOr(&tmaskb[key], bits);
+                        }
+                        if (cmaskb) {  // (at most 32 predicted times: bucket = time, the low word of bits)
+                            const uint32_t dirs = cf_dirs_of(cw_bits(X, (int)(w >> 2)), cf_against(w & 3u), a_state[i] == ST_DONE);
+#pragma unroll
+                            for (uint32_t dw = 0; dw < 4; dw++)
+                                if ((dirs >> dw) & 1u) atomicOr(&cmaskb[((uint32_t)key << 2) | dw], (uint32_t)bits);
                         }
                     }
                     const int slot2 = atomicAdd(&csr2[key], 1);

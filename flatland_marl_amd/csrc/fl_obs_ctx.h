@@ -63,6 +63,16 @@ struct ObsCtx {
     // path always has that agent's own item around the queried time.  tmask_m2 / u_tmask_m2 = buckets covered by at least
     // TWO items of the key, so the own item's buckets can be taken out of the test exactly; nullptr = no filter.
     const unsigned long long *tmask_m2, *u_tmask_m2;
+    // Direction filter of the classify loop (one round with time masks): per rail state (cell << 2 | walking direction) the time
+    // buckets covered by an item of the cell's key that CAN satisfy the conflict condition of conflict_flags for that direction
+    // (its agent is done, or one of the directions the test may take for it differs from the walker's and the cell has the
+    // transition against it) -- the walking agent's own items included.  No such bucket around the queried time: the query
+    // cannot hit and is not filed.  nullptr = every query is filed (FL_OBS_NO_CF_DIRS; the upstream one also beyond 32 times).
+    const unsigned long long *cmask;
+    const uint32_t *u_cmask;
+#ifdef FL_OBS_COUNTS
+    bool cf_count_only;           // FL_OBS_NO_CF_DIRS in a counting build: the masks are tested, what they reject is counted (slot 46) and filed all the same
+#endif
     const uint16_t *path;         // HBM [A][pred_cap] predicted paths of the env (state per waypoint)
     int pred_cap;
     const uint16_t *a_lp, *a_lp2, *a_tpc2;  // last waypoint in the first / second index, times per cell of the second
@@ -132,6 +142,19 @@ __device__ __forceinline__ uint32_t cw_bits(const ObsCtx &X, int r) { return X.c
 __device__ __forceinline__ uint32_t cw_slot(const ObsCtx &X, int r) { return X.cellw[r] >> 16; }
 __device__ __forceinline__ uint32_t cw_load(const ObsCtx &X, int r) { return X.cellw[r]; }
 __device__ __forceinline__ int key_of(const ObsCtx &X, int r) { return X.rkey ? (int)X.rkey[r] : r; }
+// The conflict condition of conflict_flags for an item whose direction is cd tests ONE transition bit of the walker's nibble: the one
+// against cd.  cf_dirs_of: the walking directions d (bit d) in which a cell with rail word bits16 can be walked and an item can satisfy the
+// condition -- its agent is done, or a direction the test may take for it (`against`: the OR of their bits) other than d has its bit in d's nibble.
+__device__ __forceinline__ uint32_t cf_against(uint32_t cd) { return 1u << (3u - ((cd + 2u) & 3u)); }
+__device__ __forceinline__ uint32_t cf_dirs_of(uint32_t bits16, uint32_t against, bool done) {
+    uint32_t dirs = 0;
+#pragma unroll
+    for (uint32_t d = 0; d < 4; d++) {
+        const uint32_t nib = nibble(bits16, d);
+        if (nib != 0 && (done || (nib & against & ~cf_against(d)) != 0)) dirs |= 1u << d;
+    }
+    return dirs;
+}
 // Pass B serves one builder (PB 0 = upstream, 1 = flatland_cutils) or both in one pass (PB 2): cu says which builder's
 // rules apply to a team.  PB 3 = the one-pass kernels' machinery (rounds of trees_merged, own-path filter, the fast classify loop)
 // with the flatland_cutils trees ALONE -- the launch the reference's solution makes (solution/eval_env.py:15-17 builds TreeCutils only).

@@ -99,7 +99,7 @@ __host__ __device__ constexpr int obs_scr_words(int nwaves, int A, int tw_c, int
 // LDS arrays of a launch, in carving order (obs_layout on the host decides which exist and where)
 enum { L_CELLW = 0, L_NBR, L_SNEXT, L_RKEY, L_SLOT_AGENT, L_SLOT_READY, L_CELL_TARGET, L_A_SPEED, L_A_VPOS, L_A_POS, L_A_TSLOT,
        L_A_TARGET, L_A_MALF, L_A_TPC, L_A_TQ, L_A_TQ2, L_A_RAW, L_RTYPE, L_A_LP, L_A_N, L_A_SRANK, L_A_DIR, L_A_STATE, L_A_FREE, L_A_DEAD, L_MISC, L_TEAM_META, L_WAVE_SCR,
-       L_CSR, L_ITEMS, L_WL, L_PARTIAL, L_TMASK, L_TMASK2, L_NH, L_CSR2, L_TMASKB, L_TMASKB2, L_ITEMS2, L_A_LP2, L_A_TPC2, L_BKREL, L_SEG, L_DM, L_HOP8, L_COUNT };
+       L_CSR, L_ITEMS, L_WL, L_PARTIAL, L_TMASK, L_TMASK2, L_NH, L_CSR2, L_TMASKB, L_TMASKB2, L_ITEMS2, L_A_LP2, L_A_TPC2, L_BKREL, L_SEG, L_DM, L_HOP8, L_CMASK, L_CMASKB, L_COUNT };
 #define L_ABSENT 0xFFFFFFFFu
 struct ObsLayout {
     unsigned off[L_COUNT];  // byte offset into the dynamic LDS, L_ABSENT = not in this launch
@@ -119,6 +119,7 @@ struct ObsOptions { int nt, wl_bytes, tab, nh, tmask, dual, items, snext, partia
 struct ObsDims { int Rcap, A, Ucap, rkey; };                   // capacities of the batch (rkey: colliding prediction keys, H > W)
 struct ObsShape { int merged, tw_c, tw_t, tpw_t, tree_pred; };  // what of ObsArgs decides sizes
 
+__host__ __device__ constexpr bool obs_has_cf_dirs(const ObsShape &P, const ObsOptions &o) { return P.merged == 1 && o.tmask != 0; }
 __host__ __device__ constexpr unsigned obs_al16(unsigned long long bytes) { return (unsigned)((bytes + 15ull) & ~15ull); }
 __host__ __device__ constexpr ObsLayout obs_layout_c(const ObsDims &d, const ObsShape &P, const ObsOptions &o) {
     ObsLayout L = {};
@@ -169,6 +170,10 @@ __host__ __device__ constexpr ObsLayout obs_layout_c(const ObsDims &d, const Obs
         OBS_PUT(L_A_LP2, A * 2); OBS_PUT(L_A_TPC2, A * 2); OBS_PUT(L_A_TQ2, A * 8);
     }
     if (o.fb) OBS_PUT(L_BKREL, K1 * (OBS_FB_NB + 2) * 2);
+    // one round with time masks: per (rail cell, walking direction) the time buckets in which some item of the cell's key can satisfy the
+    // conflict condition (the classify loop files no query that cannot hit, see wg_pass_b) -- 64 bits for the flatland_cutils index, 32 for the
+    // upstream predictor's (at most 32 predicted times, else the kernel leaves that one unused).  Not in 80 KB (merged 3): classes 5 / 10 are full.
+    if (obs_has_cf_dirs(P, o)) { OBS_PUT(L_CMASK, NS * 8); if (o.dual) OBS_PUT(L_CMASKB, NS * 4); }
     // the arrays sized by the number of unique targets come last: a launch class with a compile-time layout fixes everything above
     if (o.nh || o.tab) OBS_PUT(L_NH, U * R * 2);
     if (o.tab) { OBS_PUT(L_SEG, NS * 16); OBS_PUT(L_DM, U * NS * 2); OBS_PUT(L_HOP8, U * NS * 2); }
@@ -417,6 +422,7 @@ struct ObsArgs {
     int merged;        // fused launch: ONE pass B per round over the trees of both builders (trees_merged); 1: one round (at most 32 agents), 2: rounds
                        // of 32 agents, 3: rounds of 16 agents on 512 threads (at most 80 KB of LDS: two workgroups a CU)
     int wl_occ_div;    // the occupant work list gets 1 / wl_occ_div of the work-list entries, the conflict list the rest
+    int no_cf_dirs;    // FL_OBS_NO_CF_DIRS: the per-direction conflict masks (L_CMASK / L_CMASKB) are neither filled nor consulted
     int fix;           // FIXED launch class of this launch (ObsFixed<fix>: the kernel's layout is a compile-time constant), 0 = none
     const int16_t *label;  // flatland_cutils get_many(handles) with a strict subset (MODE 0 only; null: every agent): label[i] = position of agent i in
                        // the list or -1.  Only the listed agents' predictions enter the index, under their list POSITION -- the conflict test

@@ -274,6 +274,18 @@ __device__ __forceinline__ int *team_table(const ObsCtx &X, int *scr0, int team_
     return scr0 + team * team_words;
 }
 
+// A conflict entry can only lower its node's N_PC to its own tot_dist (atomicMin is the only writer), so an entry whose node already holds
+// that or less is not scanned; a stale read only fails to skip.  (-DOBS_NO_PC_SKIP: every entry is scanned.)
+template <int PB, int CAP>
+__device__ __forceinline__ bool cf_settled(const ObsCtx &X, int *scr0, int team_words, int team, int node, int tot) {
+#ifdef OBS_NO_PC_SKIP
+    return false;
+#else
+    constexpr int cap = PB >= 2 ? 32 : CAP;
+    return nt_r(team_table<PB, CAP>(X, scr0, team_words, team), cap, N_PC, node) <= tot;
+#endif
+}
+
 // late(): work that does not depend on the trees (the rest of phase 1: attribute rows, valid actions), handed out through a queue;
 // a wavefront that is done with its share of the work-list step takes some while the others finish theirs.
 struct NoLateWork { __device__ __forceinline__ void operator()() const {} };
@@ -345,6 +357,9 @@ __device__ __forceinline__ void wg_pass_b(const ObsCtx &X, int tid, int nt, int 
         const bool self_filter = PB >= 2 && X.tmask_m2 != nullptr;
         const uint16_t *path_t = X.path;
         int lp_t = 0, tpc_t = 1;
+        // direction filter: the team's mask array (64-bit entries for the flatland_cutils index, 32-bit for the upstream predictor's), or none
+        const bool cf_any = PB >= 2 && (X.cmask != nullptr || X.u_cmask != nullptr);
+        bool cf_t = false;
         auto enter_team = [&]() __attribute__((always_inline)) {
             target = X.a_target[handle];
             cu = pb_cu<PB>(X, team);
@@ -356,6 +371,7 @@ __device__ __forceinline__ void wg_pass_b(const ObsCtx &X, int tid, int nt, int 
                 lp_t = cu ? X.a_lp[handle] : X.a_lp2[handle];
                 tpc_t = cu ? X.a_tpc[handle] : X.a_tpc2[handle];
             }
+            if (PB >= 2 && cf_any) cf_t = cu ? X.cmask != nullptr : X.u_cmask != nullptr;
         };
         enter_team();
         // state of the piece being walked
@@ -384,7 +400,7 @@ __device__ __forceinline__ void wg_pass_b(const ObsCtx &X, int tid, int nt, int 
         const bool has_snext = FAST || X.snext != nullptr, has_tmask = FAST || X.tmask != nullptr;
         // what the loop body needs of the current cell, requested one iteration ahead
         uint32_t cw = 0, sn = 0, ct = 0, n_inw = 0, own_w = 0, n_se = 0, n_tv = 0;
-        unsigned long long tm = 0, tm2 = 0;
+        unsigned long long tm = 0, tm2 = 0, cm = 0;
         int c_hi = 0, c_lo = 0;
         auto request = [&]() __attribute__((always_inline)) {
             if (FAST && self_filter) own_w = path_t[min(tot, lp_t)];  // HBM (L2): the longest latency first (an LDS copy of the paths made no difference)
@@ -393,6 +409,9 @@ __device__ __forceinline__ void wg_pass_b(const ObsCtx &X, int tid, int nt, int 
             if (FAST || X.Tn > 0) {
                 const int key = FAST ? cell : key_of(X, cell);
                 if (has_tmask) { tm = tmask_t[key]; if (FAST && self_filter) tm2 = tmask2_t[key]; }
+                if (FAST && cf_any && cf_t) {
+                    if (cu) cm = X.cmask[((uint32_t)cell << 2) | dd]; else cm = (unsigned long long)X.u_cmask[((uint32_t)cell << 2) | dd];
+                }
                 else { c_hi = X.csr_end[key]; c_lo = key > 0 ? X.csr_end[key - 1] : 0; }
             }
             if (PB != 1 && PB != 3) ct = X.cell_target[cell >> 5];
@@ -432,6 +451,14 @@ __device__ __forceinline__ void wg_pass_b(const ObsCtx &X, int tid, int nt, int 
                             others = (tm & ~(((2ull << o2) - 1ull) & ~((1ull << o1) - 1ull))) | tm2;
                         }
                         cand = ((uint32_t)(others >> b1) & ((2u << (b2 - b1)) - 1u)) != 0u;
+                        if (FAST && cf_any && cf_t) {  // ... and one that can conflict with a walker in this direction?
+                            const bool can = ((uint32_t)(cm >> b1) & ((2u << (b2 - b1)) - 1u)) != 0u;
+#ifdef FL_OBS_COUNTS
+                            if (cand && !can && X.dbg) atomicAdd((unsigned long long *)&X.dbg[46], 1ull);
+                            if (!X.cf_count_only)
+#endif
+                            cand = cand && can;
+                        }
                     } else {
                         cand = c_hi > c_lo;
                     }
@@ -525,6 +552,7 @@ __device__ __forceinline__ void wg_pass_b(const ObsCtx &X, int tid, int nt, int 
             const uint2 w = wl_cf_get(X, e);
             const int cell = (int)((w.x & 0xFFFFFFu) >> 2), team = (int)(w.x >> 24);
             const int handle = pb_handle<PB>(X, team_meta, team), tot = (int)(w.y & 511u);
+            if (cf_settled<PB, CAP>(X, scr0, team_words, team, (int)(w.y >> 24), tot)) continue;
             const bool cu = pb_cu<PB>(X, team);
             const int pt = pt_of<PB>(X, cu, handle, tot);
             const ListRange R = list_range<PB>(X, cu, cell, pt);
@@ -583,6 +611,7 @@ __device__ __forceinline__ void wg_pass_b(const ObsCtx &X, int tid, int nt, int 
             cu = pb_cu<PB>(X, team);
             pt = pt_of<PB>(X, cu, handle, tot);
             R = list_range<PB>(X, cu, cell, pt);
+            if (cf_settled<PB, CAP>(X, scr0, team_words, team, (int)(w.y >> 24), tot)) R.n = 0;   // (no scan, no further chunks, nothing to file)
             nch = 1 + min(max(R.n - CF_FIRST + CF_CHUNK - 1, 0) / CF_CHUNK, 62);  // an absurdly long list: the last chunk takes the rest
             const uint32_t f = R.n > 0 ? conflict_flags<PB, ITL, TWO>(X, cu, handle, cell, w.x & 3u, pt, R, 0, min(R.n, CF_FIRST)) : 0u;
 #ifdef FL_OBS_COUNTS  // with FL_OBS_TIMING: statistics of the conflict entries (they slow the step down; first chunks only)
@@ -631,7 +660,9 @@ __device__ __forceinline__ void wg_pass_b(const ObsCtx &X, int tid, int nt, int 
         const bool cu = pb_cu<PB>(X, team);
         const int pt = pt_of<PB>(X, cu, handle, tot);
         const ListRange R = list_range<PB>(X, cu, cell, pt);
-        const uint32_t f = conflict_flags<PB, ITL, TWO>(X, cu, handle, cell, w.x & 3u, pt, R, CF_FIRST + (chunk - 1) * CF_CHUNK, chunk == 62 ? R.n : min(R.n, CF_FIRST + chunk * CF_CHUNK));
+        // (the node is in the first entry's word; a settled entry's chunk is counted down without a scan)
+        const bool settled = cf_settled<PB, CAP>(X, scr0, team_words, team, (int)(wl_cf_get(X, first).y >> 24), tot);
+        const uint32_t f = settled ? 0u : conflict_flags<PB, ITL, TWO>(X, cu, handle, cell, w.x & 3u, pt, R, CF_FIRST + (chunk - 1) * CF_CHUNK, chunk == 62 ? R.n : min(R.n, CF_FIRST + chunk * CF_CHUNK));
         const uint32_t old = wl_cf_done(X, first, (f & 63u) << 15);
         if (((old >> 9) & 63u) == 1u && conflict_hit((old >> 15) & 63u)) {  // the last chunk of its key
             constexpr int cap = PB >= 2 ? 32 : CAP;

@@ -112,6 +112,9 @@ def report():
     if c[:, :, 27].max() > 0:  # a -DFL_OBS_COUNTS build
       print("conflict entries (cutils | upstream): items in their lists %.0f | %.0f, queried beyond the fine buckets %.0f | %.0f, somebody else there %.0f | %.0f, conflicts %.0f | %.0f, only the walking agent itself there %.0f | %.0f" %
             (c[:, :, 27].mean(), c[:, :, 59].mean(), c[:, :, 28].mean(), c[:, :, 60].mean(), c[:, :, 29].mean(), c[:, :, 61].mean(), c[:, :, 30].mean(), c[:, :, 62].mean(), c[:, :, 31].mean(), c[:, :, 63].mean()))
+    if c[:, :, 27].max() > 0 and c[:, :, 32].max() == 0:  # (-DFL_OBS_COUNTS, a kernel with one pass B: slot 46 is free there)
+        print("classified cells with somebody else around the queried time that the direction masks reject: %.0f (%s)" %
+              (c[:, :, 46].mean(), "counted only, filed all the same: FL_OBS_NO_CF_DIRS" if os.environ.get("FL_OBS_NO_CF_DIRS") else "not filed"))
     print("work-list entries (sum over rounds): occupant %.0f / %.0f, conflict %.0f / %.0f  (cutils / upstream)" %
           (c[:, :, 9].mean(), c[:, :, 41].mean(), c[:, :, 10].mean(), c[:, :, 42].mean()))
     if c[:, :, 58].max() > 0:
