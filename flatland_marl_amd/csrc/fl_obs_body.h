@@ -553,14 +553,29 @@ __device__ __forceinline__ void obs_body(const FlDev &d, const FlObsScratch &S, 
         }
         if (stored) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // in the L2 before the barrier that ends the phase
     };
-    auto late_jobs = [&]() __attribute__((always_inline)) {
-        while (late_p1) {
+    // One round of trees (MERGED 1): behind those, the topology piece of the flatland_cutils trees (cutils_rows_orders: adjacency, padding
+    // and absent rows, evaluation orders), two trees a job as a wavefront holds two teams of 32 lanes; any wavefront takes any job.  It
+    // reads what pass A left (team_meta: node_base, levels; N_PH / N_SE of the tree's table), which pass B does not write.  The call
+    // behind pass B's last barrier (after_barrier) takes what is left -- everything under FL_OBS_NO_EARLY_TOPO.
+    constexpr bool TOPO_JOBS = MERGED == 1 && OBS_TOPO_JOBS;
+    auto late_jobs = [&](bool after_barrier = false) __attribute__((always_inline)) {
+        while (late_p1 && !(TOPO_JOBS && after_barrier)) {
             int j = 0;
             if (lane == 0) j = atomicAdd(&misc[7], 1);
             j = __builtin_amdgcn_readfirstlane(j);
             if (j >= n_p1_all) break;
             const int i = 2 * j + (lane >> 5);
             if (i < A) phase1b(i, lane & 31, phase1b_load(i));
+        }
+        while (TOPO_JOBS && (after_barrier || P.no_early_topo == 0)) {
+            int j = 0;
+            if (lane == 0) j = atomicAdd(&misc[5], 1);
+            j = __builtin_amdgcn_readfirstlane(j);
+            if (2 * j >= min(A, 32)) break;
+            const int t = 2 * j + (lane >> 5);
+            const bool have_t = t < A;
+            cutils_rows_orders<OBS_CAP_C, !UP, 1>(X, d, P, b, t, have_t, lane & 31, merged_table_c(wave_scr, min(t, 31)),
+                                                  have_t ? team_meta[64 + t] : 1, have_t ? team_meta[192 + t] : 0, (float)T);
         }
     };
     if (do_p1 && (!p1_beside_walk || X.Tn == 0)) {
@@ -942,6 +957,11 @@ __device__ __forceinline__ void obs_body(const FlDev &d, const FlObsScratch &S, 
         // instead of eight -- and the first four of the agent the wavefront takes NEXT are requested before the items of this
         // one are emitted)
         constexpr int FU = 4;
+#ifdef OBS_NO_LEAN_FILL
+        constexpr bool LEAN_FILL = false;
+#else
+        constexpr bool LEAN_FILL = MERGED == 1;   // the one-round kernels (classes 1, 6, 11, runtime carving of MODES 3 / 6); every other kernel keeps the body below
+#endif
         uint32_t pfv[FU] = {0, 0, 0, 0}, pfn[FU] = {0, 0, 0, 0}, pfp[FU] = {0, 0, 0, 0};
         auto prefetch = [&](int ia) __attribute__((always_inline)) {
             if (reuse || ia >= A) return;
@@ -1064,6 +1084,67 @@ __device__ __forceinline__ void obs_body(const FlDev &d, const FlObsScratch &S, 
                 }
                 const bool to_end = k == lp || tlo + span - 1 >= tlast;
                 const int key = key_of(X, (int)(w >> 2));
+                if (LEAN_FILL) {
+                    // One-round kernels: every wavefront runs this body once or twice, so its length is the phase.  The same ORs and
+                    // list slots as below, ordered so that the LDS round trips overlap: the returning atomics of both indices go
+                    // out first, the direction masks (cf_dirs_swar, no loop over the nibbles; the second index's four 32-bit words
+                    // as two 64-bit ORs) are worked out and ORed while those are in flight, and what depends on a returned value
+                    // -- the second-item masks, the item stores -- comes last.
+                    const int b1 = tb_of(tlo, X.tshift), b2 = tb_of(to_end ? tlast : tlo + span - 1, X.tshift);
+                    const unsigned long long bits = ((2ull << b2) - 1ull) & ~((1ull << b1) - 1ull);
+                    const bool second = k <= lp2, done = a_state[i] == ST_DONE;
+                    const int tlo2 = k * tpc2, tlast2 = Tn2 - 1;
+                    const bool to_end2 = k == lp2 || tlo2 + tpc2 - 1 >= tlast2;
+                    unsigned long long bits2 = 0ull, seen = 0ull, seen2 = 0ull;
+                    int slot2 = 0;
+                    if (X.tmask && X.tmask_m2) seen = atomicOr(&tmask[key], bits);
+                    else if (X.tmask) atomicOr(&tmask[key], bits);
+                    if (second) {
+                        if (p_use_tmask) {
+                            const int c1 = tb_of(tlo2, tshift2), c2 = tb_of(to_end2 ? tlast2 : tlo2 + tpc2 - 1, tshift2);
+                            bits2 = ((2ull << c2) - 1ull) & ~((1ull << c1) - 1ull);
+                            if (X.tmask_m2) seen2 = atomicOr(&tmaskb[key], bits2);
+                            else atomicOr(&tmaskb[key], bits2);
+                        }
+                        slot2 = atomicAdd(&csr2[key], 1);
+                    }
+                    const uint32_t rail = cw_bits(X, (int)(w >> 2));
+                    if (X.tmask && cmask) {
+                        const uint32_t dirs = cf_dirs_swar(rail, cf_against(w & 3u) | cf_against(dnext) | cf_against(dprev), done);
+#pragma unroll
+                        for (uint32_t dw = 0; dw < 4; dw++)
+                            if ((dirs >> dw) & 1u) atomicOr(&cmask[((uint32_t)key << 2) | dw], bits);
+                    }
+                    if (second && p_use_tmask && cmaskb) {  // (at most 32 predicted times: bucket = time, the low word of bits2)
+                        const uint32_t dirs = cf_dirs_swar(rail, cf_against(w & 3u), done);
+                        const unsigned long long lo32 = (unsigned long long)(uint32_t)bits2;
+                        const unsigned long long v01 = ((dirs & 1u) ? lo32 : 0ull) | ((dirs & 2u) ? lo32 << 32 : 0ull);
+                        const unsigned long long v23 = ((dirs & 4u) ? lo32 : 0ull) | ((dirs & 8u) ? lo32 << 32 : 0ull);
+                        unsigned long long *cb = reinterpret_cast<unsigned long long *>(cmaskb) + ((uint32_t)key << 1);   // words (key << 2 | 0, 1) and (2, 3)
+                        if (v01) atomicOr(&cb[0], v01);
+                        if (v23) atomicOr(&cb[1], v23);
+                    }
+                    const uint32_t item = IT_MAKE(lab ? (int)lab[i] : i, tlo, to_end, span, dprev, dnext, w & 3u);
+                    if (bk) {
+                        const int thi = to_end ? tlast : tlo + span - 1;
+                        int c1 = min(tlo >> bk_shift, bk_nb - 1), c2 = min(thi >> bk_shift, bk_nb - 1);
+                        if (bk_lds && to_end) c1 = c2 = bk_nb;
+                        for (int bb = c1; bb <= c2; bb++) {
+                            const int kb = key * bk_w + bb;
+                            const uint32_t old = atomicAdd(&bkc[kb >> 1], (kb & 1) ? 0x10000u : 1u);
+                            csr_items[csr[key] + (int)((kb & 1) ? (old >> 16) : (old & 0xFFFFu))] = item;
+                        }
+                    } else {
+                        const int slot = atomicAdd(&csr[key], 1);
+                        csr_items[slot] = item;
+                    }
+                    if (seen & bits) atomicOr(&tmask_m2[key], seen & bits);  // covered by a second item
+                    if (second) {
+                        if (seen2 & bits2) atomicOr(&tmaskb_m2[key], seen2 & bits2);
+                        items2[slot2] = IT_MAKE(i, tlo2, to_end2, tpc2, dprev, k < lp2 ? dnext : (w & 3u), w & 3u);
+                    }
+                    continue;
+                }
                 if (X.tmask) {  // time buckets this item covers
                     const int b1 = tb_of(tlo, X.tshift), b2 = tb_of(to_end ? tlast : tlo + span - 1, X.tshift);
                     const unsigned long long bits = ((2ull << b2) - 1ull) & ~((1ull << b1) - 1ull);

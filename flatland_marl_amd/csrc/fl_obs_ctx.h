@@ -155,6 +155,15 @@ __device__ __forceinline__ uint32_t cf_dirs_of(uint32_t bits16, uint32_t against
     }
     return dirs;
 }
+// The same set without the loop over the nibbles: the rail word masked with `against` in every nibble (0xDE7B: nibble d without the bit of
+// cf_against(d)), then one bit per non-empty nibble (nibble d sits at bit 4 (3 - d)) gathered into bits 12 .. 15 by one multiplication
+// (the sixteen partial products land on sixteen different bits: no carries).
+__device__ __forceinline__ uint32_t cf_dirs_swar(uint32_t bits16, uint32_t against, bool done) {
+    const uint32_t x = done ? bits16 : (bits16 & (against * 0x1111u) & 0xDE7Bu);
+    uint32_t y = x | (x >> 1);
+    y = (y | (y >> 2)) & 0x1111u;
+    return ((y * 0x8421u) >> 12) & 15u;
+}
 // Pass B serves one builder (PB 0 = upstream, 1 = flatland_cutils) or both in one pass (PB 2): cu says which builder's
 // rules apply to a team.  PB 3 = the one-pass kernels' machinery (rounds of trees_merged, own-path filter, the fast classify loop)
 // with the flatland_cutils trees ALONE -- the launch the reference's solution makes (solution/eval_env.py:15-17 builds TreeCutils only).

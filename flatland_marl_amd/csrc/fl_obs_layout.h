@@ -410,6 +410,7 @@ struct ObsArgs {
     double *props;
     double *tree_out;
     int n_tree_nodes;
+    int no_early_topo; // FL_OBS_NO_EARLY_TOPO (one-round kernels): the topology piece of the flatland_cutils trees runs behind pass B's last barrier
     long long *dbg;  // diagnostic builds only (-DFL_OBS_TIMING): per-env phase clocks
     int tw_c, tw_t, tpw_t;  // node-table words per team of the cutils / upstream builder (0 = builder not in this launch), upstream teams per wavefront
     int compact_t;     // upstream trees in compact slots (no direction of a cell of the batch has more than two transitions)

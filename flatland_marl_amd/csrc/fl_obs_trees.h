@@ -358,7 +358,17 @@ __device__ __forceinline__ void cutils_pass_a(const ObsCtx &X, const FlDev &d, c
 // I64 (the launches of the builder alone): when P.out64 is set the three index tensors are written as the POLICY takes them -- int64, the
 // adjacency's parent / child columns offset by tree * max_nodes with tree = b * A + agent, every negative entry (padding, action -1) -2 (plfActor.get_feature's casts +
 // Network.modify_adjacency, solution/plfActor.py:48-74, nn/net_tree.py:105-116) -- instead of int32 + a second kernel (fl_policy_pack).
-template <int TC = OBS_CAP_C, bool I64 = false>
+// -DOBS_NO_EARLY_TOPO (A/B builds): the one-round kernels call both pieces back to back behind pass B, as every other kernel does
+#ifdef OBS_NO_EARLY_TOPO
+constexpr bool OBS_TOPO_JOBS = false;
+#else
+constexpr bool OBS_TOPO_JOBS = true;
+#endif
+// PIECES: 1 = the topology piece -- adjacency, padding rows, rows of absent nodes, both evaluation orders: what pass A left in the node
+// table (N_PH, N_SE) and node_base / levels decide all of it, so it may run before pass B is over (pass B writes N_INCL .. N_MS of these
+// tables and nothing else: N_OT, which shares N_PH's number, exists in the upstream tables only); 2 = the feature piece -- the rows of
+// the real nodes from pass B's accumulators; 3 = both, back to back.  The two pieces write disjoint bytes.
+template <int TC = OBS_CAP_C, bool I64 = false, int PIECES = 3>
 __device__ __forceinline__ void cutils_rows_orders(const ObsCtx &X, const FlDev &d, const ObsArgs &P, int b, int i, bool have, int gl,
                                                    const int *scr, int node_base, int levels, float max_dist) {
     constexpr int CAP = TC;
@@ -374,21 +384,25 @@ __device__ __forceinline__ void cutils_rows_orders(const ObsCtx &X, const FlDev 
             int32_t *adj = ADJ + (size_t)(idx - 1) * 3;
             long long *adj64 = ADJ64 + (size_t)(idx - 1) * 3;
             if (idx < node_base) {
+                if (PIECES & 1) {
                 const uint32_t ph = (uint32_t)nt_r(scr, CAP, N_PH, idx);
                 if (w64) { out_store(&adj64[0], tree_off + (long long)((int)(ph & 0xFFu) - 2)); out_store(&adj64[1], tree_off + (long long)idx); const int act = (int)((ph >> 8) & 3u) - 1; out_store(&adj64[2], act < 0 ? -2ll : (long long)act); }   // (adjacency[adjacency < 0] = -2 takes the action column too)
                 else {
                 out_store(&adj[0], (int32_t)((int)(ph & 0xFFu) - 2)); out_store(&adj[1], (int32_t)idx); out_store(&adj[2], (int32_t)((int)((ph >> 8) & 3u) - 1));
                 }
+                }
                 if (nt_start((uint32_t)nt_r(scr, CAP, N_SE, idx)) < 0) {
+                    if (PIECES & 1) {
                     const double nn[12] = {INFINITY, INFINITY, INFINITY, INFINITY, INFINITY, INFINITY, INFINITY, -1, -1, -1, -1, -1};
                     scale_and_store(nn, max_dist, A, F + (size_t)idx * 12);
-                } else {
+                    }
+                } else if (PIECES & 2) {
                     double f[12];
                     node_row<true>(X, i, scr, CAP, idx, f);
                     if (nt_flags((uint32_t)nt_r(scr, CAP, N_UF, idx)) & ND_ZERO) atomicCAS(&d.err[b], 0, FL_ERR_ZERO_TRANSITION);  // treeobs.cpp:529-535 throws
                     scale_and_store(f, max_dist, A, F + (size_t)idx * 12);
                 }
-            } else {  // padding rows when the queue ran dry (treeobs.cpp:268-276, 245-249)
+            } else if (PIECES & 1) {  // padding rows when the queue ran dry (treeobs.cpp:268-276, 245-249)
                 const double nn[12] = {INFINITY, INFINITY, INFINITY, INFINITY, INFINITY, INFINITY, INFINITY, -1, -1, -1, -1, -1};
                 scale_and_store(nn, max_dist, A, F + (size_t)idx * 12);
                 if (w64) { out_store(&adj64[0], -2ll); out_store(&adj64[1], -2ll); out_store(&adj64[2], -2ll); }
@@ -398,7 +412,7 @@ __device__ __forceinline__ void cutils_rows_orders(const ObsCtx &X, const FlDev 
     }
     // calculate_evaluation_orders (tool.h:468-524): order = height above the leaves.  Lane k holds node k; a node's
     // children are consecutive nodes, so heights settle after as many shuffle rounds as the tree has levels.
-    {
+    if (PIECES & 1) {
         const uint32_t ph = gl < node_base ? (uint32_t)nt_r(scr, CAP, N_PH, gl) : 0u;
         const int fc = (int)(ph >> 10);      // 0 = no children pushed
         const int parent = gl < node_base ? (int)(ph & 0xFFu) - 2 : -2;
@@ -529,8 +543,18 @@ __device__ __forceinline__ void trees_merged(ObsCtx &X, const FlDev &d, const Ob
         wg_pass_b<UP ? 2 : 3, OBS_CAP_C, ITL, LATE, MULTI>(X, wave * 64 + lane, nwaves * 64, UP ? 2 * ROUND : ROUND, wave_scr, 0, team_meta, late);
         if (base == 0) late();  // (whatever the queue still holds)
         TREE_STAMP(X, 7);
-        if (ct < ROUND) cutils_rows_orders<OBS_CAP_C, !UP>(X, d, P, b, i_c, have_c, gl, scr_c, node_base, levels, max_dist);
-        if (wave_has_u) upstream_rows<16, CT, true, 32>(X, P, b, i_u, have_u, tl, scr_u, rowmask);
+        if (MULTI || !OBS_TOPO_JOBS) {
+            if (ct < ROUND) cutils_rows_orders<OBS_CAP_C, !UP>(X, d, P, b, i_c, have_c, gl, scr_c, node_base, levels, max_dist);
+            if (wave_has_u) upstream_rows<16, CT, true, 32>(X, P, b, i_u, have_u, tl, scr_u, rowmask);
+        } else {
+            // one round: the topology piece of every tree was a job of the late queue (obs_body: late_jobs), taken beside the conflict
+            // scan by whoever was free; only the rows of the real nodes wait for pass B.  late(true) hands out the topology jobs that
+            // are left: none, or -- FL_OBS_NO_EARLY_TOPO -- all of them.
+            if (ct < ROUND) cutils_rows_orders<OBS_CAP_C, !UP, 2>(X, d, P, b, i_c, have_c, gl, scr_c, node_base, levels, max_dist);
+            if (wave_has_u) upstream_rows<16, CT, true, 32>(X, P, b, i_u, have_u, tl, scr_u, rowmask);
+            TREE_STAMP(X, 8);
+            late(true);
+        }
         team_sync();
         TREE_STAMP(X, 16);
     }
