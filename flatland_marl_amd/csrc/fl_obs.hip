@@ -39,6 +39,7 @@ static bool obs_no_split() { static const bool v = getenv("FL_OBS_NO_SPLIT") != 
 static bool obs_no_cutils_merge() { static const bool v = getenv("FL_OBS_NO_CUTILS_MERGE") != nullptr; return v; }  // the builder alone on the stand-alone kernel, as before round 6
 static bool obs_verbose_on() { static const bool v = getenv("FL_OBS_VERBOSE") != nullptr; return v; }               // print the configuration obs_pick_config chose
 static bool obs_no_cf_dirs() { static const bool v = getenv("FL_OBS_NO_CF_DIRS") != nullptr; return v; }            // classify loop: file every query, whatever the directions of the key's items
+static bool obs_pb_ceil_split() { static const bool v = getenv("FL_OBS_PB_CEIL_SPLIT") != nullptr; return v; }    // pass B: ceil(total / nt) cells a lane until none are left, as before the even slices
 static bool obs_no_early_topo() { static const bool v = getenv("FL_OBS_NO_EARLY_TOPO") != nullptr; return v; }      // one-round kernels: adjacency / padding rows / orders behind pass B, not beside its conflict scan
 static bool obs_no_wl_head() { static const bool v = getenv("FL_OBS_NO_WL_HEAD") != nullptr; return v; }            // HBM work lists without their LDS head (rules out the classes that have one)
 
@@ -544,6 +545,7 @@ static int obs_run(FlObsScratch &o, const FlDev &d, ObsArgs &P, const int *h_R, 
         if (!o.keep_rows || P.max_depth > 3) { o.rowmask = nullptr; P.keep_rows = 0; o.rows_out = nullptr; }
     }
     P.no_cf_dirs = obs_no_cf_dirs();
+    P.pb_ceil_split = obs_pb_ceil_split();
     P.no_early_topo = obs_no_early_topo();
     obs_verbose(P);
     obs_keep_verify(d, P, rowmask, s);

@@ -314,6 +314,7 @@ __device__ __forceinline__ void obs_body(const FlDev &d, const FlObsScratch &S, 
     X.u_csr_end = csr2; X.u_items = items2; X.u_tmask = tmaskb; X.a_tq2 = a_tq2;
     X.tmask_m2 = merged ? tmask_m2 : nullptr; X.u_tmask_m2 = tmaskb_m2;
     X.cmask = cmask; X.u_cmask = cmaskb;
+    X.pb_ceil_split = P.pb_ceil_split != 0;
 #ifdef FL_OBS_COUNTS
     X.cf_count_only = P.no_cf_dirs != 0;
 #endif

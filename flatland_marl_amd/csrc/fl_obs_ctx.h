@@ -70,6 +70,7 @@ struct ObsCtx {
     // cannot hit and is not filed.  nullptr = every query is filed (FL_OBS_NO_CF_DIRS; the upstream one also beyond 32 times).
     const unsigned long long *cmask;
     const uint32_t *u_cmask;
+    bool pb_ceil_split;           // FL_OBS_PB_CEIL_SPLIT: pass B gives every lane ceil(total / nt) cells until none are left (see fl_obs_slices.h)
 #ifdef FL_OBS_COUNTS
     bool cf_count_only;           // FL_OBS_NO_CF_DIRS in a counting build: the masks are tested, what they reject is counted (slot 46) and filed all the same
 #endif

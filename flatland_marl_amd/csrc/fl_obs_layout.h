@@ -424,6 +424,7 @@ struct ObsArgs {
                        // of 32 agents, 3: rounds of 16 agents on 512 threads (at most 80 KB of LDS: two workgroups a CU)
     int wl_occ_div;    // the occupant work list gets 1 / wl_occ_div of the work-list entries, the conflict list the rest
     int no_cf_dirs;    // FL_OBS_NO_CF_DIRS: the per-direction conflict masks (L_CMASK / L_CMASKB) are neither filled nor consulted
+    int pb_ceil_split; // FL_OBS_PB_CEIL_SPLIT: pass B splits a round's cells as before the even slices of fl_obs_slices.h (same-build comparisons)
     int fix;           // FIXED launch class of this launch (ObsFixed<fix>: the kernel's layout is a compile-time constant), 0 = none
     const int16_t *label;  // flatland_cutils get_many(handles) with a strict subset (MODE 0 only; null: every agent): label[i] = position of agent i in
                        // the list or -1.  Only the listed agents' predictions enter the index, under their list POSITION -- the conflict test

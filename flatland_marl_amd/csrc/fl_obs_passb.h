@@ -1,8 +1,10 @@
 // fl_obs_passb.h -- pass B of the trees: the agent-dependent features of every visited cell of every node.  The visited cells
-// of ALL trees of a round are split evenly over ALL lanes of the workgroup; a lane only classifies its cells, the cells that
-// need work go to two work lists that are processed one entry per lane on packed wavefronts.  Device code.
+// of ALL trees of a round are split over the lanes of the workgroup in slices that differ by at most one cell (fl_obs_slices.h); a lane
+// only classifies its cells, the cells that need work go to two work lists that are processed one entry per lane on packed
+// wavefronts.  Device code.
 #pragma once
 #include "fl_obs_ctx.h"
+#include "fl_obs_slices.h"
 
 // The feature block of ONE visited cell of a branch walk (treeobs.cpp:322-465 / observations.py:296-371) is split in
 // two event handlers that merge straight into the node's accumulators (sc = the team's node table) with LDS atomics:
@@ -200,8 +202,9 @@ __device__ __forceinline__ void team_sync() {
 
 // Pass B of the trees.  team_prepare: per team (= one agent's tree), inclusive prefix of the nodes' visit counts, a link
 // from every node to the next node that has cells, and reset of the node accumulators.  wg_pass_b: the visited cells of ALL
-// nodes of ALL trees of the batch are split evenly over ALL lanes of the workgroup; every lane walks its slice (search
-// for its first team / node, a skip to the slice start, then ONE lock-step loop over its cells).
+// nodes of ALL trees of the batch are split over the lanes of the workgroup: total / nt cells a lane and one more for the first
+// total % nt lanes, so that no wavefront is left without cells while others walk a cell more (fl_obs_slices.h).  Every lane walks
+// its slice (search for its first team / node, a skip to the slice start, then ONE lock-step loop over its cells).
 //
 // N_INCL word of node k: inclusive prefix (24 bits) | index of the next node with cells << 24 (0xFF = none).
 // Returns the team's number of cells; first_real = its first node with cells (0xFF = none).
@@ -303,15 +306,17 @@ __device__ __forceinline__ void wg_pass_b(const ObsCtx &X, int tid, int nt, int 
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) { const int u = __shfl_up(tincl, off); if (lane >= off) tincl += u; }
     const int total = __builtin_amdgcn_readlane(tincl, 63);
-    const int q = (total + nt - 1) / nt;
-    int pos = tid * q;
-    const int end = min(pos + q, total);
+    // the lanes' slices (fl_obs_slices.h): total / nt cells each and one more for the first total % nt lanes
+    const PbSplit split = pb_split(total, nt, X.pb_ceil_split);
+    int pos = pb_lane_begin(split, tid);
+    const int end = pb_lane_end(split, tid);
     // first team whose inclusive prefix exceeds pos: the wavefront's first cell by a scalar binary search (v_readlane, no LDS),
     // then every lane counts the few team boundaries inside the wavefront's range
-    const int wpos0 = __builtin_amdgcn_readfirstlane(tid >> 6) * 64 * q;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wpos0 = pb_wave_first(split, wv);
     int team = 0, t_excl = 0;
     if (wpos0 < total) {
-        const int wlast = min(wpos0 + 64 * q, total) - 1;
+        const int wlast = pb_wave_last(split, wv);
         int ulo = 0, uhi = n_teams - 1;
         while (ulo < uhi) {
             const int mid = (ulo + uhi) >> 1;
@@ -329,6 +334,12 @@ __device__ __forceinline__ void wg_pass_b(const ObsCtx &X, int tid, int nt, int 
 #ifdef FL_OBS_TIMING
     const long long dbg_t1 = (long long)wall_clock64();
     int dbg_skip = 0;
+    const int dbg_cells = end - pos;  // (lane 0 of a wavefront has its longest slice)
+#endif
+#ifdef FL_OBS_COUNTS
+    // wave-iterations of the classify loop and those in which some lane of the wavefront moved to another team (slots 44 / 45, summed
+    // over the rounds), wavefronts without a cell (47), the split (49: q << 20 | rem, the largest of the rounds)
+    int cnt_iter = 0, cnt_switch = 0;
 #endif
     if (pos < end) {
         constexpr int cap = PB >= 2 ? 32 : CAP;   // words between the fields of a node table
@@ -474,6 +485,9 @@ __device__ __forceinline__ void wg_pass_b(const ObsCtx &X, int tid, int nt, int 
             pos++;
             left--;
             const bool more = pos < end;
+#ifdef FL_OBS_COUNTS
+            bool cnt_moved = false;
+#endif
             if (more) {
                 if (left > 0) {  // keep walking along the only transition
                     const uint32_t s2 = has_snext ? sn : chain_next(X, ((uint32_t)cell << 2) | dd, cw & 0xFFFFu);
@@ -483,6 +497,9 @@ __device__ __forceinline__ void wg_pass_b(const ObsCtx &X, int tid, int nt, int 
                     if (nxt < nn) {
                         node = nxt;
                     } else {  // next team with cells (the prefix says cells remain)
+#ifdef FL_OBS_COUNTS
+                        cnt_moved = true;
+#endif
                         do { team++; } while (team < n_teams - 1 && team_meta[team] == 0);
                         vs = team_table<PB, CAP>(X, scr0, team_words, team);
                         nn = team_meta[64 + team];
@@ -499,6 +516,10 @@ __device__ __forceinline__ void wg_pass_b(const ObsCtx &X, int tid, int nt, int 
                 }
                 request();
             }
+#ifdef FL_OBS_COUNTS
+            cnt_iter++;
+            cnt_switch += __ballot(cnt_moved) != 0ull;
+#endif
             // file the current cell
             int i_occ, i_cf;
             wl_reserve2_finish(resv, m_occ, m_cf, i_occ, i_cf);
@@ -523,8 +544,18 @@ __device__ __forceinline__ void wg_pass_b(const ObsCtx &X, int tid, int nt, int 
     if (X.dbg && lane == 0) {
         const long long dbg_t2 = (long long)wall_clock64();
         // slowest lane of the env: slice-loop ticks << 40 | cells per lane << 20 | cells skipped
-        atomicMax((unsigned long long *)&X.dbg[25], ((unsigned long long)(dbg_t2 - dbg_t1) << 40) | ((unsigned long long)q << 20) | (unsigned long long)dbg_skip);
+        atomicMax((unsigned long long *)&X.dbg[25], ((unsigned long long)(dbg_t2 - dbg_t1) << 40) | ((unsigned long long)dbg_cells << 20) | (unsigned long long)dbg_skip);
         atomicMax((unsigned long long *)&X.dbg[26], (unsigned long long)total);
+    }
+#endif
+#ifdef FL_OBS_COUNTS
+    // Kernels with ONE pass B only read these: stage 2 of a two-stage kernel keeps its stamps at dbg_base 32 (44 / 45 are its work-list marks, 47 its
+    // running stamp), so it does not count, and what its stage 1 counted is overwritten there (tools/obs_phase_clocks.py prints no counts then).
+    if (X.dbg && lane == 0 && X.dbg_base == 0) {  // (lane 0 stays in the loop as long as any lane of its wavefront: no slice is longer than the first)
+        atomicAdd((unsigned long long *)&X.dbg[44], (unsigned long long)cnt_iter);
+        atomicAdd((unsigned long long *)&X.dbg[45], (unsigned long long)cnt_switch);
+        if (wpos0 >= total) atomicAdd((unsigned long long *)&X.dbg[47], 1ull);
+        if (tid == 0) atomicMax((unsigned long long *)&X.dbg[49], ((unsigned long long)split.q << 20) | (unsigned long long)split.rem);
     }
 #endif
     __syncthreads();

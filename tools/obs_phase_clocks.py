@@ -115,6 +115,14 @@ def report():
     if c[:, :, 27].max() > 0 and c[:, :, 32].max() == 0:  # (-DFL_OBS_COUNTS, a kernel with one pass B: slot 46 is free there)
         print("classified cells with somebody else around the queried time that the direction masks reject: %.0f (%s)" %
               (c[:, :, 46].mean(), "counted only, filed all the same: FL_OBS_NO_CF_DIRS" if os.environ.get("FL_OBS_NO_CF_DIRS") else "not filed"))
+    # (-DFL_OBS_COUNTS, a kernel with one pass B: stage 2 of the two-stage kernels keeps its own stamps in the slots 44 .. 49)
+    # the classify loop by wavefront, and how pass B split the cells (fl_obs_slices.h)
+    if c[:, :, 27].max() > 0 and c[:, :, 32].max() == 0 and c[:, :, 44].max() > 0:
+        sp = c[:, :, 49].astype(np.uint64)
+        print("classify loop (sum over rounds): wave-iterations %.1f, with a lane moving to another team %.1f (%.0f %%), wavefronts without a cell %.2f; split (largest round): cells / lanes %.2f, remainder %.0f%s" %
+              (c[:, :, 44].mean(), c[:, :, 45].mean(), 100.0 * c[:, :, 45].sum() / c[:, :, 44].sum(), c[:, :, 47].mean(),
+               (sp >> np.uint64(20)).astype(np.float64).mean(), (sp & np.uint64(0xFFFFF)).astype(np.float64).mean(),
+               "  (FL_OBS_PB_CEIL_SPLIT: ceil(cells / lanes) a lane until none are left)" if os.environ.get("FL_OBS_PB_CEIL_SPLIT") else ""))
     print("work-list entries (sum over rounds): occupant %.0f / %.0f, conflict %.0f / %.0f  (cutils / upstream)" %
           (c[:, :, 9].mean(), c[:, :, 41].mean(), c[:, :, 10].mean(), c[:, :, 42].mean()))
     if c[:, :, 58].max() > 0:
