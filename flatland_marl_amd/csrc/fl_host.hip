@@ -12,8 +12,10 @@
 #include "fl_internal.h"
 #include "fl_obs.h"
 #include "fl_global.h"
+#include "fl_predict.h"
 #include "fl_tree_lstm.h"
 #include "../../include/flatland_train.h"
+#include "../../include/flatland_predict.h"
 #include "fl_tree_lstm_bwd.h"
 
 static thread_local char g_err[512] = "";
@@ -66,6 +68,7 @@ struct fl_batch {
     std::vector<uint8_t> h_loaded, h_dirty;  // dirty: loaded since the last commit
     std::vector<uint8_t> h_rtype;
     uint8_t *mask_dev;   // [B] staging of host-side env masks (fl_reset, fl_commit after a live replacement)
+    uint32_t *rcell_dev; // [B][Rcap] cell id of a rail index (the copy of h_rcell; fl_predict turns waypoints back into cells)
     uint8_t *need_dev;   // [B] the envs whose slabs a commit / full rebuild (re)builds: the OWNERS of shared static tables (FlDev::tab)
     // shared static tables: h_key = content id of env b's map side (rail grid + unique targets), h_tab = the owner of its tables,
     // h_built = content id of what env b's slabs hold on the device (0 = nothing yet)
@@ -126,6 +129,7 @@ int fl_create(int B, int A, int H, int W, int device, fl_batch **out) {
     h->h_loaded.assign(B, 0); h->h_dirty.assign(B, 0);
     h->h_key.assign(B, 0); h->h_built.assign(B, 0); h->h_tab.assign(B, 0); h->h_need.assign(B, 0);
     h->need_dev = nullptr;
+    h->rcell_dev = nullptr;
     memset(&h->obs, 0, sizeof h->obs);
     h->last_obs_launch[0] = -1;   // (no observation launch yet)
     *out = h;
@@ -267,6 +271,7 @@ static int upload_envs(fl_batch *h, int b0, int nb) {
     UPLOAD_RANGE(d.grid, h->h_gridx, b * HW, n * HW); UPLOAD_RANGE(d.ridx, h->h_ridx, b * HW, n * HW);
     UPLOAD_RANGE(d.rgrid, h->h_rgrid, b * Rcap, n * Rcap); UPLOAD_RANGE(d.rtype, h->h_rtype, b * Rcap, n * Rcap); UPLOAD_RANGE(d.nbr, h->h_nbr, b * Rcap * 4, n * Rcap * 4);
     if (d.rkey) UPLOAD_RANGE(d.rkey, h->h_rkey, b * Rcap, n * Rcap);
+    UPLOAD_RANGE(h->rcell_dev, h->h_rcell, b * Rcap, n * Rcap);
     UPLOAD_RANGE(d.ut_r, h->h_ut_r, b * Ucap, n * Ucap);
     const size_t g0 = b * A, ng = n * A;
     UPLOAD_RANGE(d.init_pos, h->h_init_pos, g0, ng); UPLOAD_RANGE(d.target, h->h_target, g0, ng);
@@ -437,6 +442,7 @@ int fl_commit(fl_batch *h) {
             memset(&h->obs, 0, sizeof h->obs);
             h->mask_dev = nullptr;
             h->need_dev = nullptr;
+            h->rcell_dev = nullptr;
             std::fill(h->h_built.begin(), h->h_built.end(), 0);
         }
         int Ucap = h->reserve_U > 1 ? h->reserve_U : 1, Rcap = h->reserve_R > 1 ? h->reserve_R : 1;
@@ -468,6 +474,7 @@ int fl_commit(fl_batch *h) {
         DALLOC(d.spk, BA); DALLOC(d.speed, BA);
         DALLOC(d.pos, BA); DALLOC(d.old_pos, BA); DALLOC(d.arrival, BA); DALLOC(d.malf, BA); DALLOC(d.pk, BA);
         DALLOC(h->mask_dev, B); DALLOC(h->need_dev, B); DALLOC(d.tab, B);
+        DALLOC(h->rcell_dev, (size_t)B * Rcap);
         if (fl_step_prepare() != FL_OK) { set_err("fl_commit: hipFuncSetAttribute failed"); return FL_ERR_HIP; }
         int rc = fl_obs_alloc(h->obs, d, h->stream, h->allocs);
         if (rc != FL_OK) { set_err("fl_commit: observation scratch allocation failed"); return rc; }
@@ -520,6 +527,12 @@ int fl_commit(fl_batch *h) {
     do {                                                                       \
         if (!(h) || !(h)->committed) { set_err("handle not committed"); return FL_ERR_ARG; } \
         HIPCHK(hipSetDevice((h)->device));                                     \
+    } while (0)
+
+// (the argument checks of an entry point that promises them before any HIP call)
+#define NEED_COMMIT_NOHIP(h)                                                   \
+    do {                                                                       \
+        if (!(h) || !(h)->committed) { set_err("handle not committed"); return FL_ERR_ARG; } \
     } while (0)
 
 int fl_set_rng(fl_batch *h, const uint32_t *mt_key, const int32_t *mt_pos) {
@@ -1116,6 +1129,23 @@ int fl_obs_global(fl_batch *h, int b0, int nb, int elem_bytes, void *rail_dev, v
     }
     if (fl_launch_obs_global(h->d, b0, nb, elem_bytes, h->obs.n_cu, rail_dev, agents_state_dev, targets_dev, h->stream) != FL_OK) {
         set_err("fl_obs_global: a %d x %d map needs more bands of cells than one launch holds", h->H, h->W);
+        return FL_ERR_ARG;
+    }
+    HIPCHK(hipGetLastError());
+    return FL_OK;
+}
+
+int fl_predict(fl_batch *h, int b0, int nb, int max_depth, int elem_kind, void *pred_dev, int32_t *path_dev, int32_t *path_len_dev) {
+    NEED_COMMIT_NOHIP(h);
+    if (b0 < 0 || nb < 1 || b0 > h->B - nb) { set_err("fl_predict: env range [%d, %d + %d) is not inside [0, %d)", b0, b0, nb, h->B); return FL_ERR_ARG; }
+    if (max_depth < 1 || max_depth > FLP_MAX_DEPTH) { set_err("fl_predict: max_depth must be in 1 .. %d, got %d", FLP_MAX_DEPTH, max_depth); return FL_ERR_ARG; }
+    if (elem_kind != 0 && elem_kind != 1) { set_err("fl_predict: elem_kind must be 0 (float64) or 1 (int32), got %d", elem_kind); return FL_ERR_ARG; }
+    if (!pred_dev && !path_dev && !path_len_dev) { set_err("fl_predict: every output buffer is NULL"); return FL_ERR_ARG; }
+    if ((path_dev == nullptr) != (path_len_dev == nullptr)) { set_err("fl_predict: path_dev and path_len_dev go together"); return FL_ERR_ARG; }
+    if ((uintptr_t)pred_dev & 15u) { set_err("fl_predict: pred_dev must be 16-byte aligned"); return FL_ERR_ARG; }
+    HIPCHK(hipSetDevice(h->device));
+    if (fl_launch_predict(h->d, h->rcell_dev, b0, nb, max_depth, elem_kind, h->obs.n_cu, pred_dev, path_dev, path_len_dev, h->stream) != FL_OK) {
+        set_err("fl_predict: %d envs of %d agents are more workgroups than one launch holds", nb, h->A);
         return FL_ERR_ARG;
     }
     HIPCHK(hipGetLastError());

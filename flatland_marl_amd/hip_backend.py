@@ -85,9 +85,14 @@ _TRAIN_ABI = {
     "fl_tree_lstm_backward_workspace_bytes": ([i32, i32], C.c_size_t),
     "fl_tree_lstm_backward": ([i32, i32] + [vp] * 15 + [i32] + [vp] * 7 + [C.c_size_t, vp], i32),
 }
+# name -> (argtypes, restype) of every function include/flatland_predict.h declares, in the header's order
+_PREDICT_ABI = {
+    "fl_predict": ([vp, i32, i32, i32, i32, vp, vp, vp], i32),
+}
 SYMBOLS = tuple(_ABI)      # every symbol include/flatland_hip.h declares
 POLICY_SYMBOLS = tuple(_POLICY_ABI)      # ... and include/flatland_policy.h
 TRAIN_SYMBOLS = tuple(_TRAIN_ABI)      # ... and include/flatland_train.h
+PREDICT_SYMBOLS = tuple(_PREDICT_ABI)      # ... and include/flatland_predict.h
 POLICY_HEAD_NPARAMS = 38
 POLICY_SELECT = {None: 0, "soft": 1, "hard": 2}
 POLICY_U_REFERENCE = 0.3745401188473625      # numpy.random.RandomState(42).random_sample(): the reference seeds before every draw
@@ -124,7 +129,7 @@ def lib():
         # otherwise torch.cuda finds no device once the library below has pulled in the system runtime
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
-        for name, (args, res) in {**_ABI, **_DEBUG_ABI, **_POLICY_ABI, **_TRAIN_ABI}.items():
+        for name, (args, res) in {**_ABI, **_DEBUG_ABI, **_POLICY_ABI, **_TRAIN_ABI, **_PREDICT_ABI}.items():
             fn = getattr(L, name, None)        # (a library from bench.py --lib or a tool's LIB_PATH may predate the newer ones)
             if fn is not None:
                 fn.argtypes, fn.restype = args, res
@@ -312,6 +317,7 @@ class BatchedRailEnv:
         self._tree = {}                       # (depth,) -> the upstream-tree tensor of that depth
         self._info = self._metrics = self._scores = self._pol = self._pol64 = None     # output tensors, made at the first use
         self._glob = {}                       # (dtype, b0, nb) -> obs_global's three tensors
+        self._pred = {}                       # (max_depth, dtype, b0, nb) -> predictions' tensor, (max_depth, b0, nb) -> its two path tensors
         self.use_torch_stream()
 
     def _load(self, b, e):
@@ -579,6 +585,38 @@ class BatchedRailEnv:
                                  tgt.data_ptr()))
         return (r if rail else None), ast, tgt
 
+    def predictions(self, max_depth=20, dtype=None, envs=None, paths=False):
+        """flatland.envs.predictions.ShortestPathPredictorForRailEnv(max_depth).get() (predictions.py:97-180) for every agent of the
+        envs `envs` (the forms obs_global takes), one launch (fl_predict): pred [nb, A, max_depth + 1, 5] with the rows (time, row, col,
+        direction, action), dtype torch.float64 (default: the reference's) or torch.int32 (the same values).  paths=True: (pred,
+        waypoints [nb, A, max_depth, 3] int32, length [nb, A] int32) -- get_shortest_paths(distance_map, max_depth)
+        (rail_env_shortest_paths.py:203-274) as (row, col, direction) with -1 behind the path's length, length 0 = None.  The buffers
+        are cached per (max_depth, dtype, range) and rewritten by every call."""
+        t = self.torch
+        dtype = t.float64 if dtype is None else dtype
+        if dtype not in (t.float64, t.int32):
+            raise ValueError("predictions: dtype has to be torch.float64 or torch.int32, got %r" % (dtype,))
+        max_depth = int(max_depth)
+        if not 1 <= max_depth <= 500:
+            raise ValueError("predictions: max_depth has to be in 1 .. 500, got %d" % max_depth)
+        b0, nb = self._env_range(envs)
+        if not (0 <= b0 and nb >= 1 and b0 + nb <= self.B):
+            raise ValueError("predictions: env range [%d, %d) is not inside [0, %d)" % (b0, b0 + nb, self.B))
+        key = (max_depth, dtype, b0, nb)
+        if key not in self._pred:
+            self._pred[key] = t.empty((nb, self.A, max_depth + 1, 5), dtype=dtype, device=self.device)
+        pred = self._pred[key]
+        wp = ln = None
+        if paths:
+            pkey = (max_depth, b0, nb)
+            if pkey not in self._pred:
+                self._pred[pkey] = (t.empty((nb, self.A, max_depth, 3), dtype=t.int32, device=self.device),
+                                    t.empty((nb, self.A), dtype=t.int32, device=self.device))
+            wp, ln = self._pred[pkey]
+        _chk(_sym("fl_predict")(self.h, b0, nb, max_depth, 0 if dtype == t.float64 else 1, pred.data_ptr(),
+                                wp.data_ptr() if paths else None, ln.data_ptr() if paths else None))
+        return (pred, wp, ln) if paths else pred
+
     # ---- read-backs
     def state(self):
         st = np.zeros((self.B, self.A, STATE_COLS), dtype=np.int32)
@@ -757,6 +795,11 @@ class MixedBatch:
         """GlobalObsForRailEnv per group (fl_obs_global): one (rail, agents_state, targets) triple per shape group, its env axis in the
         group's batch order (pick(i, ...) gives env i's slices)"""
         return self._each(lambda g: g.obs_global(dtype, None, rail))
+
+    def predictions(self, max_depth=20, dtype=None, paths=False):
+        """ShortestPathPredictorForRailEnv(max_depth).get() per group (fl_predict): one result of BatchedRailEnv.predictions per shape
+        group, its env axis in the group's batch order (pick(i, ...) gives env i's slices)"""
+        return self._each(lambda g: g.predictions(max_depth, dtype, None, paths))
 
     def state(self, i):
         g, b = self.where[i]

@@ -5,7 +5,9 @@
 
 `TreeObsForRailEnv(max_nodes, max_pred_depth)` replaces the pybind11 class `flatland_cutils.TreeObsForRailEnv`
 (flatland_cutils/src/main.cpp:17-22), `TreeObsUpstream(max_depth, predictor)` replaces
-`flatland.envs.observations.TreeObsForRailEnv` (observations.py:34-532).  Like the reference module they keep whatever object
+`flatland.envs.observations.TreeObsForRailEnv` (observations.py:34-532), `ShortestPathPredictorForRailEnv(max_depth)` replaces the predictor of
+flatland/envs/predictions.py:86-180 (get() -> {handle: [max_depth + 1, 5]}, env.dev_pred_dict, get_shortest_paths(); behind
+`TreeObsUpstream` or behind the reference's own TreeObsForRailEnv(predictor=...)).  Like the reference module they keep whatever object
 `set_env` hands them (treeobs.cpp:17-21 -- at that time a reference RailEnv has no rail yet, rail_env.py:178-179) and read it
 again on every call, duck-typed:
 
@@ -34,7 +36,7 @@ check of the static side compares the agents' line / timetable arrays.  `get_man
 arrays themselves instead of the nested lists the pybind11 casters of the reference build.
 """
 from . import rail_env as _re
-from .rail_env import TreeObsForRailEnv, GlobalObsForRailEnv, _EnvBinding  # noqa: F401
+from .rail_env import TreeObsForRailEnv, GlobalObsForRailEnv, ShortestPathPredictorForRailEnv, _EnvBinding  # noqa: F401
 
 # The builders themselves are rail_env's: one class per kind, for this library's RailEnv (read in place on the device) and for any
 # other env object (mirrored through _EnvBinding).  Here are the names with the reference's constructor arguments.

@@ -567,6 +567,89 @@ class GlobalObsForRailEnv(_DeviceObs):
         return {h: (self.rail_obs, ast[h], tgt[h]) for h in handles}
 
 
+Waypoint = collections.namedtuple("Waypoint", ["position", "direction"])      # rail_trainrun_data_structures.py: ((row, col), direction)
+
+
+class OrderedSet(dict):
+    """what the reference keeps in env.dev_pred_dict (flatland/utils/ordered_set.py): a set that iterates in insertion order"""
+
+    def __init__(self, items=()):
+        super().__init__((x, None) for x in items)
+
+    def add(self, x):
+        self[x] = None
+
+    def __repr__(self):
+        return "OrderedSet(%r)" % (list(self),)
+
+
+class ShortestPathPredictorForRailEnv:
+    """flatland.envs.predictions.ShortestPathPredictorForRailEnv(max_depth) (predictions.py:86-180), for any env object: get() ->
+    {handle: float64 [max_depth + 1, 5]} with the rows (time, row, col, direction, action), computed by the GPU for every agent in
+    one launch (fl_predict).  Like the reference get() tests `if handle:` -- get(0) and get(None) return every agent, get(3) agent 3
+    alone -- and leaves env.dev_pred_dict[handle], the ordered set of the (row, col, direction) visited (:158-177).
+    get_shortest_paths(max_depth) is rail_env_shortest_paths.get_shortest_paths(env.distance_map, max_depth) (:203-274).
+    The reference's TreeObsForRailEnv never calls predictor.reset() (observations.py:57-58): with a caller-owned env the static side
+    is read at the first get() after set_env() (and again after a reset() of an env that counts its resets); reset() reads it again."""
+
+    def __init__(self, max_depth=20, *, device=0, verify_distance_map=False):
+        self.max_depth = max_depth
+        self.env = None
+        self._bind = _EnvBinding(device, verify_distance_map)
+        self._src = self._bind
+        self._loaded = None        # the env's num_resets when the static side was read (True: an env without that counter)
+
+    def set_env(self, env):
+        self.env = env
+        self._src = _OwnBatch(env) if isinstance(env, RailEnv) else self._bind
+        self._loaded = None
+
+    def _resets(self):
+        n = getattr(self.env, "num_resets", None)
+        return True if n is None else n
+
+    def reset(self):
+        self._src.load_static(self.env)
+        self._loaded = self._resets()
+
+    def _batch(self, what):
+        if self._loaded is None or self._loaded != self._resets():
+            self.reset()
+        b = self._src.current(self.env, what)
+        if b is None:
+            raise RuntimeError("%s before the env's reset()" % what)
+        return b
+
+    def get(self, handle=None):
+        b = self._batch("ShortestPathPredictorForRailEnv.get()")
+        pred = b.predictions(int(self.max_depth))
+        b.check()
+        arr = pred[0].cpu().numpy()
+        handles = [handle] if handle else range(b.A)          # predictions.py:121-123: `if handle:`
+        dev = getattr(self.env, "dev_pred_dict", None)
+        if dev is None:
+            try:
+                self.env.dev_pred_dict = dev = {}
+            except AttributeError:
+                dev = None
+        out = {}
+        for h in handles:
+            p = arr[h].copy()
+            out[h] = p
+            if dev is not None:
+                own_dir = int(p[0, 3])                        # (a stop row is filed under agent.direction, :163)
+                dev[h] = OrderedSet((int(r[1]), int(r[2]), own_dir if r[4] == RailEnvActions.STOP_MOVING else int(r[3])) for r in p[1:])
+        return out
+
+    def get_shortest_paths(self, max_depth=None):
+        """{handle: [Waypoint((row, col), direction), ...] or None}: at most max_depth waypoints (default: the predictor's depth)"""
+        b = self._batch("ShortestPathPredictorForRailEnv.get_shortest_paths()")
+        _, wp, ln = b.predictions(int(self.max_depth if max_depth is None else max_depth), paths=True)
+        b.check()
+        wp, ln = wp[0].cpu().numpy(), ln[0].cpu().numpy()
+        return {h: [Waypoint((int(r), int(c)), int(d)) for r, c, d in wp[h, :ln[h]]] if ln[h] else None for h in range(b.A)}
+
+
 class _FromDescription:
     """what `env.rail_generator` / `env.line_generator` are on an env made from a description or a file (the reference:
     rail_from_file / line_from_file closures, rail_generators.py:116-145, line_generators.py:168-206): hands the env's own rail /

@@ -1,7 +1,9 @@
-"""flatland.envs.predictions.ShortestPathPredictorForRailEnv(max_depth) (predictions.py:91-180): here only the holder of the
-depth -- the prediction itself is part of the observation kernel"""
+"""flatland.envs.predictions.ShortestPathPredictorForRailEnv(max_depth) (predictions.py:86-180): get() and get_shortest_paths() are
+computed on the GPU (fl_predict); the tree builders still read only `max_depth` from it -- their prediction is part of the observation
+kernel"""
+from flatland_marl_amd.plugin import ShortestPathPredictorForRailEnv as _Predictor
 
 
-class ShortestPathPredictorForRailEnv:
+class ShortestPathPredictorForRailEnv(_Predictor):
     def __init__(self, max_depth=20):
-        self.max_depth = max_depth
+        super().__init__(max_depth)
