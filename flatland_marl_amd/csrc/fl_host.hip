@@ -13,9 +13,11 @@
 #include "fl_obs.h"
 #include "fl_global.h"
 #include "fl_predict.h"
+#include "fl_wrappers.h"
 #include "fl_tree_lstm.h"
 #include "../../include/flatland_train.h"
 #include "../../include/flatland_predict.h"
+#include "../../include/flatland_wrappers.h"
 #include "fl_tree_lstm_bwd.h"
 
 static thread_local char g_err[512] = "";
@@ -69,6 +71,7 @@ struct fl_batch {
     std::vector<uint8_t> h_rtype;
     uint8_t *mask_dev;   // [B] staging of host-side env masks (fl_reset, fl_commit after a live replacement)
     uint32_t *rcell_dev; // [B][Rcap] cell id of a rail index (the copy of h_rcell; fl_predict turns waypoints back into cells)
+    uint8_t *cellkind_dev; // [B][H*W] bit 0 switch, bit 1 switch neighbour (k_decision_cells; the owners' slabs, as every static table)
     uint8_t *need_dev;   // [B] the envs whose slabs a commit / full rebuild (re)builds: the OWNERS of shared static tables (FlDev::tab)
     // shared static tables: h_key = content id of env b's map side (rail grid + unique targets), h_tab = the owner of its tables,
     // h_built = content id of what env b's slabs hold on the device (0 = nothing yet)
@@ -130,6 +133,7 @@ int fl_create(int B, int A, int H, int W, int device, fl_batch **out) {
     h->h_key.assign(B, 0); h->h_built.assign(B, 0); h->h_tab.assign(B, 0); h->h_need.assign(B, 0);
     h->need_dev = nullptr;
     h->rcell_dev = nullptr;
+    h->cellkind_dev = nullptr;
     memset(&h->obs, 0, sizeof h->obs);
     h->last_obs_launch[0] = -1;   // (no observation launch yet)
     *out = h;
@@ -420,6 +424,12 @@ static int launch_table_kernels(fl_batch *h, const uint8_t *mask_dev, bool throu
     HIPCHK(hipGetLastError());
     fl_launch_hop8(h->d, mask_dev, h->stream);
     HIPCHK(hipGetLastError());
+    // the decision cells are a function of the rail grid alone: built for the owners a commit or a full rebuild names, not by a
+    // masked rebuild (through_tab), which finds the grid -- and so this table -- as the last commit left it
+    if (!through_tab) {
+        fl_launch_decision_cells(h->d, mask_dev, h->cellkind_dev, h->stream);
+        HIPCHK(hipGetLastError());
+    }
     return FL_OK;
 }
 
@@ -443,6 +453,7 @@ int fl_commit(fl_batch *h) {
             h->mask_dev = nullptr;
             h->need_dev = nullptr;
             h->rcell_dev = nullptr;
+            h->cellkind_dev = nullptr;
             std::fill(h->h_built.begin(), h->h_built.end(), 0);
         }
         int Ucap = h->reserve_U > 1 ? h->reserve_U : 1, Rcap = h->reserve_R > 1 ? h->reserve_R : 1;
@@ -475,6 +486,7 @@ int fl_commit(fl_batch *h) {
         DALLOC(d.pos, BA); DALLOC(d.old_pos, BA); DALLOC(d.arrival, BA); DALLOC(d.malf, BA); DALLOC(d.pk, BA);
         DALLOC(h->mask_dev, B); DALLOC(h->need_dev, B); DALLOC(d.tab, B);
         DALLOC(h->rcell_dev, (size_t)B * Rcap);
+        DALLOC(h->cellkind_dev, B * HW);
         if (fl_step_prepare() != FL_OK) { set_err("fl_commit: hipFuncSetAttribute failed"); return FL_ERR_HIP; }
         int rc = fl_obs_alloc(h->obs, d, h->stream, h->allocs);
         if (rc != FL_OK) { set_err("fl_commit: observation scratch allocation failed"); return rc; }
@@ -1148,6 +1160,38 @@ int fl_predict(fl_batch *h, int b0, int nb, int max_depth, int elem_kind, void *
         set_err("fl_predict: %d envs of %d agents are more workgroups than one launch holds", nb, h->A);
         return FL_ERR_ARG;
     }
+    HIPCHK(hipGetLastError());
+    return FL_OK;
+}
+
+int fl_action_space(fl_batch *h, int b0, int nb, int elem_kind, uint8_t *sp_action_dev, void *sp_dist_dev, uint8_t *sp_count_dev,
+                    uint8_t *on_decision_dev, const uint8_t *reduced_dev, uint8_t *actions_dev) {
+    NEED_COMMIT_NOHIP(h);
+    if (b0 < 0 || nb < 1 || b0 > h->B - nb) { set_err("fl_action_space: env range [%d, %d + %d) is not inside [0, %d)", b0, b0, nb, h->B); return FL_ERR_ARG; }
+    if (elem_kind != 0 && elem_kind != 1) { set_err("fl_action_space: elem_kind must be 0 (float64) or 1 (int32), got %d", elem_kind); return FL_ERR_ARG; }
+    if (!sp_action_dev && !sp_dist_dev && !sp_count_dev && !on_decision_dev && !actions_dev && !reduced_dev) { set_err("fl_action_space: every output buffer is NULL"); return FL_ERR_ARG; }
+    if ((sp_action_dev == nullptr) != (sp_dist_dev == nullptr) || (sp_action_dev == nullptr) != (sp_count_dev == nullptr)) {
+        set_err("fl_action_space: sp_action_dev, sp_dist_dev and sp_count_dev go together");
+        return FL_ERR_ARG;
+    }
+    if ((reduced_dev == nullptr) != (actions_dev == nullptr)) { set_err("fl_action_space: reduced_dev and actions_dev go together"); return FL_ERR_ARG; }
+    if ((uintptr_t)sp_dist_dev & (elem_kind == 0 ? 7u : 3u)) { set_err("fl_action_space: sp_dist_dev must be %d-byte aligned", elem_kind == 0 ? 8 : 4); return FL_ERR_ARG; }
+    HIPCHK(hipSetDevice(h->device));
+    if (fl_launch_action_space(h->d, h->cellkind_dev, b0, nb, elem_kind, h->obs.n_cu, sp_action_dev, sp_dist_dev, sp_count_dev, on_decision_dev, reduced_dev,
+                               actions_dev, h->stream) != FL_OK) {
+        set_err("fl_action_space: %d envs of %d agents are more workgroups than one launch holds", nb, h->A);
+        return FL_ERR_ARG;
+    }
+    HIPCHK(hipGetLastError());
+    return FL_OK;
+}
+
+int fl_decision_cells(fl_batch *h, int b0, int nb, uint8_t *cells_dev) {
+    NEED_COMMIT_NOHIP(h);
+    if (b0 < 0 || nb < 1 || b0 > h->B - nb) { set_err("fl_decision_cells: env range [%d, %d + %d) is not inside [0, %d)", b0, b0, nb, h->B); return FL_ERR_ARG; }
+    if (!cells_dev) { set_err("fl_decision_cells: cells_dev is NULL"); return FL_ERR_ARG; }
+    HIPCHK(hipSetDevice(h->device));
+    fl_launch_decision_cells_out(h->d, h->cellkind_dev, b0, nb, cells_dev, h->stream);
     HIPCHK(hipGetLastError());
     return FL_OK;
 }

@@ -89,10 +89,16 @@ _TRAIN_ABI = {
 _PREDICT_ABI = {
     "fl_predict": ([vp, i32, i32, i32, i32, vp, vp, vp], i32),
 }
+# ... of every function include/flatland_wrappers.h declares
+_WRAPPERS_ABI = {
+    "fl_action_space": ([vp, i32, i32, i32, vp, vp, vp, vp, vp, vp], i32),
+    "fl_decision_cells": ([vp, i32, i32, vp], i32),
+}
 SYMBOLS = tuple(_ABI)      # every symbol include/flatland_hip.h declares
 POLICY_SYMBOLS = tuple(_POLICY_ABI)      # ... and include/flatland_policy.h
 TRAIN_SYMBOLS = tuple(_TRAIN_ABI)      # ... and include/flatland_train.h
 PREDICT_SYMBOLS = tuple(_PREDICT_ABI)      # ... and include/flatland_predict.h
+WRAPPERS_SYMBOLS = tuple(_WRAPPERS_ABI)      # ... and include/flatland_wrappers.h
 POLICY_HEAD_NPARAMS = 38
 POLICY_SELECT = {None: 0, "soft": 1, "hard": 2}
 POLICY_U_REFERENCE = 0.3745401188473625      # numpy.random.RandomState(42).random_sample(): the reference seeds before every draw
@@ -129,7 +135,7 @@ def lib():
         # otherwise torch.cuda finds no device once the library below has pulled in the system runtime
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
-        for name, (args, res) in {**_ABI, **_DEBUG_ABI, **_POLICY_ABI, **_TRAIN_ABI, **_PREDICT_ABI}.items():
+        for name, (args, res) in {**_ABI, **_DEBUG_ABI, **_POLICY_ABI, **_TRAIN_ABI, **_PREDICT_ABI, **_WRAPPERS_ABI}.items():
             fn = getattr(L, name, None)        # (a library from bench.py --lib or a tool's LIB_PATH may predate the newer ones)
             if fn is not None:
                 fn.argtypes, fn.restype = args, res
@@ -318,6 +324,7 @@ class BatchedRailEnv:
         self._info = self._metrics = self._scores = self._pol = self._pol64 = None     # output tensors, made at the first use
         self._glob = {}                       # (dtype, b0, nb) -> obs_global's three tensors
         self._pred = {}                       # (max_depth, dtype, b0, nb) -> predictions' tensor, (max_depth, b0, nb) -> its two path tensors
+        self._wrap = {}                       # (kind, ..., b0, nb) -> the tensors of the reduced action space (fl_action_space, fl_decision_cells)
         self.use_torch_stream()
 
     def _load(self, b, e):
@@ -617,6 +624,80 @@ class BatchedRailEnv:
                                 wp.data_ptr() if paths else None, ln.data_ptr() if paths else None))
         return (pred, wp, ln) if paths else pred
 
+    # ---- the reduced action space of flatland/contrib/wrappers/flatland_wrappers.py
+    def _wrap_range(self, who, envs):
+        b0, nb = self._env_range(envs)
+        if not (0 <= b0 and nb >= 1 and b0 + nb <= self.B):
+            raise ValueError("%s: env range [%d, %d) is not inside [0, %d)" % (who, b0, b0 + nb, self.B))
+        return b0, nb
+
+    def _wrap_buffer(self, key, shape, dtype):
+        if key not in self._wrap:
+            self._wrap[key] = self.torch.empty(shape, dtype=dtype, device=self.device)
+        return self._wrap[key]
+
+    def _reduced(self, who, reduced, nb):
+        """a host array or a device tensor -> contiguous uint8 [nb, A] on the device"""
+        t = self.torch
+        if not (isinstance(reduced, t.Tensor) and reduced.is_cuda):
+            a = np.asarray(reduced)
+            if a.dtype.kind not in "iub" or a.shape != (nb, self.A) or (a.size and (a.min() < 0 or a.max() > 255)):
+                raise ValueError("%s: reduced has to hold integers 0 .. 255 of shape (%d, %d), got %s %r" % (who, nb, self.A, a.dtype, a.shape))
+            reduced = t.as_tensor(np.ascontiguousarray(a, dtype=np.uint8)).to(self.device)
+        if reduced.dtype != t.uint8 or tuple(reduced.shape) != (nb, self.A):
+            raise ValueError("%s: reduced has to be a uint8 tensor of shape (%d, %d), got %s %r" % (who, nb, self.A, reduced.dtype, tuple(reduced.shape)))
+        if reduced.device != self.device:
+            raise ValueError("%s: reduced lies on %s, the batch on %s" % (who, reduced.device, self.device))
+        return reduced.contiguous()
+
+    def shortest_path_actions(self, dtype=None, envs=None):
+        """possible_actions_sorted_by_distance(env, handle) (flatland_wrappers.py:14-56) for every agent of the envs `envs` (the forms
+        obs_global takes), one launch (fl_action_space): (actions u8 [nb, A, 3] RailEnvActions, distance [nb, A, 3], count u8 [nb, A]).
+        dtype torch.float64 (default: the reference's values, inf = unreachable) or torch.int32 (INT32_MAX = unreachable); behind
+        `count` the slots hold action 0 and infinity.  The buffers are cached per (dtype, range) and rewritten by every call."""
+        t = self.torch
+        dtype = t.float64 if dtype is None else dtype
+        if dtype not in (t.float64, t.int32):
+            raise ValueError("shortest_path_actions: dtype has to be torch.float64 or torch.int32, got %r" % (dtype,))
+        b0, nb = self._wrap_range("shortest_path_actions", envs)
+        act = self._wrap_buffer(("sp_action", b0, nb), (nb, self.A, 3), t.uint8)
+        dist = self._wrap_buffer(("sp_dist", dtype, b0, nb), (nb, self.A, 3), dtype)
+        cnt = self._wrap_buffer(("sp_count", b0, nb), (nb, self.A), t.uint8)
+        _chk(_sym("fl_action_space")(self.h, b0, nb, 0 if dtype == t.float64 else 1, act.data_ptr(), dist.data_ptr(), cnt.data_ptr(),
+                                     None, None, None))
+        return act, dist, cnt
+
+    def on_decision_cell(self, envs=None):
+        """SkipNoChoiceCellsWrapper.on_decision_cell(agent) (flatland_wrappers.py:197-198) for every agent of the envs `envs`: u8 [nb, A],
+        1 = off the map or DONE, on its own start cell, on a switch or next to one (fl_action_space)"""
+        b0, nb = self._wrap_range("on_decision_cell", envs)
+        dec = self._wrap_buffer(("on_decision", b0, nb), (nb, self.A), self.torch.uint8)
+        _chk(_sym("fl_action_space")(self.h, b0, nb, 0, None, None, None, dec.data_ptr(), None, None))
+        return dec
+
+    def decision_cells(self, envs=None):
+        """find_all_cells_where_agent_can_choose(env) (flatland_wrappers.py:145-176) of the envs `envs`: u8 [nb, H, W], bit 0 = switch,
+        bit 1 = neighbour of a switch (fl_decision_cells; the table is built with the env's static tables)"""
+        b0, nb = self._wrap_range("decision_cells", envs)
+        cells = self._wrap_buffer(("cells", b0, nb), (nb, self.H, self.W), self.torch.uint8)
+        _chk(_sym("fl_decision_cells")(self.h, b0, nb, cells.data_ptr()))
+        return cells
+
+    def reduced_actions(self, reduced, envs=None):
+        """ShortestPathActionWrapper.step's translation (flatland_wrappers.py:131-138) for the envs `envs`: reduced u8 [nb, A] with
+        0 = do nothing, 1 = shortest path, 2 = second shortest path (3 = third where a list has three), 255 = agent not in the dict
+        -> u8 [nb, A] RailEnvActions, what step() takes.  An entry the agent's list does not have gives 0 (the reference raises
+        IndexError)."""
+        b0, nb = self._wrap_range("reduced_actions", envs)
+        reduced = self._reduced("reduced_actions", reduced, nb)
+        out = self._wrap_buffer(("actions", b0, nb), (nb, self.A), self.torch.uint8)
+        _chk(_sym("fl_action_space")(self.h, b0, nb, 0, None, None, None, None, reduced.data_ptr(), out.data_ptr()))
+        return out
+
+    def step_shortest_path(self, reduced, auto_reset=False, filter_required=False):
+        """step(reduced_actions(reduced), ...): the translation and the tick back to back on the batch's stream, nothing in between"""
+        return self.step(self.reduced_actions(reduced), auto_reset, filter_required)
+
     # ---- read-backs
     def state(self):
         st = np.zeros((self.B, self.A, STATE_COLS), dtype=np.int32)
@@ -771,6 +852,23 @@ class MixedBatch:
             per[g][b] = np.asarray(a, dtype=np.uint8)
         return self._on_streams(lambda k, g: g.step(per[k], auto_reset=auto_reset, filter_required=filter_required))
 
+    def _per_group(self, rows):
+        per = [np.full((g.B, g.A), ACTION_ABSENT, dtype=np.uint8) for g in self.groups]
+        for i, a in enumerate(rows):
+            g, b = self.where[i]
+            per[g][b] = np.asarray(a, dtype=np.uint8)
+        return per
+
+    def reduced_actions(self, reduced):
+        """reduced: one uint8 array [A_i] per env in the caller's env order -> BatchedRailEnv.reduced_actions per shape group"""
+        per = self._per_group(reduced)
+        return self._on_streams(lambda k, g: g.reduced_actions(per[k]))
+
+    def step_shortest_path(self, reduced, auto_reset=False, filter_required=False):
+        """reduced as reduced_actions takes it; per group the translation and the tick on the group's stream"""
+        per = self._per_group(reduced)
+        return self._on_streams(lambda k, g: g.step_shortest_path(per[k], auto_reset=auto_reset, filter_required=filter_required))
+
     def stream_of(self, i):
         """stream id of env i in the on-device action stream of step_synth (groups in order, envs of a group consecutive)"""
         g, b = self.where[i]
@@ -800,6 +898,19 @@ class MixedBatch:
         """ShortestPathPredictorForRailEnv(max_depth).get() per group (fl_predict): one result of BatchedRailEnv.predictions per shape
         group, its env axis in the group's batch order (pick(i, ...) gives env i's slices)"""
         return self._each(lambda g: g.predictions(max_depth, dtype, None, paths))
+
+    def shortest_path_actions(self, dtype=None):
+        """possible_actions_sorted_by_distance per group (fl_action_space): one result of BatchedRailEnv.shortest_path_actions per shape
+        group, its env axis in the group's batch order (pick(i, ...) gives env i's slices)"""
+        return self._each(lambda g: g.shortest_path_actions(dtype))
+
+    def on_decision_cell(self):
+        """SkipNoChoiceCellsWrapper.on_decision_cell per group"""
+        return self._each(lambda g: g.on_decision_cell())
+
+    def decision_cells(self):
+        """find_all_cells_where_agent_can_choose per group (fl_decision_cells)"""
+        return self._each(lambda g: g.decision_cells())
 
     def state(self, i):
         g, b = self.where[i]

@@ -846,6 +846,183 @@ class RailEnv:
         return obs, self.rewards_dict, self.dones, self.get_info_dict()
 
 
+# ---- flatland/contrib/wrappers/flatland_wrappers.py: the reduced action space most training code puts in front of RailEnv.
+# The lists, the flags and the cell sets are computed on the device (fl_action_space, fl_decision_cells), one read-back per call;
+# the wrappers' loops are the reference's host loops.  DeadlockWrapper is left out: see the shim module and DESIGN.md section 7.
+def _batch_of(env):
+    b = getattr(env, "_batch", None)      # (a wrapper hands the attribute of the env it wraps on)
+    if b is None:
+        raise RuntimeError("the env has no batch yet: reset() it first")
+    return b
+
+
+def possible_actions_sorted_by_distance(env, handle):
+    """flatland_wrappers.py:14-56: the moves agent `handle` has, [(RailEnvActions, distance)] sorted by the distance map, of length 2
+    (a single move is doubled) or 3; distance is a numpy float64, and the int 0 of [(DO_NOTHING, 0)] * 2 for an agent that is neither
+    READY_TO_DEPART nor on the map.  The reference's prints are not reproduced."""
+    b = _batch_of(env)
+    act, dist, cnt = b.shortest_path_actions()
+    b.check()
+    row = b.torch.cat([act[0, handle].to(dist.dtype), dist[0, handle], cnt[0, handle:handle + 1].to(dist.dtype)]).cpu().numpy()
+    n = int(row[6])
+    state = env.agents[handle].state
+    if state != TrainState.READY_TO_DEPART and not state.is_on_map_state():
+        return [(RailEnvActions.DO_NOTHING, 0)] * 2
+    return [(RailEnvActions(int(row[k])), np.float64(row[3 + k])) for k in range(n)]
+
+
+def find_all_cells_where_agent_can_choose(env):
+    """flatland_wrappers.py:145-176: (switches, switches_neighbors, decision_cells) as sets of (row, col).  Cells with rail only: the
+    reference also lists the empty cell a malformed switch points at, where no agent can stand."""
+    b = _batch_of(env)
+    cells = b.decision_cells()[0].cpu().numpy()
+    b.check()
+    switches = {(int(r), int(c)) for r, c in zip(*np.nonzero(cells & 1))}
+    neighbors = {(int(r), int(c)) for r, c in zip(*np.nonzero(cells & 2))}
+    return switches, neighbors, switches | neighbors
+
+
+class RailEnvWrapper:  # flatland_wrappers.py:59-119
+    def __init__(self, env):
+        self.env = env
+        assert self.env is not None
+        assert self.env.rail is not None, "Reset original environment first!"
+        assert self.env.agents is not None, "Reset original environment first!"
+        assert len(self.env.agents) > 0, "Reset original environment first!"
+
+    def __getattr__(self, name):
+        """Expose any other attributes of the underlying environment."""
+        if name == "env":
+            raise AttributeError(name)
+        return getattr(self.env, name)
+
+    @property
+    def rail(self):
+        return self.env.rail
+
+    @property
+    def width(self):
+        return self.env.width
+
+    @property
+    def height(self):
+        return self.env.height
+
+    @property
+    def agent_positions(self):
+        return self.env.agent_positions
+
+    def get_num_agents(self):
+        return self.env.get_num_agents()
+
+    def get_agent_handles(self):
+        return self.env.get_agent_handles()
+
+    def step(self, action_dict):
+        return self.env.step(action_dict)
+
+    def reset(self, **kwargs):
+        obs, info = self.env.reset(**kwargs)
+        return obs, info
+
+
+class ShortestPathActionWrapper(RailEnvWrapper):  # flatland_wrappers.py:122-141
+    def step(self, action_dict):
+        """action_dict: {handle: 0 = do nothing, 1 = shortest path, 2 = second shortest path}; translated on the device
+        (BatchedRailEnv.reduced_actions), one read-back.  An entry the agent's list does not have raises IndexError like the reference."""
+        b = _batch_of(self.env)
+        A = self.env.get_num_agents()
+        reduced = np.full((1, A), 255, dtype=np.uint8)
+        passed = {}      # (a handle outside the env, an action outside 0 .. 254: handed on as it came, the env deals with it)
+        for h, a in action_dict.items():
+            if 0 <= int(h) < A and 0 <= int(a) < 255:
+                reduced[0, int(h)] = int(a)
+            else:
+                passed[h] = a
+        acts = b.reduced_actions(reduced)
+        cnt = b.shortest_path_actions()[2]
+        b.check()
+        both = b.torch.stack([acts[0], cnt[0]]).cpu().numpy()
+        transformed = {}
+        for h, a in action_dict.items():
+            if h in passed:
+                transformed[h] = a
+            elif int(a) == 0:
+                transformed[h] = a
+            else:
+                if int(a) - 1 >= int(both[1, int(h)]):
+                    raise IndexError("list index out of range")
+                transformed[h] = RailEnvActions(int(both[0, int(h)]))
+        return self.env.step(transformed)
+
+
+class SkipNoChoiceCellsWrapper(RailEnvWrapper):  # flatland_wrappers.py:179-258
+    def __init__(self, env, accumulate_skipped_rewards, discounting):
+        super().__init__(env)
+        self.accumulate_skipped_rewards = accumulate_skipped_rewards
+        self.discounting = discounting
+        self.switches = None
+        self.switches_neighbors = None
+        self.decision_cells = None
+        self.skipped_rewards = collections.defaultdict(list)
+        self.reset_cells()
+
+    def _flags(self):
+        b = _batch_of(self.env)
+        flags = b.on_decision_cell()[0].cpu().numpy()
+        b.check()
+        return flags
+
+    def on_decision_cell(self, agent):
+        return bool(self._flags()[agent.handle])
+
+    def on_switch(self, agent):
+        return agent.position in self.switches
+
+    def next_to_switch(self, agent):
+        return agent.position in self.switches_neighbors
+
+    def reset_cells(self):
+        self.switches, self.switches_neighbors, self.decision_cells = find_all_cells_where_agent_can_choose(self.env)
+
+    def step(self, action_dict):
+        """the reference's loop: the env is stepped -- with an EMPTY action dict from the second time on -- until an agent is done or on a
+        decision cell; the skipped rewards are summed on the host in the reference's order (a reversed Horner scheme)"""
+        o, r, d, i = {}, {}, {}, {}
+        i["action_required"] = dict()
+        i["malfunction"] = dict()
+        i["speed"] = dict()
+        i["state"] = dict()
+        while len(o) == 0:
+            obs, reward, done, info = self.env.step(action_dict)
+            flags = self._flags()      # (one read-back for the agents of this step)
+            for agent_id, agent_obs in obs.items():
+                if done[agent_id] or flags[agent_id]:
+                    o[agent_id] = agent_obs
+                    r[agent_id] = reward[agent_id]
+                    d[agent_id] = done[agent_id]
+                    i["action_required"][agent_id] = info["action_required"][agent_id]
+                    i["malfunction"][agent_id] = info["malfunction"][agent_id]
+                    i["speed"][agent_id] = info["speed"][agent_id]
+                    i["state"][agent_id] = info["state"][agent_id]
+                    if self.accumulate_skipped_rewards:
+                        discounted_skipped_reward = r[agent_id]
+                        for skipped_reward in reversed(self.skipped_rewards[agent_id]):
+                            discounted_skipped_reward = self.discounting * discounted_skipped_reward + skipped_reward
+                        r[agent_id] = discounted_skipped_reward
+                        self.skipped_rewards[agent_id] = []
+                elif self.accumulate_skipped_rewards:
+                    self.skipped_rewards[agent_id].append(reward[agent_id])
+            d["__all__"] = done["__all__"]
+            action_dict = {}
+        return o, r, d, i
+
+    def reset(self, **kwargs):
+        obs, info = self.env.reset(**kwargs)
+        self.reset_cells()      # (the cells can change with the map)
+        return obs, info
+
+
 class LocalTestEnvWrapper:
     """Counterpart of solution/eval_env.py:9-114 (TestEnvWrapper / LocalTestEnvWrapper)."""
 
