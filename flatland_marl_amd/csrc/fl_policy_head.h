@@ -58,6 +58,7 @@ struct FphArgs {
     float *logits, *value;
     unsigned char *actions;
     float *emb, *xa, *xb, *ao, *qkv, *val;     // workspace: [R][256] x 4, [R][768], [R]
+    float *y3;                                 // the third block's output [R][256], or NULL (inference): fl_policy_head_forward_saved
 };
 
 __device__ __forceinline__ fph_f32x16 fph_mfma(float a, float b, fph_f32x16 c) {
@@ -405,6 +406,7 @@ __global__ void __launch_bounds__(FPH_THREADS) k_ph_block(FphArgs p, int blk, co
         return;
     }
     fph_load_tile(ba, 0, p.emb + (size_t)row0 * FPH_E, FPH_E, FPH_E / 4, rows, tid);
+    if (p.y3) fph_store_tile(bx, p.y3 + (size_t)row0 * FPH_E, rows, tid);
     __syncthreads();
     fph_f32x16 out = {};
     fph_head(ba, bx, bh, p.p + FPH_P_ACTOR, FPH_ACT, out, wave, col, hh);

@@ -1,7 +1,9 @@
-// fl_policy_head.hip -- entry points of include/flatland_policy.h: the checks (all before any HIP call) and the launches of the
-// kernels in fl_policy_head.h.
+// fl_policy_head.hip -- entry points of include/flatland_policy.h and include/flatland_policy_train.h: the checks (all before any
+// HIP call) and the launches of the kernels in fl_policy_head.h and fl_policy_head_bwd.h.
 #include "../../include/flatland_policy.h"
+#include "../../include/flatland_policy_train.h"
 #include "fl_policy_head.h"
+#include "fl_policy_head_bwd.h"
 
 size_t fl_policy_head_workspace_bytes(int n_envs, int n_agents) {
     if (n_envs <= 0 || n_agents <= 0) return 0;
@@ -9,24 +11,62 @@ size_t fl_policy_head_workspace_bytes(int n_envs, int n_agents) {
     return (R * FPH_ROW_FLOATS * sizeof(float) + 15) / 16 * 16;
 }
 
+// sizes, NULLs and alignment of what the forward's entry points share; `fn` names the caller in the message
+static int fph_check(const char *fn, int n_envs, int n_agents, const float *const *params, const void *const *ptrs,
+                     const char *const *names, int n) {
+    if (n_envs <= 0 || n_agents < 1 || n_agents > FPH_MAX_A || (long long)n_envs * n_agents > INT32_MAX / (3 * FPH_E)) {
+        fl_set_error("%s: bad sizes (n_envs %d, n_agents %d; 1 <= n_envs, 1 <= n_agents <= %d)", fn, n_envs, n_agents, FPH_MAX_A);
+        return FL_ERR_ARG;
+    }
+    if (!params) { fl_set_error("%s: params is NULL", fn); return FL_ERR_ARG; }
+    for (int i = 0; i < n; i++) {
+        if (!ptrs[i]) { fl_set_error("%s: %s is NULL", fn, names[i]); return FL_ERR_ARG; }
+        if ((uintptr_t)ptrs[i] % 16) { fl_set_error("%s: %s is not 16-byte aligned", fn, names[i]); return FL_ERR_ARG; }
+    }
+    for (int i = 0; i < FPH_NPARAMS; i++) {
+        if (!params[i]) { fl_set_error("%s: parameter %d is NULL", fn, i); return FL_ERR_ARG; }
+        if ((uintptr_t)params[i] % 16) { fl_set_error("%s: parameter %d is not 16-byte aligned", fn, i); return FL_ERR_ARG; }
+    }
+    return FL_OK;
+}
+
+// the forward's launches; block i's attention output goes to ao[i], its q k v are read from qkv[i]
+static int fph_launch(const char *fn, FphArgs a, float *const (&ao)[3], float *const (&qkv)[3], hipStream_t s) {
+    // more than 64 KiB of dynamic LDS needs the attribute
+    if (hipFuncSetAttribute((const void *)k_ph_embed, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FPH_LDS_EMBED) != hipSuccess ||
+        hipFuncSetAttribute((const void *)k_ph_block<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FPH_LDS_BLOCK) != hipSuccess ||
+        hipFuncSetAttribute((const void *)k_ph_block<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FPH_LDS_LAST) != hipSuccess) {
+        fl_set_error("%s: hipFuncSetAttribute failed: %s", fn, hipGetErrorString(hipGetLastError()));
+        return FL_ERR_HIP;
+    }
+    const int tiles = (a.R + FPH_ROWS - 1) / FPH_ROWS;
+    const int qtiles = a.B * ((a.A + FPH_ROWS - 1) / FPH_ROWS);
+    a.qkv = qkv[0];
+    hipLaunchKernelGGL(k_ph_embed, dim3(tiles), dim3(FPH_THREADS), FPH_LDS_EMBED, s, a);
+    const float *xin[3] = {a.emb, a.xa, a.xb};
+    float *xout[3] = {a.xa, a.xb, nullptr};
+    for (int blk = 0; blk < 3; blk++) {
+        a.qkv = qkv[blk]; a.ao = ao[blk];
+        hipLaunchKernelGGL(k_ph_attn, dim3(qtiles), dim3(FPH_THREADS), 0, s, a);
+        if (blk < 2) {
+            a.qkv = qkv[blk + 1];
+            hipLaunchKernelGGL(k_ph_block<false>, dim3(tiles), dim3(FPH_THREADS), FPH_LDS_BLOCK, s, a, blk, xin[blk], xout[blk]);
+        } else {
+            hipLaunchKernelGGL(k_ph_block<true>, dim3(tiles), dim3(FPH_THREADS), FPH_LDS_LAST, s, a, blk, xin[blk], xout[blk]);
+        }
+    }
+    if (a.value) hipLaunchKernelGGL(k_ph_value, dim3(a.B), dim3(64), 0, s, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { fl_set_error("%s: launch failed: %s", fn, hipGetErrorString(e)); return FL_ERR_HIP; }
+    return FL_OK;
+}
+
 int fl_policy_head(int n_envs, int n_agents, const float *attr_dev, const float *tree_dev, const float *const *params,
                    const uint8_t *valid_actions_dev, int select, double u, float *logits_dev, float *value_dev,
                    uint8_t *actions_dev, void *workspace_dev, size_t workspace_bytes, void *hip_stream) {
-    if (n_envs <= 0 || n_agents < 1 || n_agents > FPH_MAX_A || (long long)n_envs * n_agents > INT32_MAX / (3 * FPH_E)) {
-        fl_set_error("fl_policy_head: bad sizes (n_envs %d, n_agents %d; 1 <= n_envs, 1 <= n_agents <= %d)", n_envs, n_agents, FPH_MAX_A);
-        return FL_ERR_ARG;
-    }
-    if (!params) { fl_set_error("fl_policy_head: params is NULL"); return FL_ERR_ARG; }
     const void *f16[] = {attr_dev, tree_dev, logits_dev, workspace_dev};
     const char *f16n[] = {"attr", "tree", "logits", "workspace"};
-    for (int i = 0; i < 4; i++) {
-        if (!f16[i]) { fl_set_error("fl_policy_head: %s is NULL", f16n[i]); return FL_ERR_ARG; }
-        if ((uintptr_t)f16[i] % 16) { fl_set_error("fl_policy_head: %s is not 16-byte aligned", f16n[i]); return FL_ERR_ARG; }
-    }
-    for (int i = 0; i < FPH_NPARAMS; i++) {
-        if (!params[i]) { fl_set_error("fl_policy_head: parameter %d is NULL", i); return FL_ERR_ARG; }
-        if ((uintptr_t)params[i] % 16) { fl_set_error("fl_policy_head: parameter %d is not 16-byte aligned", i); return FL_ERR_ARG; }
-    }
+    if (fph_check("fl_policy_head", n_envs, n_agents, params, f16, f16n, 4) != FL_OK) return FL_ERR_ARG;
     if (value_dev && (uintptr_t)value_dev % 16) { fl_set_error("fl_policy_head: value is not 16-byte aligned"); return FL_ERR_ARG; }
     if (select < 0 || select > 2) { fl_set_error("fl_policy_head: select must be 0 (none), 1 (soft) or 2 (hard), got %d", select); return FL_ERR_ARG; }
     if (select != 0 && (!valid_actions_dev || !actions_dev)) {
@@ -50,27 +90,119 @@ int fl_policy_head(int n_envs, int n_agents, const float *attr_dev, const float 
     float *ws = (float *)workspace_dev;
     a.emb = ws; a.xa = ws + R * FPH_E; a.xb = ws + 2 * R * FPH_E; a.ao = ws + 3 * R * FPH_E;
     a.qkv = ws + 4 * R * FPH_E; a.val = ws + 7 * R * FPH_E;
+    a.y3 = nullptr;
+    float *const ao[3] = {a.ao, a.ao, a.ao}, *const qkv[3] = {a.qkv, a.qkv, a.qkv};
+    return fph_launch("fl_policy_head", a, ao, qkv, (hipStream_t)hip_stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- training
+size_t fl_policy_head_saved_bytes(int n_envs, int n_agents) {
+    if (n_envs <= 0 || n_agents <= 0) return 0;
+    const size_t R = (size_t)n_envs * n_agents;
+    return (R * FPB_SAVED_FLOATS * sizeof(float) + 15) / 16 * 16;
+}
+
+size_t fl_policy_head_backward_rows_bytes(int n_envs, int n_agents) {
+    if (n_envs <= 0 || n_agents <= 0) return 0;
+    return (size_t)n_envs * n_agents * FPB_ROW_FLOATS * sizeof(float);
+}
+
+size_t fl_policy_head_backward_workspace_bytes(int n_envs, int n_agents) {
+    if (n_envs <= 0 || n_agents <= 0) return 0;
+    return (size_t)n_envs * n_agents * FPB_STATS * sizeof(float);
+}
+
+int fl_policy_head_forward_saved(int n_envs, int n_agents, const float *attr_dev, const float *tree_dev, const float *const *params,
+                                 float *logits_dev, float *value_dev, void *saved_dev, size_t saved_bytes, void *hip_stream) {
+    const char *fn = "fl_policy_head_forward_saved";
+    const void *f16[] = {attr_dev, tree_dev, logits_dev, saved_dev};
+    const char *f16n[] = {"attr", "tree", "logits", "saved"};
+    if (fph_check(fn, n_envs, n_agents, params, f16, f16n, 4) != FL_OK) return FL_ERR_ARG;
+    if (value_dev && (uintptr_t)value_dev % 16) { fl_set_error("%s: value is not 16-byte aligned", fn); return FL_ERR_ARG; }
+    const size_t need = fl_policy_head_saved_bytes(n_envs, n_agents);
+    if (saved_bytes < need) {
+        fl_set_error("%s: saved buffer of %zu bytes, %zu needed (fl_policy_head_saved_bytes)", fn, saved_bytes, need);
+        return FL_ERR_ARG;
+    }
+    FphArgs a;
+    a.B = n_envs; a.A = n_agents; a.R = n_envs * n_agents;
+    a.select = 0; a.u = 0.0;
+    a.attr = attr_dev; a.tree = tree_dev;
+    for (int i = 0; i < FPH_NPARAMS; i++) a.p[i] = params[i];
+    a.valid = nullptr; a.logits = logits_dev; a.value = value_dev; a.actions = nullptr;
+    const size_t R = (size_t)a.R;
+    float *sv = (float *)saved_dev;
+    a.emb = sv; a.xa = sv + R * FPH_E; a.xb = sv + 2 * R * FPH_E; a.y3 = sv + 3 * R * FPH_E;
+    float *const ao[3] = {sv + 4 * R * FPH_E, sv + 5 * R * FPH_E, sv + 6 * R * FPH_E};
+    float *const qkv[3] = {sv + 7 * R * FPH_E, sv + 10 * R * FPH_E, sv + 13 * R * FPH_E};
+    a.ao = ao[0]; a.qkv = qkv[0]; a.val = sv + 16 * R * FPH_E;
+    return fph_launch(fn, a, ao, qkv, (hipStream_t)hip_stream);
+}
+
+int fl_policy_head_backward(int n_envs, int n_agents, const float *attr_dev, const float *tree_dev, const float *const *params,
+                            const void *saved_dev, const float *grad_logits_dev, const float *grad_value_dev, float *grad_tree_dev,
+                            void *rows_dev, size_t rows_bytes, void *workspace_dev, size_t workspace_bytes, void *hip_stream) {
+    const char *fn = "fl_policy_head_backward";
+    const void *f16[] = {attr_dev, tree_dev, saved_dev, grad_tree_dev, rows_dev, workspace_dev};
+    const char *f16n[] = {"attr", "tree", "saved", "grad_tree", "rows", "workspace"};
+    if (fph_check(fn, n_envs, n_agents, params, f16, f16n, 6) != FL_OK) return FL_ERR_ARG;
+    if (!grad_logits_dev && !grad_value_dev) { fl_set_error("%s: grad_logits and grad_value are both NULL", fn); return FL_ERR_ARG; }
+    if ((uintptr_t)grad_logits_dev % 16) { fl_set_error("%s: grad_logits is not 16-byte aligned", fn); return FL_ERR_ARG; }
+    if ((uintptr_t)grad_value_dev % 16) { fl_set_error("%s: grad_value is not 16-byte aligned", fn); return FL_ERR_ARG; }
+    const size_t need_r = fl_policy_head_backward_rows_bytes(n_envs, n_agents), need_w = fl_policy_head_backward_workspace_bytes(n_envs, n_agents);
+    if (rows_bytes < need_r) {
+        fl_set_error("%s: rows of %zu bytes, %zu needed (fl_policy_head_backward_rows_bytes)", fn, rows_bytes, need_r);
+        return FL_ERR_ARG;
+    }
+    if (workspace_bytes < need_w) {
+        fl_set_error("%s: workspace of %zu bytes, %zu needed (fl_policy_head_backward_workspace_bytes)", fn, workspace_bytes, need_w);
+        return FL_ERR_ARG;
+    }
+
+    FpbArgs a;
+    a.B = n_envs; a.A = n_agents; a.R = n_envs * n_agents;
+    a.attr = attr_dev;
+    for (int i = 0; i < FPH_NPARAMS; i++) a.p[i] = params[i];
+    const size_t R = (size_t)a.R;
+    const float *sv = (const float *)saved_dev;
+    for (int i = 0; i < 4; i++) a.y[i] = sv + i * R * FPH_E;
+    for (int i = 0; i < 3; i++) { a.ao[i] = sv + (4 + i) * R * FPH_E; a.qkv[i] = sv + (7 + 3 * i) * R * FPH_E; }
+    a.gl = grad_logits_dev; a.gv = grad_value_dev; a.gtree = grad_tree_dev;
+    float *rw = (float *)rows_dev;
+    const auto take = [&](size_t n) { float *q = rw; rw += R * n; return q; };     // the order of include/flatland_policy_train.h
+    for (int i = 0; i < 3; i++) a.a_dz[i] = take(FPH_E);
+    a.a_dz[3] = take(FPH_H);
+    for (int i = 0; i < 3; i++) a.a_h[i] = take(FPH_E);
+    for (int i = 0; i < 3; i++) {
+        a.dqkv[i] = take(3 * FPH_E); a.dout[i] = take(FPH_E); a.dz[i] = take(FPH_E);
+        a.o[i] = take(FPH_E); a.dc[i] = take(FPH_E); a.dy[i] = take(FPH_E);
+    }
+    a.dy[3] = take(FPH_E);
+    for (int hd = 0; hd < 2; hd++) {
+        a.h_dz[hd][0] = take(FPH_E); a.h_dz[hd][1] = take(FPH_H); a.h_dz[hd][2] = take(hd ? 4 : 8);
+        a.h_h[hd][0] = take(FPH_E); a.h_h[hd][1] = take(FPH_H);
+    }
+    a.stats = (float *)workspace_dev;
 
     hipStream_t s = (hipStream_t)hip_stream;
-    // more than 64 KiB of dynamic LDS needs the attribute
-    if (hipFuncSetAttribute((const void *)k_ph_embed, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FPH_LDS_EMBED) != hipSuccess ||
-        hipFuncSetAttribute((const void *)k_ph_block<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FPH_LDS_BLOCK) != hipSuccess ||
-        hipFuncSetAttribute((const void *)k_ph_block<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FPH_LDS_LAST) != hipSuccess) {
-        fl_set_error("fl_policy_head: hipFuncSetAttribute failed: %s", hipGetErrorString(hipGetLastError()));
+    if (hipFuncSetAttribute((const void *)k_pb_heads, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FPB_LDS_HEADS) != hipSuccess ||
+        hipFuncSetAttribute((const void *)k_pb_block, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FPB_LDS_BLOCK) != hipSuccess ||
+        hipFuncSetAttribute((const void *)k_pb_inproj, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FPB_LDS_INPROJ) != hipSuccess ||
+        hipFuncSetAttribute((const void *)k_pb_attr, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FPB_LDS_ATTR) != hipSuccess) {
+        fl_set_error("%s: hipFuncSetAttribute failed: %s", fn, hipGetErrorString(hipGetLastError()));
         return FL_ERR_HIP;
     }
     const int tiles = (a.R + FPH_ROWS - 1) / FPH_ROWS;
     const int qtiles = n_envs * ((n_agents + FPH_ROWS - 1) / FPH_ROWS);
-    hipLaunchKernelGGL(k_ph_embed, dim3(tiles), dim3(FPH_THREADS), FPH_LDS_EMBED, s, a);
-    const float *xin[3] = {a.emb, a.xa, a.xb};
-    float *xout[3] = {a.xa, a.xb, nullptr};
-    for (int blk = 0; blk < 3; blk++) {
-        hipLaunchKernelGGL(k_ph_attn, dim3(qtiles), dim3(FPH_THREADS), 0, s, a);
-        if (blk < 2) hipLaunchKernelGGL(k_ph_block<false>, dim3(tiles), dim3(FPH_THREADS), FPH_LDS_BLOCK, s, a, blk, xin[blk], xout[blk]);
-        else hipLaunchKernelGGL(k_ph_block<true>, dim3(tiles), dim3(FPH_THREADS), FPH_LDS_LAST, s, a, blk, xin[blk], xout[blk]);
+    hipLaunchKernelGGL(k_pb_heads, dim3(tiles), dim3(FPH_THREADS), FPB_LDS_HEADS, s, a);
+    for (int blk = 2; blk >= 0; blk--) {
+        hipLaunchKernelGGL(k_pb_block, dim3(tiles), dim3(FPH_THREADS), FPB_LDS_BLOCK, s, a, blk);
+        hipLaunchKernelGGL(k_pb_attn_q, dim3(qtiles), dim3(FPH_THREADS), 0, s, a, blk);
+        hipLaunchKernelGGL(k_pb_attn_kv, dim3(qtiles), dim3(FPH_THREADS), 0, s, a, blk);
+        hipLaunchKernelGGL(k_pb_inproj, dim3(tiles), dim3(FPH_THREADS), FPB_LDS_INPROJ, s, a, blk);
     }
-    if (value_dev) hipLaunchKernelGGL(k_ph_value, dim3(n_envs), dim3(64), 0, s, a);
+    hipLaunchKernelGGL(k_pb_attr, dim3(tiles), dim3(FPH_THREADS), FPB_LDS_ATTR, s, a);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { fl_set_error("fl_policy_head: launch failed: %s", hipGetErrorString(e)); return FL_ERR_HIP; }
+    if (e != hipSuccess) { fl_set_error("%s: launch failed: %s", fn, hipGetErrorString(e)); return FL_ERR_HIP; }
     return FL_OK;
 }

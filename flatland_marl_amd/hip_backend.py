@@ -85,6 +85,14 @@ _TRAIN_ABI = {
     "fl_tree_lstm_backward_workspace_bytes": ([i32, i32], C.c_size_t),
     "fl_tree_lstm_backward": ([i32, i32] + [vp] * 15 + [i32] + [vp] * 7 + [C.c_size_t, vp], i32),
 }
+# name -> (argtypes, restype) of every function include/flatland_policy_train.h declares, in the header's order
+_POLICY_TRAIN_ABI = {
+    "fl_policy_head_saved_bytes": ([i32, i32], C.c_size_t),
+    "fl_policy_head_forward_saved": ([i32, i32, vp, vp, C.POINTER(vp), vp, vp, vp, C.c_size_t, vp], i32),
+    "fl_policy_head_backward_rows_bytes": ([i32, i32], C.c_size_t),
+    "fl_policy_head_backward_workspace_bytes": ([i32, i32], C.c_size_t),
+    "fl_policy_head_backward": ([i32, i32, vp, vp, C.POINTER(vp), vp, vp, vp, vp, vp, C.c_size_t, vp, C.c_size_t, vp], i32),
+}
 # name -> (argtypes, restype) of every function include/flatland_predict.h declares, in the header's order
 _PREDICT_ABI = {
     "fl_predict": ([vp, i32, i32, i32, i32, vp, vp, vp], i32),
@@ -97,6 +105,7 @@ _WRAPPERS_ABI = {
 SYMBOLS = tuple(_ABI)      # every symbol include/flatland_hip.h declares
 POLICY_SYMBOLS = tuple(_POLICY_ABI)      # ... and include/flatland_policy.h
 TRAIN_SYMBOLS = tuple(_TRAIN_ABI)      # ... and include/flatland_train.h
+POLICY_TRAIN_SYMBOLS = tuple(_POLICY_TRAIN_ABI)      # ... and include/flatland_policy_train.h
 PREDICT_SYMBOLS = tuple(_PREDICT_ABI)      # ... and include/flatland_predict.h
 WRAPPERS_SYMBOLS = tuple(_WRAPPERS_ABI)      # ... and include/flatland_wrappers.h
 POLICY_HEAD_NPARAMS = 38
@@ -135,7 +144,8 @@ def lib():
         # otherwise torch.cuda finds no device once the library below has pulled in the system runtime
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
-        for name, (args, res) in {**_ABI, **_DEBUG_ABI, **_POLICY_ABI, **_TRAIN_ABI, **_PREDICT_ABI, **_WRAPPERS_ABI}.items():
+        for name, (args, res) in {**_ABI, **_DEBUG_ABI, **_POLICY_ABI, **_TRAIN_ABI, **_POLICY_TRAIN_ABI, **_PREDICT_ABI,
+                                  **_WRAPPERS_ABI}.items():
             fn = getattr(L, name, None)        # (a library from bench.py --lib or a tool's LIB_PATH may predate the newer ones)
             if fn is not None:
                 fn.argtypes, fn.restype = args, res
@@ -280,6 +290,91 @@ def policy_head(agents_attr, tree_embedding, params, logits, value=None, valid_a
                 POLICY_U_REFERENCE if u is None else float(u), logits.data_ptr(), opt(value), opt(actions), ws.data_ptr(),
                 ws.numel(), C.c_void_p(s)))
     return logits
+
+
+# (name, floats a row) of the arrays of saved_dev and rows_dev, in their order (include/flatland_policy_train.h): array k of R rows
+# starts at R * (the floats a row of the arrays before it)
+POLICY_SAVED_LAYOUT = ((("emb", 256), ("y1", 256), ("y2", 256), ("y3", 256)) + tuple(("c%d" % i, 256) for i in range(3))
+                       + tuple(("qkv%d" % i, 768) for i in range(3)) + (("val", 1),))
+POLICY_ROWS_LAYOUT = ((("attr.dz0", 256), ("attr.dz2", 256), ("attr.dz4", 256), ("attr.dz6", 128), ("attr.h1", 256), ("attr.h2", 256),
+                       ("attr.h3", 256))
+                      + tuple(("%s%d" % (n, i), k) for i in range(3)
+                              for n, k in (("dqkv", 768), ("do", 256), ("dz", 256), ("o", 256), ("dc", 256), ("dy", 256)))
+                      + (("dy3", 256),)
+                      + tuple(("%s.%s" % (h, n), k) for h, last in (("actor", 8), ("critic", 4))
+                              for n, k in (("dz0", 256), ("dz2", 128), ("dz4", last), ("u1", 256), ("u2", 128))))
+POLICY_SAVED_FLOATS = sum(k for _, k in POLICY_SAVED_LAYOUT)      # 4 097
+POLICY_ROW_FLOATS = sum(k for _, k in POLICY_ROWS_LAYOUT)      # 9 612
+
+
+def policy_views(buf, layout, R):
+    """name -> the [R, n] view ([R] for n = 1) of every array of a float32 saved / rows buffer of R rows"""
+    out, off = {}, 0
+    for name, k in layout:
+        v = buf[off * R:(off + k) * R]
+        out[name] = v if k == 1 else v.view(R, k)
+        off += k
+    return out
+
+
+def policy_saved_floats(B, A):
+    """the float32 elements of a saved buffer of B envs x A agents (fl_policy_head_saved_bytes: whole 16 bytes)"""
+    return _sym("fl_policy_head_saved_bytes")(B, A) // 4
+
+
+def _policy_train_check(what, agents_attr, tree_embedding, params):
+    import torch
+    if len(params) != POLICY_HEAD_NPARAMS:
+        raise ValueError("%s: %d parameters, %d expected" % (what, len(params), POLICY_HEAD_NPARAMS))
+    dev = agents_attr.device
+    B, A = agents_attr.shape[:2]
+    for name, o, n in [("agents_attr", agents_attr, B * A * 83), ("tree_embedding", tree_embedding, B * A * 128)] + \
+            [("parameter %d" % i, w, 1) for i, w in enumerate(params)]:
+        if o.dtype != torch.float32 or o.device != dev or not o.is_contiguous() or o.numel() < n:
+            raise ValueError("%s: %s must be a contiguous float32 tensor of at least %d elements on %s" % (what, name, n, dev))
+    return B, A, dev
+
+
+def policy_head_forward_saved(agents_attr, tree_embedding, params, logits, value, saved):
+    """fl_policy_head without the action choice, keeping what the backward reads (fl_policy_head_forward_saved,
+    include/flatland_policy_train.h) on torch's current stream of the inputs' device.  Inputs and params as for policy_head; logits
+    f32 [B, A, 5]; value f32 [B] or None; saved: a float32 tensor of at least B * A * POLICY_SAVED_FLOATS elements."""
+    import torch
+    B, A, dev = _policy_train_check("policy_head_forward_saved", agents_attr, tree_embedding, params)
+    for name, o, n in (("logits", logits, B * A * 5), ("value", value, B), ("saved", saved, policy_saved_floats(B, A))):
+        if o is not None and (o.dtype != torch.float32 or o.device != dev or not o.is_contiguous() or o.numel() < n):
+            raise ValueError("policy_head_forward_saved: %s must be a contiguous float32 tensor of at least %d elements on %s" % (name, n, dev))
+    fn = _sym("fl_policy_head_forward_saved")
+    ptrs = (vp * POLICY_HEAD_NPARAMS)(*[w.data_ptr() for w in params])
+    with torch.cuda.device(dev):
+        s = torch.cuda.current_stream(dev).cuda_stream
+        _chk(fn(B, A, agents_attr.data_ptr(), tree_embedding.data_ptr(), ptrs, logits.data_ptr(),
+                None if value is None else value.data_ptr(), saved.data_ptr(), saved.numel() * 4, C.c_void_p(s)))
+    return logits
+
+
+def policy_head_backward(agents_attr, tree_embedding, params, saved, grad_logits, grad_value, grad_tree, rows):
+    """The gradient of the policy head up to the sums over the rows (fl_policy_head_backward, include/flatland_policy_train.h) on
+    torch's current stream of the inputs' device, with a workspace from torch's allocator.  saved: what policy_head_forward_saved
+    left on the same inputs; grad_logits f32 [B, A, 5] or None; grad_value f32 [B] or None; grad_tree f32 [B, A, 128] (out); rows: a
+    float32 tensor of at least B * A * POLICY_ROW_FLOATS elements (out).  No parameter gradient is written:
+    policy.policy_head_param_grads forms them from the rows."""
+    import torch
+    B, A, dev = _policy_train_check("policy_head_backward", agents_attr, tree_embedding, params)
+    for name, o, n in (("saved", saved, policy_saved_floats(B, A)), ("grad_logits", grad_logits, B * A * 5),
+                       ("grad_value", grad_value, B), ("grad_tree", grad_tree, B * A * 128), ("rows", rows, B * A * POLICY_ROW_FLOATS)):
+        if o is not None and (o.dtype != torch.float32 or o.device != dev or not o.is_contiguous() or o.numel() < n):
+            raise ValueError("policy_head_backward: %s must be a contiguous float32 tensor of at least %d elements on %s" % (name, n, dev))
+    fn = _sym("fl_policy_head_backward")
+    ptrs = (vp * POLICY_HEAD_NPARAMS)(*[w.data_ptr() for w in params])
+    nbytes = _sym("fl_policy_head_backward_workspace_bytes")(B, A)
+    opt = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    with torch.cuda.device(dev):
+        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+        s = torch.cuda.current_stream(dev).cuda_stream
+        _chk(fn(B, A, agents_attr.data_ptr(), tree_embedding.data_ptr(), ptrs, saved.data_ptr(), opt(grad_logits), opt(grad_value),
+                grad_tree.data_ptr(), rows.data_ptr(), rows.numel() * 4, ws.data_ptr(), ws.numel(), C.c_void_p(s)))
+    return grad_tree
 
 
 class BatchedRailEnv:

@@ -11,7 +11,15 @@ TreeLSTM(trainable=True) (or m.trainable = True) makes forward / roots different
 forward is the same kernel (every node, c kept), the backward is fl_tree_lstm_backward (include/flatland_train.h) for everything
 that follows the tree order, then the parameter gradients as float32 matrix products over all nodes, in chunks of
 BACKWARD_CHUNK_TREES trees added in order.  Two backward passes on the same inputs give the same bits.  The forest gets no
-gradient.  The head (fl_policy_head) is still inference only; Network.forward_torch is its path with autograd.
+gradient.
+
+The head is inference only by default too: its backward raises.  Network(trainable=True) (or net.trainable = True,
+Network.from_module(m, trainable=True)) makes head / forward differentiable with respect to the 38 head parameters and the tree
+embedding: the forward is fl_policy_head_forward_saved (include/flatland_policy_train.h: the inference kernels, every block's q k v
+and attention output kept; the same bits), the backward fl_policy_head_backward for everything per row and per env, then the 38
+parameter gradients as the same float32 block products, in chunks of whole envs of at most HEAD_BACKWARD_CHUNK_ROWS rows added in
+order.  agents_attr gets no gradient.  With both switches set one loss.backward() through Network.forward trains all 46 parameters
+without a torch eager op on the forward path; Network.forward_torch / head_torch stay the head through torch's eager ops.
 
 Swap it into the reference's Network:  net.tree_lstm = TreeLSTM.from_module(net.tree_lstm)
 or take the whole network:              net = Network.from_module(net)
@@ -289,12 +297,116 @@ class _Head(torch.autograd.Function):
         raise NotImplementedError("Network (fl_policy_head) is inference only: no backward; forward_torch is the path with autograd")
 
 
+# (env, agent) rows a fl_policy_head_backward launch: saved forward + rows are 54.9 KB a row, 1.8 GB a chunk (8 192 rows measured
+# 1.4x the unchunked forward at cfg5: 20 envs of 400 agents are one workgroup a CU and a launch tail per chunk)
+HEAD_BACKWARD_CHUNK_ROWS = 32768
+
+
+def head_chunks(B, A):
+    """[(first env, env behind the last)]: the envs in order, in chunks of whole envs (the attention never crosses an env) of at most
+    HEAD_BACKWARD_CHUNK_ROWS rows -- of one env where a single env has more"""
+    per = max(1, HEAD_BACKWARD_CHUNK_ROWS // A)
+    return [(e0, min(B, e0 + per)) for e0 in range(0, B, per)]
+
+
+def policy_head_param_grads(attr, sv, rw, actor=True, critic=True):
+    """the 38 parameter gradients, in HEAD_PARAM_ORDER, from fl_policy_head_backward's rows (include/flatland_policy_train.h): attr
+    f32 [R, 83], sv / rw = hip_backend.policy_views of the saved forward / of the rows.  dW = sum over the rows of dZ^T X, db = sum of
+    dZ (_tn, _colsum).  actor / critic False: that head's six are None (its rows were not written)."""
+    def lin(dz, *xs):
+        return [torch.cat([_tn(dz, x) for x in xs], dim=1) if len(xs) > 1 else _tn(dz, xs[0]), _colsum(dz)]
+    out = lin(rw["attr.dz0"], attr) + lin(rw["attr.dz2"], rw["attr.h1"]) + lin(rw["attr.dz4"], rw["attr.h2"]) \
+        + lin(rw["attr.dz6"], rw["attr.h3"])
+    for i, y in enumerate(("emb", "y1", "y2")):
+        out += lin(rw["dqkv%d" % i], sv[y]) + lin(rw["do%d" % i], sv["c%d" % i]) + lin(rw["dz%d" % i], sv[y], rw["o%d" % i])
+    for name, n, on in (("actor", ACTIONS, actor), ("critic", 1, critic)):
+        if on:
+            out += lin(rw[name + ".dz0"], sv["emb"], sv["y3"]) + lin(rw[name + ".dz2"], rw[name + ".u1"]) \
+                + lin(rw[name + ".dz4"][:, :n].contiguous(), rw[name + ".u2"])
+        else:
+            out += [None] * 6
+    return out
+
+
+def _aligned(t):
+    """t, or a copy of it where a slice of whole envs does not start on 16 bytes"""
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+class _HeadTrain(torch.autograd.Function):
+    """fl_policy_head_forward_saved per chunk of envs (with a mode: fl_policy_head's action choice behind it), and behind it
+    fl_policy_head_backward + the parameter products, the chunks' gradients added in order"""
+
+    @staticmethod
+    def forward(ctx, agents_attr, tree_embedding, valid_actions, mode, u, with_value, *weights):
+        B, A = agents_attr.shape[:2]
+        dev = agents_attr.device
+        chunks = head_chunks(B, A)
+        logits, values, saved = [], [], []
+        for e0, e1 in chunks:
+            lg = torch.empty((e1 - e0, A, ACTIONS), dtype=torch.float32, device=dev)
+            va = torch.empty((e1 - e0,), dtype=torch.float32, device=dev) if with_value else None
+            sv = torch.empty(hip_backend.policy_saved_floats(e1 - e0, A), dtype=torch.float32, device=dev)
+            hip_backend.policy_head_forward_saved(_aligned(agents_attr[e0:e1]), tree_embedding[e0:e1], weights, lg, va, sv)
+            logits.append(lg), values.append(va), saved.append(sv)
+        logits = logits[0] if len(chunks) == 1 else torch.cat(logits)
+        value = (values[0] if len(chunks) == 1 else torch.cat(values)) if with_value else None
+        actions = None
+        if mode is not None:                         # the choice is part of fl_policy_head's last kernel: that call once more
+            actions = torch.empty((B, A), dtype=torch.uint8, device=dev)
+            hip_backend.policy_head(agents_attr, tree_embedding, weights, torch.empty_like(logits), None, valid_actions, actions, mode, u)
+            ctx.mark_non_differentiable(actions)
+        ctx.chunks, ctx.n_saved, ctx.with_value = chunks, len(saved), with_value
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(agents_attr, tree_embedding, *saved, *weights)
+        return (logits,) + ((value,) if with_value else ()) + ((actions,) if actions is not None else ())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_logits, *more):
+        agents_attr, tree_embedding = ctx.saved_tensors[:2]
+        saved = ctx.saved_tensors[2:2 + ctx.n_saved]
+        weights = ctx.saved_tensors[2 + ctx.n_saved:]
+        B, A = agents_attr.shape[:2]
+        dev = agents_attr.device
+        g_value = more[0] if ctx.with_value else None
+        nothing = (None,) * (6 + len(weights))
+        if g_logits is None and g_value is None:
+            return nothing
+        if g_logits is not None:
+            g_logits = g_logits.to(torch.float32).contiguous().view(B, A, ACTIONS)
+        if g_value is not None:
+            g_value = g_value.to(torch.float32).contiguous().view(B)
+        total, gtree = None, []
+        for (e0, e1), sv in zip(ctx.chunks, saved):
+            R = (e1 - e0) * A
+            attr = _aligned(agents_attr[e0:e1])
+            rows = torch.empty(R * hip_backend.POLICY_ROW_FLOATS, dtype=torch.float32, device=dev)
+            gt = torch.empty((e1 - e0, A, OUT_FEATURES), dtype=torch.float32, device=dev)
+            hip_backend.policy_head_backward(attr, tree_embedding[e0:e1], weights, sv,
+                                             None if g_logits is None else _aligned(g_logits[e0:e1]),
+                                             None if g_value is None else _aligned(g_value[e0:e1]), gt, rows)
+            part = policy_head_param_grads(attr.view(R, AGENT_ATTR), hip_backend.policy_views(sv, hip_backend.POLICY_SAVED_LAYOUT, R),
+                                           hip_backend.policy_views(rows, hip_backend.POLICY_ROWS_LAYOUT, R),
+                                           g_logits is not None, g_value is not None)
+            total = part if total is None else [None if v is None else w + v for w, v in zip(total, part)]
+            gtree.append(gt)
+        gtree = gtree[0] if len(gtree) == 1 else torch.cat(gtree)
+        need = ctx.needs_input_grad
+        return (None, gtree if need[1] else None, None, None, None, None) + tuple(g if k else None for g, k in zip(total, need[6:]))
+
+
 class Network(nn.Module):
     """The reference's Network (solution/nn/net_tree.py:32-103) with its submodule names and shapes, so load_state_dict of a
-    reference checkpoint works unchanged; tree_lstm is this file's TreeLSTM, everything after it runs as fl_policy_head."""
+    reference checkpoint works unchanged; tree_lstm is this file's TreeLSTM, everything after it runs as fl_policy_head.
+    trainable (a plain attribute, settable): False = the head is inference only, backward raises; True = with grad mode on, head
+    and forward are differentiable with respect to the 38 head parameters and the tree embedding (fl_policy_head_forward_saved,
+    fl_policy_head_backward), their values the same bits as the inference path's.  With tree_lstm.trainable set as well one
+    loss.backward() trains all 46 parameters."""
 
-    def __init__(self):
+    def __init__(self, trainable=False):
         super().__init__()
+        self.trainable = bool(trainable)
         self.tree_lstm = TreeLSTM(IN_FEATURES, OUT_FEATURES)
         self.attr_embedding = _mlp((AGENT_ATTR, 2 * HIDDEN, 2 * HIDDEN, 2 * HIDDEN, HIDDEN), True)
         self.transformer = nn.Sequential(*[Transformer(EMBED, HEADS) for _ in range(3)])
@@ -302,10 +414,11 @@ class Network(nn.Module):
         self.critic_net = _mlp((2 * EMBED, 2 * HIDDEN, HIDDEN, 1), False)
 
     @classmethod
-    def from_module(cls, m):
+    def from_module(cls, m, trainable=False):
         """a Network that shares m's parameters (m: the reference's Network or one of these)"""
         obj = cls.__new__(cls)
         nn.Module.__init__(obj)
+        obj.trainable = bool(trainable)
         obj.tree_lstm = TreeLSTM.from_module(m.tree_lstm, trainable=getattr(m.tree_lstm, "trainable", False))
         obj.attr_embedding = m.attr_embedding
         blocks = []
@@ -391,7 +504,12 @@ class Network(nn.Module):
             raise ValueError("Network: u must be in [0, 1), got %r" % (u,))
         self._check_head_inputs(agents_attr, tree_embedding, valid_actions if mode is not None else None)
         ws = self._head_weights(agents_attr.device)
-        out = list(_Head.apply(agents_attr, tree_embedding, valid_actions if mode is not None else None, mode, u, bool(value), *ws))
+        train = self.trainable and torch.is_grad_enabled()
+        if train and agents_attr.requires_grad:
+            raise ValueError("Network: agents_attr gets no gradient (fl_policy_head_backward differentiates with respect to the "
+                             "parameters and the tree embedding only): detach it")
+        out = list((_HeadTrain if train else _Head).apply(agents_attr, tree_embedding, valid_actions if mode is not None else None,
+                                                          mode, u, bool(value), *ws))
         logits = out.pop(0)
         val = out.pop(0) if value else None
         return ([logits], val) + ((out.pop(0),) if mode is not None else ())
@@ -399,8 +517,14 @@ class Network(nn.Module):
     def forward(self, agents_attr, forest, adjacency, node_order, edge_order):
         """([logits [B, A, 5]], value [B]) as the reference's forward returns them.  The inputs are the tensors of
         BatchedRailEnv.obs_policy(): the adjacency is ALREADY MODIFIED (global node ids, negatives -2) -- the reference's forward
-        modifies it itself (net_tree.py:75, 105-116), this one does not."""
-        tree = self.tree_lstm.roots(forest, adjacency, node_order, edge_order)
+        modifies it itself (net_tree.py:75, 105-116), this one does not.  With trainable set the head's gradient on the tree
+        embedding is the upstream of TreeLSTM.roots: with tree_lstm.trainable as well all 46 parameters get gradients, without it
+        the encoder's output enters as a constant."""
+        if self.trainable and not self.tree_lstm.trainable:
+            with torch.no_grad():
+                tree = self.tree_lstm.roots(forest, adjacency, node_order, edge_order)
+        else:
+            tree = self.tree_lstm.roots(forest, adjacency, node_order, edge_order)
         return self.head(agents_attr, tree)
 
     def act(self, agents_attr, forest, adjacency, node_order, edge_order, valid_actions, mode="soft", u=None):

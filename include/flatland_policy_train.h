@@ -1,0 +1,92 @@
+/* flatland_policy_train.h -- training the policy network after its tree encoder on the GPU: the gradient of fl_policy_head.
+ * Exported by libflatland_hip.so next to include/flatland_policy.h (whose sizes, parameter list and layouts these use) and
+ * include/flatland_hip.h (error codes, fl_last_error).
+ *
+ *   fl_policy_head_forward_saved   fl_policy_head without the action choice, keeping what the backward reads
+ *   fl_policy_head_backward        what autograd computes through Network.forward after tree_lstm (solution/nn/net_tree.py:82-103),
+ *                                  up to the parameter gradients' last step: the sums over the rows
+ *
+ * Stateless: device pointers, everything enqueued on hip_stream (the forward's 8 launches, 7 with value_dev NULL; the backward's
+ * 14), no host synchronisation, no allocation.  Float32 end to end.  attr_dev, tree_dev, params: as for fl_policy_head.
+ *
+ * ---- the forward, per row r = (env e, agent a), g = the exact (erf) GELU
+ *   h1 = g(W0 x + b0)  h2 = g(W2 h1 + b2)  h3 = g(W4 h2 + b4)  a4 = g(W6 h3 + b6)      (attr_embedding)
+ *   emb = [a4 | tree]   y_0 = emb
+ *   block i = 0, 1, 2:  qkv_i = Win_i y_i + bin_i;  per head P = softmax(q k^T / 8) over the env's A agents;  c_i = concat(P v);
+ *                       o_i = Wo_i c_i + bo_i;  z_i = Wm_i [y_i | o_i] + bm_i;  y_{i+1} = g(z_i)
+ *   both = [emb | y_3];  actor_net and critic_net: u1 = g(V0 both + c0), u2 = g(V2 u1 + c2), out = V4 u2 + c4
+ *   logits = actor's out;  value_e = mean over a of critic's out
+ *
+ * fl_policy_head_forward_saved launches fl_policy_head's kernels with other pointers: logits_dev and value_dev hold the same bits
+ * as fl_policy_head gives on the same inputs (select = 0).  saved_dev: at least fl_policy_head_saved_bytes(n_envs, n_agents)
+ * bytes, 16-byte aligned, R = n_envs * n_agents rows, 4 097 floats (16 388 B) a row, one array after the other:
+ *     emb f32[R][256]   y_1 f32[R][256]   y_2 f32[R][256]   y_3 f32[R][256]
+ *     c_0, c_1, c_2 f32[R][256] each      qkv_0, qkv_1, qkv_2 f32[R][768] each      critic's out f32[R]
+ * (every float of it is written, the critic's out only with value_dev given).
+ *
+ * ---- the backward.  Given Gl = dL/dlogits (grad_logits_dev f32[B][A][5] or NULL) and Gv = dL/dvalue (grad_value_dev f32[B] or
+ * NULL; not both NULL), g'(z) = (1 + erf(z / sqrt 2)) / 2 + z exp(-z^2 / 2) / sqrt(2 pi):
+ *   last layers     dout = Gl (actor), Gv[e] / A (critic)
+ *   a linear layer  Z = W X + b stored [out][in]:  dX = dZ W, the product over the OUT dimension
+ *   a GELU          dZ = dY g'(Z); Z is computed again from the layer's input, in the forward's order of operations (bias last)
+ *   d both          = dz0(actor) V0(actor), then + dz0(critic) V0(critic);   d emb = d both[:256], dy_3 = d both[256:]
+ *   block i = 2, 1, 0:
+ *     dz_i = dy_{i+1} g'(z_i);   [dy_i | do_i] = dz_i Wm_i;   dc_i = do_i Wo_i
+ *     per (env, head), P computed again from q, k (maximum, exponent, quotient as in the forward):
+ *       dP = dC V^T   D = rowsum(P o dP)   dS = P o (dP - D)   dq = dS K / 8   dk = dS^T Q / 8   dv = P^T dC
+ *       (D equals rowsum(dC o C); it is summed from the P and dP that dS is made of, so that sum_k dS = 0 holds to rounding:
+ *       dq cancels on that where P is flat)
+ *     dy_i += dqkv_i Win_i
+ *   y_0 = emb takes three shares, added in this order: the heads' d emb, att_mlp's dy_0, in_proj's
+ *   grad_tree = d emb[128:] (grad_tree_dev f32[B][A][128]); d emb[:128] goes on through attr_embedding; attr gets no gradient
+ *
+ * rows_dev: at least fl_policy_head_backward_rows_bytes(n_envs, n_agents) bytes, 16-byte aligned, 9 612 floats (38 448 B) a
+ * row, one array f32[R][n] after the other, in this order (n in brackets):
+ *     attr_embedding   dZ of layer 0 [256], 2 [256], 4 [256], 6 [128];  h1 [256], h2 [256], h3 [256]
+ *     block i = 0, 1, 2, one after the other:
+ *                      dqkv_i [768] (dq | dk | dv),  do_i [256],  dz_i [256],  o_i [256],  dc_i [256],  dy_i [256]
+ *     dy_3 [256]
+ *     actor_net        dZ of layer 0 [256], 2 [128], 4 [8: Gl, three zeros];  u1 [256], u2 [128]
+ *     critic_net       dZ of layer 0 [256], 2 [128], 4 [4: Gv[e] / A, three zeros];  u1 [256], u2 [128]
+ * With Gl NULL the actor's five arrays are not written, with Gv NULL the critic's; everything else always is.
+ * The 38 parameter gradients are sums over the rows, dW = sum dZ^T X and db = sum dZ, and are left to the caller:
+ *     attr_embedding.0: X = attr   .2: h1   .4: h2   .6: h3
+ *     transformer.i  in_proj: dZ = dqkv_i, X = y_i (saved)   out_proj: dZ = do_i, X = c_i (saved)   att_mlp.0: dZ = dz_i, X = [y_i | o_i]
+ *     actor_net / critic_net  .0: X = [emb | y_3] (saved)   .2: u1   .4: dZ's first 5 / 1 columns, X = u2
+ *
+ * workspace_dev: at least fl_policy_head_backward_workspace_bytes(n_envs, n_agents) bytes (48 B a row: maximum, sum and D of the
+ * row's query in each head), 16-byte aligned.
+ * With the saved forward that is 54 884 B a row: run big batches in chunks of whole envs (the attention never crosses an env).
+ *
+ * Deterministic: no float atomics, every address has one writer per launch; dk and dv come from a workgroup that owns the key
+ * tile and walks the queries in order.  Two calls on the same inputs give the same bits in grad_tree and in every row.
+ *
+ * The three byte functions return 0 for n_envs <= 0 or n_agents <= 0.
+ * FL_ERR_ARG before any HIP call: n_envs <= 0, n_agents outside [1, 1024], a NULL attr / tree / params / parameter / logits /
+ * saved / grad_tree / rows / workspace, grad_logits and grad_value both NULL, a pointer not 16-byte aligned, a short saved /
+ * rows / workspace buffer.
+ */
+#ifndef FLATLAND_POLICY_TRAIN_H
+#define FLATLAND_POLICY_TRAIN_H
+#include "flatland_policy.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define FL_POLICY_HEAD_SAVED_FLOATS 4097 /* a row of saved_dev */
+#define FL_POLICY_HEAD_ROW_FLOATS 9612   /* a row of rows_dev */
+
+size_t fl_policy_head_saved_bytes(int n_envs, int n_agents);
+int fl_policy_head_forward_saved(int n_envs, int n_agents, const float *attr_dev, const float *tree_dev, const float *const *params,
+                                 float *logits_dev, float *value_dev, void *saved_dev, size_t saved_bytes, void *hip_stream);
+size_t fl_policy_head_backward_rows_bytes(int n_envs, int n_agents);
+size_t fl_policy_head_backward_workspace_bytes(int n_envs, int n_agents);
+int fl_policy_head_backward(int n_envs, int n_agents, const float *attr_dev, const float *tree_dev, const float *const *params,
+                            const void *saved_dev, const float *grad_logits_dev, const float *grad_value_dev, float *grad_tree_dev,
+                            void *rows_dev, size_t rows_bytes, void *workspace_dev, size_t workspace_bytes, void *hip_stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif
