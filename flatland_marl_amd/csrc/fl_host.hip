@@ -14,19 +14,11 @@
 #include "fl_global.h"
 #include "fl_predict.h"
 #include "fl_wrappers.h"
-#include "fl_tree_lstm.h"
-#include "../../include/flatland_train.h"
 #include "../../include/flatland_predict.h"
 #include "../../include/flatland_wrappers.h"
-#include "fl_tree_lstm_bwd.h"
 
 static thread_local char g_err[512] = "";
-static void set_err(const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-}
+#define set_err fl_set_error        // this file's older name for it
 void fl_set_error(const char *fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
@@ -40,15 +32,6 @@ int fl_device_count(void) {
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
     return n;
 }
-
-#define HIPCHK(call)                                                                   \
-    do {                                                                               \
-        hipError_t e_ = (call);                                                        \
-        if (e_ != hipSuccess) {                                                        \
-            set_err("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-            return FL_ERR_HIP;                                                         \
-        }                                                                              \
-    } while (0)
 
 struct fl_batch {
     int B, A, H, W, device;
@@ -758,131 +741,6 @@ int fl_policy_pack(int B, int A, int E, const int32_t *adjacency_dev, const int3
         !node_order_out_dev || !edge_order_out_dev) { set_err("fl_policy_pack: bad argument"); return FL_ERR_ARG; }
     fl_launch_policy_pack(B, A, E, adjacency_dev, node_order_dev, edge_order_dev, (long long *)adjacency_out_dev,
                           (long long *)node_order_out_dev, (long long *)edge_order_out_dev, (hipStream_t)hip_stream);
-    HIPCHK(hipGetLastError());
-    return FL_OK;
-}
-
-size_t fl_tree_lstm_workspace_bytes(int n_trees, int n_nodes, int roots_only) {
-    if (n_trees <= 0 || n_nodes <= 0) return 0;
-    return (size_t)n_trees * n_nodes * FTL_M * sizeof(float) * (roots_only ? 2 : 1);
-}
-
-int fl_tree_lstm(int n_trees, int n_nodes, const float *forest_dev, const int64_t *adjacency_dev, const int64_t *node_order_dev,
-                 const int64_t *edge_order_dev, const float *w_iou_dev, const float *b_iou_dev, const float *u_iou_dev,
-                 const float *w_c_dev, const float *b_c_dev, const float *w_f_dev, const float *b_f_dev, const float *u_f_dev,
-                 int roots_only, float *h_dev, float *c_dev, int32_t *status_dev, void *workspace_dev, size_t workspace_bytes,
-                 void *hip_stream) {
-    // every check before any HIP call
-    if (n_trees <= 0 || n_nodes < 4 || n_nodes > FTL_MAX_N || n_trees > (INT32_MAX / FTL_MAX_N)) {
-        set_err("fl_tree_lstm: bad sizes (n_trees %d, n_nodes %d; 1 <= n_trees, 4 <= n_nodes <= %d)", n_trees, n_nodes, FTL_MAX_N);
-        return FL_ERR_ARG;
-    }
-    if ((n_nodes - 1) % 3 != 0) {
-        set_err("fl_tree_lstm: n_nodes %d: (n_nodes - 1) %% 3 != 0, the reference pairs every level's nodes with edge triples", n_nodes);
-        return FL_ERR_ARG;
-    }
-    if (roots_only != 0 && roots_only != 1) { set_err("fl_tree_lstm: roots_only must be 0 or 1"); return FL_ERR_ARG; }
-    const void *f16[] = {forest_dev, w_iou_dev, b_iou_dev, u_iou_dev, w_c_dev, b_c_dev, w_f_dev, b_f_dev, u_f_dev, h_dev, workspace_dev};
-    const char *f16n[] = {"forest", "w_iou", "b_iou", "u_iou", "w_c", "b_c", "w_f", "b_f", "u_f", "h", "workspace"};
-    for (int i = 0; i < 11; i++) {
-        if (!f16[i]) { set_err("fl_tree_lstm: %s is NULL", f16n[i]); return FL_ERR_ARG; }
-        if ((uintptr_t)f16[i] % 16) { set_err("fl_tree_lstm: %s is not 16-byte aligned", f16n[i]); return FL_ERR_ARG; }
-    }
-    const void *i8[] = {adjacency_dev, node_order_dev, edge_order_dev};
-    const char *i8n[] = {"adjacency", "node_order", "edge_order"};
-    for (int i = 0; i < 3; i++) {
-        if (!i8[i]) { set_err("fl_tree_lstm: %s is NULL", i8n[i]); return FL_ERR_ARG; }
-        if ((uintptr_t)i8[i] % 8) { set_err("fl_tree_lstm: %s is not 8-byte aligned", i8n[i]); return FL_ERR_ARG; }
-    }
-    if (c_dev && (uintptr_t)c_dev % 16) { set_err("fl_tree_lstm: c is not 16-byte aligned"); return FL_ERR_ARG; }
-    if (status_dev && (uintptr_t)status_dev % 4) { set_err("fl_tree_lstm: status is not 4-byte aligned"); return FL_ERR_ARG; }
-    const size_t need = fl_tree_lstm_workspace_bytes(n_trees, n_nodes, roots_only);
-    if (workspace_bytes < need) {
-        set_err("fl_tree_lstm: workspace of %zu bytes, %zu needed (fl_tree_lstm_workspace_bytes)", workspace_bytes, need);
-        return FL_ERR_ARG;
-    }
-    static int n_cu[64];
-    int dev = 0;
-    HIPCHK(hipGetDevice(&dev));
-    if (dev >= 0 && dev < 64 && n_cu[dev] == 0 &&
-        hipDeviceGetAttribute(&n_cu[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n_cu[dev] = 0;
-    FtlArgs a;
-    a.T = n_trees; a.N = n_nodes; a.roots_only = roots_only;
-    a.G = ftl_group(n_trees, dev >= 0 && dev < 64 ? n_cu[dev] : 0);
-    a.forest = forest_dev;
-    a.adj = (const long long *)adjacency_dev; a.no = (const long long *)node_order_dev; a.eo = (const long long *)edge_order_dev;
-    a.w_iou = w_iou_dev; a.b_iou = b_iou_dev; a.u_iou = u_iou_dev; a.w_c = w_c_dev; a.b_c = b_c_dev;
-    a.w_f = w_f_dev; a.b_f = b_f_dev; a.u_f = u_f_dev;
-    a.h_out = h_dev; a.c_out = c_dev; a.status = (int *)status_dev;
-    const size_t plane = (size_t)n_trees * n_nodes * FTL_M;
-    float *ws = (float *)workspace_dev;
-    if (roots_only) { a.hbuf = ws; a.cbuf = ws + plane; }
-    else { a.hbuf = h_dev; a.cbuf = c_dev ? c_dev : ws; }
-    fl_launch_tree_lstm(a, (hipStream_t)hip_stream);
-    HIPCHK(hipGetLastError());
-    return FL_OK;
-}
-
-size_t fl_tree_lstm_backward_workspace_bytes(int n_trees, int n_nodes) {
-    if (n_trees <= 0 || n_nodes <= 0) return 0;
-    return (size_t)n_trees * n_nodes * 6 * FTL_M * sizeof(float);
-}
-
-int fl_tree_lstm_backward(int n_trees, int n_nodes, const float *forest_dev, const int64_t *adjacency_dev,
-                          const int64_t *node_order_dev, const int64_t *edge_order_dev, const float *w_iou_dev,
-                          const float *b_iou_dev, const float *u_iou_dev, const float *w_c_dev, const float *b_c_dev,
-                          const float *w_f_dev, const float *b_f_dev, const float *u_f_dev, const float *h_dev, const float *c_dev,
-                          const float *grad_h_dev, int roots_only, float *da_dev, float *dc_dev, float *dg_dev, float *q_dev,
-                          int32_t *child_dev, int32_t *status_dev, void *workspace_dev, size_t workspace_bytes, void *hip_stream) {
-    // every check before any HIP call
-    if (n_trees <= 0 || n_nodes < 4 || n_nodes > FTL_MAX_N || n_trees > (INT32_MAX / FTL_MAX_N)) {
-        set_err("fl_tree_lstm_backward: bad sizes (n_trees %d, n_nodes %d; 1 <= n_trees, 4 <= n_nodes <= %d)", n_trees, n_nodes, FTL_MAX_N);
-        return FL_ERR_ARG;
-    }
-    if ((n_nodes - 1) % 3 != 0) {
-        set_err("fl_tree_lstm_backward: n_nodes %d: (n_nodes - 1) %% 3 != 0, the reference pairs every level's nodes with edge triples", n_nodes);
-        return FL_ERR_ARG;
-    }
-    if (roots_only != 0 && roots_only != 1) { set_err("fl_tree_lstm_backward: roots_only must be 0 or 1"); return FL_ERR_ARG; }
-    const void *f16[] = {forest_dev, w_iou_dev, b_iou_dev, u_iou_dev, w_c_dev, b_c_dev, w_f_dev, b_f_dev, u_f_dev, h_dev, c_dev,
-                         grad_h_dev, da_dev, dc_dev, dg_dev, q_dev, workspace_dev};
-    const char *f16n[] = {"forest", "w_iou", "b_iou", "u_iou", "w_c", "b_c", "w_f", "b_f", "u_f", "h", "c",
-                          "grad_h", "da", "dc", "dg", "q", "workspace"};
-    for (int i = 0; i < 17; i++) {
-        if (!f16[i]) { set_err("fl_tree_lstm_backward: %s is NULL", f16n[i]); return FL_ERR_ARG; }
-        if ((uintptr_t)f16[i] % 16) { set_err("fl_tree_lstm_backward: %s is not 16-byte aligned", f16n[i]); return FL_ERR_ARG; }
-    }
-    const void *i8[] = {adjacency_dev, node_order_dev, edge_order_dev};
-    const char *i8n[] = {"adjacency", "node_order", "edge_order"};
-    for (int i = 0; i < 3; i++) {
-        if (!i8[i]) { set_err("fl_tree_lstm_backward: %s is NULL", i8n[i]); return FL_ERR_ARG; }
-        if ((uintptr_t)i8[i] % 8) { set_err("fl_tree_lstm_backward: %s is not 8-byte aligned", i8n[i]); return FL_ERR_ARG; }
-    }
-    if (!child_dev) { set_err("fl_tree_lstm_backward: child is NULL"); return FL_ERR_ARG; }
-    if ((uintptr_t)child_dev % 4) { set_err("fl_tree_lstm_backward: child is not 4-byte aligned"); return FL_ERR_ARG; }
-    if (status_dev && (uintptr_t)status_dev % 4) { set_err("fl_tree_lstm_backward: status is not 4-byte aligned"); return FL_ERR_ARG; }
-    const size_t need = fl_tree_lstm_backward_workspace_bytes(n_trees, n_nodes);
-    if (workspace_bytes < need) {
-        set_err("fl_tree_lstm_backward: workspace of %zu bytes, %zu needed (fl_tree_lstm_backward_workspace_bytes)", workspace_bytes, need);
-        return FL_ERR_ARG;
-    }
-    static int n_cu[64];
-    int dev = 0;
-    HIPCHK(hipGetDevice(&dev));
-    if (dev >= 0 && dev < 64 && n_cu[dev] == 0 &&
-        hipDeviceGetAttribute(&n_cu[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n_cu[dev] = 0;
-    FtbArgs a;
-    a.T = n_trees; a.N = n_nodes; a.roots_only = roots_only;
-    a.G = ftb_group(n_trees, dev >= 0 && dev < 64 ? n_cu[dev] : 0);
-    a.forest = forest_dev;
-    a.adj = (const long long *)adjacency_dev; a.no = (const long long *)node_order_dev; a.eo = (const long long *)edge_order_dev;
-    a.w_iou = w_iou_dev; a.b_iou = b_iou_dev; a.u_iou = u_iou_dev; a.w_c = w_c_dev; a.b_c = b_c_dev;
-    a.w_f = w_f_dev; a.b_f = b_f_dev; a.u_f = u_f_dev;
-    a.h = h_dev; a.c = c_dev; a.grad_h = grad_h_dev;
-    a.da = da_dev; a.dc = dc_dev; a.dg = dg_dev; a.q = q_dev; a.child = (int *)child_dev; a.status = (int *)status_dev;
-    a.ghc = (float *)workspace_dev;
-    a.gcc = a.ghc + (size_t)n_trees * n_nodes * 3 * FTL_M;
-    fl_launch_tree_lstm_bwd(a, (hipStream_t)hip_stream);
     HIPCHK(hipGetLastError());
     return FL_OK;
 }

@@ -157,6 +157,17 @@ __host__ __device__ inline uint32_t synth_action(uint32_t seed, uint32_t b, uint
     return r >= 95 ? 0u : r >= 90 ? 4u : r >= 85 ? 3u : r >= 80 ? 1u : 2u;
 }
 
+// host side: sets the calling thread's message of fl_last_error (fl_host.hip)
+void fl_set_error(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
+#define HIPCHK(call)                                                                   \
+    do {                                                                               \
+        hipError_t e_ = (call);                                                        \
+        if (e_ != hipSuccess) {                                                        \
+            fl_set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
+            return FL_ERR_HIP;                                                         \
+        }                                                                              \
+    } while (0)
+
 // host side: a device array of n elements plus `slack` bytes, zeroed on stream s and registered in `allocs` (what the handle frees).
 // Everything a handle allocates comes from here: its behaviour must not depend on what a freed allocation of an earlier handle left
 // in the memory it got.

@@ -20,8 +20,7 @@
 // so a layer may write over its own input.
 #pragma once
 #include "fl_internal.h"
-
-void fl_set_error(const char *fmt, ...) __attribute__((format(printf, 1, 2)));   // fl_host.hip: the message of fl_last_error
+#include "fl_mfma.h"
 
 #define FPH_ATTR 83
 #define FPH_ATTR_PAD 96             // K of the first layer in LDS, zero filled
@@ -37,8 +36,6 @@ void fl_set_error(const char *fmt, ...) __attribute__((format(printf, 1, 2)));  
 #define FPH_NPARAMS 38
 #define FPH_MAX_A 1024
 #define FPH_ROW_FLOATS (4 * FPH_E + 3 * FPH_E + 1)   // workspace floats a row: embedding, two block outputs, attention, q k v, value
-
-typedef float fph_f32x16 __attribute__((ext_vector_type(16)));
 
 // parameter indices: the Network's state_dict without tree_lstm.*, in state_dict order
 enum {
@@ -61,18 +58,11 @@ struct FphArgs {
     float *y3;                                 // the third block's output [R][256], or NULL (inference): fl_policy_head_forward_saved
 };
 
-__device__ __forceinline__ fph_f32x16 fph_mfma(float a, float b, fph_f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
-}
-
 __device__ __forceinline__ float fph_gelu(float x) { return (x * 0.5f) * (1.0f + erff(x * 0.70710678118654752440f)); }
-
-// row of an accumulator register: lane l holds rows (r & 3) + 8 * (r >> 2) + 4 * (l >> 5), r = 0 .. 15, of column l & 31
-__device__ __forceinline__ int fph_row(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }
 
 // acc[b] += X[row][k] * W[j[b]][woff + k] over k in [0, K), K a multiple of 32: xrow = this lane's LDS row, w[b] = its weight row
 template <int NB>
-__device__ __forceinline__ void fph_mm(const float *xrow, int K, const float *const (&w)[NB], fph_f32x16 (&acc)[NB], int hh) {
+__device__ __forceinline__ void fph_mm(const float *xrow, int K, const float *const (&w)[NB], fl_f32x16 (&acc)[NB], int hh) {
 #pragma unroll 1
     for (int kc = 0; kc < K; kc += 32) {
         float a[16], b[NB][16];
@@ -90,12 +80,12 @@ __device__ __forceinline__ void fph_mm(const float *xrow, int K, const float *co
 #pragma unroll
         for (int s = 0; s < 16; s++)
 #pragma unroll
-            for (int n = 0; n < NB; n++) acc[n] = fph_mfma(a[s], b[n][s], acc[n]);
+            for (int n = 0; n < NB; n++) acc[n] = fl_mfma(a[s], b[n][s], acc[n]);
     }
 }
 
 // the first layer: weight rows of 83 floats (no 16-byte alignment), X zero filled up to 96
-__device__ __forceinline__ void fph_mm_attr(const float *xrow, const float *w0, const float *w1, fph_f32x16 &c0, fph_f32x16 &c1, int hh) {
+__device__ __forceinline__ void fph_mm_attr(const float *xrow, const float *w0, const float *w1, fl_f32x16 &c0, fl_f32x16 &c1, int hh) {
 #pragma unroll 1
     for (int kc = 0; kc < FPH_ATTR_PAD; kc += 32) {
         const int o = kc + 16 * hh;
@@ -104,19 +94,19 @@ __device__ __forceinline__ void fph_mm_attr(const float *xrow, const float *w0, 
             const int k = o + s;
             const float a = xrow[k];
             const float b0 = k < FPH_ATTR ? w0[k] : 0.f, b1 = k < FPH_ATTR ? w1[k] : 0.f;
-            c0 = fph_mfma(a, b0, c0);
-            c1 = fph_mfma(a, b1, c1);
+            c0 = fl_mfma(a, b0, c0);
+            c1 = fl_mfma(a, b1, c1);
         }
     }
 }
 
 // (acc + bias) [GELU] of one 32 x 32 block -> LDS columns c0 .. c0 + 31
 template <bool GELU>
-__device__ __forceinline__ void fph_to_lds(const fph_f32x16 &acc, float bias, float *dst, int c0, int col, int hh) {
+__device__ __forceinline__ void fph_to_lds(const fl_f32x16 &acc, float bias, float *dst, int c0, int col, int hh) {
 #pragma unroll
     for (int r = 0; r < 16; r++) {
         const float v = acc[r] + bias;
-        dst[fph_row(r, hh) * FPH_STRIDE + c0 + col] = GELU ? fph_gelu(v) : v;
+        dst[fl_acc_row(r, hh) * FPH_STRIDE + c0 + col] = GELU ? fph_gelu(v) : v;
     }
 }
 
@@ -143,12 +133,12 @@ __device__ __forceinline__ void fph_qkv(const float *x, const float *w, const fl
     for (int pr = 0; pr < 3; pr++) {
         const int j0 = 32 * (6 * wave + 2 * pr), j1 = j0 + 32;
         const float *const ws[2] = {w + (size_t)(j0 + col) * FPH_E, w + (size_t)(j1 + col) * FPH_E};
-        fph_f32x16 acc[2] = {};
+        fl_f32x16 acc[2] = {};
         fph_mm<2>(x + col * FPH_STRIDE, FPH_E, ws, acc, hh);
         const float b0 = bias[j0 + col], b1 = bias[j1 + col];
 #pragma unroll
         for (int r = 0; r < 16; r++) {
-            const int row = fph_row(r, hh);
+            const int row = fl_acc_row(r, hh);
             if (row < rows) {
                 out[(size_t)row * (3 * FPH_E) + j0 + col] = acc[0][r] + b0;
                 out[(size_t)row * (3 * FPH_E) + j1 + col] = acc[1][r] + b1;
@@ -158,7 +148,7 @@ __device__ __forceinline__ void fph_qkv(const float *x, const float *w, const fl
 }
 
 // Y[32][256] = [GELU](X0[32][K0] | X1[32][K1]) W^T + bias: the wave's two blocks, left in registers (bias and GELU applied by fph_to_lds)
-__device__ __forceinline__ void fph_layer256(const float *x0, int K0, const float *x1, int K1, const float *w, fph_f32x16 (&acc)[2],
+__device__ __forceinline__ void fph_layer256(const float *x0, int K0, const float *x1, int K1, const float *w, fl_f32x16 (&acc)[2],
                                              int wave, int col, int hh) {
     const int ld = K0 + K1, j0 = 64 * wave, j1 = j0 + 32;
     const float *const ws[2] = {w + (size_t)(j0 + col) * ld, w + (size_t)(j1 + col) * ld};
@@ -171,10 +161,10 @@ __device__ __forceinline__ void fph_layer256(const float *x0, int K0, const floa
 
 // a 512 -> 256 -> 128 -> n_out head (actor_net / critic_net) on [e | y]: the result of rows x n_out (n_out <= 32) in wave 0's acc
 // registers, bias added; h is scratch.  Every wave calls it (barriers inside).
-__device__ __forceinline__ void fph_head(const float *e, const float *y, float *h, const float *const *p, int n_out, fph_f32x16 &out,
+__device__ __forceinline__ void fph_head(const float *e, const float *y, float *h, const float *const *p, int n_out, fl_f32x16 &out,
                                          int wave, int col, int hh) {
     {
-        fph_f32x16 acc[2] = {};
+        fl_f32x16 acc[2] = {};
         fph_layer256(e, FPH_E, y, FPH_E, p[0], acc, wave, col, hh);
         __syncthreads();                                         // (h may still be read by the head before this one)
         fph_to_lds<true>(acc[0], p[1][64 * wave + col], h, 64 * wave, col, hh);
@@ -183,7 +173,7 @@ __device__ __forceinline__ void fph_head(const float *e, const float *y, float *
     __syncthreads();
     {
         const float *const ws[1] = {p[2] + (size_t)(32 * wave + col) * FPH_E};
-        fph_f32x16 acc[1] = {};
+        fl_f32x16 acc[1] = {};
         fph_mm<1>(h + col * FPH_STRIDE, FPH_E, ws, acc, hh);
         __syncthreads();
         fph_to_lds<true>(acc[0], p[3][32 * wave + col], h, 32 * wave, col, hh);
@@ -192,7 +182,7 @@ __device__ __forceinline__ void fph_head(const float *e, const float *y, float *
     if (wave == 0) {
         const int j = min(col, n_out - 1);                       // (columns past n_out repeat the last feature and are dropped)
         const float *const ws[1] = {p[4] + (size_t)j * FPH_H};
-        fph_f32x16 acc[1] = {};
+        fl_f32x16 acc[1] = {};
         fph_mm<1>(h + col * FPH_STRIDE, FPH_H, ws, acc, hh);
         const float b = p[5][j];
 #pragma unroll
@@ -242,7 +232,7 @@ __global__ void __launch_bounds__(FPH_THREADS) k_ph_embed(FphArgs p) {
     __syncthreads();
     const float *const *w = p.p + FPH_P_ATTR;
     {
-        fph_f32x16 acc[2] = {};
+        fl_f32x16 acc[2] = {};
         fph_mm_attr(b0 + col * FPH_STRIDE, w[0] + (size_t)(64 * wave + col) * FPH_ATTR, w[0] + (size_t)(64 * wave + 32 + col) * FPH_ATTR,
                     acc[0], acc[1], hh);
         fph_to_lds<true>(acc[0], w[1][64 * wave + col], b1, 64 * wave, col, hh);
@@ -251,7 +241,7 @@ __global__ void __launch_bounds__(FPH_THREADS) k_ph_embed(FphArgs p) {
     __syncthreads();
     for (int l = 1; l <= 2; l++) {                               // 256 -> 256 twice: b1 -> b0 -> b1
         float *src = l == 1 ? b1 : b0, *dst = l == 1 ? b0 : b1;
-        fph_f32x16 acc[2] = {};
+        fl_f32x16 acc[2] = {};
         fph_layer256(src, FPH_E, nullptr, 0, w[2 * l], acc, wave, col, hh);
         fph_to_lds<true>(acc[0], w[2 * l + 1][64 * wave + col], dst, 64 * wave, col, hh);
         fph_to_lds<true>(acc[1], w[2 * l + 1][64 * wave + 32 + col], dst, 64 * wave + 32, col, hh);
@@ -259,7 +249,7 @@ __global__ void __launch_bounds__(FPH_THREADS) k_ph_embed(FphArgs p) {
     }
     {                                                            // 256 -> 128: b1 -> b0[:, :128]; the tree embedding beside it
         const float *const ws[1] = {w[6] + (size_t)(32 * wave + col) * FPH_E};
-        fph_f32x16 acc[1] = {};
+        fl_f32x16 acc[1] = {};
         fph_mm<1>(b1 + col * FPH_STRIDE, FPH_E, ws, acc, hh);
         fph_to_lds<true>(acc[0], w[7][32 * wave + col], b0, 32 * wave, col, hh);
         fph_load_tile(b0, FPH_H, p.tree + (size_t)row0 * FPH_H, FPH_H, FPH_H / 4, rows, tid);
@@ -295,7 +285,7 @@ __global__ void __launch_bounds__(FPH_THREADS) k_ph_attn(FphArgs p) {
     float mx[16], sum[16];
 #pragma unroll
     for (int r = 0; r < 16; r++) { mx[r] = -INFINITY; sum[r] = 0.f; }
-    fph_f32x16 o0 = {}, o1 = {};
+    fl_f32x16 o0 = {}, o1 = {};
 
 #pragma unroll 1
     for (int pass = 0; pass < 2; pass++) {
@@ -303,7 +293,7 @@ __global__ void __launch_bounds__(FPH_THREADS) k_ph_attn(FphArgs p) {
         for (int k0 = 0; k0 < A; k0 += 32) {
             const bool live = k0 + col < A;                       // this lane's key (score column)
             const float *krow = qkv + (size_t)min(k0 + col, A - 1) * (3 * FPH_E) + FPH_E + head * FPH_D;
-            fph_f32x16 s = {};
+            fl_f32x16 s = {};
 #pragma unroll
             for (int c = 0; c < 2; c++) {
                 float kb[16];
@@ -313,7 +303,7 @@ __global__ void __launch_bounds__(FPH_THREADS) k_ph_attn(FphArgs p) {
                     kb[4 * q] = v.x; kb[4 * q + 1] = v.y; kb[4 * q + 2] = v.z; kb[4 * q + 3] = v.w;
                 }
 #pragma unroll
-                for (int t = 0; t < 16; t++) s = fph_mfma(qa[c][t], kb[t], s);
+                for (int t = 0; t < 16; t++) s = fl_mfma(qa[c][t], kb[t], s);
             }
             if (pass == 0) {
                 if (live) {
@@ -327,7 +317,7 @@ __global__ void __launch_bounds__(FPH_THREADS) k_ph_attn(FphArgs p) {
             for (int r = 0; r < 16; r++) {
                 const float e = live ? expf((s[r] - mx[r]) * 0.125f) : 0.f;
                 sum[r] += e;
-                sp[fph_row(r, hh) * FPH_PSTRIDE + col] = e;
+                sp[fl_acc_row(r, hh) * FPH_PSTRIDE + col] = e;
             }
             __syncthreads();
             float pa[16];
@@ -344,8 +334,8 @@ __global__ void __launch_bounds__(FPH_THREADS) k_ph_attn(FphArgs p) {
                     const float *vrow = qkv + (size_t)key * (3 * FPH_E) + 2 * FPH_E + head * FPH_D;
                     v0 = vrow[col]; v1 = vrow[32 + col];
                 }
-                o0 = fph_mfma(pa[t], v0, o0);
-                o1 = fph_mfma(pa[t], v1, o1);
+                o0 = fl_mfma(pa[t], v0, o0);
+                o1 = fl_mfma(pa[t], v1, o1);
             }
         }
         // a row's maximum / sum over the 32 lanes that hold its columns (a butterfly: every lane ends with the same value)
@@ -363,7 +353,7 @@ __global__ void __launch_bounds__(FPH_THREADS) k_ph_attn(FphArgs p) {
     float *out = p.ao + base * FPH_E + head * FPH_D;
 #pragma unroll
     for (int r = 0; r < 16; r++) {
-        const int qi = q0 + fph_row(r, hh);
+        const int qi = q0 + fl_acc_row(r, hh);
         if (qi < A) {
             out[(size_t)qi * FPH_E + col] = o0[r] / sum[r];
             out[(size_t)qi * FPH_E + 32 + col] = o1[r] / sum[r];
@@ -385,7 +375,7 @@ __global__ void __launch_bounds__(FPH_THREADS) k_ph_block(FphArgs p, int blk, co
     fph_load_tile(ba, 0, p.ao + (size_t)row0 * FPH_E, FPH_E, FPH_E / 4, rows, tid);
     __syncthreads();
     {                                                            // out_proj, over the attention output
-        fph_f32x16 acc[2] = {};
+        fl_f32x16 acc[2] = {};
         fph_layer256(ba, FPH_E, nullptr, 0, w[2], acc, wave, col, hh);
         __syncthreads();
         fph_to_lds<false>(acc[0], w[3][64 * wave + col], ba, 64 * wave, col, hh);
@@ -393,7 +383,7 @@ __global__ void __launch_bounds__(FPH_THREADS) k_ph_block(FphArgs p, int blk, co
     }
     __syncthreads();
     {                                                            // att_mlp on [input | attention], over the input
-        fph_f32x16 acc[2] = {};
+        fl_f32x16 acc[2] = {};
         fph_layer256(bx, FPH_E, ba, FPH_E, w[4], acc, wave, col, hh);
         __syncthreads();
         fph_to_lds<true>(acc[0], w[5][64 * wave + col], bx, 64 * wave, col, hh);
@@ -408,12 +398,12 @@ __global__ void __launch_bounds__(FPH_THREADS) k_ph_block(FphArgs p, int blk, co
     fph_load_tile(ba, 0, p.emb + (size_t)row0 * FPH_E, FPH_E, FPH_E / 4, rows, tid);
     if (p.y3) fph_store_tile(bx, p.y3 + (size_t)row0 * FPH_E, rows, tid);
     __syncthreads();
-    fph_f32x16 out = {};
+    fl_f32x16 out = {};
     fph_head(ba, bx, bh, p.p + FPH_P_ACTOR, FPH_ACT, out, wave, col, hh);
     if (wave == 0 && col < FPH_ACT) {
 #pragma unroll
         for (int r = 0; r < 16; r++) {
-            const int row = fph_row(r, hh);
+            const int row = fl_acc_row(r, hh);
             s_lg[row][col] = out[r];
             if (row < rows) p.logits[(size_t)(row0 + row) * FPH_ACT + col] = out[r];
         }
@@ -423,7 +413,7 @@ __global__ void __launch_bounds__(FPH_THREADS) k_ph_block(FphArgs p, int blk, co
         if (wave == 0 && col == 0) {
 #pragma unroll
             for (int r = 0; r < 16; r++) {
-                const int row = fph_row(r, hh);
+                const int row = fl_acc_row(r, hh);
                 if (row < rows) p.val[row0 + row] = out[r];
             }
         }

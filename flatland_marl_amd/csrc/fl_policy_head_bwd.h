@@ -43,22 +43,14 @@ __device__ __forceinline__ float fpb_dgelu(float z) {
     return 0.5f * (1.0f + erff(z * 0.70710678118654752440f)) + z * (expf(-0.5f * z * z) * 0.39894228040143267794f);
 }
 
-__device__ __forceinline__ void fpb_ld16(const float *src, float (&a)[16]) {
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const float4 v = ((const float4 *)src)[q];
-        a[4 * q] = v.x; a[4 * q + 1] = v.y; a[4 * q + 2] = v.z; a[4 * q + 3] = v.w;
-    }
-}
-
 // acc[n] += dZ[row][j] * W[j][k_n + col] over j in [0, J), J a multiple of 32: dzrow = this lane's LDS row, wc[n] = W + k_n + col
 template <int NB>
-__device__ __forceinline__ void fpb_mmT(const float *dzrow, int J, const float *const (&wc)[NB], int ld, fph_f32x16 (&acc)[NB], int hh) {
+__device__ __forceinline__ void fpb_mmT(const float *dzrow, int J, const float *const (&wc)[NB], int ld, fl_f32x16 (&acc)[NB], int hh) {
 #pragma unroll 1
     for (int jc = 0; jc < J; jc += 32) {
         const int o = jc + 16 * hh;
         float a[16], b[NB][16];
-        fpb_ld16(dzrow + o, a);
+        fl_ld16(dzrow + o, a);
 #pragma unroll
         for (int s = 0; s < 16; s++)
 #pragma unroll
@@ -66,17 +58,17 @@ __device__ __forceinline__ void fpb_mmT(const float *dzrow, int J, const float *
 #pragma unroll
         for (int s = 0; s < 16; s++)
 #pragma unroll
-            for (int n = 0; n < NB; n++) acc[n] = fph_mfma(a[s], b[n][s], acc[n]);
+            for (int n = 0; n < NB; n++) acc[n] = fl_mfma(a[s], b[n][s], acc[n]);
     }
 }
 
 // a recomputed layer's block: z = acc + bias; GELU(z) -> LDS column c (lds may be NULL) and the rows' X (xg may be NULL);
 // g'(z) -> the block's dZ slot.  xg and slot point at the tile's first row.
-__device__ __forceinline__ void fpb_fwd_out(const fph_f32x16 &acc, float bias, float *lds, int c, float *xg, float *slot, int ld,
+__device__ __forceinline__ void fpb_fwd_out(const fl_f32x16 &acc, float bias, float *lds, int c, float *xg, float *slot, int ld,
                                             int rows, int hh) {
 #pragma unroll
     for (int r = 0; r < 16; r++) {
-        const int row = fph_row(r, hh);
+        const int row = fl_acc_row(r, hh);
         const float z = acc[r] + bias, h = fph_gelu(z);
         if (lds) lds[row * FPH_STRIDE + c] = h;
         if (row < rows) {
@@ -87,10 +79,10 @@ __device__ __forceinline__ void fpb_fwd_out(const fph_f32x16 &acc, float bias, f
 }
 
 // dZ = acc * g'(z) (waiting in the slot) -> LDS column c and the slot; rows past the tile's last are zero in LDS
-__device__ __forceinline__ void fpb_bwd_out(const fph_f32x16 &acc, float *lds, int c, float *slot, int ld, int rows, int hh) {
+__device__ __forceinline__ void fpb_bwd_out(const fl_f32x16 &acc, float *lds, int c, float *slot, int ld, int rows, int hh) {
 #pragma unroll
     for (int r = 0; r < 16; r++) {
-        const int row = fph_row(r, hh);
+        const int row = fl_acc_row(r, hh);
         float d = 0.f;
         if (row < rows) {
             d = acc[r] * slot[(size_t)row * ld + c];
@@ -126,7 +118,7 @@ __global__ void __launch_bounds__(FPH_THREADS) k_pb_heads(FpbArgs p) {
         }
         __syncthreads();
         {                                                        // layer 0 again: h1 -> t2 and the rows, g' -> dz0's slot
-            fph_f32x16 acc[2] = {};
+            fl_f32x16 acc[2] = {};
             fph_layer256(te, FPH_E, ty, FPH_E, w[0], acc, wave, col, hh);
             float *h1 = p.h_h[hd][0] + (size_t)row0 * FPH_E;
             fpb_fwd_out(acc[0], w[1][64 * wave + col], t2, 64 * wave + col, h1, dz0, FPH_E, rows, hh);
@@ -136,7 +128,7 @@ __global__ void __launch_bounds__(FPH_THREADS) k_pb_heads(FpbArgs p) {
         {                                                        // layer 2 again: h2 -> the rows; dz2 = (dz4 W4) g'(z2) -> t2[:, :128]
             const int f = 32 * wave + col;
             const float *const ws[1] = {w[2] + (size_t)f * FPH_E};
-            fph_f32x16 acc[1] = {};
+            fl_f32x16 acc[1] = {};
             fph_mm<1>(t2 + col * FPH_STRIDE, FPH_E, ws, acc, hh);
             const float b = w[3][f];
             float w4[FPH_ACT];
@@ -145,7 +137,7 @@ __global__ void __launch_bounds__(FPH_THREADS) k_pb_heads(FpbArgs p) {
             __syncthreads();                                     // every wave has read h1
 #pragma unroll
             for (int r = 0; r < 16; r++) {
-                const int row = fph_row(r, hh);
+                const int row = fl_acc_row(r, hh);
                 const float z = acc[0][r] + b;
                 float s = 0.f;
                 for (int j = 0; j < FPH_ACT; j++) s += s_g[row][j] * w4[j];
@@ -161,7 +153,7 @@ __global__ void __launch_bounds__(FPH_THREADS) k_pb_heads(FpbArgs p) {
         {                                                        // dz0 = (dz2 W2) g'(z1) -> t3
             const int k0 = 64 * wave, k1 = k0 + 32;
             const float *const wc[2] = {w[2] + k0 + col, w[2] + k1 + col};
-            fph_f32x16 acc[2] = {};
+            fl_f32x16 acc[2] = {};
             fpb_mmT<2>(t2 + col * FPH_STRIDE, FPH_H, wc, FPH_E, acc, hh);
             fpb_bwd_out(acc[0], t3, k0 + col, dz0, FPH_E, rows, hh);
             fpb_bwd_out(acc[1], t3, k1 + col, dz0, FPH_E, rows, hh);
@@ -171,12 +163,12 @@ __global__ void __launch_bounds__(FPH_THREADS) k_pb_heads(FpbArgs p) {
         for (int t = 0; t < 2; t++) {                            // d both = dz0 W0: columns 0 .. 255 -> d emb, 256 .. 511 -> dy_3
             const int k0 = 32 * (4 * wave + 2 * t);
             const float *const wc[2] = {w[0] + k0 + col, w[0] + k0 + 32 + col};
-            fph_f32x16 acc[2] = {};
+            fl_f32x16 acc[2] = {};
             fpb_mmT<2>(t3 + col * FPH_STRIDE, FPH_E, wc, 2 * FPH_E, acc, hh);
             float *dst = (k0 < FPH_E ? p.dy[0] + k0 : p.dy[3] + (k0 - FPH_E)) + (size_t)row0 * FPH_E + col;
 #pragma unroll
             for (int r = 0; r < 16; r++) {
-                const int row = fph_row(r, hh);
+                const int row = fl_acc_row(r, hh);
                 if (row < rows) {
                     float *d = dst + (size_t)row * FPH_E;
                     d[0] = first ? acc[0][r] : d[0] + acc[0][r];     // the critic's after the actor's
@@ -202,7 +194,7 @@ __global__ void __launch_bounds__(FPH_THREADS) k_pb_block(FpbArgs p, int blk) {
     fph_load_tile(ba, 0, p.ao[blk] + t0, FPH_E, FPH_E / 4, rows, tid);
     __syncthreads();
     {                                                            // out_proj again: o -> ba and the rows
-        fph_f32x16 acc[2] = {};
+        fl_f32x16 acc[2] = {};
         fph_layer256(ba, FPH_E, nullptr, 0, w[2], acc, wave, col, hh);
         __syncthreads();
 #pragma unroll
@@ -211,7 +203,7 @@ __global__ void __launch_bounds__(FPH_THREADS) k_pb_block(FpbArgs p, int blk) {
             const float b = w[3][c];
 #pragma unroll
             for (int r = 0; r < 16; r++) {
-                const int row = fph_row(r, hh);
+                const int row = fl_acc_row(r, hh);
                 const float v = acc[n][r] + b;
                 ba[row * FPH_STRIDE + c] = v;
                 if (row < rows) p.o[blk][t0 + (size_t)row * FPH_E + c] = v;
@@ -220,7 +212,7 @@ __global__ void __launch_bounds__(FPH_THREADS) k_pb_block(FpbArgs p, int blk) {
     }
     __syncthreads();
     {                                                            // att_mlp again: dz = dy_{i+1} g'(z) -> bz and the rows
-        fph_f32x16 acc[2] = {};
+        fl_f32x16 acc[2] = {};
         fph_layer256(bx, FPH_E, ba, FPH_E, w[4], acc, wave, col, hh);
 #pragma unroll
         for (int n = 0; n < 2; n++) {
@@ -228,7 +220,7 @@ __global__ void __launch_bounds__(FPH_THREADS) k_pb_block(FpbArgs p, int blk) {
             const float b = w[5][c];
 #pragma unroll
             for (int r = 0; r < 16; r++) {
-                const int row = fph_row(r, hh);
+                const int row = fl_acc_row(r, hh);
                 float d = 0.f;
                 if (row < rows) {
                     d = p.dy[blk + 1][t0 + (size_t)row * FPH_E + c] * fpb_dgelu(acc[n][r] + b);
@@ -243,14 +235,14 @@ __global__ void __launch_bounds__(FPH_THREADS) k_pb_block(FpbArgs p, int blk) {
     for (int t = 0; t < 2; t++) {                                // d [y | o] = dz W_m: waves 0, 1 -> dy_i, waves 2, 3 -> do (ba and the rows)
         const int k0 = 32 * (4 * wave + 2 * t);
         const float *const wc[2] = {w[4] + k0 + col, w[4] + k0 + 32 + col};
-        fph_f32x16 acc[2] = {};
+        fl_f32x16 acc[2] = {};
         fpb_mmT<2>(bz + col * FPH_STRIDE, FPH_E, wc, 2 * FPH_E, acc, hh);
         const bool left = k0 < FPH_E;
         const int c = (left ? k0 : k0 - FPH_E) + col;
         float *dst = (left ? p.dy[blk] : p.dout[blk]) + t0 + c;
 #pragma unroll
         for (int r = 0; r < 16; r++) {
-            const int row = fph_row(r, hh);
+            const int row = fl_acc_row(r, hh);
             float v0 = acc[0][r], v1 = acc[1][r];
             if (row < rows) {
                 float *d = dst + (size_t)row * FPH_E;
@@ -266,11 +258,11 @@ __global__ void __launch_bounds__(FPH_THREADS) k_pb_block(FpbArgs p, int blk) {
     {                                                            // dc = do W_o
         const int k0 = 64 * wave;
         const float *const wc[2] = {w[2] + k0 + col, w[2] + k0 + 32 + col};
-        fph_f32x16 acc[2] = {};
+        fl_f32x16 acc[2] = {};
         fpb_mmT<2>(ba + col * FPH_STRIDE, FPH_E, wc, FPH_E, acc, hh);
 #pragma unroll
         for (int r = 0; r < 16; r++) {
-            const int row = fph_row(r, hh);
+            const int row = fl_acc_row(r, hh);
             if (row < rows) {
                 p.dc[blk][t0 + (size_t)row * FPH_E + k0 + col] = acc[0][r];
                 p.dc[blk][t0 + (size_t)row * FPH_E + k0 + 32 + col] = acc[1][r];
@@ -300,14 +292,14 @@ __global__ void __launch_bounds__(FPH_THREADS) k_pb_attn_q(FpbArgs p, int blk) {
         const float *dcrow = p.dc[blk] + (base + qi) * FPH_E + head * FPH_D;
 #pragma unroll
         for (int c = 0; c < 2; c++) {
-            fpb_ld16(qkv + qi * (3 * FPH_E) + head * FPH_D + 32 * c + 16 * hh, qa[c]);
-            fpb_ld16(dcrow + 32 * c + 16 * hh, da[c]);
+            fl_ld16(qkv + qi * (3 * FPH_E) + head * FPH_D + 32 * c + 16 * hh, qa[c]);
+            fl_ld16(dcrow + 32 * c + 16 * hh, da[c]);
         }
     }
     float mx[16], sum[16], D[16];
 #pragma unroll
     for (int r = 0; r < 16; r++) { mx[r] = -INFINITY; sum[r] = 0.f; D[r] = 0.f; }
-    fph_f32x16 o0 = {}, o1 = {};
+    fl_f32x16 o0 = {}, o1 = {};
 
 #pragma unroll 1
     for (int pass = 0; pass < 4; pass++) {
@@ -315,13 +307,13 @@ __global__ void __launch_bounds__(FPH_THREADS) k_pb_attn_q(FpbArgs p, int blk) {
         for (int k0 = 0; k0 < A; k0 += 32) {
             const bool live = k0 + col < A;
             const float *krow = qkv + (size_t)min(k0 + col, A - 1) * (3 * FPH_E) + FPH_E + head * FPH_D;
-            fph_f32x16 s = {};
+            fl_f32x16 s = {};
 #pragma unroll
             for (int c = 0; c < 2; c++) {
                 float kb[16];
-                fpb_ld16(krow + 32 * c + 16 * hh, kb);
+                fl_ld16(krow + 32 * c + 16 * hh, kb);
 #pragma unroll
-                for (int t = 0; t < 16; t++) s = fph_mfma(qa[c][t], kb[t], s);
+                for (int t = 0; t < 16; t++) s = fl_mfma(qa[c][t], kb[t], s);
             }
             if (pass == 0) {
                 if (live) {
@@ -335,13 +327,13 @@ __global__ void __launch_bounds__(FPH_THREADS) k_pb_attn_q(FpbArgs p, int blk) {
                 for (int r = 0; r < 16; r++) sum[r] += live ? expf((s[r] - mx[r]) * 0.125f) : 0.f;
                 continue;
             }
-            fph_f32x16 dp = {};
+            fl_f32x16 dp = {};
 #pragma unroll
             for (int c = 0; c < 2; c++) {
                 float vb[16];
-                fpb_ld16(krow + FPH_E + 32 * c + 16 * hh, vb);
+                fl_ld16(krow + FPH_E + 32 * c + 16 * hh, vb);
 #pragma unroll
-                for (int t = 0; t < 16; t++) dp = fph_mfma(da[c][t], vb[t], dp);
+                for (int t = 0; t < 16; t++) dp = fl_mfma(da[c][t], vb[t], dp);
             }
             if (pass == 2) {
 #pragma unroll
@@ -352,11 +344,11 @@ __global__ void __launch_bounds__(FPH_THREADS) k_pb_attn_q(FpbArgs p, int blk) {
 #pragma unroll
             for (int r = 0; r < 16; r++) {
                 const float pr = live ? expf((s[r] - mx[r]) * 0.125f) / sum[r] : 0.f;
-                sp[fph_row(r, hh) * FPH_PSTRIDE + col] = live ? pr * (dp[r] - D[r]) : 0.f;
+                sp[fl_acc_row(r, hh) * FPH_PSTRIDE + col] = live ? pr * (dp[r] - D[r]) : 0.f;
             }
             __syncthreads();
             float pa[16];
-            fpb_ld16(sp + col * FPH_PSTRIDE + 16 * hh, pa);
+            fl_ld16(sp + col * FPH_PSTRIDE + 16 * hh, pa);
 #pragma unroll
             for (int t = 0; t < 16; t++) {
                 const int key = k0 + 16 * hh + t;
@@ -365,8 +357,8 @@ __global__ void __launch_bounds__(FPH_THREADS) k_pb_attn_q(FpbArgs p, int blk) {
                     const float *kr = qkv + (size_t)key * (3 * FPH_E) + FPH_E + head * FPH_D;
                     v0 = kr[col]; v1 = kr[32 + col];
                 }
-                o0 = fph_mfma(pa[t], v0, o0);
-                o1 = fph_mfma(pa[t], v1, o1);
+                o0 = fl_mfma(pa[t], v0, o0);
+                o1 = fl_mfma(pa[t], v1, o1);
             }
         }
         if (pass < 3) {
@@ -385,7 +377,7 @@ __global__ void __launch_bounds__(FPH_THREADS) k_pb_attn_q(FpbArgs p, int blk) {
     float *out = p.dqkv[blk] + base * (3 * FPH_E) + head * FPH_D;
 #pragma unroll
     for (int r = 0; r < 16; r++) {
-        const int qi = q0 + fph_row(r, hh);
+        const int qi = q0 + fl_acc_row(r, hh);
         if (qi < A) {
             out[(size_t)qi * (3 * FPH_E) + col] = o0[r] * 0.125f;
             out[(size_t)qi * (3 * FPH_E) + 32 + col] = o1[r] * 0.125f;
@@ -415,11 +407,11 @@ __global__ void __launch_bounds__(FPH_THREADS) k_pb_attn_kv(FpbArgs p, int blk) 
         const float *krow = qkv + (size_t)min(k0 + col, A - 1) * (3 * FPH_E) + FPH_E;
 #pragma unroll
         for (int c = 0; c < 2; c++) {
-            fpb_ld16(krow + 32 * c + 16 * hh, ka[c]);
-            fpb_ld16(krow + FPH_E + 32 * c + 16 * hh, va[c]);
+            fl_ld16(krow + 32 * c + 16 * hh, ka[c]);
+            fl_ld16(krow + FPH_E + 32 * c + 16 * hh, va[c]);
         }
     }
-    fph_f32x16 dk0 = {}, dk1 = {}, dv0 = {}, dv1 = {};
+    fl_f32x16 dk0 = {}, dk1 = {}, dv0 = {}, dv1 = {};
 #pragma unroll 1
     for (int q0 = 0; q0 < A; q0 += 32) {
         const bool live = q0 + col < A;                          // this lane's query (column)
@@ -427,26 +419,26 @@ __global__ void __launch_bounds__(FPH_THREADS) k_pb_attn_kv(FpbArgs p, int blk) 
         const float *qrow = qkv + qi * (3 * FPH_E), *dcrow = dc + qi * FPH_E;
         const float *st = p.stats + (base + qi) * FPB_STATS + 3 * head;
         const float mx = st[0], sum = st[1], D = st[2];
-        fph_f32x16 s = {}, dp = {};
+        fl_f32x16 s = {}, dp = {};
 #pragma unroll
         for (int c = 0; c < 2; c++) {
             float qb[16], db[16];
-            fpb_ld16(qrow + 32 * c + 16 * hh, qb);
-            fpb_ld16(dcrow + 32 * c + 16 * hh, db);
+            fl_ld16(qrow + 32 * c + 16 * hh, qb);
+            fl_ld16(dcrow + 32 * c + 16 * hh, db);
 #pragma unroll
-            for (int t = 0; t < 16; t++) { s = fph_mfma(ka[c][t], qb[t], s); dp = fph_mfma(va[c][t], db[t], dp); }
+            for (int t = 0; t < 16; t++) { s = fl_mfma(ka[c][t], qb[t], s); dp = fl_mfma(va[c][t], db[t], dp); }
         }
         __syncthreads();                                         // the previous tile's P^T and dS^T have been read
 #pragma unroll
         for (int r = 0; r < 16; r++) {
             const float pr = live ? expf((s[r] - mx) * 0.125f) / sum : 0.f;
-            spp[fph_row(r, hh) * FPH_PSTRIDE + col] = pr;
-            sps[fph_row(r, hh) * FPH_PSTRIDE + col] = live ? pr * (dp[r] - D) : 0.f;
+            spp[fl_acc_row(r, hh) * FPH_PSTRIDE + col] = pr;
+            sps[fl_acc_row(r, hh) * FPH_PSTRIDE + col] = live ? pr * (dp[r] - D) : 0.f;
         }
         __syncthreads();
         float pa[16], sa[16];
-        fpb_ld16(spp + col * FPH_PSTRIDE + 16 * hh, pa);
-        fpb_ld16(sps + col * FPH_PSTRIDE + 16 * hh, sa);
+        fl_ld16(spp + col * FPH_PSTRIDE + 16 * hh, pa);
+        fl_ld16(sps + col * FPH_PSTRIDE + 16 * hh, sa);
 #pragma unroll
         for (int t = 0; t < 16; t++) {
             const int qq = q0 + 16 * hh + t;
@@ -455,14 +447,14 @@ __global__ void __launch_bounds__(FPH_THREADS) k_pb_attn_kv(FpbArgs p, int blk) 
                 const float *cr = dc + (size_t)qq * FPH_E, *qr = qkv + (size_t)qq * (3 * FPH_E);
                 c0 = cr[col]; c1 = cr[32 + col]; x0 = qr[col]; x1 = qr[32 + col];
             }
-            dv0 = fph_mfma(pa[t], c0, dv0); dv1 = fph_mfma(pa[t], c1, dv1);
-            dk0 = fph_mfma(sa[t], x0, dk0); dk1 = fph_mfma(sa[t], x1, dk1);
+            dv0 = fl_mfma(pa[t], c0, dv0); dv1 = fl_mfma(pa[t], c1, dv1);
+            dk0 = fl_mfma(sa[t], x0, dk0); dk1 = fl_mfma(sa[t], x1, dk1);
         }
     }
     float *out = p.dqkv[blk] + base * (3 * FPH_E) + head * FPH_D;
 #pragma unroll
     for (int r = 0; r < 16; r++) {
-        const int ki = k0 + fph_row(r, hh);
+        const int ki = k0 + fl_acc_row(r, hh);
         if (ki < A) {
             float *o = out + (size_t)ki * (3 * FPH_E);
             o[FPH_E + col] = dk0[r] * 0.125f; o[FPH_E + 32 + col] = dk1[r] * 0.125f;
@@ -487,12 +479,12 @@ __global__ void __launch_bounds__(FPH_THREADS) k_pb_inproj(FpbArgs p, int blk) {
     const float *w = p.p[FPH_P_BLOCK + 6 * blk];
     const int k0 = 64 * wave;
     const float *const wc[2] = {w + k0 + col, w + k0 + 32 + col};
-    fph_f32x16 acc[2] = {};
+    fl_f32x16 acc[2] = {};
     fpb_mmT<2>(s_f + col * FPB_QSTRIDE, 3 * FPH_E, wc, FPH_E, acc, hh);
     float *dst = p.dy[blk] + (size_t)row0 * FPH_E + k0 + col;
 #pragma unroll
     for (int r = 0; r < 16; r++) {
-        const int row = fph_row(r, hh);
+        const int row = fl_acc_row(r, hh);
         if (row < rows) {
             float *d = dst + (size_t)row * FPH_E;
             d[0] = d[0] + acc[0][r];
@@ -520,7 +512,7 @@ __global__ void __launch_bounds__(FPH_THREADS) k_pb_attr(FpbArgs p) {
     __syncthreads();
     const float *const *w = p.p + FPH_P_ATTR;
     {
-        fph_f32x16 acc[2] = {};
+        fl_f32x16 acc[2] = {};
         fph_mm_attr(b0 + col * FPH_STRIDE, w[0] + (size_t)(64 * wave + col) * FPH_ATTR, w[0] + (size_t)(64 * wave + 32 + col) * FPH_ATTR,
                     acc[0], acc[1], hh);
         fpb_fwd_out(acc[0], w[1][64 * wave + col], b1, 64 * wave + col, p.a_h[0] + t0, p.a_dz[0] + t0, FPH_E, rows, hh);
@@ -529,7 +521,7 @@ __global__ void __launch_bounds__(FPH_THREADS) k_pb_attr(FpbArgs p) {
     __syncthreads();
     for (int l = 1; l <= 2; l++) {                               // 256 -> 256 twice: b1 -> b0 -> b1
         float *src = l == 1 ? b1 : b0, *dst = l == 1 ? b0 : b1;
-        fph_f32x16 acc[2] = {};
+        fl_f32x16 acc[2] = {};
         fph_layer256(src, FPH_E, nullptr, 0, w[2 * l], acc, wave, col, hh);
         fpb_fwd_out(acc[0], w[2 * l + 1][64 * wave + col], dst, 64 * wave + col, p.a_h[l] + t0, p.a_dz[l] + t0, FPH_E, rows, hh);
         fpb_fwd_out(acc[1], w[2 * l + 1][64 * wave + 32 + col], dst, 64 * wave + 32 + col, p.a_h[l] + t0, p.a_dz[l] + t0, FPH_E, rows, hh);
@@ -538,12 +530,12 @@ __global__ void __launch_bounds__(FPH_THREADS) k_pb_attr(FpbArgs p) {
     {                                                            // 256 -> 128 again; dz6 = d emb[:128] g'(z6) -> b0[:, :128]
         const int f = 32 * wave + col;
         const float *const ws[1] = {w[6] + (size_t)f * FPH_E};
-        fph_f32x16 acc[1] = {};
+        fl_f32x16 acc[1] = {};
         fph_mm<1>(b1 + col * FPH_STRIDE, FPH_E, ws, acc, hh);
         const float b = w[7][f];
 #pragma unroll
         for (int r = 0; r < 16; r++) {
-            const int row = fph_row(r, hh);
+            const int row = fl_acc_row(r, hh);
             float d = 0.f;
             if (row < rows) {
                 d = p.dy[0][t0 + (size_t)row * FPH_E + f] * fpb_dgelu(acc[0][r] + b);
@@ -556,7 +548,7 @@ __global__ void __launch_bounds__(FPH_THREADS) k_pb_attr(FpbArgs p) {
     {                                                            // dz4 = (dz6 W6) g'(z4) -> b1
         const int k0 = 64 * wave;
         const float *const wc[2] = {w[6] + k0 + col, w[6] + k0 + 32 + col};
-        fph_f32x16 acc[2] = {};
+        fl_f32x16 acc[2] = {};
         fpb_mmT<2>(b0 + col * FPH_STRIDE, FPH_H, wc, FPH_E, acc, hh);
         fpb_bwd_out(acc[0], b1, k0 + col, p.a_dz[2] + t0, FPH_E, rows, hh);
         fpb_bwd_out(acc[1], b1, k0 + 32 + col, p.a_dz[2] + t0, FPH_E, rows, hh);
@@ -566,7 +558,7 @@ __global__ void __launch_bounds__(FPH_THREADS) k_pb_attr(FpbArgs p) {
         float *src = l == 2 ? b1 : b0, *dst = l == 2 ? b0 : b1;
         const int k0 = 64 * wave;
         const float *const wc[2] = {w[2 * l] + k0 + col, w[2 * l] + k0 + 32 + col};
-        fph_f32x16 acc[2] = {};
+        fl_f32x16 acc[2] = {};
         fpb_mmT<2>(src + col * FPH_STRIDE, FPH_E, wc, FPH_E, acc, hh);
         fpb_bwd_out(acc[0], dst, k0 + col, p.a_dz[l - 1] + t0, FPH_E, rows, hh);
         fpb_bwd_out(acc[1], dst, k0 + 32 + col, p.a_dz[l - 1] + t0, FPH_E, rows, hh);

@@ -1,0 +1,130 @@
+// fl_tree_lstm.hip -- entry points of the policy's tree encoder: fl_tree_lstm (include/flatland_hip.h) and its gradient
+// fl_tree_lstm_backward (include/flatland_train.h).  The checks (all before any HIP call) and the launches of the kernels in
+// fl_tree_lstm.h and fl_tree_lstm_bwd.h.  No env handle: plain pointers and sizes.
+#include <algorithm>
+
+#include "../../include/flatland_hip.h"
+#include "../../include/flatland_train.h"
+#include "fl_tree_lstm.h"
+#include "fl_tree_lstm_bwd.h"
+
+struct FtlPtr {
+    const void *p;
+    const char *name;
+    int align;
+    bool may_be_null;
+};
+
+// sizes, then the pointers' NULLs and alignment in the table's order, then the workspace; `fn` names the caller in the message
+static int ftl_check(const char *fn, int n_trees, int n_nodes, int roots_only, const FtlPtr *tab, int n, size_t workspace_bytes,
+                     size_t need) {
+    if (n_trees <= 0 || n_nodes < 4 || n_nodes > FTL_MAX_N || n_trees > (INT32_MAX / FTL_MAX_N)) {
+        fl_set_error("%s: bad sizes (n_trees %d, n_nodes %d; 1 <= n_trees, 4 <= n_nodes <= %d)", fn, n_trees, n_nodes, FTL_MAX_N);
+        return FL_ERR_ARG;
+    }
+    if ((n_nodes - 1) % 3 != 0) {
+        fl_set_error("%s: n_nodes %d: (n_nodes - 1) %% 3 != 0, the reference pairs every level's nodes with edge triples", fn, n_nodes);
+        return FL_ERR_ARG;
+    }
+    if (roots_only != 0 && roots_only != 1) { fl_set_error("%s: roots_only must be 0 or 1", fn); return FL_ERR_ARG; }
+    for (int i = 0; i < n; i++) {
+        if (!tab[i].p && !tab[i].may_be_null) { fl_set_error("%s: %s is NULL", fn, tab[i].name); return FL_ERR_ARG; }
+        if ((uintptr_t)tab[i].p % tab[i].align) {
+            fl_set_error("%s: %s is not %d-byte aligned", fn, tab[i].name, tab[i].align);
+            return FL_ERR_ARG;
+        }
+    }
+    if (workspace_bytes < need) {
+        fl_set_error("%s: workspace of %zu bytes, %zu needed (%s_workspace_bytes)", fn, workspace_bytes, need, fn);
+        return FL_ERR_ARG;
+    }
+    return FL_OK;
+}
+
+// the members both kernels take; G from the current device's CU count (looked up once a device)
+static int ftl_trees(const char *fn, FtlTrees &a, int n_trees, int n_nodes, int roots_only, const float *forest,
+                     const int64_t *adjacency, const int64_t *node_order, const int64_t *edge_order, const float *const (&w)[8],
+                     int32_t *status) {
+    static int n_cu[64];
+    int dev = 0;
+    const hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) { fl_set_error("%s: hipGetDevice failed: %s", fn, hipGetErrorString(e)); return FL_ERR_HIP; }
+    if (dev >= 0 && dev < 64 && n_cu[dev] == 0 &&
+        hipDeviceGetAttribute(&n_cu[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n_cu[dev] = 0;
+    a.T = n_trees; a.N = n_nodes; a.roots_only = roots_only;
+    a.G = ftl_group(n_trees, dev >= 0 && dev < 64 ? n_cu[dev] : 0);
+    a.forest = forest;
+    a.adj = (const long long *)adjacency; a.no = (const long long *)node_order; a.eo = (const long long *)edge_order;
+    a.w_iou = w[0]; a.b_iou = w[1]; a.u_iou = w[2]; a.w_c = w[3]; a.b_c = w[4]; a.w_f = w[5]; a.b_f = w[6]; a.u_f = w[7];
+    a.status = (int *)status;
+    return FL_OK;
+}
+
+static int ftl_launched(const char *fn) {
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { fl_set_error("%s: launch failed: %s", fn, hipGetErrorString(e)); return FL_ERR_HIP; }
+    return FL_OK;
+}
+
+size_t fl_tree_lstm_workspace_bytes(int n_trees, int n_nodes, int roots_only) {
+    if (n_trees <= 0 || n_nodes <= 0) return 0;
+    return (size_t)n_trees * n_nodes * FTL_M * sizeof(float) * (roots_only ? 2 : 1);
+}
+
+int fl_tree_lstm(int n_trees, int n_nodes, const float *forest_dev, const int64_t *adjacency_dev, const int64_t *node_order_dev,
+                 const int64_t *edge_order_dev, const float *w_iou_dev, const float *b_iou_dev, const float *u_iou_dev,
+                 const float *w_c_dev, const float *b_c_dev, const float *w_f_dev, const float *b_f_dev, const float *u_f_dev,
+                 int roots_only, float *h_dev, float *c_dev, int32_t *status_dev, void *workspace_dev, size_t workspace_bytes,
+                 void *hip_stream) {
+    const char *fn = "fl_tree_lstm";
+    const FtlPtr tab[] = {{forest_dev, "forest", 16}, {w_iou_dev, "w_iou", 16}, {b_iou_dev, "b_iou", 16}, {u_iou_dev, "u_iou", 16},
+                          {w_c_dev, "w_c", 16}, {b_c_dev, "b_c", 16}, {w_f_dev, "w_f", 16}, {b_f_dev, "b_f", 16}, {u_f_dev, "u_f", 16},
+                          {h_dev, "h", 16}, {workspace_dev, "workspace", 16},
+                          {adjacency_dev, "adjacency", 8}, {node_order_dev, "node_order", 8}, {edge_order_dev, "edge_order", 8},
+                          {c_dev, "c", 16, true}, {status_dev, "status", 4, true}};
+    if (ftl_check(fn, n_trees, n_nodes, roots_only, tab, sizeof tab / sizeof tab[0], workspace_bytes,
+                  fl_tree_lstm_workspace_bytes(n_trees, n_nodes, roots_only)) != FL_OK) return FL_ERR_ARG;
+    FtlArgs a;
+    const int rc = ftl_trees(fn, a, n_trees, n_nodes, roots_only, forest_dev, adjacency_dev, node_order_dev, edge_order_dev,
+                             {w_iou_dev, b_iou_dev, u_iou_dev, w_c_dev, b_c_dev, w_f_dev, b_f_dev, u_f_dev}, status_dev);
+    if (rc != FL_OK) return rc;
+    a.h_out = h_dev; a.c_out = c_dev;
+    const size_t plane = (size_t)n_trees * n_nodes * FTL_M;
+    float *ws = (float *)workspace_dev;
+    if (roots_only) { a.hbuf = ws; a.cbuf = ws + plane; }
+    else { a.hbuf = h_dev; a.cbuf = c_dev ? c_dev : ws; }
+    fl_launch_tree_lstm(a, (hipStream_t)hip_stream);
+    return ftl_launched(fn);
+}
+
+size_t fl_tree_lstm_backward_workspace_bytes(int n_trees, int n_nodes) {
+    if (n_trees <= 0 || n_nodes <= 0) return 0;
+    return (size_t)n_trees * n_nodes * 6 * FTL_M * sizeof(float);
+}
+
+int fl_tree_lstm_backward(int n_trees, int n_nodes, const float *forest_dev, const int64_t *adjacency_dev,
+                          const int64_t *node_order_dev, const int64_t *edge_order_dev, const float *w_iou_dev,
+                          const float *b_iou_dev, const float *u_iou_dev, const float *w_c_dev, const float *b_c_dev,
+                          const float *w_f_dev, const float *b_f_dev, const float *u_f_dev, const float *h_dev, const float *c_dev,
+                          const float *grad_h_dev, int roots_only, float *da_dev, float *dc_dev, float *dg_dev, float *q_dev,
+                          int32_t *child_dev, int32_t *status_dev, void *workspace_dev, size_t workspace_bytes, void *hip_stream) {
+    const char *fn = "fl_tree_lstm_backward";
+    const FtlPtr tab[] = {{forest_dev, "forest", 16}, {w_iou_dev, "w_iou", 16}, {b_iou_dev, "b_iou", 16}, {u_iou_dev, "u_iou", 16},
+                          {w_c_dev, "w_c", 16}, {b_c_dev, "b_c", 16}, {w_f_dev, "w_f", 16}, {b_f_dev, "b_f", 16}, {u_f_dev, "u_f", 16},
+                          {h_dev, "h", 16}, {c_dev, "c", 16}, {grad_h_dev, "grad_h", 16}, {da_dev, "da", 16}, {dc_dev, "dc", 16},
+                          {dg_dev, "dg", 16}, {q_dev, "q", 16}, {workspace_dev, "workspace", 16},
+                          {adjacency_dev, "adjacency", 8}, {node_order_dev, "node_order", 8}, {edge_order_dev, "edge_order", 8},
+                          {child_dev, "child", 4}, {status_dev, "status", 4, true}};
+    if (ftl_check(fn, n_trees, n_nodes, roots_only, tab, sizeof tab / sizeof tab[0], workspace_bytes,
+                  fl_tree_lstm_backward_workspace_bytes(n_trees, n_nodes)) != FL_OK) return FL_ERR_ARG;
+    FtbArgs a;
+    const int rc = ftl_trees(fn, a, n_trees, n_nodes, roots_only, forest_dev, adjacency_dev, node_order_dev, edge_order_dev,
+                             {w_iou_dev, b_iou_dev, u_iou_dev, w_c_dev, b_c_dev, w_f_dev, b_f_dev, u_f_dev}, status_dev);
+    if (rc != FL_OK) return rc;
+    a.h = h_dev; a.c = c_dev; a.grad_h = grad_h_dev;
+    a.da = da_dev; a.dc = dc_dev; a.dg = dg_dev; a.q = q_dev; a.child = (int *)child_dev;
+    a.ghc = (float *)workspace_dev;
+    a.gcc = a.ghc + (size_t)n_trees * n_nodes * 3 * FTL_M;
+    fl_launch_tree_lstm_bwd(a, (hipStream_t)hip_stream);
+    return ftl_launched(fn);
+}
