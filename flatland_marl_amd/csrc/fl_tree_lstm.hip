@@ -1,12 +1,15 @@
-// fl_tree_lstm.hip -- entry points of the policy's tree encoder: fl_tree_lstm (include/flatland_hip.h) and its gradient
-// fl_tree_lstm_backward (include/flatland_train.h).  The checks (all before any HIP call) and the launches of the kernels in
-// fl_tree_lstm.h and fl_tree_lstm_bwd.h.  No env handle: plain pointers and sizes.
+// fl_tree_lstm.hip -- entry points of the policy's tree encoder: fl_tree_lstm (include/flatland_hip.h), its gradient
+// fl_tree_lstm_backward (include/flatland_train.h) and the inference forward with bf16 matrix operands, fl_tree_lstm_bf16 with
+// fl_tree_lstm_pack_bf16 (include/flatland_policy_bf16.h).  The checks (all before any HIP call) and the launches of the kernels in
+// fl_tree_lstm.h, fl_tree_lstm_bwd.h and fl_tree_lstm_bf16.h.  No env handle: plain pointers and sizes.
 #include <algorithm>
 
 #include "../../include/flatland_hip.h"
+#include "../../include/flatland_policy_bf16.h"
 #include "../../include/flatland_train.h"
 #include "fl_tree_lstm.h"
 #include "fl_tree_lstm_bwd.h"
+#include "fl_tree_lstm_bf16.h"
 
 struct FtlPtr {
     const void *p;
@@ -126,5 +129,59 @@ int fl_tree_lstm_backward(int n_trees, int n_nodes, const float *forest_dev, con
     a.ghc = (float *)workspace_dev;
     a.gcc = a.ghc + (size_t)n_trees * n_nodes * 3 * FTL_M;
     fl_launch_tree_lstm_bwd(a, (hipStream_t)hip_stream);
+    return ftl_launched(fn);
+}
+
+size_t fl_tree_lstm_bf16_packed_bytes(void) { return (size_t)FTL16_PACKED * sizeof(__bf16); }
+
+int fl_tree_lstm_pack_bf16(const float *u_iou_dev, const float *w_c_dev, const float *u_f_dev, void *packed_dev, size_t packed_bytes,
+                           void *hip_stream) {
+    const char *fn = "fl_tree_lstm_pack_bf16";
+    const FtlPtr tab[] = {{u_iou_dev, "u_iou", 16}, {w_c_dev, "w_c", 16}, {u_f_dev, "u_f", 16}, {packed_dev, "packed", 16}};
+    for (const FtlPtr &t : tab) {
+        if (!t.p) { fl_set_error("%s: %s is NULL", fn, t.name); return FL_ERR_ARG; }
+        if ((uintptr_t)t.p % t.align) { fl_set_error("%s: %s is not %d-byte aligned", fn, t.name, t.align); return FL_ERR_ARG; }
+    }
+    if (packed_bytes < fl_tree_lstm_bf16_packed_bytes()) {
+        fl_set_error("%s: packed buffer of %zu bytes, %zu needed (fl_tree_lstm_bf16_packed_bytes)", fn, packed_bytes,
+                     fl_tree_lstm_bf16_packed_bytes());
+        return FL_ERR_ARG;
+    }
+    fl_launch_tree_lstm_pack_bf16(u_iou_dev, w_c_dev, u_f_dev, packed_dev, (hipStream_t)hip_stream);
+    return ftl_launched(fn);
+}
+
+size_t fl_tree_lstm_bf16_workspace_bytes(int n_trees, int n_nodes, int roots_only) {
+    return fl_tree_lstm_workspace_bytes(n_trees, n_nodes, roots_only);
+}
+
+int fl_tree_lstm_bf16(int n_trees, int n_nodes, const float *forest_dev, const int64_t *adjacency_dev, const int64_t *node_order_dev,
+                      const int64_t *edge_order_dev, const float *w_iou_dev, const float *b_iou_dev, const float *b_c_dev,
+                      const float *w_f_dev, const float *b_f_dev, const void *packed_dev, size_t packed_bytes, int roots_only,
+                      float *h_dev, float *c_dev, int32_t *status_dev, void *workspace_dev, size_t workspace_bytes, void *hip_stream) {
+    const char *fn = "fl_tree_lstm_bf16";
+    const FtlPtr tab[] = {{forest_dev, "forest", 16}, {w_iou_dev, "w_iou", 16}, {b_iou_dev, "b_iou", 16}, {b_c_dev, "b_c", 16},
+                          {w_f_dev, "w_f", 16}, {b_f_dev, "b_f", 16}, {packed_dev, "packed", 16},
+                          {h_dev, "h", 16}, {workspace_dev, "workspace", 16},
+                          {adjacency_dev, "adjacency", 8}, {node_order_dev, "node_order", 8}, {edge_order_dev, "edge_order", 8},
+                          {c_dev, "c", 16, true}, {status_dev, "status", 4, true}};
+    if (ftl_check(fn, n_trees, n_nodes, roots_only, tab, sizeof tab / sizeof tab[0], workspace_bytes,
+                  fl_tree_lstm_bf16_workspace_bytes(n_trees, n_nodes, roots_only)) != FL_OK) return FL_ERR_ARG;
+    if (packed_bytes < fl_tree_lstm_bf16_packed_bytes()) {
+        fl_set_error("%s: packed buffer of %zu bytes, %zu needed (fl_tree_lstm_bf16_packed_bytes)", fn, packed_bytes,
+                     fl_tree_lstm_bf16_packed_bytes());
+        return FL_ERR_ARG;
+    }
+    Ftl16Args a;
+    const int rc = ftl_trees(fn, a, n_trees, n_nodes, roots_only, forest_dev, adjacency_dev, node_order_dev, edge_order_dev,
+                             {w_iou_dev, b_iou_dev, nullptr, nullptr, b_c_dev, w_f_dev, b_f_dev, nullptr}, status_dev);
+    if (rc != FL_OK) return rc;
+    a.packed = (const __bf16 *)packed_dev;
+    a.h_out = h_dev; a.c_out = c_dev;
+    const size_t plane = (size_t)n_trees * n_nodes * FTL_M;
+    float *ws = (float *)workspace_dev;
+    if (roots_only) { a.hbuf = ws; a.cbuf = ws + plane; }
+    else { a.hbuf = h_dev; a.cbuf = c_dev ? c_dev : ws; }
+    fl_launch_tree_lstm_bf16(a, (hipStream_t)hip_stream);
     return ftl_launched(fn);
 }

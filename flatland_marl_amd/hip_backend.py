@@ -102,12 +102,20 @@ _WRAPPERS_ABI = {
     "fl_action_space": ([vp, i32, i32, i32, vp, vp, vp, vp, vp, vp], i32),
     "fl_decision_cells": ([vp, i32, i32, vp], i32),
 }
+# ... of every function include/flatland_policy_bf16.h declares
+_POLICY_BF16_ABI = {
+    "fl_tree_lstm_bf16_packed_bytes": ([], C.c_size_t),
+    "fl_tree_lstm_pack_bf16": ([vp, vp, vp, vp, C.c_size_t, vp], i32),
+    "fl_tree_lstm_bf16_workspace_bytes": ([i32, i32, i32], C.c_size_t),
+    "fl_tree_lstm_bf16": ([i32, i32] + [vp] * 10 + [C.c_size_t, i32, vp, vp, vp, vp, C.c_size_t, vp], i32),
+}
 SYMBOLS = tuple(_ABI)      # every symbol include/flatland_hip.h declares
 POLICY_SYMBOLS = tuple(_POLICY_ABI)      # ... and include/flatland_policy.h
 TRAIN_SYMBOLS = tuple(_TRAIN_ABI)      # ... and include/flatland_train.h
 POLICY_TRAIN_SYMBOLS = tuple(_POLICY_TRAIN_ABI)      # ... and include/flatland_policy_train.h
 PREDICT_SYMBOLS = tuple(_PREDICT_ABI)      # ... and include/flatland_predict.h
 WRAPPERS_SYMBOLS = tuple(_WRAPPERS_ABI)      # ... and include/flatland_wrappers.h
+POLICY_BF16_SYMBOLS = tuple(_POLICY_BF16_ABI)      # ... and include/flatland_policy_bf16.h
 POLICY_HEAD_NPARAMS = 38
 POLICY_SELECT = {None: 0, "soft": 1, "hard": 2}
 POLICY_U_REFERENCE = 0.3745401188473625      # numpy.random.RandomState(42).random_sample(): the reference seeds before every draw
@@ -145,7 +153,7 @@ def lib():
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
         for name, (args, res) in {**_ABI, **_DEBUG_ABI, **_POLICY_ABI, **_TRAIN_ABI, **_POLICY_TRAIN_ABI, **_PREDICT_ABI,
-                                  **_WRAPPERS_ABI}.items():
+                                  **_WRAPPERS_ABI, **_POLICY_BF16_ABI}.items():
             fn = getattr(L, name, None)        # (a library from bench.py --lib or a tool's LIB_PATH may predate the newer ones)
             if fn is not None:
                 fn.argtypes, fn.restype = args, res
@@ -221,6 +229,59 @@ def tree_lstm(forest, adjacency, node_order, edge_order, weights, roots_only, h,
         s = torch.cuda.current_stream(forest.device).cuda_stream
         _chk(fn(T, N, forest.data_ptr(), adjacency.data_ptr(), node_order.data_ptr(), edge_order.data_ptr(),
                 *[w.data_ptr() for w in weights], int(roots_only), h.data_ptr(),
+                None if c is None else c.data_ptr(), None if status is None else status.data_ptr(),
+                ws.data_ptr(), ws.numel(), C.c_void_p(s)))
+    return h
+
+
+def tree_lstm_pack_bf16(weights, out=None):
+    """The three recurrent matrices rounded to bf16 in one buffer (fl_tree_lstm_pack_bf16, include/flatland_policy_bf16.h) on
+    torch's current stream of the weights' device.  weights: the eight tensors tree_lstm takes, of which U_iou.weight, W_c.weight and
+    U_f.weight (items 2, 3, 7) are read; out: a uint8 tensor of at least fl_tree_lstm_bf16_packed_bytes() bytes to pack into (None:
+    a new one).  Returns the packed buffer: pack again after the weights changed."""
+    import torch
+    if len(weights) != 8:
+        raise ValueError("tree_lstm_pack_bf16: %d weights, 8 expected" % len(weights))
+    u_iou, w_c, u_f = weights[2], weights[3], weights[7]
+    dev = u_iou.device
+    for name, w, n in (("U_iou.weight", u_iou, 384 * 384), ("W_c.weight", w_c, 128 * 384), ("U_f.weight", u_f, 128 * 128)):
+        if w.dtype != torch.float32 or w.device != dev or not w.is_contiguous() or w.numel() != n:
+            raise ValueError("tree_lstm_pack_bf16: %s must be a contiguous float32 tensor of %d elements on %s" % (name, n, dev))
+    fn = _sym("fl_tree_lstm_pack_bf16")
+    nbytes = _sym("fl_tree_lstm_bf16_packed_bytes")()
+    with torch.cuda.device(dev):
+        if out is None:
+            out = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        elif out.dtype != torch.uint8 or out.device != dev or not out.is_contiguous() or out.numel() < nbytes:
+            raise ValueError("tree_lstm_pack_bf16: out must be a contiguous uint8 tensor of at least %d elements on %s" % (nbytes, dev))
+        s = torch.cuda.current_stream(dev).cuda_stream
+        _chk(fn(u_iou.data_ptr(), w_c.data_ptr(), u_f.data_ptr(), out.data_ptr(), out.numel(), C.c_void_p(s)))
+    return out
+
+
+def tree_lstm_bf16(forest, adjacency, node_order, edge_order, weights, packed, roots_only, h, c=None, status=None):
+    """TreeLSTM.forward with bf16 matrix operands in the three recurrent products (fl_tree_lstm_bf16,
+    include/flatland_policy_bf16.h), for inference, on torch's current stream of the inputs' device, with a workspace from torch's
+    allocator.  Inputs, weights (the eight of tree_lstm: the five float32 ones are read), h, c and status as for tree_lstm; packed:
+    what tree_lstm_pack_bf16 made of the same weights."""
+    import torch
+    N = forest.shape[-2]
+    T = forest.numel() // (N * 12)
+    fn = _sym("fl_tree_lstm_bf16")
+    if len(weights) != 8:
+        raise ValueError("tree_lstm_bf16: %d weights, 8 expected" % len(weights))
+    rows = (T if roots_only else T * N) * 128
+    for name, o in (("h", h), ("c", c)):
+        if o is not None and (o.dtype != torch.float32 or o.device != forest.device or not o.is_contiguous() or o.numel() < rows):
+            raise ValueError("tree_lstm_bf16: %s must be a contiguous float32 tensor of at least %d elements on %s" % (name, rows, forest.device))
+    if packed.dtype != torch.uint8 or packed.device != forest.device or not packed.is_contiguous():
+        raise ValueError("tree_lstm_bf16: packed must be a contiguous uint8 tensor on %s (tree_lstm_pack_bf16)" % (forest.device,))
+    nbytes = _sym("fl_tree_lstm_bf16_workspace_bytes")(T, N, int(roots_only))
+    with torch.cuda.device(forest.device):
+        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=forest.device)
+        s = torch.cuda.current_stream(forest.device).cuda_stream
+        _chk(fn(T, N, forest.data_ptr(), adjacency.data_ptr(), node_order.data_ptr(), edge_order.data_ptr(),
+                *[weights[i].data_ptr() for i in (0, 1, 4, 5, 6)], packed.data_ptr(), packed.numel(), int(roots_only), h.data_ptr(),
                 None if c is None else c.data_ptr(), None if status is None else status.data_ptr(),
                 ws.data_ptr(), ws.numel(), C.c_void_p(s)))
     return h

@@ -21,6 +21,12 @@ parameter gradients as the same float32 block products, in chunks of whole envs 
 order.  agents_attr gets no gradient.  With both switches set one loss.backward() through Network.forward trains all 46 parameters
 without a torch eager op on the forward path; Network.forward_torch / head_torch stay the head through torch's eager ops.
 
+TreeLSTM(precision="bf16") (or m.precision = "bf16", Network(precision="bf16")) is the encoder for rolling out a trained policy:
+fl_tree_lstm_bf16 (include/flatland_policy_bf16.h) runs the three recurrent products U_iou h_k, U_f h_k and W_c (f * c_k) on the
+bf16 matrix instruction with float32 sums; W x, the biases, the gates and h / c stay float32, a leaf is computed as before.  The
+module packs the three matrices to bf16 on first use and again whenever one of them changed, so the promise above holds.  It is
+inference only: with trainable set it runs under torch.no_grad() and raises under grad mode.  The head stays float32.
+
 Swap it into the reference's Network:  net.tree_lstm = TreeLSTM.from_module(net.tree_lstm)
 or take the whole network:              net = Network.from_module(net)
 """
@@ -31,6 +37,7 @@ from . import hip_backend
 
 IN_FEATURES = 12      # FeatureParserConfig.node_sz
 OUT_FEATURES = 128    # NetworkConfig.tree_embedding_sz
+PRECISIONS = ("f32", "bf16")
 PARAM_ORDER = ("W_iou.weight", "W_iou.bias", "U_iou.weight", "W_c.weight", "W_c.bias", "W_f.weight", "W_f.bias", "U_f.weight")
 
 
@@ -140,15 +147,40 @@ class _Forward(torch.autograd.Function):
         raise NotImplementedError("TreeLSTM (fl_tree_lstm) is inference only: no backward")
 
 
+class _ForwardBf16(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, forest, adjacency, node_order, edge_order, roots_only, status, packed, *weights):
+        B, A, N = forest.shape[:3]
+        T = B * A
+        h = torch.empty((T if roots_only else T * N, OUT_FEATURES), dtype=torch.float32, device=forest.device)
+        hip_backend.tree_lstm_bf16(forest, adjacency, node_order, edge_order, weights, packed, roots_only, h, status=status)
+        return h
+
+    @staticmethod
+    def backward(ctx, *grads):
+        raise NotImplementedError("TreeLSTM (fl_tree_lstm_bf16) is inference only: no backward; training runs precision='f32'")
+
+
+def _precision(value):
+    if value not in PRECISIONS:
+        raise ValueError("TreeLSTM: precision must be 'f32' or 'bf16', got %r" % (value,))
+    return value
+
+
 class TreeLSTM(nn.Module):
     """TreeLSTM(in_features=12, out_features=128) on fl_tree_lstm; forward(forest, adjacency, node_order, edge_order) returns
     h of every node, [B*A*N, 128] f32, as the reference does; roots(...) returns node 0 of every tree, [B, A, 128].
     trainable (a plain attribute, settable): False = inference only, backward raises; True = with grad mode on, forward and roots
-    are differentiable with respect to the parameters (fl_tree_lstm_backward), their values the same bits as the inference path's."""
+    are differentiable with respect to the parameters (fl_tree_lstm_backward), their values the same bits as the inference path's.
+    precision (a plain attribute, settable): "f32" = fl_tree_lstm; "bf16" = fl_tree_lstm_bf16, the recurrent products with bf16
+    operands and float32 sums, inference only -- together with trainable it runs under torch.no_grad() and raises ValueError under
+    grad mode (training stays float32: the backward recomputes float32 gates from the saved h / c)."""
 
-    def __init__(self, in_features=IN_FEATURES, out_features=OUT_FEATURES, trainable=False):
+    def __init__(self, in_features=IN_FEATURES, out_features=OUT_FEATURES, trainable=False, precision="f32"):
         super().__init__()
         self.trainable = bool(trainable)
+        self.precision = _precision(precision)
+        self._packed = {}      # stream -> (what was packed, the bf16 buffer): see _packed_weights
         if (in_features, out_features) != (IN_FEATURES, OUT_FEATURES):
             raise ValueError("TreeLSTM: only in_features=%d, out_features=%d exist here, got %d, %d"
                              % (IN_FEATURES, OUT_FEATURES, in_features, out_features))
@@ -161,7 +193,7 @@ class TreeLSTM(nn.Module):
         self.U_f = nn.Linear(out_features, out_features, bias=False)
 
     @classmethod
-    def from_module(cls, m, trainable=False):
+    def from_module(cls, m, trainable=False, precision="f32"):
         """a TreeLSTM that shares m's parameters (m: the reference's TreeLSTM or one of these)"""
         if (m.in_features, m.out_features) != (IN_FEATURES, OUT_FEATURES):
             raise ValueError("TreeLSTM.from_module: only in_features=%d, out_features=%d exist here, got %d, %d"
@@ -170,6 +202,8 @@ class TreeLSTM(nn.Module):
         nn.Module.__init__(obj)
         obj.in_features, obj.out_features = m.in_features, m.out_features
         obj.trainable = bool(trainable)
+        obj.precision = _precision(precision)
+        obj._packed = {}
         for name in ("W_iou", "U_iou", "W_c", "W_f", "U_f"):
             setattr(obj, name, getattr(m, name))
         return obj
@@ -184,6 +218,20 @@ class TreeLSTM(nn.Module):
                                 % (name, device, w.dtype, w.device, "" if w.is_contiguous() else ", not contiguous"))
             ws.append(w)
         return ws
+
+    def _packed_weights(self, ws, device):
+        """the bf16 buffer of U_iou, W_c and U_f for torch's current stream: packed at the first use on that stream, and again when
+        one of the three is another tensor (data_ptr) or was written in place (_version) since -- load_state_dict and an optimizer
+        step both are; a write through `.data` bumps no version and is not seen (clear self._packed after one).  One buffer a
+        stream, packed and read on that stream only, so no launch waits on another stream's."""
+        stream = torch.cuda.current_stream(device)
+        key = tuple((w.data_ptr(), w._version) for w in (ws[2], ws[3], ws[7]))
+        slot = (device, stream.cuda_stream)
+        have = self._packed.get(slot)
+        if have is None or have[0] != key:
+            buf = hip_backend.tree_lstm_pack_bf16(ws, None if have is None else have[1])
+            self._packed[slot] = have = (key, buf)
+        return have[1]
 
     @staticmethod
     def _check_inputs(forest, adjacency, node_order, edge_order):
@@ -213,14 +261,22 @@ class TreeLSTM(nn.Module):
                              "each level's nodes with triples of its edges)" % N)
 
     def _run(self, forest, adjacency, node_order, edge_order, roots_only, check):
+        bf16 = _precision(self.precision) == "bf16"
+        train = self.trainable and torch.is_grad_enabled()
+        if bf16 and train:
+            raise ValueError("TreeLSTM: precision='bf16' is inference only (fl_tree_lstm_backward recomputes float32 gates): run it "
+                             "under torch.no_grad(), or train with precision='f32'")
         self._check_inputs(forest, adjacency, node_order, edge_order)
         ws = self._weights(forest.device)
         status = torch.zeros(1, dtype=torch.int32, device=forest.device) if check else None
-        train = self.trainable and torch.is_grad_enabled()
         if train and forest.requires_grad:
             raise ValueError("TreeLSTM: the forest gets no gradient (fl_tree_lstm_backward differentiates with respect to the "
                              "parameters only): detach it")
-        out = (_TrainForward if train else _Forward).apply(forest, adjacency, node_order, edge_order, roots_only, status, *ws)
+        if bf16:
+            out = _ForwardBf16.apply(forest, adjacency, node_order, edge_order, roots_only, status,
+                                     self._packed_weights(ws, forest.device), *ws)
+        else:
+            out = (_TrainForward if train else _Forward).apply(forest, adjacency, node_order, edge_order, roots_only, status, *ws)
         if check:
             bad = int(status.item())
             if bad:
@@ -402,24 +458,28 @@ class Network(nn.Module):
     trainable (a plain attribute, settable): False = the head is inference only, backward raises; True = with grad mode on, head
     and forward are differentiable with respect to the 38 head parameters and the tree embedding (fl_policy_head_forward_saved,
     fl_policy_head_backward), their values the same bits as the inference path's.  With tree_lstm.trainable set as well one
-    loss.backward() trains all 46 parameters."""
+    loss.backward() trains all 46 parameters.
+    precision: the tree encoder's (tree_lstm.precision, which stays settable): "bf16" = fl_tree_lstm_bf16 for roll-outs.  Only the
+    encoder has a bf16 path: the head (fl_policy_head) stays float32 whatever the precision."""
 
-    def __init__(self, trainable=False):
+    def __init__(self, trainable=False, precision="f32"):
         super().__init__()
         self.trainable = bool(trainable)
-        self.tree_lstm = TreeLSTM(IN_FEATURES, OUT_FEATURES)
+        self.tree_lstm = TreeLSTM(IN_FEATURES, OUT_FEATURES, precision=precision)
         self.attr_embedding = _mlp((AGENT_ATTR, 2 * HIDDEN, 2 * HIDDEN, 2 * HIDDEN, HIDDEN), True)
         self.transformer = nn.Sequential(*[Transformer(EMBED, HEADS) for _ in range(3)])
         self.actor_net = _mlp((2 * EMBED, 2 * HIDDEN, HIDDEN, ACTIONS), False)
         self.critic_net = _mlp((2 * EMBED, 2 * HIDDEN, HIDDEN, 1), False)
 
     @classmethod
-    def from_module(cls, m, trainable=False):
-        """a Network that shares m's parameters (m: the reference's Network or one of these)"""
+    def from_module(cls, m, trainable=False, precision=None):
+        """a Network that shares m's parameters (m: the reference's Network or one of these); precision: the tree encoder's, None =
+        m.tree_lstm's own ("f32" for the reference's)"""
         obj = cls.__new__(cls)
         nn.Module.__init__(obj)
         obj.trainable = bool(trainable)
-        obj.tree_lstm = TreeLSTM.from_module(m.tree_lstm, trainable=getattr(m.tree_lstm, "trainable", False))
+        obj.tree_lstm = TreeLSTM.from_module(m.tree_lstm, trainable=getattr(m.tree_lstm, "trainable", False),
+                                             precision=getattr(m.tree_lstm, "precision", "f32") if precision is None else precision)
         obj.attr_embedding = m.attr_embedding
         blocks = []
         for b in m.transformer:
