@@ -845,9 +845,7 @@ __device__ __forceinline__ void obs_body(const FlDev &d, const FlObsScratch &S, 
                 int loc[PER], tot = 0;
 #pragma unroll
                 for (int q = 0; q < PER; q++) { loc[q] = q < per ? partial[lane * per + q] : 0; tot += loc[q]; }
-                int incl = tot;
-#pragma unroll
-                for (int off = 1; off < 64; off <<= 1) { const int v = __shfl_up(incl, off); if (lane >= off) incl += v; }
+                const int incl = wave_incl_scan<64>(tot);
                 int run = incl - tot;
 #pragma unroll
                 for (int q = 0; q < PER; q++) { if (q < per) partial[lane * per + q] = run; run += loc[q]; }
@@ -891,9 +889,7 @@ __device__ __forceinline__ void obs_body(const FlDev &d, const FlObsScratch &S, 
                 int loc[PER], tot = 0;
 #pragma unroll
                 for (int q = 0; q < PER; q++) { loc[q] = q < per ? partial[lane * per + q] : 0; tot += loc[q]; }
-                int incl = tot;
-#pragma unroll
-                for (int off = 1; off < 64; off <<= 1) { const int v = __shfl_up(incl, off); if (lane >= off) incl += v; }
+                const int incl = wave_incl_scan<64>(tot);
                 int run = incl - tot;
 #pragma unroll
                 for (int q = 0; q < PER; q++) { if (q < per) partial[lane * per + q] = run; run += loc[q]; }
@@ -1002,10 +998,7 @@ __device__ __forceinline__ void obs_body(const FlDev &d, const FlObsScratch &S, 
                     const int per = (A + 63) >> 6, a_lo = min(lane * per, A), a_hi = min(a_lo + per, A);
                     int sum = 0;
                     for (int ia = a_lo; ia < a_hi; ia++) sum += pre16[ia + 1];
-                    int incl = sum;
-#pragma unroll
-                    for (int off = 1; off < 64; off <<= 1) { const int v = __shfl_up(incl, off); if (lane >= off) incl += v; }
-                    int run = incl - sum;
+                    int run = wave_incl_scan<64>(sum) - sum;
                     for (int ia = a_lo; ia < a_hi; ia++) { run += pre16[ia + 1]; pre16[ia + 1] = (uint16_t)run; }
                 }
                 __syncthreads();

@@ -81,6 +81,23 @@ struct ObsCtx {
     int dbg_base;
 };
 
+// Inclusive prefix sum over every segment of W consecutive lanes (16, 32 or 64) of a wavefront, all 64 lanes active.  Data-parallel
+// primitives instead of log2(W) dependent __shfl_up steps: a shuffle is a ds_bpermute, an LDS round trip, and the scans of the trees
+// phase sit where every wavefront of the workgroup waits for them (behind a barrier, in front of the classify loop).  row_shr:n shifts
+// inside a row of 16 lanes (a lane without a source adds 0), row_bcast:15 adds lane 15 of rows 0 / 2 to rows 1 / 3, row_bcast:31 lane
+// 31 to rows 2 and 3 -- the same sums in another order of additions (integers: the same bits).
+template <int W>
+__device__ __forceinline__ int wave_incl_scan(int v) {
+    static_assert(W == 16 || W == 32 || W == 64, "segments of 16, 32 or 64 lanes");
+    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);   // row_shr:1
+    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);   // row_shr:2
+    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false);   // row_shr:4
+    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);   // row_shr:8
+    if (W >= 32) v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);   // row_bcast:15 into rows 1 and 3
+    if (W >= 64) v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);   // row_bcast:31 into rows 2 and 3
+    return v;
+}
+
 // The observation tensors are written once and never read back by the kernel: their stores carry the non-temporal hint (round 5;
 // -DOBS_NO_NT_STORES: plain stores), so that a gigabyte of rows streaming through the L2 does not push out the lines the launch keeps
 // coming back to -- the shared static tables, the prediction items, the work lists' tails, the next step's state.  Same box: cfg3

@@ -226,10 +226,7 @@ __device__ __forceinline__ int team_prepare(bool have, int tl, int n_nodes, int 
 #pragma unroll
     for (int c = 0; c < NCH; c++) {
         const int k = c * TEAM + tl;
-        int incl = v[c];
-#pragma unroll
-        for (int off = 1; off < TEAM; off <<= 1) { const int u = __shfl_up(incl, off, TEAM); if (tl >= off) incl += u; }
-        incl += run_base;
+        int incl = wave_incl_scan<TEAM>(v[c]) + run_base;
         int nxt = 0xFF;
 #pragma unroll
         for (int c2 = NCH - 1; c2 > c; c2--)
@@ -302,9 +299,7 @@ __device__ __forceinline__ void wg_pass_b(const ObsCtx &X, int tid, int nt, int 
     const int lane = tid & 63;
     // inclusive prefix over the teams' cell counts, one team per lane (n_teams <= 64); every wavefront computes it
     const int tv = lane < n_teams ? team_meta[lane] : 0;
-    int tincl = tv;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { const int u = __shfl_up(tincl, off); if (lane >= off) tincl += u; }
+    const int tincl = wave_incl_scan<64>(tv);
     const int total = __builtin_amdgcn_readlane(tincl, 63);
     // the lanes' slices (fl_obs_slices.h): total / nt cells each and one more for the first total % nt lanes
     const PbSplit split = pb_split(total, nt, X.pb_ceil_split);
@@ -605,14 +600,7 @@ __device__ __forceinline__ void wg_pass_b(const ObsCtx &X, int tid, int nt, int 
                 atomicMin(&nt_w(sc, cap, N_PC, (int)(w.y >> 24)), tot);
             }
         }
-        WAVE_MARK(X, 13, 17);
-        WL_ACC(X, 1);
-        late();
-        WL_ACC(X, 2);
-        __syncthreads();
-        WL_ACC(X, 5);
-        return;
-    }
+    } else {
     constexpr int CF_CHUNK = ITL ? CF_CHUNK_LDS : CF_CHUNK_HBM;
     // ... and the lane of the first entry takes CF_FIRST items itself (more than one chunk's worth measured slower: the wavefront waits
     // for its longest scan)
@@ -675,11 +663,18 @@ __device__ __forceinline__ void wg_pass_b(const ObsCtx &X, int tid, int nt, int 
             }
         }
     }
+    }
+    // (ONE call site for both ways through the conflict entries: late() is a few thousand instructions of inlined code)
     WAVE_MARK(X, 13, 17);
     WL_ACC(X, 1);
     late();
     WL_ACC(X, 2);
     __syncthreads();
+    if (*X.long_lists == 0) {  // (no further chunks were pushed)
+        WL_ACC(X, 5);
+        return;
+    }
+    constexpr int CF_CHUNK = ITL ? CF_CHUNK_LDS : CF_CHUNK_HBM, CF_FIRST = ITL ? CF_CHUNK_LDS : CF_FIRST_HBM;
     WAVE_MARK(X, 14, -1);
     WL_ACC(X, 3);
     const int n_cf2 = min(X.wl_cnt[1], X.wl_cf_cap);   // (workgroup-uniform)

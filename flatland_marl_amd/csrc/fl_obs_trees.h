@@ -541,7 +541,7 @@ __device__ __forceinline__ void trees_merged(ObsCtx &X, const FlDev &d, const Ob
             if (u >= 0 && tl == 0) { team_meta[id] = have_u ? cells : 0; team_meta[64 + id] = have_u ? ns : 1; team_meta[256 + id] = first; }
         }
         wg_pass_b<UP ? 2 : 3, OBS_CAP_C, ITL, LATE, MULTI>(X, wave * 64 + lane, nwaves * 64, UP ? 2 * ROUND : ROUND, wave_scr, 0, team_meta, late);
-        if (base == 0) late();  // (whatever the queue still holds)
+        // (the late queue is empty here: every wavefront took jobs in wg_pass_b until none were left and did its own before the step's last barrier)
         TREE_STAMP(X, 7);
         if (MULTI || !OBS_TOPO_JOBS) {
             if (ct < ROUND) cutils_rows_orders<OBS_CAP_C, !UP>(X, d, P, b, i_c, have_c, gl, scr_c, node_base, levels, max_dist);
