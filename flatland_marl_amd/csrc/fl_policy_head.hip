@@ -1,8 +1,11 @@
 // fl_policy_head.hip -- entry points of include/flatland_policy.h and include/flatland_policy_train.h: the checks (all before any
-// HIP call) and the launches of the kernels in fl_policy_head.h and fl_policy_head_bwd.h.
+// HIP call) and the launches of the kernels in fl_policy_head.h and fl_policy_head_bwd.h; behind them those of
+// include/flatland_policy_head_bf16.h and fl_policy_head_bf16.h.
 #include "../../include/flatland_policy.h"
 #include "../../include/flatland_policy_train.h"
+#include "../../include/flatland_policy_head_bf16.h"
 #include "fl_policy_head.h"
+#include "fl_policy_head_bf16.h"
 #include "fl_policy_head_bwd.h"
 
 size_t fl_policy_head_workspace_bytes(int n_envs, int n_agents) {
@@ -27,6 +30,19 @@ static int fph_check(const char *fn, int n_envs, int n_agents, const float *cons
         if (!params[i]) { fl_set_error("%s: parameter %d is NULL", fn, i); return FL_ERR_ARG; }
         if ((uintptr_t)params[i] % 16) { fl_set_error("%s: parameter %d is not 16-byte aligned", fn, i); return FL_ERR_ARG; }
     }
+    return FL_OK;
+}
+
+// value, select, the mask, the actions and u of fl_policy_head and fl_policy_head_bf16
+static int fph_check_choice(const char *fn, const float *value_dev, const uint8_t *valid_actions_dev, int select, double u,
+                            const uint8_t *actions_dev) {
+    if (value_dev && (uintptr_t)value_dev % 16) { fl_set_error("%s: value is not 16-byte aligned", fn); return FL_ERR_ARG; }
+    if (select < 0 || select > 2) { fl_set_error("%s: select must be 0 (none), 1 (soft) or 2 (hard), got %d", fn, select); return FL_ERR_ARG; }
+    if (select != 0 && (!valid_actions_dev || !actions_dev)) {
+        fl_set_error("%s: select %d needs valid_actions and actions", fn, select);
+        return FL_ERR_ARG;
+    }
+    if (!(u >= 0.0 && u < 1.0)) { fl_set_error("%s: u must be in [0, 1), got %g", fn, u); return FL_ERR_ARG; }
     return FL_OK;
 }
 
@@ -67,13 +83,7 @@ int fl_policy_head(int n_envs, int n_agents, const float *attr_dev, const float 
     const void *f16[] = {attr_dev, tree_dev, logits_dev, workspace_dev};
     const char *f16n[] = {"attr", "tree", "logits", "workspace"};
     if (fph_check("fl_policy_head", n_envs, n_agents, params, f16, f16n, 4) != FL_OK) return FL_ERR_ARG;
-    if (value_dev && (uintptr_t)value_dev % 16) { fl_set_error("fl_policy_head: value is not 16-byte aligned"); return FL_ERR_ARG; }
-    if (select < 0 || select > 2) { fl_set_error("fl_policy_head: select must be 0 (none), 1 (soft) or 2 (hard), got %d", select); return FL_ERR_ARG; }
-    if (select != 0 && (!valid_actions_dev || !actions_dev)) {
-        fl_set_error("fl_policy_head: select %d needs valid_actions and actions", select);
-        return FL_ERR_ARG;
-    }
-    if (!(u >= 0.0 && u < 1.0)) { fl_set_error("fl_policy_head: u must be in [0, 1), got %g", u); return FL_ERR_ARG; }
+    if (fph_check_choice("fl_policy_head", value_dev, valid_actions_dev, select, u, actions_dev) != FL_OK) return FL_ERR_ARG;
     const size_t need = fl_policy_head_workspace_bytes(n_envs, n_agents);
     if (workspace_bytes < need) {
         fl_set_error("fl_policy_head: workspace of %zu bytes, %zu needed (fl_policy_head_workspace_bytes)", workspace_bytes, need);
@@ -202,6 +212,99 @@ int fl_policy_head_backward(int n_envs, int n_agents, const float *attr_dev, con
         hipLaunchKernelGGL(k_pb_inproj, dim3(tiles), dim3(FPH_THREADS), FPB_LDS_INPROJ, s, a, blk);
     }
     hipLaunchKernelGGL(k_pb_attr, dim3(tiles), dim3(FPH_THREADS), FPB_LDS_ATTR, s, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { fl_set_error("%s: launch failed: %s", fn, hipGetErrorString(e)); return FL_ERR_HIP; }
+    return FL_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- bf16 inference
+size_t fl_policy_head_bf16_packed_bytes(void) { return (size_t)FPH16_PACKED * sizeof(__bf16); }
+
+size_t fl_policy_head_bf16_workspace_bytes(int n_envs, int n_agents) {
+    if (n_envs <= 0 || n_agents <= 0) return 0;
+    const size_t R = (size_t)n_envs * n_agents;
+    return (R * FPH16_ROW_BYTES + 15) / 16 * 16;
+}
+
+// the parameter index and K of the 16 packed matrices, in state_dict order
+static const int FPH16_SRC[FPH16_NMAT] = {2, 4, 6, 8, 10, 12, 14, 16, 18, 20, 22, 24, 26, 28, 32, 34};
+static const int FPH16_K[FPH16_NMAT] = {256, 256, 256, 256, 256, 512, 256, 256, 512, 256, 256, 512, 512, 256, 512, 256};
+static const int FPH16_ROWS_OF[FPH16_NMAT] = {256, 256, 128, 768, 256, 256, 768, 256, 256, 768, 256, 256, 256, 128, 256, 128};
+
+int fl_policy_head_pack_bf16(const float *const *params, void *packed_dev, size_t packed_bytes, void *hip_stream) {
+    const char *fn = "fl_policy_head_pack_bf16";
+    if (!params) { fl_set_error("%s: params is NULL", fn); return FL_ERR_ARG; }
+    for (int m = 0; m < FPH16_NMAT; m++) {
+        const int i = FPH16_SRC[m];
+        if (!params[i]) { fl_set_error("%s: parameter %d is NULL", fn, i); return FL_ERR_ARG; }
+        if ((uintptr_t)params[i] % 16) { fl_set_error("%s: parameter %d is not 16-byte aligned", fn, i); return FL_ERR_ARG; }
+    }
+    if (!packed_dev) { fl_set_error("%s: packed is NULL", fn); return FL_ERR_ARG; }
+    if ((uintptr_t)packed_dev % 16) { fl_set_error("%s: packed is not 16-byte aligned", fn); return FL_ERR_ARG; }
+    if (packed_bytes < fl_policy_head_bf16_packed_bytes()) {
+        fl_set_error("%s: packed buffer of %zu bytes, %zu needed (fl_policy_head_bf16_packed_bytes)", fn, packed_bytes,
+                     fl_policy_head_bf16_packed_bytes());
+        return FL_ERR_ARG;
+    }
+    Fph16Pack a;
+    int off = 0;
+    for (int m = 0; m < FPH16_NMAT; m++) {
+        a.src[m] = params[FPH16_SRC[m]]; a.K[m] = FPH16_K[m]; a.off[m] = off;
+        off += FPH16_ROWS_OF[m] * FPH16_K[m];
+    }
+    a.off[FPH16_NMAT] = off;
+    hipLaunchKernelGGL(k_ph16_pack, dim3((FPH16_PACKED + 255) / 256), dim3(256), 0, (hipStream_t)hip_stream, a, (__bf16 *)packed_dev);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { fl_set_error("%s: launch failed: %s", fn, hipGetErrorString(e)); return FL_ERR_HIP; }
+    return FL_OK;
+}
+
+int fl_policy_head_bf16(int n_envs, int n_agents, const float *attr_dev, const float *tree_dev, const float *const *params,
+                        const void *packed_dev, size_t packed_bytes, const uint8_t *valid_actions_dev, int select, double u,
+                        float *logits_dev, float *value_dev, uint8_t *actions_dev, void *workspace_dev, size_t workspace_bytes,
+                        void *hip_stream) {
+    const char *fn = "fl_policy_head_bf16";
+    const void *f16[] = {attr_dev, tree_dev, logits_dev, workspace_dev, packed_dev};
+    const char *f16n[] = {"attr", "tree", "logits", "workspace", "packed"};
+    if (fph_check(fn, n_envs, n_agents, params, f16, f16n, 5) != FL_OK) return FL_ERR_ARG;
+    if (fph_check_choice(fn, value_dev, valid_actions_dev, select, u, actions_dev) != FL_OK) return FL_ERR_ARG;
+    const size_t need = fl_policy_head_bf16_workspace_bytes(n_envs, n_agents);
+    if (workspace_bytes < need) {
+        fl_set_error("%s: workspace of %zu bytes, %zu needed (fl_policy_head_bf16_workspace_bytes)", fn, workspace_bytes, need);
+        return FL_ERR_ARG;
+    }
+    if (packed_bytes < fl_policy_head_bf16_packed_bytes()) {
+        fl_set_error("%s: packed buffer of %zu bytes, %zu needed (fl_policy_head_bf16_packed_bytes)", fn, packed_bytes,
+                     fl_policy_head_bf16_packed_bytes());
+        return FL_ERR_ARG;
+    }
+
+    Fph16Args a;
+    a.B = n_envs; a.A = n_agents; a.R = n_envs * n_agents;
+    a.select = select; a.u = u;
+    a.attr = attr_dev; a.tree = tree_dev;
+    for (int i = 0; i < FPH_NPARAMS; i++) a.p[i] = params[i];
+    a.valid = valid_actions_dev; a.logits = logits_dev; a.value = value_dev; a.actions = actions_dev;
+    const size_t R = (size_t)a.R;
+    float *ws = (float *)workspace_dev;
+    a.emb = ws; a.xa = ws + R * FPH_E; a.xb = ws + 2 * R * FPH_E; a.ao = ws + 3 * R * FPH_E;
+    a.qkv = nullptr; a.y3 = nullptr;
+    a.qkv16 = (__bf16 *)(ws + 4 * R * FPH_E);
+    a.val = (float *)(a.qkv16 + R * 3 * FPH_E);
+    a.packed = (const __bf16 *)packed_dev;
+
+    hipStream_t s = (hipStream_t)hip_stream;
+    const int tiles = (a.R + FPH_ROWS - 1) / FPH_ROWS;
+    const int qtiles = a.B * ((a.A + FPH_ROWS - 1) / FPH_ROWS);
+    hipLaunchKernelGGL(k_ph16_embed, dim3(tiles), dim3(FPH_THREADS), 0, s, a);
+    const float *xin[3] = {a.emb, a.xa, a.xb};
+    float *xout[3] = {a.xa, a.xb, nullptr};
+    for (int blk = 0; blk < 3; blk++) {
+        hipLaunchKernelGGL(k_ph16_attn, dim3(qtiles), dim3(FPH_THREADS), 0, s, a);
+        if (blk < 2) hipLaunchKernelGGL(k_ph16_block<false>, dim3(tiles), dim3(FPH_THREADS), 0, s, a, blk, xin[blk], xout[blk]);
+        else hipLaunchKernelGGL(k_ph16_block<true>, dim3(tiles), dim3(FPH_THREADS), 0, s, a, blk, xin[blk], xout[blk]);
+    }
+    if (a.value) hipLaunchKernelGGL(k_ph_value, dim3(a.B), dim3(64), 0, s, (FphArgs)a);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { fl_set_error("%s: launch failed: %s", fn, hipGetErrorString(e)); return FL_ERR_HIP; }
     return FL_OK;

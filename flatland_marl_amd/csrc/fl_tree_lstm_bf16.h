@@ -34,15 +34,9 @@
 #define FTL16_UNROLL 4                                  // K = 16 steps whose loads are issued together
 #endif
 
-typedef __bf16 fl_bf16x8 __attribute__((ext_vector_type(8)));
-
 struct Ftl16Args : FtlArgs {
     const __bf16 *packed;           // fl_tree_lstm_pack_bf16's buffer; u_iou, w_c, u_f of FtlTrees are NULL
 };
-
-__device__ __forceinline__ fl_f32x16 fl_mfma_bf16(fl_bf16x8 a, fl_bf16x8 b, fl_f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
 
 // this lane's operands of step 0 of block `block` of a packed matrix of K columns
 template <int K>

@@ -109,6 +109,13 @@ _POLICY_BF16_ABI = {
     "fl_tree_lstm_bf16_workspace_bytes": ([i32, i32, i32], C.c_size_t),
     "fl_tree_lstm_bf16": ([i32, i32] + [vp] * 10 + [C.c_size_t, i32, vp, vp, vp, vp, C.c_size_t, vp], i32),
 }
+# ... of every function include/flatland_policy_head_bf16.h declares
+_POLICY_HEAD_BF16_ABI = {
+    "fl_policy_head_bf16_packed_bytes": ([], C.c_size_t),
+    "fl_policy_head_pack_bf16": ([C.POINTER(vp), vp, C.c_size_t, vp], i32),
+    "fl_policy_head_bf16_workspace_bytes": ([i32, i32], C.c_size_t),
+    "fl_policy_head_bf16": ([i32, i32, vp, vp, C.POINTER(vp), vp, C.c_size_t, vp, i32, C.c_double, vp, vp, vp, vp, C.c_size_t, vp], i32),
+}
 SYMBOLS = tuple(_ABI)      # every symbol include/flatland_hip.h declares
 POLICY_SYMBOLS = tuple(_POLICY_ABI)      # ... and include/flatland_policy.h
 TRAIN_SYMBOLS = tuple(_TRAIN_ABI)      # ... and include/flatland_train.h
@@ -116,7 +123,10 @@ POLICY_TRAIN_SYMBOLS = tuple(_POLICY_TRAIN_ABI)      # ... and include/flatland_
 PREDICT_SYMBOLS = tuple(_PREDICT_ABI)      # ... and include/flatland_predict.h
 WRAPPERS_SYMBOLS = tuple(_WRAPPERS_ABI)      # ... and include/flatland_wrappers.h
 POLICY_BF16_SYMBOLS = tuple(_POLICY_BF16_ABI)      # ... and include/flatland_policy_bf16.h
+POLICY_HEAD_BF16_SYMBOLS = tuple(_POLICY_HEAD_BF16_ABI)      # ... and include/flatland_policy_head_bf16.h
 POLICY_HEAD_NPARAMS = 38
+# the 16 matrices fl_policy_head_pack_bf16 rounds, as indices into the 38 parameters, in the packed buffer's order
+POLICY_HEAD_BF16_MATRICES = (2, 4, 6, 8, 10, 12, 14, 16, 18, 20, 22, 24, 26, 28, 32, 34)
 POLICY_SELECT = {None: 0, "soft": 1, "hard": 2}
 POLICY_U_REFERENCE = 0.3745401188473625      # numpy.random.RandomState(42).random_sample(): the reference seeds before every draw
 
@@ -153,7 +163,7 @@ def lib():
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
         for name, (args, res) in {**_ABI, **_DEBUG_ABI, **_POLICY_ABI, **_TRAIN_ABI, **_POLICY_TRAIN_ABI, **_PREDICT_ABI,
-                                  **_WRAPPERS_ABI, **_POLICY_BF16_ABI}.items():
+                                  **_WRAPPERS_ABI, **_POLICY_BF16_ABI, **_POLICY_HEAD_BF16_ABI}.items():
             fn = getattr(L, name, None)        # (a library from bench.py --lib or a tool's LIB_PATH may predate the newer ones)
             if fn is not None:
                 fn.argtypes, fn.restype = args, res
@@ -350,6 +360,65 @@ def policy_head(agents_attr, tree_embedding, params, logits, value=None, valid_a
         _chk(fn(B, A, agents_attr.data_ptr(), tree_embedding.data_ptr(), ptrs, opt(valid_actions), POLICY_SELECT[mode],
                 POLICY_U_REFERENCE if u is None else float(u), logits.data_ptr(), opt(value), opt(actions), ws.data_ptr(),
                 ws.numel(), C.c_void_p(s)))
+    return logits
+
+
+def policy_head_pack_bf16(weights, out=None):
+    """The head's 16 bf16 matrices in one buffer (fl_policy_head_pack_bf16, include/flatland_policy_head_bf16.h) on torch's current
+    stream of the weights' device.  weights: the 38 tensors policy_head takes, of which POLICY_HEAD_BF16_MATRICES are read; out: a
+    uint8 tensor of at least fl_policy_head_bf16_packed_bytes() bytes to pack into (None: a new one).  Returns the packed buffer:
+    pack again after the weights changed."""
+    import torch
+    if len(weights) != POLICY_HEAD_NPARAMS:
+        raise ValueError("policy_head_pack_bf16: %d parameters, %d expected" % (len(weights), POLICY_HEAD_NPARAMS))
+    dev = weights[POLICY_HEAD_BF16_MATRICES[0]].device
+    for i in POLICY_HEAD_BF16_MATRICES:
+        w = weights[i]
+        if w.dtype != torch.float32 or w.device != dev or not w.is_contiguous() or w.dim() != 2:
+            raise ValueError("policy_head_pack_bf16: parameter %d must be a contiguous float32 matrix on %s" % (i, dev))
+    fn = _sym("fl_policy_head_pack_bf16")
+    nbytes = _sym("fl_policy_head_bf16_packed_bytes")()
+    if sum(weights[i].numel() for i in POLICY_HEAD_BF16_MATRICES) * 2 != nbytes:
+        raise ValueError("policy_head_pack_bf16: the 16 matrices must have %d elements together" % (nbytes // 2))
+    ptrs = (vp * POLICY_HEAD_NPARAMS)(*[None if w is None else w.data_ptr() for w in weights])
+    with torch.cuda.device(dev):
+        if out is None:
+            out = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        elif out.dtype != torch.uint8 or out.device != dev or not out.is_contiguous() or out.numel() < nbytes:
+            raise ValueError("policy_head_pack_bf16: out must be a contiguous uint8 tensor of at least %d elements on %s" % (nbytes, dev))
+        s = torch.cuda.current_stream(dev).cuda_stream
+        _chk(fn(ptrs, out.data_ptr(), out.numel(), C.c_void_p(s)))
+    return out
+
+
+def policy_head_bf16(agents_attr, tree_embedding, params, packed, logits, value=None, valid_actions=None, actions=None, mode=None,
+                     u=None):
+    """policy_head with bf16 matrix operands in 16 of its 19 matrices (fl_policy_head_bf16, include/flatland_policy_head_bf16.h),
+    for inference, on torch's current stream of the inputs' device, with a workspace from torch's allocator.  The arguments of
+    policy_head; packed: what policy_head_pack_bf16 made of the same params."""
+    import torch
+    B, A = agents_attr.shape[:2]
+    fn = _sym("fl_policy_head_bf16")
+    if mode not in POLICY_SELECT:
+        raise ValueError("policy_head_bf16: mode must be None, 'soft' or 'hard', got %r" % (mode,))
+    if len(params) != POLICY_HEAD_NPARAMS:
+        raise ValueError("policy_head_bf16: %d parameters, %d expected" % (len(params), POLICY_HEAD_NPARAMS))
+    dev = agents_attr.device
+    for name, o, dt, n in (("logits", logits, torch.float32, B * A * 5), ("value", value, torch.float32, B),
+                           ("valid_actions", valid_actions, torch.uint8, B * A * 5), ("actions", actions, torch.uint8, B * A)):
+        if o is not None and (o.dtype != dt or o.device != dev or not o.is_contiguous() or o.numel() < n):
+            raise ValueError("policy_head_bf16: %s must be a contiguous %s tensor of at least %d elements on %s" % (name, dt, n, dev))
+    if packed.dtype != torch.uint8 or packed.device != dev or not packed.is_contiguous():
+        raise ValueError("policy_head_bf16: packed must be a contiguous uint8 tensor on %s (policy_head_pack_bf16)" % (dev,))
+    ptrs = (vp * POLICY_HEAD_NPARAMS)(*[w.data_ptr() for w in params])
+    nbytes = _sym("fl_policy_head_bf16_workspace_bytes")(B, A)
+    opt = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    with torch.cuda.device(dev):
+        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+        s = torch.cuda.current_stream(dev).cuda_stream
+        _chk(fn(B, A, agents_attr.data_ptr(), tree_embedding.data_ptr(), ptrs, packed.data_ptr(), packed.numel(), opt(valid_actions),
+                POLICY_SELECT[mode], POLICY_U_REFERENCE if u is None else float(u), logits.data_ptr(), opt(value), opt(actions),
+                ws.data_ptr(), ws.numel(), C.c_void_p(s)))
     return logits
 
 

@@ -25,7 +25,13 @@ TreeLSTM(precision="bf16") (or m.precision = "bf16", Network(precision="bf16")) 
 fl_tree_lstm_bf16 (include/flatland_policy_bf16.h) runs the three recurrent products U_iou h_k, U_f h_k and W_c (f * c_k) on the
 bf16 matrix instruction with float32 sums; W x, the biases, the gates and h / c stay float32, a leaf is computed as before.  The
 module packs the three matrices to bf16 on first use and again whenever one of them changed, so the promise above holds.  It is
-inference only: with trainable set it runs under torch.no_grad() and raises under grad mode.  The head stays float32.
+inference only: with trainable set it runs under torch.no_grad() and raises under grad mode.  The head stays float32 under it.
+
+Network(head_precision="bf16") (or net.head_precision = "bf16") is the same for the head: fl_policy_head_bf16
+(include/flatland_policy_head_bf16.h) runs 16 of the head's 19 matrices -- everything but attr_embedding.0 and the two heads' last
+layers -- and the attention's two products on the bf16 matrix instruction with float32 sums; biases, GELU, the softmax's maxima, exp
+and sums stay float32, q k v are kept in bf16.  The module packs the 16 matrices on first use and again whenever one of them changed.
+Inference only, as the encoder's.  A whole bf16 roll-out is Network(precision="bf16", head_precision="bf16").
 
 Swap it into the reference's Network:  net.tree_lstm = TreeLSTM.from_module(net.tree_lstm)
 or take the whole network:              net = Network.from_module(net)
@@ -161,9 +167,9 @@ class _ForwardBf16(torch.autograd.Function):
         raise NotImplementedError("TreeLSTM (fl_tree_lstm_bf16) is inference only: no backward; training runs precision='f32'")
 
 
-def _precision(value):
+def _precision(value, what="TreeLSTM: precision"):
     if value not in PRECISIONS:
-        raise ValueError("TreeLSTM: precision must be 'f32' or 'bf16', got %r" % (value,))
+        raise ValueError("%s must be 'f32' or 'bf16', got %r" % (what, value))
     return value
 
 
@@ -353,6 +359,25 @@ class _Head(torch.autograd.Function):
         raise NotImplementedError("Network (fl_policy_head) is inference only: no backward; forward_torch is the path with autograd")
 
 
+class _HeadBf16(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, agents_attr, tree_embedding, valid_actions, mode, u, with_value, packed, *weights):
+        B, A = agents_attr.shape[:2]
+        dev = agents_attr.device
+        logits = torch.empty((B, A, ACTIONS), dtype=torch.float32, device=dev)
+        value = torch.empty((B,), dtype=torch.float32, device=dev) if with_value else None
+        actions = torch.empty((B, A), dtype=torch.uint8, device=dev) if mode is not None else None
+        hip_backend.policy_head_bf16(agents_attr, tree_embedding, weights, packed, logits, value, valid_actions, actions, mode, u)
+        out = (logits,) + ((value,) if with_value else ()) + ((actions,) if actions is not None else ())
+        if actions is not None:
+            ctx.mark_non_differentiable(actions)
+        return out
+
+    @staticmethod
+    def backward(ctx, *grads):
+        raise NotImplementedError("Network (fl_policy_head_bf16) is inference only: no backward; training runs head_precision='f32'")
+
+
 # (env, agent) rows a fl_policy_head_backward launch: saved forward + rows are 54.9 KB a row, 1.8 GB a chunk (8 192 rows measured
 # 1.4x the unchunked forward at cfg5: 20 envs of 400 agents are one workgroup a CU and a launch tail per chunk)
 HEAD_BACKWARD_CHUNK_ROWS = 32768
@@ -459,12 +484,17 @@ class Network(nn.Module):
     and forward are differentiable with respect to the 38 head parameters and the tree embedding (fl_policy_head_forward_saved,
     fl_policy_head_backward), their values the same bits as the inference path's.  With tree_lstm.trainable set as well one
     loss.backward() trains all 46 parameters.
-    precision: the tree encoder's (tree_lstm.precision, which stays settable): "bf16" = fl_tree_lstm_bf16 for roll-outs.  Only the
-    encoder has a bf16 path: the head (fl_policy_head) stays float32 whatever the precision."""
+    precision: the tree encoder's (tree_lstm.precision, which stays settable): "bf16" = fl_tree_lstm_bf16 for roll-outs.  The head
+    stays float32 under it.
+    head_precision (a plain attribute, settable): "f32" = fl_policy_head; "bf16" = fl_policy_head_bf16 in head, forward and act: 16
+    of the head's 19 matrices and the attention's products with bf16 operands and float32 sums, inference only -- together with
+    trainable it runs under torch.no_grad() and raises ValueError under grad mode (training stays float32)."""
 
-    def __init__(self, trainable=False, precision="f32"):
+    def __init__(self, trainable=False, precision="f32", head_precision="f32"):
         super().__init__()
         self.trainable = bool(trainable)
+        self.head_precision = _precision(head_precision, "Network: head_precision")
+        self._packed = {}      # (device, stream) -> (what was packed, the bf16 buffer): see _packed_head
         self.tree_lstm = TreeLSTM(IN_FEATURES, OUT_FEATURES, precision=precision)
         self.attr_embedding = _mlp((AGENT_ATTR, 2 * HIDDEN, 2 * HIDDEN, 2 * HIDDEN, HIDDEN), True)
         self.transformer = nn.Sequential(*[Transformer(EMBED, HEADS) for _ in range(3)])
@@ -472,12 +502,15 @@ class Network(nn.Module):
         self.critic_net = _mlp((2 * EMBED, 2 * HIDDEN, HIDDEN, 1), False)
 
     @classmethod
-    def from_module(cls, m, trainable=False, precision=None):
+    def from_module(cls, m, trainable=False, precision=None, head_precision=None):
         """a Network that shares m's parameters (m: the reference's Network or one of these); precision: the tree encoder's, None =
-        m.tree_lstm's own ("f32" for the reference's)"""
+        m.tree_lstm's own ("f32" for the reference's); head_precision: None = m's own ("f32" for the reference's)"""
         obj = cls.__new__(cls)
         nn.Module.__init__(obj)
         obj.trainable = bool(trainable)
+        obj.head_precision = _precision(getattr(m, "head_precision", "f32") if head_precision is None else head_precision,
+                                        "Network: head_precision")
+        obj._packed = {}
         obj.tree_lstm = TreeLSTM.from_module(m.tree_lstm, trainable=getattr(m.tree_lstm, "trainable", False),
                                              precision=getattr(m.tree_lstm, "precision", "f32") if precision is None else precision)
         obj.attr_embedding = m.attr_embedding
@@ -506,6 +539,19 @@ class Network(nn.Module):
                                 % (name, device, w.dtype, w.device, "" if w.is_contiguous() else ", not contiguous"))
             ws.append(w)
         return ws
+
+    def _packed_head(self, ws, device):
+        """the bf16 buffer of the head's 16 matrices for torch's current stream, as TreeLSTM._packed_weights keeps the encoder's:
+        packed at the first use on that stream, and again when one of the 16 is another tensor (data_ptr) or was written in place
+        (_version) since"""
+        stream = torch.cuda.current_stream(device)
+        key = tuple((ws[i].data_ptr(), ws[i]._version) for i in hip_backend.POLICY_HEAD_BF16_MATRICES)
+        slot = (device, stream.cuda_stream)
+        have = self._packed.get(slot)
+        if have is None or have[0] != key:
+            buf = hip_backend.policy_head_pack_bf16(ws, None if have is None else have[1])
+            self._packed[slot] = have = (key, buf)
+        return have[1]
 
     @staticmethod
     def _shapes():
@@ -555,21 +601,30 @@ class Network(nn.Module):
         """Everything after the tree encoder (fl_policy_head) on agents_attr f32 [B, A, 83] and tree_embedding f32 [B, A, 128] (what
         TreeLSTM.roots returns): ([logits [B, A, 5]], value [B]) as forward returns them (value=False: the critic is not run, value is
         None); with mode "soft" / "hard" and valid_actions u8 [B, A, 5] the actions u8 [B, A] come as a third item.  u: the uniform
-        draw of "soft", None = the reference's constant (it seeds numpy with 42 before every draw)."""
+        draw of "soft", None = the reference's constant (it seeds numpy with 42 before every draw).  With head_precision "bf16" the
+        launches are fl_policy_head_bf16's."""
         if mode not in (None, "soft", "hard"):
             raise ValueError("Network: mode must be None, 'soft' or 'hard', got %r" % (mode,))
         if mode is not None and valid_actions is None:
             raise ValueError("Network: mode %r needs valid_actions" % mode)
         if u is not None and not 0.0 <= float(u) < 1.0:
             raise ValueError("Network: u must be in [0, 1), got %r" % (u,))
+        bf16 = _precision(self.head_precision, "Network: head_precision") == "bf16"
+        if bf16 and self.trainable and torch.is_grad_enabled():
+            raise ValueError("Network: head_precision='bf16' is inference only (fl_policy_head_backward belongs to the float32 "
+                             "forward): run it under torch.no_grad(), or train with head_precision='f32'")
         self._check_head_inputs(agents_attr, tree_embedding, valid_actions if mode is not None else None)
         ws = self._head_weights(agents_attr.device)
         train = self.trainable and torch.is_grad_enabled()
         if train and agents_attr.requires_grad:
             raise ValueError("Network: agents_attr gets no gradient (fl_policy_head_backward differentiates with respect to the "
                              "parameters and the tree embedding only): detach it")
-        out = list((_HeadTrain if train else _Head).apply(agents_attr, tree_embedding, valid_actions if mode is not None else None,
-                                                          mode, u, bool(value), *ws))
+        if bf16:
+            out = list(_HeadBf16.apply(agents_attr, tree_embedding, valid_actions if mode is not None else None, mode, u, bool(value),
+                                       self._packed_head(ws, agents_attr.device), *ws))
+        else:
+            out = list((_HeadTrain if train else _Head).apply(agents_attr, tree_embedding, valid_actions if mode is not None else None,
+                                                              mode, u, bool(value), *ws))
         logits = out.pop(0)
         val = out.pop(0) if value else None
         return ([logits], val) + ((out.pop(0),) if mode is not None else ())
