@@ -9,15 +9,8 @@ __device__ __forceinline__ fl_f32x16 fl_mfma(float a, float b, fl_f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
 }
 
-// the bf16 matrix instruction (v_mfma_f32_32x32x16_bf16, float32 accumulator) of fl_tree_lstm_bf16.h and fl_policy_head_bf16.h: lane
-// l holds A[row l & 31][k = 8 (l >> 5) + j] and B[k = 8 (l >> 5) + j][column l & 31], j = 0 .. 7; the accumulator's rows are fl_acc_row's
-typedef __bf16 fl_bf16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ fl_f32x16 fl_mfma_bf16(fl_bf16x8 a, fl_bf16x8 b, fl_f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-
-// row of an accumulator register: lane l holds rows (r & 3) + 8 * (r >> 2) + 4 * (l >> 5), r = 0 .. 15, of column l & 31
+// row of an accumulator register: lane l holds rows (r & 3) + 8 * (r >> 2) + 4 * (l >> 5), r = 0 .. 15, of column l & 31 (the
+// bf16 instruction of fl_bf16.h has the same accumulator)
 __device__ __forceinline__ int fl_acc_row(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }
 
 // 16 consecutive floats (16-byte aligned) -> a[0 .. 15]: a lane's operands of one chunk

@@ -7,6 +7,7 @@
 #include "fl_policy_head.h"
 #include "fl_policy_head_bf16.h"
 #include "fl_policy_head_bwd.h"
+#include "fl_policy_host.h"
 
 size_t fl_policy_head_workspace_bytes(int n_envs, int n_agents) {
     if (n_envs <= 0 || n_agents <= 0) return 0;
@@ -15,28 +16,23 @@ size_t fl_policy_head_workspace_bytes(int n_envs, int n_agents) {
 }
 
 // sizes, NULLs and alignment of what the forward's entry points share; `fn` names the caller in the message
-static int fph_check(const char *fn, int n_envs, int n_agents, const float *const *params, const void *const *ptrs,
-                     const char *const *names, int n) {
+static int fph_check(const char *fn, int n_envs, int n_agents, const float *const *params, const FlPtr *tab, int n) {
     if (n_envs <= 0 || n_agents < 1 || n_agents > FPH_MAX_A || (long long)n_envs * n_agents > INT32_MAX / (3 * FPH_E)) {
         fl_set_error("%s: bad sizes (n_envs %d, n_agents %d; 1 <= n_envs, 1 <= n_agents <= %d)", fn, n_envs, n_agents, FPH_MAX_A);
         return FL_ERR_ARG;
     }
     if (!params) { fl_set_error("%s: params is NULL", fn); return FL_ERR_ARG; }
-    for (int i = 0; i < n; i++) {
-        if (!ptrs[i]) { fl_set_error("%s: %s is NULL", fn, names[i]); return FL_ERR_ARG; }
-        if ((uintptr_t)ptrs[i] % 16) { fl_set_error("%s: %s is not 16-byte aligned", fn, names[i]); return FL_ERR_ARG; }
-    }
-    for (int i = 0; i < FPH_NPARAMS; i++) {
-        if (!params[i]) { fl_set_error("%s: parameter %d is NULL", fn, i); return FL_ERR_ARG; }
-        if ((uintptr_t)params[i] % 16) { fl_set_error("%s: parameter %d is not 16-byte aligned", fn, i); return FL_ERR_ARG; }
-    }
+    if (fl_check_ptrs(fn, tab, n) != FL_OK) return FL_ERR_ARG;
+    for (int i = 0; i < FPH_NPARAMS; i++)
+        if (fl_check_param(fn, params, i) != FL_OK) return FL_ERR_ARG;
     return FL_OK;
 }
 
 // value, select, the mask, the actions and u of fl_policy_head and fl_policy_head_bf16
 static int fph_check_choice(const char *fn, const float *value_dev, const uint8_t *valid_actions_dev, int select, double u,
                             const uint8_t *actions_dev) {
-    if (value_dev && (uintptr_t)value_dev % 16) { fl_set_error("%s: value is not 16-byte aligned", fn); return FL_ERR_ARG; }
+    const FlPtr value = {value_dev, "value", 16, true};
+    if (fl_check_ptrs(fn, &value, 1) != FL_OK) return FL_ERR_ARG;
     if (select < 0 || select > 2) { fl_set_error("%s: select must be 0 (none), 1 (soft) or 2 (hard), got %d", fn, select); return FL_ERR_ARG; }
     if (select != 0 && (!valid_actions_dev || !actions_dev)) {
         fl_set_error("%s: select %d needs valid_actions and actions", fn, select);
@@ -44,6 +40,23 @@ static int fph_check_choice(const char *fn, const float *value_dev, const uint8_
     }
     if (!(u >= 0.0 && u < 1.0)) { fl_set_error("%s: u must be in [0, 1), got %g", fn, u); return FL_ERR_ARG; }
     return FL_OK;
+}
+
+// what the three forwards' arguments share; emb, xa, xb are the first three [R][256] arrays of `buf` (the workspace, or the saved
+// buffer).  Returns buf as floats: the caller places the rest (ao, qkv, val, y3) behind them
+static float *fph_fill(FphArgs &a, int n_envs, int n_agents, const float *attr_dev, const float *tree_dev, const float *const *params,
+                       const uint8_t *valid_actions_dev, int select, double u, float *logits_dev, float *value_dev, uint8_t *actions_dev,
+                       void *buf) {
+    a.B = n_envs; a.A = n_agents; a.R = n_envs * n_agents;
+    a.select = select; a.u = u;
+    a.attr = attr_dev; a.tree = tree_dev;
+    for (int i = 0; i < FPH_NPARAMS; i++) a.p[i] = params[i];
+    a.valid = valid_actions_dev; a.logits = logits_dev; a.value = value_dev; a.actions = actions_dev;
+    const size_t R = (size_t)a.R;
+    float *f = (float *)buf;
+    a.emb = f; a.xa = f + R * FPH_E; a.xb = f + 2 * R * FPH_E;
+    a.ao = nullptr; a.qkv = nullptr; a.y3 = nullptr;
+    return f;
 }
 
 // the forward's launches; block i's attention output goes to ao[i], its q k v are read from qkv[i]
@@ -72,37 +85,27 @@ static int fph_launch(const char *fn, FphArgs a, float *const (&ao)[3], float *c
         }
     }
     if (a.value) hipLaunchKernelGGL(k_ph_value, dim3(a.B), dim3(64), 0, s, a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { fl_set_error("%s: launch failed: %s", fn, hipGetErrorString(e)); return FL_ERR_HIP; }
-    return FL_OK;
+    return fl_launched(fn);
 }
 
 int fl_policy_head(int n_envs, int n_agents, const float *attr_dev, const float *tree_dev, const float *const *params,
                    const uint8_t *valid_actions_dev, int select, double u, float *logits_dev, float *value_dev,
                    uint8_t *actions_dev, void *workspace_dev, size_t workspace_bytes, void *hip_stream) {
-    const void *f16[] = {attr_dev, tree_dev, logits_dev, workspace_dev};
-    const char *f16n[] = {"attr", "tree", "logits", "workspace"};
-    if (fph_check("fl_policy_head", n_envs, n_agents, params, f16, f16n, 4) != FL_OK) return FL_ERR_ARG;
-    if (fph_check_choice("fl_policy_head", value_dev, valid_actions_dev, select, u, actions_dev) != FL_OK) return FL_ERR_ARG;
-    const size_t need = fl_policy_head_workspace_bytes(n_envs, n_agents);
-    if (workspace_bytes < need) {
-        fl_set_error("fl_policy_head: workspace of %zu bytes, %zu needed (fl_policy_head_workspace_bytes)", workspace_bytes, need);
-        return FL_ERR_ARG;
-    }
+    const char *fn = "fl_policy_head";
+    const FlPtr tab[] = {{attr_dev, "attr", 16}, {tree_dev, "tree", 16}, {logits_dev, "logits", 16}, {workspace_dev, "workspace", 16}};
+    if (fph_check(fn, n_envs, n_agents, params, tab, 4) != FL_OK ||
+        fph_check_choice(fn, value_dev, valid_actions_dev, select, u, actions_dev) != FL_OK ||
+        fl_check_bytes(fn, "workspace", workspace_bytes, fl_policy_head_workspace_bytes(n_envs, n_agents),
+                       "fl_policy_head_workspace_bytes") != FL_OK) return FL_ERR_ARG;
 
     FphArgs a;
-    a.B = n_envs; a.A = n_agents; a.R = n_envs * n_agents;
-    a.select = select; a.u = u;
-    a.attr = attr_dev; a.tree = tree_dev;
-    for (int i = 0; i < FPH_NPARAMS; i++) a.p[i] = params[i];
-    a.valid = valid_actions_dev; a.logits = logits_dev; a.value = value_dev; a.actions = actions_dev;
+    float *ws = fph_fill(a, n_envs, n_agents, attr_dev, tree_dev, params, valid_actions_dev, select, u, logits_dev, value_dev, actions_dev,
+                         workspace_dev);
     const size_t R = (size_t)a.R;
-    float *ws = (float *)workspace_dev;
-    a.emb = ws; a.xa = ws + R * FPH_E; a.xb = ws + 2 * R * FPH_E; a.ao = ws + 3 * R * FPH_E;
-    a.qkv = ws + 4 * R * FPH_E; a.val = ws + 7 * R * FPH_E;
-    a.y3 = nullptr;
-    float *const ao[3] = {a.ao, a.ao, a.ao}, *const qkv[3] = {a.qkv, a.qkv, a.qkv};
-    return fph_launch("fl_policy_head", a, ao, qkv, (hipStream_t)hip_stream);
+    a.val = ws + 7 * R * FPH_E;
+    float *ao1 = ws + 3 * R * FPH_E, *qkv1 = ws + 4 * R * FPH_E;          // the three blocks share one array of each
+    float *const ao[3] = {ao1, ao1, ao1}, *const qkv[3] = {qkv1, qkv1, qkv1};
+    return fph_launch(fn, a, ao, qkv, (hipStream_t)hip_stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- training
@@ -125,27 +128,18 @@ size_t fl_policy_head_backward_workspace_bytes(int n_envs, int n_agents) {
 int fl_policy_head_forward_saved(int n_envs, int n_agents, const float *attr_dev, const float *tree_dev, const float *const *params,
                                  float *logits_dev, float *value_dev, void *saved_dev, size_t saved_bytes, void *hip_stream) {
     const char *fn = "fl_policy_head_forward_saved";
-    const void *f16[] = {attr_dev, tree_dev, logits_dev, saved_dev};
-    const char *f16n[] = {"attr", "tree", "logits", "saved"};
-    if (fph_check(fn, n_envs, n_agents, params, f16, f16n, 4) != FL_OK) return FL_ERR_ARG;
-    if (value_dev && (uintptr_t)value_dev % 16) { fl_set_error("%s: value is not 16-byte aligned", fn); return FL_ERR_ARG; }
-    const size_t need = fl_policy_head_saved_bytes(n_envs, n_agents);
-    if (saved_bytes < need) {
-        fl_set_error("%s: saved buffer of %zu bytes, %zu needed (fl_policy_head_saved_bytes)", fn, saved_bytes, need);
+    const FlPtr tab[] = {{attr_dev, "attr", 16}, {tree_dev, "tree", 16}, {logits_dev, "logits", 16}, {saved_dev, "saved", 16}};
+    const FlPtr value = {value_dev, "value", 16, true};
+    if (fph_check(fn, n_envs, n_agents, params, tab, 4) != FL_OK || fl_check_ptrs(fn, &value, 1) != FL_OK ||
+        fl_check_bytes(fn, "saved buffer", saved_bytes, fl_policy_head_saved_bytes(n_envs, n_agents), "fl_policy_head_saved_bytes") != FL_OK)
         return FL_ERR_ARG;
-    }
     FphArgs a;
-    a.B = n_envs; a.A = n_agents; a.R = n_envs * n_agents;
-    a.select = 0; a.u = 0.0;
-    a.attr = attr_dev; a.tree = tree_dev;
-    for (int i = 0; i < FPH_NPARAMS; i++) a.p[i] = params[i];
-    a.valid = nullptr; a.logits = logits_dev; a.value = value_dev; a.actions = nullptr;
+    float *sv = fph_fill(a, n_envs, n_agents, attr_dev, tree_dev, params, nullptr, 0, 0.0, logits_dev, value_dev, nullptr, saved_dev);
     const size_t R = (size_t)a.R;
-    float *sv = (float *)saved_dev;
-    a.emb = sv; a.xa = sv + R * FPH_E; a.xb = sv + 2 * R * FPH_E; a.y3 = sv + 3 * R * FPH_E;
+    a.y3 = sv + 3 * R * FPH_E;
     float *const ao[3] = {sv + 4 * R * FPH_E, sv + 5 * R * FPH_E, sv + 6 * R * FPH_E};
     float *const qkv[3] = {sv + 7 * R * FPH_E, sv + 10 * R * FPH_E, sv + 13 * R * FPH_E};
-    a.ao = ao[0]; a.qkv = qkv[0]; a.val = sv + 16 * R * FPH_E;
+    a.val = sv + 16 * R * FPH_E;
     return fph_launch(fn, a, ao, qkv, (hipStream_t)hip_stream);
 }
 
@@ -153,21 +147,16 @@ int fl_policy_head_backward(int n_envs, int n_agents, const float *attr_dev, con
                             const void *saved_dev, const float *grad_logits_dev, const float *grad_value_dev, float *grad_tree_dev,
                             void *rows_dev, size_t rows_bytes, void *workspace_dev, size_t workspace_bytes, void *hip_stream) {
     const char *fn = "fl_policy_head_backward";
-    const void *f16[] = {attr_dev, tree_dev, saved_dev, grad_tree_dev, rows_dev, workspace_dev};
-    const char *f16n[] = {"attr", "tree", "saved", "grad_tree", "rows", "workspace"};
-    if (fph_check(fn, n_envs, n_agents, params, f16, f16n, 6) != FL_OK) return FL_ERR_ARG;
+    const FlPtr tab[] = {{attr_dev, "attr", 16}, {tree_dev, "tree", 16}, {saved_dev, "saved", 16}, {grad_tree_dev, "grad_tree", 16},
+                         {rows_dev, "rows", 16}, {workspace_dev, "workspace", 16}};
+    const FlPtr grads[] = {{grad_logits_dev, "grad_logits", 16, true}, {grad_value_dev, "grad_value", 16, true}};
+    if (fph_check(fn, n_envs, n_agents, params, tab, 6) != FL_OK) return FL_ERR_ARG;
     if (!grad_logits_dev && !grad_value_dev) { fl_set_error("%s: grad_logits and grad_value are both NULL", fn); return FL_ERR_ARG; }
-    if ((uintptr_t)grad_logits_dev % 16) { fl_set_error("%s: grad_logits is not 16-byte aligned", fn); return FL_ERR_ARG; }
-    if ((uintptr_t)grad_value_dev % 16) { fl_set_error("%s: grad_value is not 16-byte aligned", fn); return FL_ERR_ARG; }
-    const size_t need_r = fl_policy_head_backward_rows_bytes(n_envs, n_agents), need_w = fl_policy_head_backward_workspace_bytes(n_envs, n_agents);
-    if (rows_bytes < need_r) {
-        fl_set_error("%s: rows of %zu bytes, %zu needed (fl_policy_head_backward_rows_bytes)", fn, rows_bytes, need_r);
-        return FL_ERR_ARG;
-    }
-    if (workspace_bytes < need_w) {
-        fl_set_error("%s: workspace of %zu bytes, %zu needed (fl_policy_head_backward_workspace_bytes)", fn, workspace_bytes, need_w);
-        return FL_ERR_ARG;
-    }
+    if (fl_check_ptrs(fn, grads, 2) != FL_OK ||
+        fl_check_bytes(fn, "rows", rows_bytes, fl_policy_head_backward_rows_bytes(n_envs, n_agents),
+                       "fl_policy_head_backward_rows_bytes") != FL_OK ||
+        fl_check_bytes(fn, "workspace", workspace_bytes, fl_policy_head_backward_workspace_bytes(n_envs, n_agents),
+                       "fl_policy_head_backward_workspace_bytes") != FL_OK) return FL_ERR_ARG;
 
     FpbArgs a;
     a.B = n_envs; a.A = n_agents; a.R = n_envs * n_agents;
@@ -212,9 +201,7 @@ int fl_policy_head_backward(int n_envs, int n_agents, const float *attr_dev, con
         hipLaunchKernelGGL(k_pb_inproj, dim3(tiles), dim3(FPH_THREADS), FPB_LDS_INPROJ, s, a, blk);
     }
     hipLaunchKernelGGL(k_pb_attr, dim3(tiles), dim3(FPH_THREADS), FPB_LDS_ATTR, s, a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { fl_set_error("%s: launch failed: %s", fn, hipGetErrorString(e)); return FL_ERR_HIP; }
-    return FL_OK;
+    return fl_launched(fn);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- bf16 inference
@@ -228,35 +215,26 @@ size_t fl_policy_head_bf16_workspace_bytes(int n_envs, int n_agents) {
 
 // the parameter index and K of the 16 packed matrices, in state_dict order
 static const int FPH16_SRC[FPH16_NMAT] = {2, 4, 6, 8, 10, 12, 14, 16, 18, 20, 22, 24, 26, 28, 32, 34};
-static const int FPH16_K[FPH16_NMAT] = {256, 256, 256, 256, 256, 512, 256, 256, 512, 256, 256, 512, 512, 256, 512, 256};
-static const int FPH16_ROWS_OF[FPH16_NMAT] = {256, 256, 128, 768, 256, 256, 768, 256, 256, 768, 256, 256, 256, 128, 256, 128};
+static constexpr int FPH16_K[FPH16_NMAT] = {256, 256, 256, 256, 256, 512, 256, 256, 512, 256, 256, 512, 512, 256, 512, 256};
+static constexpr int FPH16_ROWS_OF[FPH16_NMAT] = {256, 256, 128, 768, 256, 256, 768, 256, 256, 768, 256, 256, 256, 128, 256, 128};
+constexpr int fph16_elements(int m = 0) { return m == FPH16_NMAT ? 0 : FPH16_ROWS_OF[m] * FPH16_K[m] + fph16_elements(m + 1); }
+static_assert(fph16_elements() == FPH16_PACKED, "the pack kernel writes as many elements as fl_policy_head_bf16_packed_bytes counts");
+
+static int fph16_check_packed(const char *fn, size_t packed_bytes) {
+    return fl_check_bytes(fn, "packed buffer", packed_bytes, fl_policy_head_bf16_packed_bytes(), "fl_policy_head_bf16_packed_bytes");
+}
 
 int fl_policy_head_pack_bf16(const float *const *params, void *packed_dev, size_t packed_bytes, void *hip_stream) {
     const char *fn = "fl_policy_head_pack_bf16";
     if (!params) { fl_set_error("%s: params is NULL", fn); return FL_ERR_ARG; }
-    for (int m = 0; m < FPH16_NMAT; m++) {
-        const int i = FPH16_SRC[m];
-        if (!params[i]) { fl_set_error("%s: parameter %d is NULL", fn, i); return FL_ERR_ARG; }
-        if ((uintptr_t)params[i] % 16) { fl_set_error("%s: parameter %d is not 16-byte aligned", fn, i); return FL_ERR_ARG; }
-    }
-    if (!packed_dev) { fl_set_error("%s: packed is NULL", fn); return FL_ERR_ARG; }
-    if ((uintptr_t)packed_dev % 16) { fl_set_error("%s: packed is not 16-byte aligned", fn); return FL_ERR_ARG; }
-    if (packed_bytes < fl_policy_head_bf16_packed_bytes()) {
-        fl_set_error("%s: packed buffer of %zu bytes, %zu needed (fl_policy_head_bf16_packed_bytes)", fn, packed_bytes,
-                     fl_policy_head_bf16_packed_bytes());
-        return FL_ERR_ARG;
-    }
-    Fph16Pack a;
-    int off = 0;
-    for (int m = 0; m < FPH16_NMAT; m++) {
-        a.src[m] = params[FPH16_SRC[m]]; a.K[m] = FPH16_K[m]; a.off[m] = off;
-        off += FPH16_ROWS_OF[m] * FPH16_K[m];
-    }
-    a.off[FPH16_NMAT] = off;
-    hipLaunchKernelGGL(k_ph16_pack, dim3((FPH16_PACKED + 255) / 256), dim3(256), 0, (hipStream_t)hip_stream, a, (__bf16 *)packed_dev);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { fl_set_error("%s: launch failed: %s", fn, hipGetErrorString(e)); return FL_ERR_HIP; }
-    return FL_OK;
+    for (int m = 0; m < FPH16_NMAT; m++)
+        if (fl_check_param(fn, params, FPH16_SRC[m]) != FL_OK) return FL_ERR_ARG;
+    const FlPtr packed = {packed_dev, "packed", 16};
+    if (fl_check_ptrs(fn, &packed, 1) != FL_OK || fph16_check_packed(fn, packed_bytes) != FL_OK) return FL_ERR_ARG;
+    FlBf16Pack<FPH16_NMAT> a;
+    for (int m = 0; m < FPH16_NMAT; m++) { a.src[m] = params[FPH16_SRC[m]]; a.K[m] = FPH16_K[m]; }
+    fl_launch_bf16_pack(a, FPH16_ROWS_OF, packed_dev, (hipStream_t)hip_stream);       // (a.off[16] = FPH16_PACKED)
+    return fl_launched(fn);
 }
 
 int fl_policy_head_bf16(int n_envs, int n_agents, const float *attr_dev, const float *tree_dev, const float *const *params,
@@ -264,31 +242,19 @@ int fl_policy_head_bf16(int n_envs, int n_agents, const float *attr_dev, const f
                         float *logits_dev, float *value_dev, uint8_t *actions_dev, void *workspace_dev, size_t workspace_bytes,
                         void *hip_stream) {
     const char *fn = "fl_policy_head_bf16";
-    const void *f16[] = {attr_dev, tree_dev, logits_dev, workspace_dev, packed_dev};
-    const char *f16n[] = {"attr", "tree", "logits", "workspace", "packed"};
-    if (fph_check(fn, n_envs, n_agents, params, f16, f16n, 5) != FL_OK) return FL_ERR_ARG;
-    if (fph_check_choice(fn, value_dev, valid_actions_dev, select, u, actions_dev) != FL_OK) return FL_ERR_ARG;
-    const size_t need = fl_policy_head_bf16_workspace_bytes(n_envs, n_agents);
-    if (workspace_bytes < need) {
-        fl_set_error("%s: workspace of %zu bytes, %zu needed (fl_policy_head_bf16_workspace_bytes)", fn, workspace_bytes, need);
-        return FL_ERR_ARG;
-    }
-    if (packed_bytes < fl_policy_head_bf16_packed_bytes()) {
-        fl_set_error("%s: packed buffer of %zu bytes, %zu needed (fl_policy_head_bf16_packed_bytes)", fn, packed_bytes,
-                     fl_policy_head_bf16_packed_bytes());
-        return FL_ERR_ARG;
-    }
+    const FlPtr tab[] = {{attr_dev, "attr", 16}, {tree_dev, "tree", 16}, {logits_dev, "logits", 16}, {workspace_dev, "workspace", 16},
+                         {packed_dev, "packed", 16}};
+    if (fph_check(fn, n_envs, n_agents, params, tab, 5) != FL_OK ||
+        fph_check_choice(fn, value_dev, valid_actions_dev, select, u, actions_dev) != FL_OK ||
+        fl_check_bytes(fn, "workspace", workspace_bytes, fl_policy_head_bf16_workspace_bytes(n_envs, n_agents),
+                       "fl_policy_head_bf16_workspace_bytes") != FL_OK ||
+        fph16_check_packed(fn, packed_bytes) != FL_OK) return FL_ERR_ARG;
 
     Fph16Args a;
-    a.B = n_envs; a.A = n_agents; a.R = n_envs * n_agents;
-    a.select = select; a.u = u;
-    a.attr = attr_dev; a.tree = tree_dev;
-    for (int i = 0; i < FPH_NPARAMS; i++) a.p[i] = params[i];
-    a.valid = valid_actions_dev; a.logits = logits_dev; a.value = value_dev; a.actions = actions_dev;
+    float *ws = fph_fill(a, n_envs, n_agents, attr_dev, tree_dev, params, valid_actions_dev, select, u, logits_dev, value_dev, actions_dev,
+                         workspace_dev);
     const size_t R = (size_t)a.R;
-    float *ws = (float *)workspace_dev;
-    a.emb = ws; a.xa = ws + R * FPH_E; a.xb = ws + 2 * R * FPH_E; a.ao = ws + 3 * R * FPH_E;
-    a.qkv = nullptr; a.y3 = nullptr;
+    a.ao = ws + 3 * R * FPH_E;
     a.qkv16 = (__bf16 *)(ws + 4 * R * FPH_E);
     a.val = (float *)(a.qkv16 + R * 3 * FPH_E);
     a.packed = (const __bf16 *)packed_dev;
@@ -305,7 +271,5 @@ int fl_policy_head_bf16(int n_envs, int n_agents, const float *attr_dev, const f
         else hipLaunchKernelGGL(k_ph16_block<true>, dim3(tiles), dim3(FPH_THREADS), 0, s, a, blk, xin[blk], xout[blk]);
     }
     if (a.value) hipLaunchKernelGGL(k_ph_value, dim3(a.B), dim3(64), 0, s, (FphArgs)a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { fl_set_error("%s: launch failed: %s", fn, hipGetErrorString(e)); return FL_ERR_HIP; }
-    return FL_OK;
+    return fl_launched(fn);
 }

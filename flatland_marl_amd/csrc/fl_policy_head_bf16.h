@@ -20,8 +20,7 @@
 //
 // LDS tiles are bytes: a bf16 row of 256 is 512 bytes = 32 slots of 16 bytes; a ds_read_b128 is conflict free when the row stride
 // in 16-byte slots is odd (fl_tree_lstm_bf16.h), so rows are padded to 33 slots (528 bytes), the [x | a] rows of 512 to 65 (1040).
-// Lane l of a K = 16 step holds A[row l & 31][k = 8 (l >> 5) + j] and B[k][col l & 31], j = 0 .. 7: one 16-byte read of its LDS
-// row and one of the packed weights a step.
+// What a lane holds of a K = 16 step, and the format of each of the 16 packed matrices: fl_bf16.h.
 //
 // The attention computes the scores TRANSPOSED, X = k q^T (A operand: 32 keys, B operand: the tile's 32 queries), so a lane holds
 // one query's scores of 16 keys in its accumulator registers: the row maximum and the row sum are sums inside a lane and one
@@ -34,6 +33,7 @@
 // workspace stays the documented one.  A wave stages its own head's chunk: 4 loads of 16 bytes (4 keys x 8 d) and 8 stores of 8
 // bytes (4 keys of one d) a lane.
 #pragma once
+#include "fl_bf16.h"
 #include "fl_policy_head.h"
 
 #define FPH16_STRIDE 528                // bytes a staged bf16 row of 256: 33 slots
@@ -41,12 +41,8 @@
 #define FPH16_ASTRIDE 100               // floats a row of the float32 attribute tile (96 used): 4 mod 32
 #define FPH16_HSTRIDE 132               // floats a row of a head's float32 hidden tile (128 used): 4 mod 32, 528 bytes
 #define FPH16_VSTRIDE 80                // bytes a row of the transposed v chunk (32 keys): 5 slots
-#define FPH16_STEP 512                  // bf16 a packed step: 64 lanes x 8
 #define FPH16_NMAT 16
 #define FPH16_ROW_BYTES (4 * FPH_E * 4 + 3 * FPH_E * 2 + 4)       // workspace bytes a row: 5636
-#ifndef FPH16_UNROLL
-#define FPH16_UNROLL 4
-#endif
 
 // the 16 packed matrices in state_dict order: element offsets in the packed buffer
 enum {
@@ -62,28 +58,6 @@ struct Fph16Args : FphArgs {
     __bf16 *qkv16;                      // workspace: bf16 [R][768]; FphArgs::qkv is unused
 };
 
-struct Fph16Pack {
-    const float *src[FPH16_NMAT];
-    int off[FPH16_NMAT + 1];            // element offset of matrix m; off[16] = FPH16_PACKED
-    int K[FPH16_NMAT];
-};
-
-// this lane's operands of step 0 of block `block` (32 output features) of a packed matrix of K columns
-__device__ __forceinline__ const __bf16 *fph16_wblock(const __bf16 *w, int K, int block, int lane) {
-    return w + (size_t)block * (K / 16) * FPH16_STEP + lane * 8;
-}
-
-// acc[n] += A[row][k] * W_n[col][k] over `steps` K = 16 steps; arow = this lane's staged row + 8 hh, w[n] = fph16_wblock
-template <int NB>
-__device__ __forceinline__ void fph16_mm(const __bf16 *arow, int steps, const __bf16 *const (&w)[NB], fl_f32x16 (&acc)[NB]) {
-#pragma unroll FPH16_UNROLL
-    for (int s = 0; s < steps; s++) {
-        const fl_bf16x8 a = *(const fl_bf16x8 *)(arow + 16 * s);
-#pragma unroll
-        for (int n = 0; n < NB; n++) acc[n] = fl_mfma_bf16(a, *(const fl_bf16x8 *)(w[n] + s * FPH16_STEP), acc[n]);
-    }
-}
-
 // this lane's A row of a tile: row `col`, column c0, its k half of a step
 __device__ __forceinline__ const __bf16 *fph16_arow(const unsigned char *tile, int stride, int c0, int col, int hh) {
     return (const __bf16 *)(tile + col * stride) + c0 + 8 * hh;
@@ -92,8 +66,8 @@ __device__ __forceinline__ const __bf16 *fph16_arow(const unsigned char *tile, i
 // a layer of 256 outputs: the wave's two blocks 2 wave, 2 wave + 1 of a packed matrix of K columns over a tile's columns c0 .. c0 + K
 __device__ __forceinline__ void fph16_layer256(const unsigned char *tile, int stride, int c0, int K, const __bf16 *w, fl_f32x16 (&acc)[2],
                                                int wave, int lane) {
-    const __bf16 *const ws[2] = {fph16_wblock(w, K, 2 * wave, lane), fph16_wblock(w, K, 2 * wave + 1, lane)};
-    fph16_mm<2>(fph16_arow(tile, stride, c0, lane & 31, lane >> 5), K / 16, ws, acc);
+    const __bf16 *const ws[2] = {fl_bf16_block(w, K, 2 * wave, lane), fl_bf16_block(w, K, 2 * wave + 1, lane)};
+    fl_bf16_mm<2>(fph16_arow(tile, stride, c0, lane & 31, lane >> 5), K / 16, ws, acc);
 }
 
 // (acc + bias) [GELU] of one 32 x 32 block: rounded to bf16 -> tile columns c0 + col; the float32 value -> g[row][col] of the
@@ -120,8 +94,7 @@ __device__ __forceinline__ void fph16_load_tile(unsigned char *tile, int stride,
         fl_bf16x8 o = {};
         if (r < rows) {
             const float4 a = ((const float4 *)(src + (size_t)r * ld))[2 * q], b = ((const float4 *)(src + (size_t)r * ld))[2 * q + 1];
-            o[0] = (__bf16)a.x; o[1] = (__bf16)a.y; o[2] = (__bf16)a.z; o[3] = (__bf16)a.w;
-            o[4] = (__bf16)b.x; o[5] = (__bf16)b.y; o[6] = (__bf16)b.z; o[7] = (__bf16)b.w;
+            o = fl_bf16_round8(a, b);
             if (copy) {
                 ((float4 *)(copy + (size_t)r * ldc))[2 * q] = a;
                 ((float4 *)(copy + (size_t)r * ldc))[2 * q + 1] = b;
@@ -139,9 +112,9 @@ __device__ __forceinline__ void fph16_qkv(const unsigned char *tile, int stride,
 #pragma unroll 1
     for (int pr = 0; pr < 3; pr++) {
         const int b0 = 6 * wave + 2 * pr, j0 = 32 * b0, j1 = j0 + 32;
-        const __bf16 *const ws[2] = {fph16_wblock(w, FPH_E, b0, lane), fph16_wblock(w, FPH_E, b0 + 1, lane)};
+        const __bf16 *const ws[2] = {fl_bf16_block(w, FPH_E, b0, lane), fl_bf16_block(w, FPH_E, b0 + 1, lane)};
         fl_f32x16 acc[2] = {};
-        fph16_mm<2>(arow, FPH_E / 16, ws, acc);
+        fl_bf16_mm<2>(arow, FPH_E / 16, ws, acc);
         const float bb0 = bias[j0 + col], bb1 = bias[j1 + col];
 #pragma unroll
         for (int r = 0; r < 16; r++) {
@@ -184,10 +157,9 @@ __global__ void __launch_bounds__(FPH_THREADS) k_ph16_embed(Fph16Args p) {
     }
     float *emb = p.emb + (size_t)row0 * FPH_E;
     {                                                            // 256 -> 128: tile 0 -> tile 1[:, :128] and emb; the tree embedding beside it
-        const __bf16 *const ws[1] = {fph16_wblock(p.packed + FPH16_ATTR6, FPH_E, wave, lane)};
-        fl_f32x16 acc[1] = {};
-        fph16_mm<1>(fph16_arow(s_t[0], FPH16_STRIDE, 0, col, hh), FPH_E / 16, ws, acc);
-        fph16_to_lds<true>(acc[0], w[7][32 * wave + col], s_t[1], FPH16_STRIDE, 32 * wave, col, hh, emb + 32 * wave, FPH_E, rows);
+        fl_f32x16 acc = {};
+        fl_bf16_mm(fph16_arow(s_t[0], FPH16_STRIDE, 0, col, hh), FPH_E / 16, fl_bf16_block(p.packed + FPH16_ATTR6, FPH_E, wave, lane), acc);
+        fph16_to_lds<true>(acc, w[7][32 * wave + col], s_t[1], FPH16_STRIDE, 32 * wave, col, hh, emb + 32 * wave, FPH_E, rows);
         fph16_load_tile(s_t[1], FPH16_STRIDE, FPH_H, p.tree + (size_t)row0 * FPH_H, FPH_H, FPH_H / 8, rows, tid, emb + FPH_H, FPH_E);
     }
     __syncthreads();
@@ -297,13 +269,12 @@ __device__ __forceinline__ void fph16_head(const unsigned char *tile, unsigned c
     __syncthreads();
     float *hf = (float *)h;
     {
-        const __bf16 *const ws[1] = {fph16_wblock(w2, FPH_E, wave, lane)};
-        fl_f32x16 acc[1] = {};
-        fph16_mm<1>(fph16_arow(h, FPH16_STRIDE, 0, col, hh), FPH_E / 16, ws, acc);
+        fl_f32x16 acc = {};
+        fl_bf16_mm(fph16_arow(h, FPH16_STRIDE, 0, col, hh), FPH_E / 16, fl_bf16_block(w2, FPH_E, wave, lane), acc);
         __syncthreads();
         const float b = p[3][32 * wave + col];
 #pragma unroll
-        for (int r = 0; r < 16; r++) hf[fl_acc_row(r, hh) * FPH16_HSTRIDE + 32 * wave + col] = fph_gelu(acc[0][r] + b);
+        for (int r = 0; r < 16; r++) hf[fl_acc_row(r, hh) * FPH16_HSTRIDE + 32 * wave + col] = fph_gelu(acc[r] + b);
     }
     __syncthreads();
     if (wave == 0) {
@@ -378,19 +349,4 @@ __global__ void __launch_bounds__(FPH_THREADS) k_ph16_block(Fph16Args p, int blk
     __syncthreads();
     if (p.select && tid < rows)
         p.actions[row0 + tid] = (unsigned char)fph_choose(s_lg[tid], p.valid + (size_t)(row0 + tid) * FPH_ACT, p.select, p.u);
-}
-
-// fl_policy_head_pack_bf16: element i of the packed buffer = bf16(its source element), round to nearest even (v_cvt_pk_bf16_f32)
-__global__ void __launch_bounds__(256) k_ph16_pack(Fph16Pack a, __bf16 *dst) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= FPH16_PACKED) return;
-    const float *src = a.src[0];
-    int K = a.K[0], off = 0;
-#pragma unroll
-    for (int k = 1; k < FPH16_NMAT; k++)
-        if (i >= a.off[k]) { src = a.src[k]; K = a.K[k]; off = a.off[k]; }
-    const int e = i - off;
-    const int j = e & 7, l = (e >> 3) & 63, t = e / FPH16_STEP;
-    const int step = t % (K / 16), block = t / (K / 16);
-    dst[i] = (__bf16)src[(size_t)(32 * block + (l & 31)) * K + 16 * step + 8 * (l >> 5) + j];
 }

@@ -10,16 +10,10 @@
 #include "fl_tree_lstm.h"
 #include "fl_tree_lstm_bwd.h"
 #include "fl_tree_lstm_bf16.h"
-
-struct FtlPtr {
-    const void *p;
-    const char *name;
-    int align;
-    bool may_be_null;
-};
+#include "fl_policy_host.h"
 
 // sizes, then the pointers' NULLs and alignment in the table's order, then the workspace; `fn` names the caller in the message
-static int ftl_check(const char *fn, int n_trees, int n_nodes, int roots_only, const FtlPtr *tab, int n, size_t workspace_bytes,
+static int ftl_check(const char *fn, int n_trees, int n_nodes, int roots_only, const FlPtr *tab, int n, size_t workspace_bytes,
                      size_t need) {
     if (n_trees <= 0 || n_nodes < 4 || n_nodes > FTL_MAX_N || n_trees > (INT32_MAX / FTL_MAX_N)) {
         fl_set_error("%s: bad sizes (n_trees %d, n_nodes %d; 1 <= n_trees, 4 <= n_nodes <= %d)", fn, n_trees, n_nodes, FTL_MAX_N);
@@ -30,18 +24,14 @@ static int ftl_check(const char *fn, int n_trees, int n_nodes, int roots_only, c
         return FL_ERR_ARG;
     }
     if (roots_only != 0 && roots_only != 1) { fl_set_error("%s: roots_only must be 0 or 1", fn); return FL_ERR_ARG; }
-    for (int i = 0; i < n; i++) {
-        if (!tab[i].p && !tab[i].may_be_null) { fl_set_error("%s: %s is NULL", fn, tab[i].name); return FL_ERR_ARG; }
-        if ((uintptr_t)tab[i].p % tab[i].align) {
-            fl_set_error("%s: %s is not %d-byte aligned", fn, tab[i].name, tab[i].align);
-            return FL_ERR_ARG;
-        }
-    }
-    if (workspace_bytes < need) {
-        fl_set_error("%s: workspace of %zu bytes, %zu needed (%s_workspace_bytes)", fn, workspace_bytes, need, fn);
-        return FL_ERR_ARG;
-    }
-    return FL_OK;
+    if (fl_check_ptrs(fn, tab, n) != FL_OK) return FL_ERR_ARG;
+    char sizer[64];
+    snprintf(sizer, sizeof sizer, "%s_workspace_bytes", fn);
+    return fl_check_bytes(fn, "workspace", workspace_bytes, need, sizer);
+}
+
+static int ftl16_check_packed(const char *fn, size_t packed_bytes) {
+    return fl_check_bytes(fn, "packed buffer", packed_bytes, fl_tree_lstm_bf16_packed_bytes(), "fl_tree_lstm_bf16_packed_bytes");
 }
 
 // the members both kernels take; G from the current device's CU count (looked up once a device)
@@ -63,10 +53,12 @@ static int ftl_trees(const char *fn, FtlTrees &a, int n_trees, int n_nodes, int 
     return FL_OK;
 }
 
-static int ftl_launched(const char *fn) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { fl_set_error("%s: launch failed: %s", fn, hipGetErrorString(e)); return FL_ERR_HIP; }
-    return FL_OK;
+// the outputs, and where a forward keeps every node's h and c: in the outputs themselves, or (roots_only, or no c) in the workspace
+static void ftl_planes(FtlArgs &a, float *h_dev, float *c_dev, void *workspace_dev) {
+    a.h_out = h_dev; a.c_out = c_dev;
+    float *ws = (float *)workspace_dev;
+    if (a.roots_only) { a.hbuf = ws; a.cbuf = ws + (size_t)a.T * a.N * FTL_M; }
+    else { a.hbuf = h_dev; a.cbuf = c_dev ? c_dev : ws; }
 }
 
 size_t fl_tree_lstm_workspace_bytes(int n_trees, int n_nodes, int roots_only) {
@@ -80,7 +72,7 @@ int fl_tree_lstm(int n_trees, int n_nodes, const float *forest_dev, const int64_
                  int roots_only, float *h_dev, float *c_dev, int32_t *status_dev, void *workspace_dev, size_t workspace_bytes,
                  void *hip_stream) {
     const char *fn = "fl_tree_lstm";
-    const FtlPtr tab[] = {{forest_dev, "forest", 16}, {w_iou_dev, "w_iou", 16}, {b_iou_dev, "b_iou", 16}, {u_iou_dev, "u_iou", 16},
+    const FlPtr tab[] = {{forest_dev, "forest", 16}, {w_iou_dev, "w_iou", 16}, {b_iou_dev, "b_iou", 16}, {u_iou_dev, "u_iou", 16},
                           {w_c_dev, "w_c", 16}, {b_c_dev, "b_c", 16}, {w_f_dev, "w_f", 16}, {b_f_dev, "b_f", 16}, {u_f_dev, "u_f", 16},
                           {h_dev, "h", 16}, {workspace_dev, "workspace", 16},
                           {adjacency_dev, "adjacency", 8}, {node_order_dev, "node_order", 8}, {edge_order_dev, "edge_order", 8},
@@ -91,13 +83,9 @@ int fl_tree_lstm(int n_trees, int n_nodes, const float *forest_dev, const int64_
     const int rc = ftl_trees(fn, a, n_trees, n_nodes, roots_only, forest_dev, adjacency_dev, node_order_dev, edge_order_dev,
                              {w_iou_dev, b_iou_dev, u_iou_dev, w_c_dev, b_c_dev, w_f_dev, b_f_dev, u_f_dev}, status_dev);
     if (rc != FL_OK) return rc;
-    a.h_out = h_dev; a.c_out = c_dev;
-    const size_t plane = (size_t)n_trees * n_nodes * FTL_M;
-    float *ws = (float *)workspace_dev;
-    if (roots_only) { a.hbuf = ws; a.cbuf = ws + plane; }
-    else { a.hbuf = h_dev; a.cbuf = c_dev ? c_dev : ws; }
+    ftl_planes(a, h_dev, c_dev, workspace_dev);
     fl_launch_tree_lstm(a, (hipStream_t)hip_stream);
-    return ftl_launched(fn);
+    return fl_launched(fn);
 }
 
 size_t fl_tree_lstm_backward_workspace_bytes(int n_trees, int n_nodes) {
@@ -112,7 +100,7 @@ int fl_tree_lstm_backward(int n_trees, int n_nodes, const float *forest_dev, con
                           const float *grad_h_dev, int roots_only, float *da_dev, float *dc_dev, float *dg_dev, float *q_dev,
                           int32_t *child_dev, int32_t *status_dev, void *workspace_dev, size_t workspace_bytes, void *hip_stream) {
     const char *fn = "fl_tree_lstm_backward";
-    const FtlPtr tab[] = {{forest_dev, "forest", 16}, {w_iou_dev, "w_iou", 16}, {b_iou_dev, "b_iou", 16}, {u_iou_dev, "u_iou", 16},
+    const FlPtr tab[] = {{forest_dev, "forest", 16}, {w_iou_dev, "w_iou", 16}, {b_iou_dev, "b_iou", 16}, {u_iou_dev, "u_iou", 16},
                           {w_c_dev, "w_c", 16}, {b_c_dev, "b_c", 16}, {w_f_dev, "w_f", 16}, {b_f_dev, "b_f", 16}, {u_f_dev, "u_f", 16},
                           {h_dev, "h", 16}, {c_dev, "c", 16}, {grad_h_dev, "grad_h", 16}, {da_dev, "da", 16}, {dc_dev, "dc", 16},
                           {dg_dev, "dg", 16}, {q_dev, "q", 16}, {workspace_dev, "workspace", 16},
@@ -129,7 +117,7 @@ int fl_tree_lstm_backward(int n_trees, int n_nodes, const float *forest_dev, con
     a.ghc = (float *)workspace_dev;
     a.gcc = a.ghc + (size_t)n_trees * n_nodes * 3 * FTL_M;
     fl_launch_tree_lstm_bwd(a, (hipStream_t)hip_stream);
-    return ftl_launched(fn);
+    return fl_launched(fn);
 }
 
 size_t fl_tree_lstm_bf16_packed_bytes(void) { return (size_t)FTL16_PACKED * sizeof(__bf16); }
@@ -137,18 +125,10 @@ size_t fl_tree_lstm_bf16_packed_bytes(void) { return (size_t)FTL16_PACKED * size
 int fl_tree_lstm_pack_bf16(const float *u_iou_dev, const float *w_c_dev, const float *u_f_dev, void *packed_dev, size_t packed_bytes,
                            void *hip_stream) {
     const char *fn = "fl_tree_lstm_pack_bf16";
-    const FtlPtr tab[] = {{u_iou_dev, "u_iou", 16}, {w_c_dev, "w_c", 16}, {u_f_dev, "u_f", 16}, {packed_dev, "packed", 16}};
-    for (const FtlPtr &t : tab) {
-        if (!t.p) { fl_set_error("%s: %s is NULL", fn, t.name); return FL_ERR_ARG; }
-        if ((uintptr_t)t.p % t.align) { fl_set_error("%s: %s is not %d-byte aligned", fn, t.name, t.align); return FL_ERR_ARG; }
-    }
-    if (packed_bytes < fl_tree_lstm_bf16_packed_bytes()) {
-        fl_set_error("%s: packed buffer of %zu bytes, %zu needed (fl_tree_lstm_bf16_packed_bytes)", fn, packed_bytes,
-                     fl_tree_lstm_bf16_packed_bytes());
-        return FL_ERR_ARG;
-    }
+    const FlPtr tab[] = {{u_iou_dev, "u_iou", 16}, {w_c_dev, "w_c", 16}, {u_f_dev, "u_f", 16}, {packed_dev, "packed", 16}};
+    if (fl_check_ptrs(fn, tab, 4) != FL_OK || ftl16_check_packed(fn, packed_bytes) != FL_OK) return FL_ERR_ARG;
     fl_launch_tree_lstm_pack_bf16(u_iou_dev, w_c_dev, u_f_dev, packed_dev, (hipStream_t)hip_stream);
-    return ftl_launched(fn);
+    return fl_launched(fn);
 }
 
 size_t fl_tree_lstm_bf16_workspace_bytes(int n_trees, int n_nodes, int roots_only) {
@@ -160,28 +140,20 @@ int fl_tree_lstm_bf16(int n_trees, int n_nodes, const float *forest_dev, const i
                       const float *w_f_dev, const float *b_f_dev, const void *packed_dev, size_t packed_bytes, int roots_only,
                       float *h_dev, float *c_dev, int32_t *status_dev, void *workspace_dev, size_t workspace_bytes, void *hip_stream) {
     const char *fn = "fl_tree_lstm_bf16";
-    const FtlPtr tab[] = {{forest_dev, "forest", 16}, {w_iou_dev, "w_iou", 16}, {b_iou_dev, "b_iou", 16}, {b_c_dev, "b_c", 16},
+    const FlPtr tab[] = {{forest_dev, "forest", 16}, {w_iou_dev, "w_iou", 16}, {b_iou_dev, "b_iou", 16}, {b_c_dev, "b_c", 16},
                           {w_f_dev, "w_f", 16}, {b_f_dev, "b_f", 16}, {packed_dev, "packed", 16},
                           {h_dev, "h", 16}, {workspace_dev, "workspace", 16},
                           {adjacency_dev, "adjacency", 8}, {node_order_dev, "node_order", 8}, {edge_order_dev, "edge_order", 8},
                           {c_dev, "c", 16, true}, {status_dev, "status", 4, true}};
     if (ftl_check(fn, n_trees, n_nodes, roots_only, tab, sizeof tab / sizeof tab[0], workspace_bytes,
-                  fl_tree_lstm_bf16_workspace_bytes(n_trees, n_nodes, roots_only)) != FL_OK) return FL_ERR_ARG;
-    if (packed_bytes < fl_tree_lstm_bf16_packed_bytes()) {
-        fl_set_error("%s: packed buffer of %zu bytes, %zu needed (fl_tree_lstm_bf16_packed_bytes)", fn, packed_bytes,
-                     fl_tree_lstm_bf16_packed_bytes());
-        return FL_ERR_ARG;
-    }
+                  fl_tree_lstm_bf16_workspace_bytes(n_trees, n_nodes, roots_only)) != FL_OK ||
+        ftl16_check_packed(fn, packed_bytes) != FL_OK) return FL_ERR_ARG;
     Ftl16Args a;
     const int rc = ftl_trees(fn, a, n_trees, n_nodes, roots_only, forest_dev, adjacency_dev, node_order_dev, edge_order_dev,
                              {w_iou_dev, b_iou_dev, nullptr, nullptr, b_c_dev, w_f_dev, b_f_dev, nullptr}, status_dev);
     if (rc != FL_OK) return rc;
     a.packed = (const __bf16 *)packed_dev;
-    a.h_out = h_dev; a.c_out = c_dev;
-    const size_t plane = (size_t)n_trees * n_nodes * FTL_M;
-    float *ws = (float *)workspace_dev;
-    if (roots_only) { a.hbuf = ws; a.cbuf = ws + plane; }
-    else { a.hbuf = h_dev; a.cbuf = c_dev ? c_dev : ws; }
+    ftl_planes(a, h_dev, c_dev, workspace_dev);
     fl_launch_tree_lstm_bf16(a, (hipStream_t)hip_stream);
-    return ftl_launched(fn);
+    return fl_launched(fn);
 }

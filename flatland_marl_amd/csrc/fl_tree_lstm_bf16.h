@@ -5,22 +5,18 @@
 //
 // What differs from k_tree_lstm: U_iou [h_k1|h_k2|h_k3], U_f h_kj and W_c [f_1*c_k1|f_2*c_k2|f_3*c_k3] run as
 // v_mfma_f32_32x32x16_bf16 with a float32 accumulator.  The weights come rounded to bf16 (round to nearest even) from
-// fl_tree_lstm_pack_bf16, in the order the kernel streams them (below); h_k is rounded when a tile is staged, f_j * c_kj when it is
+// fl_tree_lstm_pack_bf16, in the order the kernel streams them (fl_bf16.h); h_k is rounded when a tile is staged, f_j * c_kj when it is
 // written over the tile.  W_iou x and W_f x (K = 12) stay exact float32 MFMA steps on top of the recurrent sum started from zero, as
 // in ftl_pre_iou; biases, sigmoid / tanh and the h / c planes the next level reads stay float32.
 //
 // Tile: 32 nodes (FTL_ROWS), wave w computes hidden units 32w .. 32w+31, as in k_tree_lstm.  A staged row is [x f32 x 12 | h_k
 // bf16 x 384] = 816 bytes = 204 dwords, with no padding: a ds_read_b128 is served in groups of 16 lanes whose rows (lane & 31) are
 // a full set of residues mod 16, and a bank row has 16 slots of 16 bytes, so the 16 rows of a group hit 16 distinct slots when the
-// stride in 16-byte slots is odd -- 816 / 16 = 51.  Lane l of a K = 16 step holds A[row l & 31][k = 8 (l >> 5) + j] and B[k][col
-// l & 31], j = 0 .. 7: one 16-byte read of its LDS row and one of the packed weights a step.
+// stride in 16-byte slots is odd -- 816 / 16 = 51.  What a lane holds of a K = 16 step: fl_bf16.h.
 //
-// Packed weights (include/flatland_policy_bf16.h): a matrix W [R][K] is stored as R / 32 blocks of 32 rows; a block holds its K / 16
-// steps one after another, a step the 64 lanes' operands one after another, 8 bf16 each: element j of lane l of step s of block b is
-// W[32 b + (l & 31)][16 s + 8 (l >> 5) + j].  A wave's load of a step is 1 KB of consecutive bytes, eight whole 128-byte lines.  Read
-// in torch's row-major layout instead (each lane 32 bytes of its own weight row a 32-k chunk, a quarter of 32 lines a load) the kernel
-// measured 338 / 4 495 us at cfg2 / cfg3 against 297 / 4 083 us (profiles/tree_lstm_bf16_variants.json).
+// Packed weights: fl_tree_lstm_pack_bf16's buffer holds U_iou, W_c and U_f one after another, each in the format of fl_bf16.h.
 #pragma once
+#include "fl_bf16.h"
 #include "fl_tree_lstm.h"
 
 #define FTL16_XBYTES (FTL_F * 4)                        // the float32 features in front of a staged row
@@ -29,44 +25,10 @@
 #define FTL16_W_C (3 * FTL_M * 3 * FTL_M)
 #define FTL16_U_F (FTL16_W_C + FTL_M * 3 * FTL_M)
 #define FTL16_PACKED (FTL16_U_F + FTL_M * FTL_M)        // 212 992 bf16 = 425 984 bytes
-#define FTL16_STEP 512                                  // bf16 a packed step: 64 lanes x 8
-#ifndef FTL16_UNROLL
-#define FTL16_UNROLL 4                                  // K = 16 steps whose loads are issued together
-#endif
 
 struct Ftl16Args : FtlArgs {
     const __bf16 *packed;           // fl_tree_lstm_pack_bf16's buffer; u_iou, w_c, u_f of FtlTrees are NULL
 };
-
-// this lane's operands of step 0 of block `block` of a packed matrix of K columns
-template <int K>
-__device__ __forceinline__ const __bf16 *ftl16_block(const __bf16 *w, int block, int lane) {
-    return w + (size_t)block * (K / 16) * FTL16_STEP + lane * 8;
-}
-
-// acc += A[row][k] * W[32 b + col][k] over k in [0, K), K a multiple of 16; arow = this lane's staged h_k / f*c_k row + 8 hh,
-// wl = ftl16_block of the matrix
-template <int K>
-__device__ __forceinline__ void ftl16_gemm1(const __bf16 *arow, const __bf16 *wl, fl_f32x16 &acc) {
-#pragma unroll FTL16_UNROLL
-    for (int s = 0; s < K / 16; s++)
-        acc = fl_mfma_bf16(*(const fl_bf16x8 *)(arow + 16 * s), *(const fl_bf16x8 *)(wl + s * FTL16_STEP), acc);
-}
-
-// the same for three blocks at once (i, o, u of one hidden unit), sharing the A operand
-template <int K>
-__device__ __forceinline__ void ftl16_gemm3(const __bf16 *arow, const __bf16 *w0, const __bf16 *w1, const __bf16 *w2, fl_f32x16 &c0,
-                                            fl_f32x16 &c1, fl_f32x16 &c2) {
-#pragma unroll FTL16_UNROLL
-    for (int s = 0; s < K / 16; s++) {
-        const fl_bf16x8 a = *(const fl_bf16x8 *)(arow + 16 * s);
-        const fl_bf16x8 b0 = *(const fl_bf16x8 *)(w0 + s * FTL16_STEP), b1 = *(const fl_bf16x8 *)(w1 + s * FTL16_STEP),
-                        b2 = *(const fl_bf16x8 *)(w2 + s * FTL16_STEP);
-        c0 = fl_mfma_bf16(a, b0, c0);
-        c1 = fl_mfma_bf16(a, b1, c1);
-        c2 = fl_mfma_bf16(a, b2, c2);
-    }
-}
 
 // stage [x | bf16(h_k1) | bf16(h_k2) | bf16(h_k3)] of a tile of level n in 16-byte units (3 of x, 16 a child); h = the float32 plane
 // that holds every node's h, rowg / rowch = a tile row's global node id and its children's (-1 = zero)
@@ -88,8 +50,7 @@ __device__ __forceinline__ void ftl16_stage(unsigned char *s_t, const int *rowg,
             fl_bf16x8 o = {};
             if (ch >= 0) {
                 const float4 a = ((const float4 *)h)[(size_t)ch * (M / 4) + 2 * qq], b = ((const float4 *)h)[(size_t)ch * (M / 4) + 2 * qq + 1];
-                o[0] = (__bf16)a.x; o[1] = (__bf16)a.y; o[2] = (__bf16)a.z; o[3] = (__bf16)a.w;
-                o[4] = (__bf16)b.x; o[5] = (__bf16)b.y; o[6] = (__bf16)b.z; o[7] = (__bf16)b.w;
+                o = fl_bf16_round8(a, b);
             }
             *(fl_bf16x8 *)(row + 16 * q) = o;
         }
@@ -166,10 +127,13 @@ __global__ void __launch_bounds__(FTL_THREADS) k_tree_lstm_bf16(Ftl16Args p) {
             const float *xrow = (const float *)(s_t + col * FTL16_STRIDE);              // this lane's A row (MFMA row = lane & 31)
             const __bf16 *hrow = (const __bf16 *)(s_t + col * FTL16_STRIDE + FTL16_XBYTES) + 8 * hh;    // ... and its k half of a step
             const fl_f32x16 zero = {};
-            fl_f32x16 ai = zero, ao = zero, au = zero;
-            if (n > 0)          // the i, o, u rows of this wave's hidden units: blocks w, 4 + w, 8 + w of U_iou
-                ftl16_gemm3<3 * FTL_M>(hrow, ftl16_block<3 * FTL_M>(u_iou, wave, lane), ftl16_block<3 * FTL_M>(u_iou, 4 + wave, lane),
-                                       ftl16_block<3 * FTL_M>(u_iou, 8 + wave, lane), ai, ao, au);
+            fl_f32x16 iou[3] = {zero, zero, zero};
+            if (n > 0) {        // the i, o, u rows of this wave's hidden units: blocks w, 4 + w, 8 + w of U_iou
+                const __bf16 *const ws[3] = {fl_bf16_block(u_iou, 3 * M, wave, lane), fl_bf16_block(u_iou, 3 * M, 4 + wave, lane),
+                                             fl_bf16_block(u_iou, 3 * M, 8 + wave, lane)};
+                fl_bf16_mm<3>(hrow, 3 * M / 16, ws, iou);
+            }
+            fl_f32x16 &ai = iou[0], &ao = iou[1], &au = iou[2];
             ftl_wx(xrow, p.w_iou, j0, M + j0, 2 * M + j0, col, ai, ao, au, 3, hh);       // exact float32, on top of U h
             const float bi = p.b_iou[j0 + col], bo = p.b_iou[M + j0 + col], bu = p.b_iou[2 * M + j0 + col];
             float iu[16], og[16], cc[16];
@@ -186,7 +150,7 @@ __global__ void __launch_bounds__(FTL_THREADS) k_tree_lstm_bf16(Ftl16Args p) {
 #pragma unroll
                 for (int j = 0; j < 3; j++) {
                     fl_f32x16 af = zero;
-                    ftl16_gemm1<FTL_M>(hrow + j * M, ftl16_block<FTL_M>(u_f, wave, lane), af);
+                    fl_bf16_mm(hrow + j * M, M / 16, fl_bf16_block(u_f, M, wave, lane), af);
 #pragma unroll
                     for (int r = 0; r < 16; r++) {
                         const int row = fl_acc_row(r, hh);
@@ -205,7 +169,7 @@ __global__ void __launch_bounds__(FTL_THREADS) k_tree_lstm_bf16(Ftl16Args p) {
                     }
                 __syncthreads();
                 fl_f32x16 ac = zero;
-                ftl16_gemm1<3 * FTL_M>(hrow, ftl16_block<3 * FTL_M>(w_c, wave, lane), ac);
+                fl_bf16_mm(hrow, 3 * M / 16, fl_bf16_block(w_c, 3 * M, wave, lane), ac);
                 const float bc = p.b_c[j0 + col];
 #pragma unroll
                 for (int r = 0; r < 16; r++) cc[r] = iu[r] + (ac[r] + bc);
@@ -229,22 +193,12 @@ __global__ void __launch_bounds__(FTL_THREADS) k_tree_lstm_bf16(Ftl16Args p) {
     }
 }
 
-// fl_tree_lstm_pack_bf16: element i of the packed buffer = bf16(its source element), round to nearest even (v_cvt_pk_bf16_f32)
-__global__ void __launch_bounds__(256) k_tree_lstm_pack_bf16(const float *u_iou, const float *w_c, const float *u_f, __bf16 *dst) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= FTL16_PACKED) return;
-    const float *src = i < FTL16_W_C ? u_iou : i < FTL16_U_F ? w_c : u_f;
-    const int K = i < FTL16_U_F ? 3 * FTL_M : FTL_M;
-    const int e = i - (i < FTL16_W_C ? FTL16_U_IOU : i < FTL16_U_F ? FTL16_W_C : FTL16_U_F);
-    const int j = e & 7, l = (e >> 3) & 63, t = e / FTL16_STEP;
-    const int step = t % (K / 16), block = t / (K / 16);
-    dst[i] = (__bf16)src[(size_t)(32 * block + (l & 31)) * K + 16 * step + 8 * (l >> 5) + j];
-}
-
 static inline void fl_launch_tree_lstm_bf16(const Ftl16Args &a, hipStream_t s) {
     hipLaunchKernelGGL(k_tree_lstm_bf16, dim3((a.T + a.G - 1) / a.G), dim3(FTL_THREADS), 0, s, a);
 }
 
+// fl_tree_lstm_pack_bf16: the three matrices at FTL16_U_IOU, FTL16_W_C, FTL16_U_F
 static inline void fl_launch_tree_lstm_pack_bf16(const float *u_iou, const float *w_c, const float *u_f, void *dst, hipStream_t s) {
-    hipLaunchKernelGGL(k_tree_lstm_pack_bf16, dim3((FTL16_PACKED + 255) / 256), dim3(256), 0, s, u_iou, w_c, u_f, (__bf16 *)dst);
+    FlBf16Pack<3> a = {{u_iou, w_c, u_f}, {}, {3 * FTL_M, 3 * FTL_M, FTL_M}};
+    fl_launch_bf16_pack(a, {3 * FTL_M, FTL_M, FTL_M}, dst, s);
 }

@@ -191,6 +191,32 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def _check_tensors(what, dev, specs, torch_names=False):
+    """The tensor checks of the policy wrappers.  specs: (name, tensor or None, dtype, minimum elements or None); a tensor that is
+    given must be contiguous, of that dtype, on dev, and hold at least that many elements.  The message names the dtype as
+    "float32", or with torch_names as "torch.float32"."""
+    for name, o, dt, n in specs:
+        if o is not None and (o.dtype != dt or o.device != dev or not o.is_contiguous() or (n is not None and o.numel() < n)):
+            raise ValueError("%s: %s must be a contiguous %s tensor %son %s"
+                             % (what, name, dt if torch_names else str(dt).replace("torch.", ""),
+                                "" if n is None else "of at least %d elements " % n, dev))
+
+
+def _call(fn, dev, workspace_bytes, *args):
+    """fn(*args[, workspace, its bytes], stream) on torch's current stream of dev, with a workspace from torch's allocator
+    (workspace_bytes None: the entry point takes none); raises on a refusal"""
+    import torch
+    with torch.cuda.device(dev):
+        if workspace_bytes is not None:
+            ws = torch.empty(max(workspace_bytes, 16), dtype=torch.uint8, device=dev)
+            args += (ws.data_ptr(), ws.numel())
+        _chk(fn(*args, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+
+
+def _opt(t):
+    return None if t is None else t.data_ptr()
+
+
 def malf_threshold(rate):
     """ceil((1 - exp(-rate)) * 2**53): `np_random.rand() < _malfunction_prob(rate)` as a 53-bit integer
     compare (malfunction_generators.py:24-33,46-53)."""
@@ -225,23 +251,48 @@ def tree_lstm(forest, adjacency, node_order, edge_order, weights, roots_only, h,
     forest f32 [..., N, 12], adjacency i64 [..., N-1, 3] (modified), node_order i64 [..., N], edge_order i64 [..., N-1], all
     contiguous on one device; weights = (W_iou.weight, W_iou.bias, U_iou.weight, W_c.weight, W_c.bias, W_f.weight, W_f.bias,
     U_f.weight), f32 contiguous; h (and c, if given) f32 [T*N, 128] or, roots_only, [T, 128]; status i32 [1] or None."""
+    return _tree_lstm("tree_lstm", forest, adjacency, node_order, edge_order, weights, None, roots_only, h, c, status)
+
+
+def _tree_lstm(what, forest, adjacency, node_order, edge_order, weights, packed, roots_only, h, c, status):
+    """tree_lstm (packed None) and tree_lstm_bf16: fl_<what>"""
     import torch
     N = forest.shape[-2]
     T = forest.numel() // (N * 12)
-    fn = _sym("fl_tree_lstm")
+    dev = forest.device
+    fn = _sym("fl_" + what)
+    bf16 = what == "tree_lstm_bf16"
+    if bf16 and len(weights) != 8:
+        raise ValueError("%s: %d weights, 8 expected" % (what, len(weights)))
     rows = (T if roots_only else T * N) * 128
-    for name, o in (("h", h), ("c", c)):
-        if o is not None and (o.dtype != torch.float32 or o.device != forest.device or not o.is_contiguous() or o.numel() < rows):
-            raise ValueError("tree_lstm: %s must be a contiguous float32 tensor of at least %d elements on %s" % (name, rows, forest.device))
-    nbytes = lib().fl_tree_lstm_workspace_bytes(T, N, int(roots_only))
-    with torch.cuda.device(forest.device):
-        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=forest.device)
-        s = torch.cuda.current_stream(forest.device).cuda_stream
-        _chk(fn(T, N, forest.data_ptr(), adjacency.data_ptr(), node_order.data_ptr(), edge_order.data_ptr(),
-                *[w.data_ptr() for w in weights], int(roots_only), h.data_ptr(),
-                None if c is None else c.data_ptr(), None if status is None else status.data_ptr(),
-                ws.data_ptr(), ws.numel(), C.c_void_p(s)))
+    _check_tensors(what, dev, (("h", h, torch.float32, rows), ("c", c, torch.float32, rows)))
+    if bf16:
+        if packed.dtype != torch.uint8 or packed.device != dev or not packed.is_contiguous():
+            raise ValueError("%s: packed must be a contiguous uint8 tensor on %s (tree_lstm_pack_bf16)" % (what, dev))
+        mats = [weights[i].data_ptr() for i in (0, 1, 4, 5, 6)] + [packed.data_ptr(), packed.numel()]
+    else:
+        mats = [w.data_ptr() for w in weights]
+    _call(fn, dev, _sym("fl_%s_workspace_bytes" % what)(T, N, int(roots_only)),
+          T, N, forest.data_ptr(), adjacency.data_ptr(), node_order.data_ptr(), edge_order.data_ptr(), *mats, int(roots_only),
+          h.data_ptr(), _opt(c), _opt(status))
     return h
+
+
+def _pack_bf16(kind, dev, out, elements, *args):
+    """The second half of tree_lstm_pack_bf16 and policy_head_pack_bf16 (kind "tree_lstm" / "policy_head"): out (None: a new
+    buffer) and the call fl_<kind>_pack_bf16(*args, out, its bytes, stream).  elements: how many the matrices have together, where
+    that is still to be compared with the buffer's size (None: checked already)"""
+    import torch
+    what = kind + "_pack_bf16"
+    fn = _sym("fl_" + what)
+    nbytes = _sym("fl_%s_bf16_packed_bytes" % kind)()
+    if elements is not None and elements * 2 != nbytes:
+        raise ValueError("%s: the 16 matrices must have %d elements together" % (what, nbytes // 2))
+    if out is None:
+        out = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    _check_tensors(what, dev, [("out", out, torch.uint8, nbytes)])
+    _call(fn, dev, None, *args, out.data_ptr(), out.numel())
+    return out
 
 
 def tree_lstm_pack_bf16(weights, out=None):
@@ -257,16 +308,7 @@ def tree_lstm_pack_bf16(weights, out=None):
     for name, w, n in (("U_iou.weight", u_iou, 384 * 384), ("W_c.weight", w_c, 128 * 384), ("U_f.weight", u_f, 128 * 128)):
         if w.dtype != torch.float32 or w.device != dev or not w.is_contiguous() or w.numel() != n:
             raise ValueError("tree_lstm_pack_bf16: %s must be a contiguous float32 tensor of %d elements on %s" % (name, n, dev))
-    fn = _sym("fl_tree_lstm_pack_bf16")
-    nbytes = _sym("fl_tree_lstm_bf16_packed_bytes")()
-    with torch.cuda.device(dev):
-        if out is None:
-            out = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        elif out.dtype != torch.uint8 or out.device != dev or not out.is_contiguous() or out.numel() < nbytes:
-            raise ValueError("tree_lstm_pack_bf16: out must be a contiguous uint8 tensor of at least %d elements on %s" % (nbytes, dev))
-        s = torch.cuda.current_stream(dev).cuda_stream
-        _chk(fn(u_iou.data_ptr(), w_c.data_ptr(), u_f.data_ptr(), out.data_ptr(), out.numel(), C.c_void_p(s)))
-    return out
+    return _pack_bf16("tree_lstm", dev, out, None, u_iou.data_ptr(), w_c.data_ptr(), u_f.data_ptr())
 
 
 def tree_lstm_bf16(forest, adjacency, node_order, edge_order, weights, packed, roots_only, h, c=None, status=None):
@@ -274,27 +316,7 @@ def tree_lstm_bf16(forest, adjacency, node_order, edge_order, weights, packed, r
     include/flatland_policy_bf16.h), for inference, on torch's current stream of the inputs' device, with a workspace from torch's
     allocator.  Inputs, weights (the eight of tree_lstm: the five float32 ones are read), h, c and status as for tree_lstm; packed:
     what tree_lstm_pack_bf16 made of the same weights."""
-    import torch
-    N = forest.shape[-2]
-    T = forest.numel() // (N * 12)
-    fn = _sym("fl_tree_lstm_bf16")
-    if len(weights) != 8:
-        raise ValueError("tree_lstm_bf16: %d weights, 8 expected" % len(weights))
-    rows = (T if roots_only else T * N) * 128
-    for name, o in (("h", h), ("c", c)):
-        if o is not None and (o.dtype != torch.float32 or o.device != forest.device or not o.is_contiguous() or o.numel() < rows):
-            raise ValueError("tree_lstm_bf16: %s must be a contiguous float32 tensor of at least %d elements on %s" % (name, rows, forest.device))
-    if packed.dtype != torch.uint8 or packed.device != forest.device or not packed.is_contiguous():
-        raise ValueError("tree_lstm_bf16: packed must be a contiguous uint8 tensor on %s (tree_lstm_pack_bf16)" % (forest.device,))
-    nbytes = _sym("fl_tree_lstm_bf16_workspace_bytes")(T, N, int(roots_only))
-    with torch.cuda.device(forest.device):
-        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=forest.device)
-        s = torch.cuda.current_stream(forest.device).cuda_stream
-        _chk(fn(T, N, forest.data_ptr(), adjacency.data_ptr(), node_order.data_ptr(), edge_order.data_ptr(),
-                *[weights[i].data_ptr() for i in (0, 1, 4, 5, 6)], packed.data_ptr(), packed.numel(), int(roots_only), h.data_ptr(),
-                None if c is None else c.data_ptr(), None if status is None else status.data_ptr(),
-                ws.data_ptr(), ws.numel(), C.c_void_p(s)))
-    return h
+    return _tree_lstm("tree_lstm_bf16", forest, adjacency, node_order, edge_order, weights, packed, roots_only, h, c, status)
 
 
 def tree_lstm_backward(forest, adjacency, node_order, edge_order, weights, h, c, grad_h, roots_only, da, dc, dg, q, child,
@@ -311,27 +333,22 @@ def tree_lstm_backward(forest, adjacency, node_order, edge_order, weights, h, c,
     dev = forest.device
     if len(weights) != 8:
         raise ValueError("tree_lstm_backward: %d weights, 8 expected" % len(weights))
-    for name, o, dt in [("forest", forest, torch.float32), ("adjacency", adjacency, torch.int64), ("node_order", node_order, torch.int64),
-                        ("edge_order", edge_order, torch.int64)] + [("weight %d" % i, w, torch.float32) for i, w in enumerate(weights)]:
-        if o.dtype != dt or o.device != dev or not o.is_contiguous():
-            raise ValueError("tree_lstm_backward: %s must be a contiguous %s tensor on %s" % (name, dt, dev))
+    _check_tensors("tree_lstm_backward", dev,
+                   [("forest", forest, torch.float32, None), ("adjacency", adjacency, torch.int64, None),
+                    ("node_order", node_order, torch.int64, None), ("edge_order", edge_order, torch.int64, None)]
+                   + [("weight %d" % i, w, torch.float32, None) for i, w in enumerate(weights)], torch_names=True)
     if adjacency.numel() != T * (N - 1) * 3 or node_order.numel() != T * N or edge_order.numel() != T * (N - 1):
         raise ValueError("tree_lstm_backward: index tensors of %d trees x %d nodes are expected" % (T, N))
-    for name, o, dt, n in (("h", h, torch.float32, T * N * 128), ("c", c, torch.float32, T * N * 128),
-                           ("grad_h", grad_h, torch.float32, (T if roots_only else T * N) * 128),
-                           ("da", da, torch.float32, T * N * 384), ("dc", dc, torch.float32, T * N * 128),
-                           ("dg", dg, torch.float32, T * N * 384), ("q", q, torch.float32, T * N * 384),
-                           ("child", child, torch.int32, T * N * 3)):
-        if o.dtype != dt or o.device != dev or not o.is_contiguous() or o.numel() < n:
-            raise ValueError("tree_lstm_backward: %s must be a contiguous %s tensor of at least %d elements on %s" % (name, dt, n, dev))
-    nbytes = _sym("fl_tree_lstm_backward_workspace_bytes")(T, N)
-    with torch.cuda.device(dev):
-        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
-        s = torch.cuda.current_stream(dev).cuda_stream
-        _chk(fn(T, N, forest.data_ptr(), adjacency.data_ptr(), node_order.data_ptr(), edge_order.data_ptr(),
-                *[w.data_ptr() for w in weights], h.data_ptr(), c.data_ptr(), grad_h.data_ptr(), int(roots_only),
-                da.data_ptr(), dc.data_ptr(), dg.data_ptr(), q.data_ptr(), child.data_ptr(),
-                None if status is None else status.data_ptr(), ws.data_ptr(), ws.numel(), C.c_void_p(s)))
+    _check_tensors("tree_lstm_backward", dev,
+                   (("h", h, torch.float32, T * N * 128), ("c", c, torch.float32, T * N * 128),
+                    ("grad_h", grad_h, torch.float32, (T if roots_only else T * N) * 128),
+                    ("da", da, torch.float32, T * N * 384), ("dc", dc, torch.float32, T * N * 128),
+                    ("dg", dg, torch.float32, T * N * 384), ("q", q, torch.float32, T * N * 384),
+                    ("child", child, torch.int32, T * N * 3)), torch_names=True)
+    _call(fn, dev, _sym("fl_tree_lstm_backward_workspace_bytes")(T, N),
+          T, N, forest.data_ptr(), adjacency.data_ptr(), node_order.data_ptr(), edge_order.data_ptr(),
+          *[w.data_ptr() for w in weights], h.data_ptr(), c.data_ptr(), grad_h.data_ptr(), int(roots_only),
+          da.data_ptr(), dc.data_ptr(), dg.data_ptr(), q.data_ptr(), child.data_ptr(), _opt(status))
 
 
 def policy_head(agents_attr, tree_embedding, params, logits, value=None, valid_actions=None, actions=None, mode=None, u=None):
@@ -339,27 +356,29 @@ def policy_head(agents_attr, tree_embedding, params, logits, value=None, valid_a
     device, with a workspace from torch's allocator.  agents_attr f32 [B, A, 83], tree_embedding f32 [B, A, 128]; params = the 38
     tensors of include/flatland_policy.h in its order, f32 contiguous; logits f32 [B, A, 5]; value f32 [B] or None (the critic is
     not run); mode None / "soft" / "hard" with valid_actions u8 [B, A, 5] and actions u8 [B, A]; u None = the reference's constant."""
+    return _policy_head("policy_head", agents_attr, tree_embedding, params, None, logits, value, valid_actions, actions, mode, u)
+
+
+def _policy_head(what, agents_attr, tree_embedding, params, packed, logits, value, valid_actions, actions, mode, u):
+    """policy_head (packed None) and policy_head_bf16: fl_<what>"""
     import torch
     B, A = agents_attr.shape[:2]
-    fn = _sym("fl_policy_head")
+    fn = _sym("fl_" + what)
     if mode not in POLICY_SELECT:
-        raise ValueError("policy_head: mode must be None, 'soft' or 'hard', got %r" % (mode,))
+        raise ValueError("%s: mode must be None, 'soft' or 'hard', got %r" % (what, mode))
     if len(params) != POLICY_HEAD_NPARAMS:
-        raise ValueError("policy_head: %d parameters, %d expected" % (len(params), POLICY_HEAD_NPARAMS))
+        raise ValueError("%s: %d parameters, %d expected" % (what, len(params), POLICY_HEAD_NPARAMS))
     dev = agents_attr.device
-    for name, o, dt, n in (("logits", logits, torch.float32, B * A * 5), ("value", value, torch.float32, B),
-                           ("valid_actions", valid_actions, torch.uint8, B * A * 5), ("actions", actions, torch.uint8, B * A)):
-        if o is not None and (o.dtype != dt or o.device != dev or not o.is_contiguous() or o.numel() < n):
-            raise ValueError("policy_head: %s must be a contiguous %s tensor of at least %d elements on %s" % (name, dt, n, dev))
-    ptrs = (vp * POLICY_HEAD_NPARAMS)(*[w.data_ptr() for w in params])
-    nbytes = _sym("fl_policy_head_workspace_bytes")(B, A)
-    opt = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-    with torch.cuda.device(dev):
-        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
-        s = torch.cuda.current_stream(dev).cuda_stream
-        _chk(fn(B, A, agents_attr.data_ptr(), tree_embedding.data_ptr(), ptrs, opt(valid_actions), POLICY_SELECT[mode],
-                POLICY_U_REFERENCE if u is None else float(u), logits.data_ptr(), opt(value), opt(actions), ws.data_ptr(),
-                ws.numel(), C.c_void_p(s)))
+    _check_tensors(what, dev, (("logits", logits, torch.float32, B * A * 5), ("value", value, torch.float32, B),
+                               ("valid_actions", valid_actions, torch.uint8, B * A * 5), ("actions", actions, torch.uint8, B * A)),
+                   torch_names=True)
+    bf16 = what == "policy_head_bf16"
+    if bf16 and (packed.dtype != torch.uint8 or packed.device != dev or not packed.is_contiguous()):
+        raise ValueError("%s: packed must be a contiguous uint8 tensor on %s (policy_head_pack_bf16)" % (what, dev))
+    weights = [(vp * POLICY_HEAD_NPARAMS)(*[w.data_ptr() for w in params])] + ([packed.data_ptr(), packed.numel()] if bf16 else [])
+    _call(fn, dev, _sym("fl_%s_workspace_bytes" % what)(B, A),
+          B, A, agents_attr.data_ptr(), tree_embedding.data_ptr(), *weights, _opt(valid_actions), POLICY_SELECT[mode],
+          POLICY_U_REFERENCE if u is None else float(u), logits.data_ptr(), _opt(value), _opt(actions))
     return logits
 
 
@@ -376,19 +395,8 @@ def policy_head_pack_bf16(weights, out=None):
         w = weights[i]
         if w.dtype != torch.float32 or w.device != dev or not w.is_contiguous() or w.dim() != 2:
             raise ValueError("policy_head_pack_bf16: parameter %d must be a contiguous float32 matrix on %s" % (i, dev))
-    fn = _sym("fl_policy_head_pack_bf16")
-    nbytes = _sym("fl_policy_head_bf16_packed_bytes")()
-    if sum(weights[i].numel() for i in POLICY_HEAD_BF16_MATRICES) * 2 != nbytes:
-        raise ValueError("policy_head_pack_bf16: the 16 matrices must have %d elements together" % (nbytes // 2))
-    ptrs = (vp * POLICY_HEAD_NPARAMS)(*[None if w is None else w.data_ptr() for w in weights])
-    with torch.cuda.device(dev):
-        if out is None:
-            out = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        elif out.dtype != torch.uint8 or out.device != dev or not out.is_contiguous() or out.numel() < nbytes:
-            raise ValueError("policy_head_pack_bf16: out must be a contiguous uint8 tensor of at least %d elements on %s" % (nbytes, dev))
-        s = torch.cuda.current_stream(dev).cuda_stream
-        _chk(fn(ptrs, out.data_ptr(), out.numel(), C.c_void_p(s)))
-    return out
+    return _pack_bf16("policy_head", dev, out, sum(weights[i].numel() for i in POLICY_HEAD_BF16_MATRICES),
+                      (vp * POLICY_HEAD_NPARAMS)(*[None if w is None else w.data_ptr() for w in weights]))
 
 
 def policy_head_bf16(agents_attr, tree_embedding, params, packed, logits, value=None, valid_actions=None, actions=None, mode=None,
@@ -396,30 +404,7 @@ def policy_head_bf16(agents_attr, tree_embedding, params, packed, logits, value=
     """policy_head with bf16 matrix operands in 16 of its 19 matrices (fl_policy_head_bf16, include/flatland_policy_head_bf16.h),
     for inference, on torch's current stream of the inputs' device, with a workspace from torch's allocator.  The arguments of
     policy_head; packed: what policy_head_pack_bf16 made of the same params."""
-    import torch
-    B, A = agents_attr.shape[:2]
-    fn = _sym("fl_policy_head_bf16")
-    if mode not in POLICY_SELECT:
-        raise ValueError("policy_head_bf16: mode must be None, 'soft' or 'hard', got %r" % (mode,))
-    if len(params) != POLICY_HEAD_NPARAMS:
-        raise ValueError("policy_head_bf16: %d parameters, %d expected" % (len(params), POLICY_HEAD_NPARAMS))
-    dev = agents_attr.device
-    for name, o, dt, n in (("logits", logits, torch.float32, B * A * 5), ("value", value, torch.float32, B),
-                           ("valid_actions", valid_actions, torch.uint8, B * A * 5), ("actions", actions, torch.uint8, B * A)):
-        if o is not None and (o.dtype != dt or o.device != dev or not o.is_contiguous() or o.numel() < n):
-            raise ValueError("policy_head_bf16: %s must be a contiguous %s tensor of at least %d elements on %s" % (name, dt, n, dev))
-    if packed.dtype != torch.uint8 or packed.device != dev or not packed.is_contiguous():
-        raise ValueError("policy_head_bf16: packed must be a contiguous uint8 tensor on %s (policy_head_pack_bf16)" % (dev,))
-    ptrs = (vp * POLICY_HEAD_NPARAMS)(*[w.data_ptr() for w in params])
-    nbytes = _sym("fl_policy_head_bf16_workspace_bytes")(B, A)
-    opt = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-    with torch.cuda.device(dev):
-        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
-        s = torch.cuda.current_stream(dev).cuda_stream
-        _chk(fn(B, A, agents_attr.data_ptr(), tree_embedding.data_ptr(), ptrs, packed.data_ptr(), packed.numel(), opt(valid_actions),
-                POLICY_SELECT[mode], POLICY_U_REFERENCE if u is None else float(u), logits.data_ptr(), opt(value), opt(actions),
-                ws.data_ptr(), ws.numel(), C.c_void_p(s)))
-    return logits
+    return _policy_head("policy_head_bf16", agents_attr, tree_embedding, params, packed, logits, value, valid_actions, actions, mode, u)
 
 
 # (name, floats a row) of the arrays of saved_dev and rows_dev, in their order (include/flatland_policy_train.h): array k of R rows
@@ -458,10 +443,9 @@ def _policy_train_check(what, agents_attr, tree_embedding, params):
         raise ValueError("%s: %d parameters, %d expected" % (what, len(params), POLICY_HEAD_NPARAMS))
     dev = agents_attr.device
     B, A = agents_attr.shape[:2]
-    for name, o, n in [("agents_attr", agents_attr, B * A * 83), ("tree_embedding", tree_embedding, B * A * 128)] + \
-            [("parameter %d" % i, w, 1) for i, w in enumerate(params)]:
-        if o.dtype != torch.float32 or o.device != dev or not o.is_contiguous() or o.numel() < n:
-            raise ValueError("%s: %s must be a contiguous float32 tensor of at least %d elements on %s" % (what, name, n, dev))
+    _check_tensors(what, dev, [("agents_attr", agents_attr, torch.float32, B * A * 83),
+                               ("tree_embedding", tree_embedding, torch.float32, B * A * 128)]
+                   + [("parameter %d" % i, w, torch.float32, 1) for i, w in enumerate(params)])
     return B, A, dev
 
 
@@ -471,15 +455,11 @@ def policy_head_forward_saved(agents_attr, tree_embedding, params, logits, value
     f32 [B, A, 5]; value f32 [B] or None; saved: a float32 tensor of at least B * A * POLICY_SAVED_FLOATS elements."""
     import torch
     B, A, dev = _policy_train_check("policy_head_forward_saved", agents_attr, tree_embedding, params)
-    for name, o, n in (("logits", logits, B * A * 5), ("value", value, B), ("saved", saved, policy_saved_floats(B, A))):
-        if o is not None and (o.dtype != torch.float32 or o.device != dev or not o.is_contiguous() or o.numel() < n):
-            raise ValueError("policy_head_forward_saved: %s must be a contiguous float32 tensor of at least %d elements on %s" % (name, n, dev))
-    fn = _sym("fl_policy_head_forward_saved")
+    _check_tensors("policy_head_forward_saved", dev, (("logits", logits, torch.float32, B * A * 5), ("value", value, torch.float32, B),
+                                                      ("saved", saved, torch.float32, policy_saved_floats(B, A))))
     ptrs = (vp * POLICY_HEAD_NPARAMS)(*[w.data_ptr() for w in params])
-    with torch.cuda.device(dev):
-        s = torch.cuda.current_stream(dev).cuda_stream
-        _chk(fn(B, A, agents_attr.data_ptr(), tree_embedding.data_ptr(), ptrs, logits.data_ptr(),
-                None if value is None else value.data_ptr(), saved.data_ptr(), saved.numel() * 4, C.c_void_p(s)))
+    _call(_sym("fl_policy_head_forward_saved"), dev, None, B, A, agents_attr.data_ptr(), tree_embedding.data_ptr(), ptrs,
+          logits.data_ptr(), _opt(value), saved.data_ptr(), saved.numel() * 4)
     return logits
 
 
@@ -491,19 +471,14 @@ def policy_head_backward(agents_attr, tree_embedding, params, saved, grad_logits
     policy.policy_head_param_grads forms them from the rows."""
     import torch
     B, A, dev = _policy_train_check("policy_head_backward", agents_attr, tree_embedding, params)
-    for name, o, n in (("saved", saved, policy_saved_floats(B, A)), ("grad_logits", grad_logits, B * A * 5),
-                       ("grad_value", grad_value, B), ("grad_tree", grad_tree, B * A * 128), ("rows", rows, B * A * POLICY_ROW_FLOATS)):
-        if o is not None and (o.dtype != torch.float32 or o.device != dev or not o.is_contiguous() or o.numel() < n):
-            raise ValueError("policy_head_backward: %s must be a contiguous float32 tensor of at least %d elements on %s" % (name, n, dev))
-    fn = _sym("fl_policy_head_backward")
+    _check_tensors("policy_head_backward", dev,
+                   (("saved", saved, torch.float32, policy_saved_floats(B, A)), ("grad_logits", grad_logits, torch.float32, B * A * 5),
+                    ("grad_value", grad_value, torch.float32, B), ("grad_tree", grad_tree, torch.float32, B * A * 128),
+                    ("rows", rows, torch.float32, B * A * POLICY_ROW_FLOATS)))
     ptrs = (vp * POLICY_HEAD_NPARAMS)(*[w.data_ptr() for w in params])
-    nbytes = _sym("fl_policy_head_backward_workspace_bytes")(B, A)
-    opt = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-    with torch.cuda.device(dev):
-        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
-        s = torch.cuda.current_stream(dev).cuda_stream
-        _chk(fn(B, A, agents_attr.data_ptr(), tree_embedding.data_ptr(), ptrs, saved.data_ptr(), opt(grad_logits), opt(grad_value),
-                grad_tree.data_ptr(), rows.data_ptr(), rows.numel() * 4, ws.data_ptr(), ws.numel(), C.c_void_p(s)))
+    _call(_sym("fl_policy_head_backward"), dev, _sym("fl_policy_head_backward_workspace_bytes")(B, A),
+          B, A, agents_attr.data_ptr(), tree_embedding.data_ptr(), ptrs, saved.data_ptr(), _opt(grad_logits), _opt(grad_value),
+          grad_tree.data_ptr(), rows.data_ptr(), rows.numel() * 4)
     return grad_tree
 
 

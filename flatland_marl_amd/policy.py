@@ -140,37 +140,53 @@ class _TrainForward(torch.autograd.Function):
 
 
 class _Forward(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, forest, adjacency, node_order, edge_order, roots_only, status, *weights):
-        B, A, N = forest.shape[:3]
-        T = B * A
-        h = torch.empty((T if roots_only else T * N, OUT_FEATURES), dtype=torch.float32, device=forest.device)
-        hip_backend.tree_lstm(forest, adjacency, node_order, edge_order, weights, roots_only, h, status=status)
-        return h
+    """the inference forward: fl_tree_lstm (packed None), or fl_tree_lstm_bf16 on the packed bf16 buffer"""
 
-    @staticmethod
-    def backward(ctx, *grads):
-        raise NotImplementedError("TreeLSTM (fl_tree_lstm) is inference only: no backward")
-
-
-class _ForwardBf16(torch.autograd.Function):
     @staticmethod
     def forward(ctx, forest, adjacency, node_order, edge_order, roots_only, status, packed, *weights):
         B, A, N = forest.shape[:3]
         T = B * A
         h = torch.empty((T if roots_only else T * N, OUT_FEATURES), dtype=torch.float32, device=forest.device)
-        hip_backend.tree_lstm_bf16(forest, adjacency, node_order, edge_order, weights, packed, roots_only, h, status=status)
+        if packed is None:
+            hip_backend.tree_lstm(forest, adjacency, node_order, edge_order, weights, roots_only, h, status=status)
+        else:
+            hip_backend.tree_lstm_bf16(forest, adjacency, node_order, edge_order, weights, packed, roots_only, h, status=status)
+        ctx.bf16 = packed is not None
         return h
 
     @staticmethod
     def backward(ctx, *grads):
-        raise NotImplementedError("TreeLSTM (fl_tree_lstm_bf16) is inference only: no backward; training runs precision='f32'")
+        if ctx.bf16:
+            raise NotImplementedError("TreeLSTM (fl_tree_lstm_bf16) is inference only: no backward; training runs precision='f32'")
+        raise NotImplementedError("TreeLSTM (fl_tree_lstm) is inference only: no backward")
 
 
 def _precision(value, what="TreeLSTM: precision"):
     if value not in PRECISIONS:
         raise ValueError("%s must be 'f32' or 'bf16', got %r" % (what, value))
     return value
+
+
+def _switches(module, trainable, attr, precision, what):
+    """the plain attributes TreeLSTM and Network share: trainable, the precision switch `attr` (`what` names it in a refusal) and
+    _packed, the cache of _packed_bf16, empty"""
+    module.trainable = bool(trainable)
+    setattr(module, attr, _precision(precision, what))
+    module._packed = {}
+
+
+def _packed_bf16(module, pack, ws, matrices, device):
+    """The bf16 buffer of the matrices ws[i], i in `matrices`, for torch's current stream, kept in module._packed as (device, stream)
+    -> (what was packed, the buffer): packed by pack(ws, the old buffer or None) at the first use on that stream, and again when one
+    of the matrices is another tensor (data_ptr) or was written in place (_version) since -- load_state_dict and an optimizer step
+    both are; a write through `.data` bumps no version and is not seen (clear module._packed after one).  One buffer a stream,
+    packed and read on that stream only, so no launch waits on another stream's."""
+    key = tuple((ws[i].data_ptr(), ws[i]._version) for i in matrices)
+    slot = (device, torch.cuda.current_stream(device).cuda_stream)
+    have = module._packed.get(slot)
+    if have is None or have[0] != key:
+        module._packed[slot] = have = (key, pack(ws, None if have is None else have[1]))
+    return have[1]
 
 
 class TreeLSTM(nn.Module):
@@ -184,9 +200,7 @@ class TreeLSTM(nn.Module):
 
     def __init__(self, in_features=IN_FEATURES, out_features=OUT_FEATURES, trainable=False, precision="f32"):
         super().__init__()
-        self.trainable = bool(trainable)
-        self.precision = _precision(precision)
-        self._packed = {}      # stream -> (what was packed, the bf16 buffer): see _packed_weights
+        _switches(self, trainable, "precision", precision, "TreeLSTM: precision")
         if (in_features, out_features) != (IN_FEATURES, OUT_FEATURES):
             raise ValueError("TreeLSTM: only in_features=%d, out_features=%d exist here, got %d, %d"
                              % (IN_FEATURES, OUT_FEATURES, in_features, out_features))
@@ -207,9 +221,7 @@ class TreeLSTM(nn.Module):
         obj = cls.__new__(cls)
         nn.Module.__init__(obj)
         obj.in_features, obj.out_features = m.in_features, m.out_features
-        obj.trainable = bool(trainable)
-        obj.precision = _precision(precision)
-        obj._packed = {}
+        _switches(obj, trainable, "precision", precision, "TreeLSTM: precision")
         for name in ("W_iou", "U_iou", "W_c", "W_f", "U_f"):
             setattr(obj, name, getattr(m, name))
         return obj
@@ -224,20 +236,6 @@ class TreeLSTM(nn.Module):
                                 % (name, device, w.dtype, w.device, "" if w.is_contiguous() else ", not contiguous"))
             ws.append(w)
         return ws
-
-    def _packed_weights(self, ws, device):
-        """the bf16 buffer of U_iou, W_c and U_f for torch's current stream: packed at the first use on that stream, and again when
-        one of the three is another tensor (data_ptr) or was written in place (_version) since -- load_state_dict and an optimizer
-        step both are; a write through `.data` bumps no version and is not seen (clear self._packed after one).  One buffer a
-        stream, packed and read on that stream only, so no launch waits on another stream's."""
-        stream = torch.cuda.current_stream(device)
-        key = tuple((w.data_ptr(), w._version) for w in (ws[2], ws[3], ws[7]))
-        slot = (device, stream.cuda_stream)
-        have = self._packed.get(slot)
-        if have is None or have[0] != key:
-            buf = hip_backend.tree_lstm_pack_bf16(ws, None if have is None else have[1])
-            self._packed[slot] = have = (key, buf)
-        return have[1]
 
     @staticmethod
     def _check_inputs(forest, adjacency, node_order, edge_order):
@@ -278,11 +276,11 @@ class TreeLSTM(nn.Module):
         if train and forest.requires_grad:
             raise ValueError("TreeLSTM: the forest gets no gradient (fl_tree_lstm_backward differentiates with respect to the "
                              "parameters only): detach it")
-        if bf16:
-            out = _ForwardBf16.apply(forest, adjacency, node_order, edge_order, roots_only, status,
-                                     self._packed_weights(ws, forest.device), *ws)
-        else:
-            out = (_TrainForward if train else _Forward).apply(forest, adjacency, node_order, edge_order, roots_only, status, *ws)
+        if train:
+            out = _TrainForward.apply(forest, adjacency, node_order, edge_order, roots_only, status, *ws)
+        else:                                        # U_iou, W_c and U_f (items 2, 3, 7) are the packed ones
+            packed = _packed_bf16(self, hip_backend.tree_lstm_pack_bf16, ws, (2, 3, 7), forest.device) if bf16 else None
+            out = _Forward.apply(forest, adjacency, node_order, edge_order, roots_only, status, packed, *ws)
         if check:
             bad = int(status.item())
             if bad:
@@ -341,25 +339,8 @@ def _mlp(sizes, last_act):
 
 
 class _Head(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, agents_attr, tree_embedding, valid_actions, mode, u, with_value, *weights):
-        B, A = agents_attr.shape[:2]
-        dev = agents_attr.device
-        logits = torch.empty((B, A, ACTIONS), dtype=torch.float32, device=dev)
-        value = torch.empty((B,), dtype=torch.float32, device=dev) if with_value else None
-        actions = torch.empty((B, A), dtype=torch.uint8, device=dev) if mode is not None else None
-        hip_backend.policy_head(agents_attr, tree_embedding, weights, logits, value, valid_actions, actions, mode, u)
-        out = (logits,) + ((value,) if with_value else ()) + ((actions,) if actions is not None else ())
-        if actions is not None:
-            ctx.mark_non_differentiable(actions)
-        return out
+    """the inference head: fl_policy_head (packed None), or fl_policy_head_bf16 on the packed bf16 buffer"""
 
-    @staticmethod
-    def backward(ctx, *grads):
-        raise NotImplementedError("Network (fl_policy_head) is inference only: no backward; forward_torch is the path with autograd")
-
-
-class _HeadBf16(torch.autograd.Function):
     @staticmethod
     def forward(ctx, agents_attr, tree_embedding, valid_actions, mode, u, with_value, packed, *weights):
         B, A = agents_attr.shape[:2]
@@ -367,15 +348,21 @@ class _HeadBf16(torch.autograd.Function):
         logits = torch.empty((B, A, ACTIONS), dtype=torch.float32, device=dev)
         value = torch.empty((B,), dtype=torch.float32, device=dev) if with_value else None
         actions = torch.empty((B, A), dtype=torch.uint8, device=dev) if mode is not None else None
-        hip_backend.policy_head_bf16(agents_attr, tree_embedding, weights, packed, logits, value, valid_actions, actions, mode, u)
+        if packed is None:
+            hip_backend.policy_head(agents_attr, tree_embedding, weights, logits, value, valid_actions, actions, mode, u)
+        else:
+            hip_backend.policy_head_bf16(agents_attr, tree_embedding, weights, packed, logits, value, valid_actions, actions, mode, u)
         out = (logits,) + ((value,) if with_value else ()) + ((actions,) if actions is not None else ())
         if actions is not None:
             ctx.mark_non_differentiable(actions)
+        ctx.bf16 = packed is not None
         return out
 
     @staticmethod
     def backward(ctx, *grads):
-        raise NotImplementedError("Network (fl_policy_head_bf16) is inference only: no backward; training runs head_precision='f32'")
+        if ctx.bf16:
+            raise NotImplementedError("Network (fl_policy_head_bf16) is inference only: no backward; training runs head_precision='f32'")
+        raise NotImplementedError("Network (fl_policy_head) is inference only: no backward; forward_torch is the path with autograd")
 
 
 # (env, agent) rows a fl_policy_head_backward launch: saved forward + rows are 54.9 KB a row, 1.8 GB a chunk (8 192 rows measured
@@ -492,9 +479,7 @@ class Network(nn.Module):
 
     def __init__(self, trainable=False, precision="f32", head_precision="f32"):
         super().__init__()
-        self.trainable = bool(trainable)
-        self.head_precision = _precision(head_precision, "Network: head_precision")
-        self._packed = {}      # (device, stream) -> (what was packed, the bf16 buffer): see _packed_head
+        _switches(self, trainable, "head_precision", head_precision, "Network: head_precision")
         self.tree_lstm = TreeLSTM(IN_FEATURES, OUT_FEATURES, precision=precision)
         self.attr_embedding = _mlp((AGENT_ATTR, 2 * HIDDEN, 2 * HIDDEN, 2 * HIDDEN, HIDDEN), True)
         self.transformer = nn.Sequential(*[Transformer(EMBED, HEADS) for _ in range(3)])
@@ -507,10 +492,8 @@ class Network(nn.Module):
         m.tree_lstm's own ("f32" for the reference's); head_precision: None = m's own ("f32" for the reference's)"""
         obj = cls.__new__(cls)
         nn.Module.__init__(obj)
-        obj.trainable = bool(trainable)
-        obj.head_precision = _precision(getattr(m, "head_precision", "f32") if head_precision is None else head_precision,
-                                        "Network: head_precision")
-        obj._packed = {}
+        _switches(obj, trainable, "head_precision", getattr(m, "head_precision", "f32") if head_precision is None else head_precision,
+                  "Network: head_precision")
         obj.tree_lstm = TreeLSTM.from_module(m.tree_lstm, trainable=getattr(m.tree_lstm, "trainable", False),
                                              precision=getattr(m.tree_lstm, "precision", "f32") if precision is None else precision)
         obj.attr_embedding = m.attr_embedding
@@ -539,19 +522,6 @@ class Network(nn.Module):
                                 % (name, device, w.dtype, w.device, "" if w.is_contiguous() else ", not contiguous"))
             ws.append(w)
         return ws
-
-    def _packed_head(self, ws, device):
-        """the bf16 buffer of the head's 16 matrices for torch's current stream, as TreeLSTM._packed_weights keeps the encoder's:
-        packed at the first use on that stream, and again when one of the 16 is another tensor (data_ptr) or was written in place
-        (_version) since"""
-        stream = torch.cuda.current_stream(device)
-        key = tuple((ws[i].data_ptr(), ws[i]._version) for i in hip_backend.POLICY_HEAD_BF16_MATRICES)
-        slot = (device, stream.cuda_stream)
-        have = self._packed.get(slot)
-        if have is None or have[0] != key:
-            buf = hip_backend.policy_head_pack_bf16(ws, None if have is None else have[1])
-            self._packed[slot] = have = (key, buf)
-        return have[1]
 
     @staticmethod
     def _shapes():
@@ -619,12 +589,13 @@ class Network(nn.Module):
         if train and agents_attr.requires_grad:
             raise ValueError("Network: agents_attr gets no gradient (fl_policy_head_backward differentiates with respect to the "
                              "parameters and the tree embedding only): detach it")
-        if bf16:
-            out = list(_HeadBf16.apply(agents_attr, tree_embedding, valid_actions if mode is not None else None, mode, u, bool(value),
-                                       self._packed_head(ws, agents_attr.device), *ws))
+        args = (agents_attr, tree_embedding, valid_actions if mode is not None else None, mode, u, bool(value))
+        if train:
+            out = list(_HeadTrain.apply(*args, *ws))
         else:
-            out = list((_HeadTrain if train else _Head).apply(agents_attr, tree_embedding, valid_actions if mode is not None else None,
-                                                              mode, u, bool(value), *ws))
+            packed = _packed_bf16(self, hip_backend.policy_head_pack_bf16, ws, hip_backend.POLICY_HEAD_BF16_MATRICES,
+                                  agents_attr.device) if bf16 else None
+            out = list(_Head.apply(*args, packed, *ws))
         logits = out.pop(0)
         val = out.pop(0) if value else None
         return ([logits], val) + ((out.pop(0),) if mode is not None else ())

@@ -4,9 +4,11 @@ cfg2 (1 x 20), cfg2 (256 x 20), cfg3 (1 024 x 80) and cfg5 (256 x 400), logits, 
 
 Times are HIP-event medians around one call through the C entry points (8 kernel launches), buffers allocated beforehand.  With
 --parent-lib the calls alternate in --rounds interleaved rounds between fl_policy_head of that library (the parent commit's
-build), fl_policy_head of this build and fl_policy_head_bf16 of this build; a round's figure is the median of --launches calls.
-Per shape the file holds every round's medians, the spread (max - min) of the parent's, whether this build's float32 median lies
-inside the parent's range, and whether the bf16 median is below the parent's by more than that spread.  fl_policy_head_pack_bf16
+build), fl_policy_head of this build and fl_policy_head_bf16 of this build -- and, where the parent exports it, the parent's own
+fl_policy_head_bf16; a round's figure is the median of --launches calls.  Per shape the file holds every round's medians, the
+spread (max - min) of the parent's, whether this build's float32 median lies inside the parent's range, and whether the bf16
+median is below the parent's by more than that spread; against the parent's bf16, whether the outputs are the same bits and this
+build's bf16 median is not above the parent's by more than the spread of the parent's bf16.  fl_policy_head_pack_bf16
 is timed on its own: the module calls it when a weight changed, not per step.
 
 --rocprof adds the time of every kernel, bf16 and float32 side by side, from a separate `rocprofv3 --kernel-trace --stats` run of
@@ -94,17 +96,23 @@ def f32_call(L, x, w):
     return call, out
 
 
-def bf16_call(hb, x, w, packed):
+def bf16_call(hb, L, x, w):
+    """the same for fl_policy_head_bf16 of library L, on the buffer that L's own fl_policy_head_pack_bf16 packs here"""
     import torch
     vp = C.c_void_p
-    fn = hb._sym("fl_policy_head_bf16")
+    for name, (argtypes, restype) in hb._POLICY_HEAD_BF16_ABI.items():
+        getattr(L, name).argtypes, getattr(L, name).restype = argtypes, restype
+    fn = L.fl_policy_head_bf16
     B, A = x[0].shape[:2]
-    ws = torch.empty(max(hb._sym("fl_policy_head_bf16_workspace_bytes")(B, A), 16), dtype=torch.uint8, device=x[0].device)
+    ws = torch.empty(max(L.fl_policy_head_bf16_workspace_bytes(B, A), 16), dtype=torch.uint8, device=x[0].device)
     out = outputs(B, A, x[0].device)
     ptrs = (vp * 38)(*[v.data_ptr() for v in w])
     s = vp(torch.cuda.current_stream().cuda_stream)
+    packed = torch.empty(L.fl_policy_head_bf16_packed_bytes(), dtype=torch.uint8, device=x[0].device)
+    rc = L.fl_policy_head_pack_bf16(ptrs, packed.data_ptr(), packed.numel(), s)
+    assert rc == 0, rc
 
-    def call(keep=(ws, out, ptrs)):
+    def call(keep=(ws, out, ptrs, packed)):
         rc = fn(B, A, x[0].data_ptr(), x[1].data_ptr(), ptrs, packed.data_ptr(), packed.numel(), x[2].data_ptr(), 1, 0.3745401188473625,
                 out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), ws.data_ptr(), ws.numel(), s)
         assert rc == 0, rc
@@ -117,12 +125,11 @@ def kernels_only(args):
     from flatland_marl_amd import hip_backend as hb
     for label, B, A in SHAPES:
         x, w = setup(B, A)
-        packed = hb.policy_head_pack_bf16(w)
-        for call, _ in (f32_call(hb.lib(), x, w), bf16_call(hb, x, w, packed)):
+        for call, _ in (f32_call(hb.lib(), x, w), bf16_call(hb, hb.lib(), x, w)):
             for _ in range(args.warmup + args.launches):
                 call()
             torch.cuda.synchronize()
-        del x, w, packed
+        del x, w
         torch.cuda.empty_cache()
 
 
@@ -137,8 +144,7 @@ def rocprof_kernel_times(args):
         rows = []
         for t in glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True):
             with open(t) as f:
-                rows += [r for r in csv.DictReader(f) if "k_ph_" in r["Kernel_Name"] or "k_ph16_" in r["Kernel_Name"]]
-        rows = [r for r in rows if "k_ph16_pack" not in r["Kernel_Name"]]
+                rows += [r for r in csv.DictReader(f) if "k_ph_" in r["Kernel_Name"] or "k_ph16_" in r["Kernel_Name"]]      # (not the pack)
         rows.sort(key=lambda r: int(r["Start_Timestamp"]))
         per = (args.warmup + args.launches) * KERNELS_A_CALL
         assert len(rows) == 2 * per * len(SHAPES), (len(rows), per)
@@ -176,17 +182,21 @@ def main():
         return
     from flatland_marl_amd import hip_backend as hb
     parent = C.CDLL(os.path.abspath(args.parent_lib)) if args.parent_lib else None
+    parent_has_bf16 = parent is not None and hasattr(parent, "fl_policy_head_bf16")
     rows, pack_us = [], None
     for label, B, A in SHAPES:
         x, w = setup(B, A)
-        packed = hb.policy_head_pack_bf16(w)
         if pack_us is None:
+            packed = hb.policy_head_pack_bf16(w)
             pack_us = [round(median_events(lambda: hb.policy_head_pack_bf16(w, packed), args.warmup, args.launches) * 1e3, 2)
                        for _ in range(args.rounds)]
+            del packed
         calls = []
         if parent is not None:
             calls.append(("parent_f32", f32_call(parent, x, w)))
-        calls += [("f32", f32_call(hb.lib(), x, w)), ("bf16", bf16_call(hb, x, w, packed))]
+        if parent_has_bf16:
+            calls.append(("parent_bf16", bf16_call(hb, parent, x, w)))
+        calls += [("f32", f32_call(hb.lib(), x, w)), ("bf16", bf16_call(hb, hb.lib(), x, w))]
         med = {k: [] for k, _ in calls}
         for _ in range(args.rounds):
             for k, (call, _) in calls:
@@ -210,6 +220,11 @@ def main():
                      f32_median_inside_parent_range=bool(lo <= mid["f32"] <= hi),
                      speedup_bf16_vs_parent_f32=round(mid["parent_f32"] / mid["bf16"], 3),
                      bf16_faster_than_parent_by_more_than_its_spread=bool(mid["parent_f32"] - mid["bf16"] > hi - lo))
+        if parent_has_bf16:
+            lo, hi = min(med["parent_bf16"]), max(med["parent_bf16"])
+            r.update(bf16_bits_equal_parent=all(bool(torch.equal(a, b)) for a, b in zip(outs["parent_bf16"], outs["bf16"])),
+                     parent_bf16_spread_us=round(hi - lo, 2),
+                     bf16_not_slower_than_parent_bf16_by_more_than_its_spread=bool(mid["bf16"] - mid["parent_bf16"] <= hi - lo))
         if ktimes:
             kf, kb = ktimes[(label, "f32")], ktimes[(label, "bf16")]
             total = sum(kb.values())
@@ -218,7 +233,7 @@ def main():
                      share_of_bf16_matrix_peak=round(bf16_flop(B, A) / (total * 1e-6) / PEAK_BF16, 5))
         rows.append(r)
         print(json.dumps(r), flush=True)
-        del calls, outs, x, w, packed
+        del calls, outs, x, w
         torch.cuda.empty_cache()
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

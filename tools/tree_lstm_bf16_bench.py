@@ -5,9 +5,11 @@ roots alone ("roots", what Network.act launches).
 
 Times are HIP-event medians around one launch through the C entry points, buffers allocated beforehand.  With --parent-lib the
 launches alternate in --rounds interleaved rounds between fl_tree_lstm of that library (the parent commit's build), fl_tree_lstm
-of this build and fl_tree_lstm_bf16 of this build; a round's figure is the median of --launches launches.  Per shape and mode the
-file holds every round's medians, the spread (max - min) of the parent's, and whether this build's float32 median lies inside
-the parent's range and the bf16 median is below the parent's by more than that spread.
+of this build and fl_tree_lstm_bf16 of this build -- and, where the parent exports it, the parent's own fl_tree_lstm_bf16; a
+round's figure is the median of --launches launches.  Per shape and mode the file holds every round's medians, the spread (max -
+min) of the parent's, and whether this build's float32 median lies inside the parent's range and the bf16 median is below the
+parent's by more than that spread; against the parent's bf16, whether the outputs are the same bits and this build's bf16 median is
+not above the parent's by more than the spread of the parent's bf16.
 
 The achieved share of the bf16 matrix peak (2 516.8 TF = 16 x the 157.3 TF float32 matrix peak, MI355X_MICROARCH.md) counts the
 FLOP of the three recurrent products alone (491 520 a node above height 0).  The weight stream is counted from the inputs: a
@@ -86,18 +88,24 @@ def f32_call(L, x, w, roots_only):
     return call, h
 
 
-def bf16_call(hb, x, w, packed, roots_only):
+def bf16_call(hb, L, x, w, roots_only):
+    """the same for fl_tree_lstm_bf16 of library L, on the buffer that L's own fl_tree_lstm_pack_bf16 packs here"""
     import torch
     vp = C.c_void_p
-    fn = hb._sym("fl_tree_lstm_bf16")
+    for name, (argtypes, restype) in hb._POLICY_BF16_ABI.items():
+        getattr(L, name).argtypes, getattr(L, name).restype = argtypes, restype
+    fn = L.fl_tree_lstm_bf16
     N = x[0].shape[-2]
     T = x[0].numel() // (N * 12)
-    n = hb._sym("fl_tree_lstm_bf16_workspace_bytes")(T, N, roots_only)
+    s = vp(torch.cuda.current_stream().cuda_stream)
+    packed = torch.empty(L.fl_tree_lstm_bf16_packed_bytes(), dtype=torch.uint8, device=x[0].device)
+    rc = L.fl_tree_lstm_pack_bf16(w[2].data_ptr(), w[3].data_ptr(), w[7].data_ptr(), packed.data_ptr(), packed.numel(), s)
+    assert rc == 0, rc
+    n = L.fl_tree_lstm_bf16_workspace_bytes(T, N, roots_only)
     ws = torch.empty(max(n, 16), dtype=torch.uint8, device=x[0].device)
     h = torch.empty((T if roots_only else T * N, 128), device=x[0].device)
-    s = vp(torch.cuda.current_stream().cuda_stream)
 
-    def call(keep=(ws, h)):
+    def call(keep=(ws, h, packed)):
         rc = fn(T, N, *[v.data_ptr() for v in x], *[w[i].data_ptr() for i in (0, 1, 4, 5, 6)], packed.data_ptr(), packed.numel(),
                 roots_only, h.data_ptr(), None, None, ws.data_ptr(), ws.numel(), s)
         assert rc == 0, rc
@@ -160,8 +168,8 @@ def main():
     cu = torch.cuda.get_device_properties(0).multi_processor_count
     params = seeded_params(7)
     w = [params[k].to(dev).contiguous() for k in PARAM_ORDER]
-    packed = hb.tree_lstm_pack_bf16(w)
     parent = C.CDLL(os.path.abspath(args.parent_lib)) if args.parent_lib else None
+    parent_has_bf16 = parent is not None and hasattr(parent, "fl_tree_lstm_bf16")
     rows = []
     for label, wl_name, B, N in SHAPES:
         x = inputs(wl_name, B, N)
@@ -174,7 +182,9 @@ def main():
             calls = []
             if parent is not None:
                 calls.append(("parent_f32", f32_call(parent, x, w, ro)))
-            calls += [("f32", f32_call(hb.lib(), x, w, ro)), ("bf16", bf16_call(hb, x, w, packed, ro))]
+            if parent_has_bf16:
+                calls.append(("parent_bf16", bf16_call(hb, parent, x, w, ro)))
+            calls += [("f32", f32_call(hb.lib(), x, w, ro)), ("bf16", bf16_call(hb, hb.lib(), x, w, ro))]
             med = {k: [] for k, _ in calls}
             for _ in range(args.rounds):
                 for k, (call, _) in calls:
@@ -199,6 +209,11 @@ def main():
                          f32_median_inside_parent_range=bool(lo <= mid["f32"] <= hi),
                          speedup_bf16_vs_parent_f32=round(mid["parent_f32"] / mid["bf16"], 3),
                          bf16_faster_than_parent_by_more_than_its_spread=bool(mid["parent_f32"] - mid["bf16"] > hi - lo))
+            if parent_has_bf16:
+                lo, hi = min(med["parent_bf16"]), max(med["parent_bf16"])
+                r.update(bf16_bits_equal_parent=bool(torch.equal(outs["parent_bf16"], outs["bf16"])),
+                         parent_bf16_spread_us=round(hi - lo, 2),
+                         bf16_not_slower_than_parent_bf16_by_more_than_its_spread=bool(mid["bf16"] - mid["parent_bf16"] <= hi - lo))
             rows.append(r)
             print(json.dumps(r), flush=True)
             del calls, outs
