@@ -825,6 +825,62 @@ __device__ __forceinline__ void obs_body(const FlDev &d, const FlObsScratch &S, 
         // exclusive scan over the keys: per-thread chunk sums, wave-0 scan of the partial sums, rescan.  With the second
         // index both counts share the scan, 16 bits each (the launcher guarantees totals below 65536).
         const bool bk_major = bk && !bk_lds;   // large maps: the items laid out bucket-major (see the fill)
+#ifdef OBS_NO_LEAN_FILL
+        constexpr bool LEAN_FILL = false;
+#else
+        constexpr bool LEAN_FILL = MERGED == 1;   // the one-round kernels (classes 1, 6, 11, runtime carving of MODES 3 / 6); every other kernel keeps the general body of the fill
+#endif
+#ifdef OBS_NO_FLAT_FILL
+        constexpr bool FLAT_FILL = false;         // the one-round kernels fill on the loop of the others: a wavefront per agent
+#else
+        constexpr bool FLAT_FILL = LEAN_FILL;
+#endif
+#ifdef FL_OBS_TIMING
+        // marks of the one-round kernels' fill (slots 33 .. 36 of the env; no stage 2 there): the latest wavefront's end of its first
+        // body and of the loop, the longest wait for the path words of a first body (since the start of the fill)
+        long long fill_t0_ = 0;
+#define FILL_MARK_T0() do { fill_t0_ = (long long)wall_clock64(); } while (0)
+#define FILL_MARK_WAIT(first) do { if (LEAN_FILL && (first)) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); \
+            if (lane == 0) atomicMax((unsigned long long *)&X.dbg[35], (unsigned long long)((long long)wall_clock64() - fill_t0_)); } } while (0)
+#define FILL_MARK_BODY(first) do { if (LEAN_FILL && (first) && lane == 0) atomicMax((unsigned long long *)&X.dbg[33], (unsigned long long)wall_clock64()); } while (0)
+#define FILL_MARK_END() do { if (LEAN_FILL && lane == 0) atomicMax((unsigned long long *)&X.dbg[34], (unsigned long long)wall_clock64()); } while (0)
+#else
+#define FILL_MARK_T0() do {} while (0)
+#define FILL_MARK_WAIT(first) do {} while (0)
+#define FILL_MARK_BODY(first) do {} while (0)
+#define FILL_MARK_END() do {} while (0)
+#endif
+        // The fill of the one-round kernels (FLAT_FILL, below the scan) lays the waypoints of all agents end to end -- agent a has the
+        // items incl[a - 1] .. incl[a] - 1, waypoint k = t - incl[a - 1] -- and gives item t to lane t of the workgroup.  a_lp[] is
+        // final behind the barrier above, so the mapping and the three path words an item needs (HBM scratch, written by the walkers)
+        // are requested HERE: the three barriers of the scan cover the round trip.  Every wavefront keeps the inclusive prefix of
+        // lp + 1 on its lanes a < A (A <= 32 in these kernels); the agents a wavefront's 64 items touch are a short range that two
+        // ballots give as scalars, and a lane counts the piece ends at or below its t through v_readlane (no LDS round trip).
+        int ff_incl = 0, ff_total = 0, ff_i = 0, ff_k = 0, ff_lp = 0;
+        uint32_t ff_w = 0, ff_wn = 0, ff_wp = 0;
+        auto ff_request = [&](int t) __attribute__((always_inline)) {   // wave-uniform call: t = t0 + lane, t0 a multiple of 64 below ff_total
+            const int t_first = __builtin_amdgcn_readfirstlane(t);
+            const int a_lo = __popcll(__ballot(ff_incl <= t_first)), a_hi = min(__popcll(__ballot(ff_incl <= t_first + 63)), A - 1);
+            int i = a_lo, start = a_lo > 0 ? __builtin_amdgcn_readlane(ff_incl, max(a_lo - 1, 0)) : 0;
+            for (int a = a_lo; a < a_hi; a++) {   // (scalar bounds; the end of agent a's piece is the start of agent a + 1's)
+                const int e = __builtin_amdgcn_readlane(ff_incl, a);
+                const bool c = e <= t;
+                i += c ? 1 : 0;
+                start = c ? e : start;
+            }
+            ff_i = i; ff_k = t - start;
+            if (t < ff_total) {
+                const uint16_t *pth = S.path + ((size_t)b * A + i) * OBS_PRED_CAP;
+                const int lpn = a_lp[i], k = t - start;
+                ff_lp = lpn;
+                ff_w = pth[k]; ff_wn = pth[min(k + 1, lpn)]; ff_wp = pth[max(k - 1, 0)];
+            }
+        };
+        if (FLAT_FILL && !bk_major) {
+            ff_incl = wave_incl_scan<64>(lane < A ? (int)a_lp[lane] + 1 : 0);   // (the lanes from A on: the total)
+            ff_total = __builtin_amdgcn_readlane(ff_incl, 63);
+            if ((wave << 6) < ff_total) ff_request(tid);
+        }
         if (!reuse && !bk_major) {
             const int chunk = (K + 1 + nt - 1) / nt;
             const int lo = min(tid * chunk, K + 1), hi = min(lo + chunk, K + 1);
@@ -949,16 +1005,12 @@ __device__ __forceinline__ void obs_body(const FlDev &d, const FlObsScratch &S, 
         if (merged && UP && !dual_fill) atomicCAS(&d.err[b], 0, FL_ERR_CAPACITY);  // (cannot happen: the LDS copy holds the exact bound)
         if (fit && !reuse) { csr_items = items_lds; X.items_lds = items_lds; }
         // fill: bumping csr[key] turns it from the start into the END offset of key's list (start = csr[key - 1]);
-        // one wavefront per agent, one lane per waypoint
+        // one wavefront per agent, one lane per waypoint -- except the one-round kernels (FLAT_FILL, see above the scan): one item
+        // space over the lanes of the workgroup, the path words requested in front of the scan
         // (the waypoints come from HBM scratch: four of them per lane are requested at once -- 500 waypoints are two round trips
         // instead of eight -- and the first four of the agent the wavefront takes NEXT are requested before the items of this
         // one are emitted)
         constexpr int FU = 4;
-#ifdef OBS_NO_LEAN_FILL
-        constexpr bool LEAN_FILL = false;
-#else
-        constexpr bool LEAN_FILL = MERGED == 1;   // the one-round kernels (classes 1, 6, 11, runtime carving of MODES 3 / 6); every other kernel keeps the body below
-#endif
         uint32_t pfv[FU] = {0, 0, 0, 0}, pfn[FU] = {0, 0, 0, 0}, pfp[FU] = {0, 0, 0, 0};
         auto prefetch = [&](int ia) __attribute__((always_inline)) {
             if (reuse || ia >= A) return;
@@ -970,6 +1022,94 @@ __device__ __forceinline__ void obs_body(const FlDev &d, const FlObsScratch &S, 
                 pfv[q] = pth[k]; pfn[q] = pth[min(k + 1, lpn)]; pfp[q] = pth[max(k - 1, 0)];
             }
         };
+        // One item of the one-round kernels (LEAN_FILL): waypoint k of agent i, w = path[k], wn / wp = the waypoints behind and in front
+        // of it (clamped to the piece 0 .. lp).  The same ORs and list slots as the general body below, ordered so that the LDS round
+        // trips overlap: the returning atomics of both indices go out first, the direction masks (cf_dirs_swar, no loop over the
+        // nibbles; the second index's four 32-bit words as two 64-bit ORs) are worked out and ORed while those are in flight, and what
+        // depends on a returned value -- the second-item masks, the item stores -- comes last.
+        auto lean_item = [&](int i, int k, int lp, int tpc, int lp2, int tpc2, uint32_t w, uint32_t wn, uint32_t wp) __attribute__((always_inline)) {
+            const int tlast = X.Tn - 1;
+            const uint32_t dnext = k < lp ? (wn & 3u) : (w & 3u), dprev = k > 0 ? (wp & 3u) : (w & 3u);
+            int tlo, span;   // closed time interval during which the agent is predicted on waypoint k (see the general body)
+            if (CUTILS) {
+                tlo = k == 0 ? 0 : (k - 1) * tpc + 1;
+                span = k == 0 ? 1 : tpc;
+            } else {
+                tlo = k * tpc;
+                span = tpc;
+            }
+            const bool to_end = k == lp || tlo + span - 1 >= tlast;
+            const int key = key_of(X, (int)(w >> 2));
+            const int b1 = tb_of(tlo, X.tshift), b2 = tb_of(to_end ? tlast : tlo + span - 1, X.tshift);
+            const unsigned long long bits = ((2ull << b2) - 1ull) & ~((1ull << b1) - 1ull);
+            const bool second = k <= lp2, done = a_state[i] == ST_DONE;
+            const int tlo2 = k * tpc2, tlast2 = Tn2 - 1;
+            const bool to_end2 = k == lp2 || tlo2 + tpc2 - 1 >= tlast2;
+            unsigned long long bits2 = 0ull, seen = 0ull, seen2 = 0ull;
+            int slot2 = 0;
+            if (X.tmask && X.tmask_m2) seen = atomicOr(&tmask[key], bits);
+            else if (X.tmask) atomicOr(&tmask[key], bits);
+            if (second) {
+                if (p_use_tmask) {
+                    const int c1 = tb_of(tlo2, tshift2), c2 = tb_of(to_end2 ? tlast2 : tlo2 + tpc2 - 1, tshift2);
+                    bits2 = ((2ull << c2) - 1ull) & ~((1ull << c1) - 1ull);
+                    if (X.tmask_m2) seen2 = atomicOr(&tmaskb[key], bits2);
+                    else atomicOr(&tmaskb[key], bits2);
+                }
+                slot2 = atomicAdd(&csr2[key], 1);
+            }
+            const uint32_t rail = cw_bits(X, (int)(w >> 2));
+            if (X.tmask && cmask) {
+                const uint32_t dirs = cf_dirs_swar(rail, cf_against(w & 3u) | cf_against(dnext) | cf_against(dprev), done);
+#pragma unroll
+                for (uint32_t dw = 0; dw < 4; dw++)
+                    if ((dirs >> dw) & 1u) atomicOr(&cmask[((uint32_t)key << 2) | dw], bits);
+            }
+            if (second && p_use_tmask && cmaskb) {  // (at most 32 predicted times: bucket = time, the low word of bits2)
+                const uint32_t dirs = cf_dirs_swar(rail, cf_against(w & 3u), done);
+                const unsigned long long lo32 = (unsigned long long)(uint32_t)bits2;
+                const unsigned long long v01 = ((dirs & 1u) ? lo32 : 0ull) | ((dirs & 2u) ? lo32 << 32 : 0ull);
+                const unsigned long long v23 = ((dirs & 4u) ? lo32 : 0ull) | ((dirs & 8u) ? lo32 << 32 : 0ull);
+                unsigned long long *cb = reinterpret_cast<unsigned long long *>(cmaskb) + ((uint32_t)key << 1);   // words (key << 2 | 0, 1) and (2, 3)
+                if (v01) atomicOr(&cb[0], v01);
+                if (v23) atomicOr(&cb[1], v23);
+            }
+            const uint32_t item = IT_MAKE(lab ? (int)lab[i] : i, tlo, to_end, span, dprev, dnext, w & 3u);
+            if (bk) {
+                const int thi = to_end ? tlast : tlo + span - 1;
+                int c1 = min(tlo >> bk_shift, bk_nb - 1), c2 = min(thi >> bk_shift, bk_nb - 1);
+                if (bk_lds && to_end) c1 = c2 = bk_nb;
+                for (int bb = c1; bb <= c2; bb++) {
+                    const int kb = key * bk_w + bb;
+                    const uint32_t old = atomicAdd(&bkc[kb >> 1], (kb & 1) ? 0x10000u : 1u);
+                    csr_items[csr[key] + (int)((kb & 1) ? (old >> 16) : (old & 0xFFFFu))] = item;
+                }
+            } else {
+                const int slot = atomicAdd(&csr[key], 1);
+                csr_items[slot] = item;
+            }
+            if (seen & bits) atomicOr(&tmask_m2[key], seen & bits);  // covered by a second item
+            if (second) {
+                if (seen2 & bits2) atomicOr(&tmaskb_m2[key], seen2 & bits2);
+                items2[slot2] = IT_MAKE(i, tlo2, to_end2, tpc2, dprev, k < lp2 ? dnext : (w & 3u), w & 3u);
+            }
+        };
+        if (FLAT_FILL && !bk_major) {
+            // One-round kernels: the waypoints of all agents as ONE item space split over the lanes of the workgroup (ff_request, in
+            // front of the key scan, found each lane's agent and waypoint and requested its three path words): one pass of the body
+            // where the env has at most nt items, whatever the number of agents.
+            FILL_MARK_T0();
+            for (int t0 = wave << 6; t0 < ff_total; t0 += nt) {   // (wave-uniform: ff_request runs with every lane)
+                const int i = ff_i, k = ff_k, lp = ff_lp;
+                const uint32_t w = ff_w, wn = ff_wn, wp = ff_wp;
+                FILL_MARK_WAIT(t0 == wave << 6);
+                if (t0 + nt < ff_total) ff_request(t0 + nt + lane);   // a further pass: its words are on the way during this one's body
+                if (t0 + lane < ff_total)
+                    lean_item(i, k, lp, a_tpc[i], dual_fill ? (int)a_lp2[i] : -1, dual_fill ? (int)a_tpc2[i] : 1, w, wn, wp);
+                FILL_MARK_BODY(t0 == wave << 6);
+            }
+            FILL_MARK_END();
+        }
         if (bk_major) {
             // Large maps: the items go to HBM scratch, hundreds of thousands of scattered 4-byte stores per env.  Laid out and EMITTED
             // bucket-major -- all items of time bucket 0 (by key), then bucket 1, ... -- the lines a CU has open at a time are one
@@ -1044,14 +1184,15 @@ __device__ __forceinline__ void obs_body(const FlDev &d, const FlObsScratch &S, 
                 __syncthreads();   // (the next bucket's prefix goes to the same scratch)
             }
         }
-        prefetch(bk_major ? A : wave);
-        for (int i = wave; !reuse && !bk_major && i < A; i += (nt >> 6)) {
+        if (!FLAT_FILL) { FILL_MARK_T0(); prefetch(bk_major ? A : wave); }
+        for (int i = wave; !FLAT_FILL && !reuse && !bk_major && i < A; i += (nt >> 6)) {
             const uint16_t *path = S.path + ((size_t)b * A + i) * OBS_PRED_CAP;
             const int lp = (lab && lab[i] < 0) ? -1 : (int)a_lp[i], tpc = a_tpc[i], tlast = X.Tn - 1;   // (not listed: no items)
             const int lp2 = dual_fill ? (int)a_lp2[i] : -1, tpc2 = dual_fill ? (int)a_tpc2[i] : 1;
             uint32_t wv[FU], wnx[FU], wpv[FU];
 #pragma unroll
             for (int q = 0; q < FU; q++) { wv[q] = pfv[q]; wnx[q] = pfn[q]; wpv[q] = pfp[q]; }
+            FILL_MARK_WAIT(i == wave);
             prefetch(i + (nt >> 6));
             for (int k0 = lane; k0 <= lp; k0 += 64 * FU) {
             if (k0 != lane) {
@@ -1078,65 +1219,8 @@ __device__ __forceinline__ void obs_body(const FlDev &d, const FlObsScratch &S, 
                 }
                 const bool to_end = k == lp || tlo + span - 1 >= tlast;
                 const int key = key_of(X, (int)(w >> 2));
-                if (LEAN_FILL) {
-                    // One-round kernels: every wavefront runs this body once or twice, so its length is the phase.  The same ORs and
-                    // list slots as below, ordered so that the LDS round trips overlap: the returning atomics of both indices go
-                    // out first, the direction masks (cf_dirs_swar, no loop over the nibbles; the second index's four 32-bit words
-                    // as two 64-bit ORs) are worked out and ORed while those are in flight, and what depends on a returned value
-                    // -- the second-item masks, the item stores -- comes last.
-                    const int b1 = tb_of(tlo, X.tshift), b2 = tb_of(to_end ? tlast : tlo + span - 1, X.tshift);
-                    const unsigned long long bits = ((2ull << b2) - 1ull) & ~((1ull << b1) - 1ull);
-                    const bool second = k <= lp2, done = a_state[i] == ST_DONE;
-                    const int tlo2 = k * tpc2, tlast2 = Tn2 - 1;
-                    const bool to_end2 = k == lp2 || tlo2 + tpc2 - 1 >= tlast2;
-                    unsigned long long bits2 = 0ull, seen = 0ull, seen2 = 0ull;
-                    int slot2 = 0;
-                    if (X.tmask && X.tmask_m2) seen = atomicOr(&tmask[key], bits);
-                    else if (X.tmask) atomicOr(&tmask[key], bits);
-                    if (second) {
-                        if (p_use_tmask) {
-                            const int c1 = tb_of(tlo2, tshift2), c2 = tb_of(to_end2 ? tlast2 : tlo2 + tpc2 - 1, tshift2);
-                            bits2 = ((2ull << c2) - 1ull) & ~((1ull << c1) - 1ull);
-                            if (X.tmask_m2) seen2 = atomicOr(&tmaskb[key], bits2);
-                            else atomicOr(&tmaskb[key], bits2);
-                        }
-                        slot2 = atomicAdd(&csr2[key], 1);
-                    }
-                    const uint32_t rail = cw_bits(X, (int)(w >> 2));
-                    if (X.tmask && cmask) {
-                        const uint32_t dirs = cf_dirs_swar(rail, cf_against(w & 3u) | cf_against(dnext) | cf_against(dprev), done);
-#pragma unroll
-                        for (uint32_t dw = 0; dw < 4; dw++)
-                            if ((dirs >> dw) & 1u) atomicOr(&cmask[((uint32_t)key << 2) | dw], bits);
-                    }
-                    if (second && p_use_tmask && cmaskb) {  // (at most 32 predicted times: bucket = time, the low word of bits2)
-                        const uint32_t dirs = cf_dirs_swar(rail, cf_against(w & 3u), done);
-                        const unsigned long long lo32 = (unsigned long long)(uint32_t)bits2;
-                        const unsigned long long v01 = ((dirs & 1u) ? lo32 : 0ull) | ((dirs & 2u) ? lo32 << 32 : 0ull);
-                        const unsigned long long v23 = ((dirs & 4u) ? lo32 : 0ull) | ((dirs & 8u) ? lo32 << 32 : 0ull);
-                        unsigned long long *cb = reinterpret_cast<unsigned long long *>(cmaskb) + ((uint32_t)key << 1);   // words (key << 2 | 0, 1) and (2, 3)
-                        if (v01) atomicOr(&cb[0], v01);
-                        if (v23) atomicOr(&cb[1], v23);
-                    }
-                    const uint32_t item = IT_MAKE(lab ? (int)lab[i] : i, tlo, to_end, span, dprev, dnext, w & 3u);
-                    if (bk) {
-                        const int thi = to_end ? tlast : tlo + span - 1;
-                        int c1 = min(tlo >> bk_shift, bk_nb - 1), c2 = min(thi >> bk_shift, bk_nb - 1);
-                        if (bk_lds && to_end) c1 = c2 = bk_nb;
-                        for (int bb = c1; bb <= c2; bb++) {
-                            const int kb = key * bk_w + bb;
-                            const uint32_t old = atomicAdd(&bkc[kb >> 1], (kb & 1) ? 0x10000u : 1u);
-                            csr_items[csr[key] + (int)((kb & 1) ? (old >> 16) : (old & 0xFFFFu))] = item;
-                        }
-                    } else {
-                        const int slot = atomicAdd(&csr[key], 1);
-                        csr_items[slot] = item;
-                    }
-                    if (seen & bits) atomicOr(&tmask_m2[key], seen & bits);  // covered by a second item
-                    if (second) {
-                        if (seen2 & bits2) atomicOr(&tmaskb_m2[key], seen2 & bits2);
-                        items2[slot2] = IT_MAKE(i, tlo2, to_end2, tpc2, dprev, k < lp2 ? dnext : (w & 3u), w & 3u);
-                    }
+                if (LEAN_FILL) {  // (OBS_NO_FLAT_FILL: the one-round kernels on this loop)
+                    lean_item(i, k, lp, tpc, lp2, tpc2, w, wnx[q], wpv[q]);
                     continue;
                 }
                 if (X.tmask) {  // time buckets this item covers
@@ -1194,7 +1278,9 @@ __device__ __forceinline__ void obs_body(const FlDev &d, const FlObsScratch &S, 
                 }
             }
             }
+            FILL_MARK_BODY(i == wave);
         }
+        if (!FLAT_FILL) FILL_MARK_END();
         __syncthreads();
 #ifdef FL_OBS_TIMING
         if (STAGE != 2 && tid == 0) {

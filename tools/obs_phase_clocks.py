@@ -85,6 +85,9 @@ def report():
     print("     hoisted pass A alone: slowest wavefront %.1f" % dur(23))
     if c[:, :, 56].max() > 0:
         print("     scan/fill: keys scanned + bucket offsets %.1f, items filled %.1f, rest (offsets to HBM) %.1f" % (seg(3, 56), seg(56, 57), seg(57, 4)))
+    if c[:, :, 34].max() > 0 and c[:, :, 32].max() == 0:   # marks of the one-round kernels' fill (latest wavefront of the env)
+        print("     fill, since keys scanned: first body done %.2f, last body done %.2f (further bodies %.2f), barrier %.2f; path words of the first body there %.2f after the fill's start" %
+              (seg(56, 33), seg(56, 34), seg(33, 34), seg(34, 57), dur(35)))
     print("  trees (sum over rounds): passA %.1f  B classify %.1f  B work lists %.1f  rows %.1f  orders %.1f   stage total %.1f" %
           (dur(6), dur(11), dur(7), dur(8), dur(16), seg(0, 5)))
     if c[:, :, 32].max() > 0:   # (the kernels with one pass B for both builders have no second stage)
