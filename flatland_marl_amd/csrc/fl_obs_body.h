@@ -1,6 +1,7 @@
 // fl_obs_body.h -- one observation build for the workgroup's env (obs_body: staging, per-agent phase, predicted paths and the
 // per-key prediction index, then the trees) and the kernel template.  Device code; the three fl_obs_m<MODE>.hip units
-// instantiate it.  DESIGN.md section 4 describes the phases; tools/obs_phase_clocks.py measures them.
+// instantiate it.  DESIGN.md section 4 describes the phases; tools/obs_phase_clocks.py measures them.  The small helpers of the prediction
+// index (waypoint interval, bucket-range mask, packed bucket counters, path words) are fl_obs_index.h; phase 2 starts with a map of its steps.
 //
 // Replaces (paths relative to /root/reference):
 //   flatland_cutils/src/loader.cpp:221-327      AgentsLoader::update (snapshot, dist_target, road_type, valid actions)
@@ -23,6 +24,7 @@
 // over all lanes, classifies them, and processes the few cells that need work from work lists on packed wavefronts; rows
 // are written straight to HBM.
 #pragma once
+#include "fl_obs_index.h"
 #include "fl_obs_trees.h"
 
 // One observation build for the workgroup's env.  STAGE 0: stand-alone; the fused launch (both builders) runs STAGE 1
@@ -585,7 +587,13 @@ __device__ __forceinline__ void obs_body(const FlDev &d, const FlObsScratch &S, 
         __syncthreads();
     }
     OBS_STAMP(2);
-    // ---- phase 2: predicted paths + per-key CSR index of (agent, waypoint, time interval)
+    // ---- phase 2: predicted paths + per-key CSR index of (agent, waypoint, time interval).  Its steps (helpers: fl_obs_index.h):
+    //   clear  csr / csr2, masks, bucket counters;  walk and count  lead_in + walk8 (half_count_bump; the last waypoint's fix-up behind
+    //   the walk: half_count_drop) beside phase1a, the hoisted pass A and drain_jobs, large maps count in a pass of their own;
+    //   scan   chunk sums, wave 0 rescans partial[], exclusive offsets;  fill  one-round kernels: flat item space (ff_request, lean_item),
+    //   large maps: bucket-major (request), every other kernel: a wavefront per agent (prefetch, body inline).  wp_interval defines the
+    //   interval; a site that writes it out does so because the helper there changed the kernels' instructions.
+    //   publish         X.csr_end / X.bk_rel_lds, or the bucket offsets to HBM (X.bk_rel, X.bk_base)
     if (X.Tn > 0) {
         // fused launch: stage 1 builds the upstream predictor's index too (same paths, one pass over the waypoints); stage 2
         // then starts at its trees.  misc[4] tells stage 2 that the second index is complete.
@@ -676,10 +684,7 @@ __device__ __forceinline__ void obs_body(const FlDev &d, const FlObsScratch &S, 
                                 if (bk_lds) {  // cutils: waypoint idx is occupied during [(idx - 1) * tpc + 1, idx * tpc] (0 for idx = 0)
                                     const int tlo = idx == 0 ? 0 : (idx - 1) * tpc_w + 1, thi = min(idx * tpc_w, tlast_w);
                                     const int b1 = min(tlo >> bk_shift, bk_nb - 1), b2 = min(thi >> bk_shift, bk_nb - 1);
-                                    for (int bb = b1; bb <= b2; bb++) {
-                                        const int kb = key * bk_w + bb;
-                                        atomicAdd(&bkc[kb >> 1], (kb & 1) ? 0x10000u : 1u);
-                                    }
+                                    for (int bb = b1; bb <= b2; bb++) half_count_bump(bkc, key * bk_w + bb);
                                     atomicAdd(&csr[key], b2 - b1 + 1);
                                     if (idx == hz1) st_hz = st;
                                 } else {
@@ -708,12 +713,9 @@ __device__ __forceinline__ void obs_body(const FlDev &d, const FlObsScratch &S, 
                 if (lp == m ? my_last == lp : j == (lp & 7)) {
                     const uint32_t s_lp = lp == m ? st : st_hz;
                     const int key = key_of(X, (int)(s_lp >> 2));
-                    const int tlo = lp == 0 ? 0 : (lp - 1) * tpc_w + 1, thi = min(lp * tpc_w, tlast_w);
+                    const int tlo = lp == 0 ? 0 : (lp - 1) * tpc_w + 1, thi = min(lp * tpc_w, tlast_w);   // (what walk8 counted it with)
                     const int b1 = min(tlo >> bk_shift, bk_nb - 1), b2 = min(thi >> bk_shift, bk_nb - 1);
-                    for (int bb = b1; bb <= b2; bb++) {
-                        const int kb = key * bk_w + bb;
-                        atomicSub(&bkc[kb >> 1], (kb & 1) ? 0x10000u : 1u);
-                    }
+                    for (int bb = b1; bb <= b2; bb++) half_count_drop(bkc, key * bk_w + bb);
                     // (bk_w is even: the count of that bucket is the low half of the key's last word, the high half collects the
                     // time buckets in which such items start)
                     atomicAdd(&bkc[(key * bk_w + bk_nb) >> 1], 1u);
@@ -796,10 +798,8 @@ __device__ __forceinline__ void obs_body(const FlDev &d, const FlObsScratch &S, 
                         const int tlo = k == 0 ? 0 : (k - 1) * tpc + 1, span = k == 0 ? 1 : tpc;
                         const int thi = (k == lp || tlo + span - 1 >= tlast) ? tlast : tlo + span - 1;
                         const int b1 = min(tlo >> bk_shift, bk_nb - 1), b2 = min(thi >> bk_shift, bk_nb - 1);
-                        for (int bb = b1; bb <= b2; bb++) {  // bucket-major: row bb, entry key + 1 (entry 0 of a row stays 0)
-                            const int kb = bb * (K + 1) + key + 1;
-                            atomicAdd(&bkc[kb >> 1], (kb & 1) ? 0x10000u : 1u);
-                        }
+                        // bucket-major: row bb, entry key + 1 (entry 0 of a row stays 0)
+                        for (int bb = b1; bb <= b2; bb++) half_count_bump(bkc, bb * (K + 1) + key + 1);
                     }
                 }
             }
@@ -825,39 +825,30 @@ __device__ __forceinline__ void obs_body(const FlDev &d, const FlObsScratch &S, 
         // exclusive scan over the keys: per-thread chunk sums, wave-0 scan of the partial sums, rescan.  With the second
         // index both counts share the scan, 16 bits each (the launcher guarantees totals below 65536).
         const bool bk_major = bk && !bk_lds;   // large maps: the items laid out bucket-major (see the fill)
-#ifdef OBS_NO_LEAN_FILL
-        constexpr bool LEAN_FILL = false;
-#else
-        constexpr bool LEAN_FILL = MERGED == 1;   // the one-round kernels (classes 1, 6, 11, runtime carving of MODES 3 / 6); every other kernel keeps the general body of the fill
-#endif
-#ifdef OBS_NO_FLAT_FILL
-        constexpr bool FLAT_FILL = false;         // the one-round kernels fill on the loop of the others: a wavefront per agent
-#else
-        constexpr bool FLAT_FILL = LEAN_FILL;
-#endif
+        constexpr bool ONE_ROUND = MERGED == 1;   // classes 1, 6, 11, runtime carving of MODES 3 / 6: the flat fill; every other kernel a wavefront per agent (large maps: bucket-major)
 #ifdef FL_OBS_TIMING
         // marks of the one-round kernels' fill (slots 33 .. 36 of the env; no stage 2 there): the latest wavefront's end of its first
         // body and of the loop, the longest wait for the path words of a first body (since the start of the fill)
         long long fill_t0_ = 0;
 #define FILL_MARK_T0() do { fill_t0_ = (long long)wall_clock64(); } while (0)
-#define FILL_MARK_WAIT(first) do { if (LEAN_FILL && (first)) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); \
+#define FILL_MARK_WAIT(first) do { if (first) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); \
             if (lane == 0) atomicMax((unsigned long long *)&X.dbg[35], (unsigned long long)((long long)wall_clock64() - fill_t0_)); } } while (0)
-#define FILL_MARK_BODY(first) do { if (LEAN_FILL && (first) && lane == 0) atomicMax((unsigned long long *)&X.dbg[33], (unsigned long long)wall_clock64()); } while (0)
-#define FILL_MARK_END() do { if (LEAN_FILL && lane == 0) atomicMax((unsigned long long *)&X.dbg[34], (unsigned long long)wall_clock64()); } while (0)
+#define FILL_MARK_BODY(first) do { if ((first) && lane == 0) atomicMax((unsigned long long *)&X.dbg[33], (unsigned long long)wall_clock64()); } while (0)
+#define FILL_MARK_END() do { if (lane == 0) atomicMax((unsigned long long *)&X.dbg[34], (unsigned long long)wall_clock64()); } while (0)
 #else
 #define FILL_MARK_T0() do {} while (0)
 #define FILL_MARK_WAIT(first) do {} while (0)
 #define FILL_MARK_BODY(first) do {} while (0)
 #define FILL_MARK_END() do {} while (0)
 #endif
-        // The fill of the one-round kernels (FLAT_FILL, below the scan) lays the waypoints of all agents end to end -- agent a has the
+        // The fill of the one-round kernels (flat fill, below the scan) lays the waypoints of all agents end to end -- agent a has the
         // items incl[a - 1] .. incl[a] - 1, waypoint k = t - incl[a - 1] -- and gives item t to lane t of the workgroup.  a_lp[] is
         // final behind the barrier above, so the mapping and the three path words an item needs (HBM scratch, written by the walkers)
         // are requested HERE: the three barriers of the scan cover the round trip.  Every wavefront keeps the inclusive prefix of
         // lp + 1 on its lanes a < A (A <= 32 in these kernels); the agents a wavefront's 64 items touch are a short range that two
         // ballots give as scalars, and a lane counts the piece ends at or below its t through v_readlane (no LDS round trip).
         int ff_incl = 0, ff_total = 0, ff_i = 0, ff_k = 0, ff_lp = 0;
-        uint32_t ff_w = 0, ff_wn = 0, ff_wp = 0;
+        PathWords ff_pw = {0, 0, 0};
         auto ff_request = [&](int t) __attribute__((always_inline)) {   // wave-uniform call: t = t0 + lane, t0 a multiple of 64 below ff_total
             const int t_first = __builtin_amdgcn_readfirstlane(t);
             const int a_lo = __popcll(__ballot(ff_incl <= t_first)), a_hi = min(__popcll(__ballot(ff_incl <= t_first + 63)), A - 1);
@@ -871,12 +862,12 @@ __device__ __forceinline__ void obs_body(const FlDev &d, const FlObsScratch &S, 
             ff_i = i; ff_k = t - start;
             if (t < ff_total) {
                 const uint16_t *pth = S.path + ((size_t)b * A + i) * OBS_PRED_CAP;
-                const int lpn = a_lp[i], k = t - start;
+                const int lpn = a_lp[i];
                 ff_lp = lpn;
-                ff_w = pth[k]; ff_wn = pth[min(k + 1, lpn)]; ff_wp = pth[max(k - 1, 0)];
+                ff_pw = path_words(pth, t - start, lpn);
             }
         };
-        if (FLAT_FILL && !bk_major) {
+        if (ONE_ROUND && !bk_major) {
             ff_incl = wave_incl_scan<64>(lane < A ? (int)a_lp[lane] + 1 : 0);   // (the lanes from A on: the total)
             ff_total = __builtin_amdgcn_readlane(ff_incl, 63);
             if ((wave << 6) < ff_total) ff_request(tid);
@@ -939,7 +930,7 @@ __device__ __forceinline__ void obs_body(const FlDev &d, const FlObsScratch &S, 
             for (int k = lo; k < hi; k++) sum += c16[k];
             partial[tid] = sum;
             __syncthreads();
-            if (wave == 0) {
+            if (wave == 0) {  // (the wave-0 rescan of the key scan above, word for word: one shared copy changes the kernels' instructions)
                 constexpr int PER = OBS_NT / 64;
                 const int per = nt >> 6;
                 int loc[PER], tot = 0;
@@ -1005,7 +996,7 @@ __device__ __forceinline__ void obs_body(const FlDev &d, const FlObsScratch &S, 
         if (merged && UP && !dual_fill) atomicCAS(&d.err[b], 0, FL_ERR_CAPACITY);  // (cannot happen: the LDS copy holds the exact bound)
         if (fit && !reuse) { csr_items = items_lds; X.items_lds = items_lds; }
         // fill: bumping csr[key] turns it from the start into the END offset of key's list (start = csr[key - 1]);
-        // one wavefront per agent, one lane per waypoint -- except the one-round kernels (FLAT_FILL, see above the scan): one item
+        // one wavefront per agent, one lane per waypoint -- except the one-round kernels (ONE_ROUND, see above the scan): one item
         // space over the lanes of the workgroup, the path words requested in front of the scan
         // (the waypoints come from HBM scratch: four of them per lane are requested at once -- 500 waypoints are two round trips
         // instead of eight -- and the first four of the agent the wavefront takes NEXT are requested before the items of this
@@ -1017,12 +1008,9 @@ __device__ __forceinline__ void obs_body(const FlDev &d, const FlObsScratch &S, 
             const uint16_t *pth = S.path + ((size_t)b * A + ia) * OBS_PRED_CAP;
             const int lpn = a_lp[ia];
 #pragma unroll
-            for (int q = 0; q < FU; q++) {
-                const int k = min(lane + 64 * q, lpn);
-                pfv[q] = pth[k]; pfn[q] = pth[min(k + 1, lpn)]; pfp[q] = pth[max(k - 1, 0)];
-            }
+            for (int q = 0; q < FU; q++) { const PathWords pw = path_words(pth, min(lane + 64 * q, lpn), lpn); pfv[q] = pw.w; pfn[q] = pw.wn; pfp[q] = pw.wp; }
         };
-        // One item of the one-round kernels (LEAN_FILL): waypoint k of agent i, w = path[k], wn / wp = the waypoints behind and in front
+        // One item of the one-round kernels (the flat fill): waypoint k of agent i, w = path[k], wn / wp = the waypoints behind and in front
         // of it (clamped to the piece 0 .. lp).  The same ORs and list slots as the general body below, ordered so that the LDS round
         // trips overlap: the returning atomics of both indices go out first, the direction masks (cf_dirs_swar, no loop over the
         // nibbles; the second index's four 32-bit words as two 64-bit ORs) are worked out and ORed while those are in flight, and what
@@ -1030,20 +1018,12 @@ __device__ __forceinline__ void obs_body(const FlDev &d, const FlObsScratch &S, 
         auto lean_item = [&](int i, int k, int lp, int tpc, int lp2, int tpc2, uint32_t w, uint32_t wn, uint32_t wp) __attribute__((always_inline)) {
             const int tlast = X.Tn - 1;
             const uint32_t dnext = k < lp ? (wn & 3u) : (w & 3u), dprev = k > 0 ? (wp & 3u) : (w & 3u);
-            int tlo, span;   // closed time interval during which the agent is predicted on waypoint k (see the general body)
-            if (CUTILS) {
-                tlo = k == 0 ? 0 : (k - 1) * tpc + 1;
-                span = k == 0 ? 1 : tpc;
-            } else {
-                tlo = k * tpc;
-                span = tpc;
-            }
-            const bool to_end = k == lp || tlo + span - 1 >= tlast;
+            const WpInterval iv = wp_interval<CUTILS>(k, lp, tpc, tlast);
+            const int tlo = iv.tlo, span = iv.span; const bool to_end = iv.to_end;
             const int key = key_of(X, (int)(w >> 2));
-            const int b1 = tb_of(tlo, X.tshift), b2 = tb_of(to_end ? tlast : tlo + span - 1, X.tshift);
-            const unsigned long long bits = ((2ull << b2) - 1ull) & ~((1ull << b1) - 1ull);
+            const unsigned long long bits = bucket_range_mask(tb_of(tlo, X.tshift), tb_of(iv.thi(), X.tshift));
             const bool second = k <= lp2, done = a_state[i] == ST_DONE;
-            const int tlo2 = k * tpc2, tlast2 = Tn2 - 1;
+            const int tlo2 = k * tpc2, tlast2 = Tn2 - 1;   // (wp_interval<false> written out: the helper here changes the kernels' instructions)
             const bool to_end2 = k == lp2 || tlo2 + tpc2 - 1 >= tlast2;
             unsigned long long bits2 = 0ull, seen = 0ull, seen2 = 0ull;
             int slot2 = 0;
@@ -1051,8 +1031,7 @@ __device__ __forceinline__ void obs_body(const FlDev &d, const FlObsScratch &S, 
             else if (X.tmask) atomicOr(&tmask[key], bits);
             if (second) {
                 if (p_use_tmask) {
-                    const int c1 = tb_of(tlo2, tshift2), c2 = tb_of(to_end2 ? tlast2 : tlo2 + tpc2 - 1, tshift2);
-                    bits2 = ((2ull << c2) - 1ull) & ~((1ull << c1) - 1ull);
+                    bits2 = bucket_range_mask(tb_of(tlo2, tshift2), tb_of(to_end2 ? tlast2 : tlo2 + tpc2 - 1, tshift2));
                     if (X.tmask_m2) seen2 = atomicOr(&tmaskb[key], bits2);
                     else atomicOr(&tmaskb[key], bits2);
                 }
@@ -1076,13 +1055,11 @@ __device__ __forceinline__ void obs_body(const FlDev &d, const FlObsScratch &S, 
             }
             const uint32_t item = IT_MAKE(lab ? (int)lab[i] : i, tlo, to_end, span, dprev, dnext, w & 3u);
             if (bk) {
-                const int thi = to_end ? tlast : tlo + span - 1;
-                int c1 = min(tlo >> bk_shift, bk_nb - 1), c2 = min(thi >> bk_shift, bk_nb - 1);
+                int c1 = min(tlo >> bk_shift, bk_nb - 1), c2 = min(iv.thi() >> bk_shift, bk_nb - 1);
                 if (bk_lds && to_end) c1 = c2 = bk_nb;
                 for (int bb = c1; bb <= c2; bb++) {
-                    const int kb = key * bk_w + bb;
-                    const uint32_t old = atomicAdd(&bkc[kb >> 1], (kb & 1) ? 0x10000u : 1u);
-                    csr_items[csr[key] + (int)((kb & 1) ? (old >> 16) : (old & 0xFFFFu))] = item;
+                    const int at = (int)half_count_bump(bkc, key * bk_w + bb);
+                    csr_items[csr[key] + at] = item;
                 }
             } else {
                 const int slot = atomicAdd(&csr[key], 1);
@@ -1094,18 +1071,18 @@ __device__ __forceinline__ void obs_body(const FlDev &d, const FlObsScratch &S, 
                 items2[slot2] = IT_MAKE(i, tlo2, to_end2, tpc2, dprev, k < lp2 ? dnext : (w & 3u), w & 3u);
             }
         };
-        if (FLAT_FILL && !bk_major) {
+        if (ONE_ROUND && !bk_major) {
             // One-round kernels: the waypoints of all agents as ONE item space split over the lanes of the workgroup (ff_request, in
             // front of the key scan, found each lane's agent and waypoint and requested its three path words): one pass of the body
             // where the env has at most nt items, whatever the number of agents.
             FILL_MARK_T0();
             for (int t0 = wave << 6; t0 < ff_total; t0 += nt) {   // (wave-uniform: ff_request runs with every lane)
                 const int i = ff_i, k = ff_k, lp = ff_lp;
-                const uint32_t w = ff_w, wn = ff_wn, wp = ff_wp;
+                const PathWords pw = ff_pw;
                 FILL_MARK_WAIT(t0 == wave << 6);
                 if (t0 + nt < ff_total) ff_request(t0 + nt + lane);   // a further pass: its words are on the way during this one's body
                 if (t0 + lane < ff_total)
-                    lean_item(i, k, lp, a_tpc[i], dual_fill ? (int)a_lp2[i] : -1, dual_fill ? (int)a_tpc2[i] : 1, w, wn, wp);
+                    lean_item(i, k, lp, a_tpc[i], dual_fill ? (int)a_lp2[i] : -1, dual_fill ? (int)a_tpc2[i] : 1, pw.w, pw.wn, pw.wp);
                 FILL_MARK_BODY(t0 == wave << 6);
             }
             FILL_MARK_END();
@@ -1144,7 +1121,7 @@ __device__ __forceinline__ void obs_body(const FlDev &d, const FlObsScratch &S, 
                 __syncthreads();
                 const int total = pre16[A];
                 // item t of the bucket -> (agent, waypoint): the last agent whose piece starts at or before t
-                uint32_t nv = 0, nn = 0, np = 0;
+                PathWords n_pw = {0, 0, 0};
                 int n_i = 0, n_k = 0;
                 auto request = [&](int t) __attribute__((always_inline)) {
                     if (t >= total) return;
@@ -1156,13 +1133,12 @@ __device__ __forceinline__ void obs_body(const FlDev &d, const FlObsScratch &S, 
                     n_i = lo_a;
                     n_k = (int)klo16[lo_a] + (t - (int)pre16[lo_a]);
                     const uint16_t *pth = S.path + ((size_t)b * A + lo_a) * OBS_PRED_CAP;
-                    const int lp = a_lp[lo_a];
-                    nv = pth[n_k]; nn = pth[min(n_k + 1, lp)]; np = pth[max(n_k - 1, 0)];
+                    n_pw = path_words(pth, n_k, a_lp[lo_a]);
                 };
                 request(tid);
                 for (int t = tid; t < total; t += nt) {
                     const int i = n_i, k = n_k;
-                    const uint32_t w = nv, wnx = nn, wpv = np;
+                    const uint32_t w = n_pw.w, wnx = n_pw.wn, wpv = n_pw.wp;
                     request(t + nt);
                     const int lp = a_lp[i], tpc = a_tpc[i];
                     const int tlo = k == 0 ? 0 : (k - 1) * tpc + 1, span = k == 0 ? 1 : tpc;
@@ -1173,114 +1149,100 @@ __device__ __forceinline__ void obs_body(const FlDev &d, const FlObsScratch &S, 
                     const int key = key_of(X, (int)(w >> 2));
                     if (X.tmask && bb == b1) {  // time-mask buckets this item covers (once per item)
                         const int m1 = tb_of(tlo, X.tshift), m2 = tb_of(thi, X.tshift);
-                        atomicOr(&tmask[key], ((2ull << m2) - 1ull) & ~((1ull << m1) - 1ull));
+                        atomicOr(&tmask[key], bucket_range_mask(m1, m2));
                     }
                     const uint32_t dnext = k < lp ? (wnx & 3u) : (w & 3u), dprev = k > 0 ? (wpv & 3u) : (w & 3u);
                     const uint32_t item = IT_MAKE(lab ? (int)lab[i] : i, tlo, to_end, span, dprev, dnext, w & 3u);
-                    const int kb = bb * K1 + key + 1;
-                    const uint32_t old = atomicAdd(&bkc[kb >> 1], (kb & 1) ? 0x10000u : 1u);
-                    csr_items[gbase + (int)((kb & 1) ? (old >> 16) : (old & 0xFFFFu))] = item;
+                    csr_items[gbase + (int)half_count_bump(bkc, bb * K1 + key + 1)] = item;
                 }
                 __syncthreads();   // (the next bucket's prefix goes to the same scratch)
             }
         }
-        if (!FLAT_FILL) { FILL_MARK_T0(); prefetch(bk_major ? A : wave); }
-        for (int i = wave; !FLAT_FILL && !reuse && !bk_major && i < A; i += (nt >> 6)) {
+        // every other kernel: a wavefront per agent, a lane per waypoint, the NEXT agent's first words prefetched (body inline: as a lambda it compiles to other code)
+        if (!ONE_ROUND) prefetch(bk_major ? A : wave);
+        for (int i = wave; !ONE_ROUND && !reuse && !bk_major && i < A; i += (nt >> 6)) {
             const uint16_t *path = S.path + ((size_t)b * A + i) * OBS_PRED_CAP;
             const int lp = (lab && lab[i] < 0) ? -1 : (int)a_lp[i], tpc = a_tpc[i], tlast = X.Tn - 1;   // (not listed: no items)
             const int lp2 = dual_fill ? (int)a_lp2[i] : -1, tpc2 = dual_fill ? (int)a_tpc2[i] : 1;
             uint32_t wv[FU], wnx[FU], wpv[FU];
 #pragma unroll
             for (int q = 0; q < FU; q++) { wv[q] = pfv[q]; wnx[q] = pfn[q]; wpv[q] = pfp[q]; }
-            FILL_MARK_WAIT(i == wave);
             prefetch(i + (nt >> 6));
             for (int k0 = lane; k0 <= lp; k0 += 64 * FU) {
-            if (k0 != lane) {
+                if (k0 != lane) {
+#pragma unroll
+                    for (int q = 0; q < FU; q++) { const PathWords pw = path_words(path, min(k0 + 64 * q, lp), lp); wv[q] = pw.w; wnx[q] = pw.wn; wpv[q] = pw.wp; }
+                }
 #pragma unroll
                 for (int q = 0; q < FU; q++) {
-                    const int k = min(k0 + 64 * q, lp);
-                    wv[q] = path[k]; wnx[q] = path[min(k + 1, lp)]; wpv[q] = path[max(k - 1, 0)];
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < FU; q++) {
-                const int k = k0 + 64 * q;
-                if (k > lp) break;
-                const uint32_t w = wv[q];
-                const uint32_t dnext = k < lp ? (wnx[q] & 3u) : (w & 3u), dprev = k > 0 ? (wpv[q] & 3u) : (w & 3u);
-                // closed time interval during which the agent is predicted on waypoint k
-                int tlo, span;
-                if (CUTILS) {  // w(t) = 0 for t = 0, min((t-1)/tpc + 1, lp) afterwards
-                    tlo = k == 0 ? 0 : (k - 1) * tpc + 1;
-                    span = k == 0 ? 1 : tpc;
-                } else {       // w(t) = min(t / tpc, lp)
-                    tlo = k * tpc;
-                    span = tpc;
-                }
-                const bool to_end = k == lp || tlo + span - 1 >= tlast;
-                const int key = key_of(X, (int)(w >> 2));
-                if (LEAN_FILL) {  // (OBS_NO_FLAT_FILL: the one-round kernels on this loop)
-                    lean_item(i, k, lp, tpc, lp2, tpc2, w, wnx[q], wpv[q]);
-                    continue;
-                }
-                if (X.tmask) {  // time buckets this item covers
-                    const int b1 = tb_of(tlo, X.tshift), b2 = tb_of(to_end ? tlast : tlo + span - 1, X.tshift);
-                    const unsigned long long bits = ((2ull << b2) - 1ull) & ~((1ull << b1) - 1ull);
-                    if (X.tmask_m2) {
-                        const unsigned long long seen = atomicOr(&tmask[key], bits);
-                        if (seen & bits) atomicOr(&tmask_m2[key], seen & bits);  // covered by a second item
+                    const int k = k0 + 64 * q;
+                    if (k > lp) break;
+                    const uint32_t w = wv[q];
+                    const uint32_t dnext = k < lp ? (wnx[q] & 3u) : (w & 3u), dprev = k > 0 ? (wpv[q] & 3u) : (w & 3u);
+                    int tlo, span;  // closed time interval of waypoint k (wp_interval written out: the helper here changes the kernels' instructions)
+                    if (CUTILS) {
+                        tlo = k == 0 ? 0 : (k - 1) * tpc + 1;
+                        span = k == 0 ? 1 : tpc;
                     } else {
-                        atomicOr(&tmask[key], bits);
+                        tlo = k * tpc;
+                        span = tpc;
                     }
-                    if (cmask) {  // ... and the walking directions for which it can satisfy the conflict condition
-                        const uint32_t dirs = cf_dirs_of(cw_bits(X, (int)(w >> 2)), cf_against(w & 3u) | cf_against(dnext) | cf_against(dprev), a_state[i] == ST_DONE);
-#pragma unroll
-                        for (uint32_t dw = 0; dw < 4; dw++)
-                            if ((dirs >> dw) & 1u) atomicOr(&cmask[((uint32_t)key << 2) | dw], bits);
-                    }
-                }
-                const uint32_t item = IT_MAKE(lab ? (int)lab[i] : i, tlo, to_end, span, dprev, dnext, w & 3u);
-                if (bk) {  // csr[key] stays the START of the key's list; the bucket's running offset is bumped
-                    const int thi = to_end ? tlast : tlo + span - 1;
-                    int b1 = min(tlo >> bk_shift, bk_nb - 1), b2 = min(thi >> bk_shift, bk_nb - 1);
-                    if (bk_lds && to_end) b1 = b2 = bk_nb;  // the bucket of the items that stay until the end
-                    for (int bb = b1; bb <= b2; bb++) {
-                        const int kb = key * bk_w + bb;
-                        const uint32_t old = atomicAdd(&bkc[kb >> 1], (kb & 1) ? 0x10000u : 1u);
-                        csr_items[csr[key] + (int)((kb & 1) ? (old >> 16) : (old & 0xFFFFu))] = item;
-                    }
-                } else {
-                    const int slot = atomicAdd(&csr[key], 1);
-                    csr_items[slot] = item;
-                }
-                if (k <= lp2) {  // the same waypoint in the upstream predictor's index: w(t) = min(t / tpc, lp)
-                    const int tlo2 = k * tpc2, tlast2 = Tn2 - 1;
-                    const bool to_end2 = k == lp2 || tlo2 + tpc2 - 1 >= tlast2;
-                    const uint32_t dnext2 = k < lp2 ? dnext : (w & 3u);
-                    if (p_use_tmask) {
-                        const int b1 = tb_of(tlo2, tshift2), b2 = tb_of(to_end2 ? tlast2 : tlo2 + tpc2 - 1, tshift2);
-                        const unsigned long long bits = ((2ull << b2) - 1ull) & ~((1ull << b1) - 1ull);
+                    const bool to_end = k == lp || tlo + span - 1 >= tlast;
+                    const int key = key_of(X, (int)(w >> 2));
+                    if (X.tmask) {  // time buckets this item covers
+                        const unsigned long long bits = bucket_range_mask(tb_of(tlo, X.tshift), tb_of(to_end ? tlast : tlo + span - 1, X.tshift));
                         if (X.tmask_m2) {
-                            const unsigned long long seen = atomicOr(&tmaskb[key], bits);
-                            if (seen & bits) atomicOr(&tmaskb_m2[key], seen & bits);
+                            const unsigned long long seen = atomicOr(&tmask[key], bits);
+                            if (seen & bits) atomicOr(&tmask_m2[key], seen & bits);  // covered by a second item
                         } else {
-                            atomicOr(&tmaskb[key], bits);
+                            atomicOr(&tmask[key], bits);
                         }
-                        if (cmaskb) {  // (at most 32 predicted times: bucket = time, the low word of bits)
-                            const uint32_t dirs = cf_dirs_of(cw_bits(X, (int)(w >> 2)), cf_against(w & 3u), a_state[i] == ST_DONE);
+                        if (cmask) {  // ... and the walking directions for which it can satisfy the conflict condition
+                            const uint32_t dirs = cf_dirs_of(cw_bits(X, (int)(w >> 2)), cf_against(w & 3u) | cf_against(dnext) | cf_against(dprev), a_state[i] == ST_DONE);
 #pragma unroll
                             for (uint32_t dw = 0; dw < 4; dw++)
-                                if ((dirs >> dw) & 1u) atomicOr(&cmaskb[((uint32_t)key << 2) | dw], (uint32_t)bits);
+                                if ((dirs >> dw) & 1u) atomicOr(&cmask[((uint32_t)key << 2) | dw], bits);
                         }
                     }
-                    const int slot2 = atomicAdd(&csr2[key], 1);
-                    items2[slot2] = IT_MAKE(i, tlo2, to_end2, tpc2, dprev, dnext2, w & 3u);
+                    const uint32_t item = IT_MAKE(lab ? (int)lab[i] : i, tlo, to_end, span, dprev, dnext, w & 3u);
+                    if (bk) {  // csr[key] stays the START of the key's list; the bucket's running offset is bumped
+                        const int thi = to_end ? tlast : tlo + span - 1;
+                        int b1 = min(tlo >> bk_shift, bk_nb - 1), b2 = min(thi >> bk_shift, bk_nb - 1);
+                        if (bk_lds && to_end) b1 = b2 = bk_nb;  // the bucket of the items that stay until the end
+                        for (int bb = b1; bb <= b2; bb++) {
+                            const int kb = key * bk_w + bb;
+                            const uint32_t old = half_count_add(bkc, kb);
+                            csr_items[csr[key] + (int)half_count_of(old, kb)] = item;
+                        }
+                    } else {
+                        const int slot = atomicAdd(&csr[key], 1);
+                        csr_items[slot] = item;
+                    }
+                    if (k <= lp2) {  // the same waypoint in the upstream predictor's index: w(t) = min(t / tpc, lp)
+                        const int tlo2 = k * tpc2, tlast2 = Tn2 - 1;
+                        const bool to_end2 = k == lp2 || tlo2 + tpc2 - 1 >= tlast2;
+                        const uint32_t dnext2 = k < lp2 ? dnext : (w & 3u);
+                        if (p_use_tmask) {
+                            const unsigned long long bits = bucket_range_mask(tb_of(tlo2, tshift2), tb_of(to_end2 ? tlast2 : tlo2 + tpc2 - 1, tshift2));
+                            if (X.tmask_m2) {
+                                const unsigned long long seen = atomicOr(&tmaskb[key], bits);
+                                if (seen & bits) atomicOr(&tmaskb_m2[key], seen & bits);
+                            } else {
+                                atomicOr(&tmaskb[key], bits);
+                            }
+                            if (cmaskb) {  // (at most 32 predicted times: bucket = time, the low word of bits)
+                                const uint32_t dirs = cf_dirs_of(cw_bits(X, (int)(w >> 2)), cf_against(w & 3u), a_state[i] == ST_DONE);
+#pragma unroll
+                                for (uint32_t dw = 0; dw < 4; dw++)
+                                    if ((dirs >> dw) & 1u) atomicOr(&cmaskb[((uint32_t)key << 2) | dw], (uint32_t)bits);
+                            }
+                        }
+                        const int slot2 = atomicAdd(&csr2[key], 1);
+                        items2[slot2] = IT_MAKE(i, tlo2, to_end2, tpc2, dprev, dnext2, w & 3u);
+                    }
                 }
             }
-            }
-            FILL_MARK_BODY(i == wave);
         }
-        if (!FLAT_FILL) FILL_MARK_END();
         __syncthreads();
 #ifdef FL_OBS_TIMING
         if (STAGE != 2 && tid == 0) {

@@ -4,6 +4,7 @@
 // wavefronts.  Device code.
 #pragma once
 #include "fl_obs_ctx.h"
+#include "fl_obs_index.h"
 #include "fl_obs_slices.h"
 
 // The feature block of ONE visited cell of a branch walk (treeobs.cpp:322-465 / observations.py:296-371) is split in
@@ -450,11 +451,11 @@ __device__ __forceinline__ void wg_pass_b(const ObsCtx &X, int tid, int nt, int 
                         if (FAST && self_filter && tot >= 1 && tot <= lp_t && (int)(own_w >> 2) == cell) {
                             // this cell is waypoint tot of the walking agent's own path: the buckets of that item (same formulas as
                             // the fill of the index) count only where a second item covers them too
+                            // (wp_interval for k = tot >= 1, written out: the helper's k == 0 case costs this loop instructions)
                             const int tlast = Tn_t - 1;
                             const int tlo = cu ? (tot - 1) * tpc_t + 1 : tot * tpc_t, te = tlo + tpc_t - 1;
                             const int thi = (tot == lp_t || te >= tlast) ? tlast : te;
-                            const int o1 = tb_of(tlo, tshift_t), o2 = tb_of(thi, tshift_t);
-                            others = (tm & ~(((2ull << o2) - 1ull) & ~((1ull << o1) - 1ull))) | tm2;
+                            others = (tm & ~bucket_range_mask(tb_of(tlo, tshift_t), tb_of(thi, tshift_t))) | tm2;
                         }
                         cand = ((uint32_t)(others >> b1) & ((2u << (b2 - b1)) - 1u)) != 0u;
                         if (FAST && cf_any && cf_t) {  // ... and one that can conflict with a walker in this direction?
