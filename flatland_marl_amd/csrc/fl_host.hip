@@ -1138,6 +1138,26 @@ extern "C" int fl_debug_obs_config_of_wide(int A, int Rcap, int Ucap, int tall, 
                                            int *out11) {
     return obs_config_of(A, Rcap, Ucap, tall, max_branch, pred_depth, max_depth, tree_pred, out11, 1);
 }
+// diagnostic (not part of the public header), no GPU needed: the whole launch plan of fl_obs_cutils* (kind 0), fl_obs_cutils_tree / fl_step_obs
+// with a tree (1) or fl_obs_tree* (2) on a device of n_cu CUs for a batch of B envs with R[b] rail cells each -- the host path of the launch up
+// to the enqueue (its limits, arguments, the preference walk, the launch class, the split class), so also what fl_debug_obs_config_of cannot
+// see: split launches, FL_OBS_KEEP_TREE_ROWS (keep_mode 1) and a handle subset (label 1).  record: the FL_OBS_LAUNCH_WORDS ints that
+// fl_debug_last_obs_launch would report after the launch; *n_fit: the envs on the launch class's body.  FL_ERR_ARG where the launch returns it.
+extern "C" int fl_debug_obs_plan(int kind, int A, int Ucap, int tall, int max_branch, int max_nodes, int pred_depth, int max_depth, int tree_pred,
+                                 int keep_mode, int label, int n_cu, const int *R, int B, int *record, int *n_fit) {
+    if (!R || B <= 0 || !record || !n_fit) return FL_ERR_ARG;
+    FlDev d;
+    memset(&d, 0, sizeof d);
+    d.B = B; d.A = A; d.Rcap = *std::max_element(R, R + B); d.Ucap = Ucap; d.max_branch = max_branch;
+    static uint16_t dummy_key;
+    static int16_t dummy_label;
+    d.rkey = tall ? &dummy_key : nullptr;
+    FlObsScratch o;
+    memset(&o, 0, sizeof o);
+    o.pred_cap = FL_OBS_MAX_PRED + 2; o.n_cu = n_cu; o.h_R = R; o.keep_rows = keep_mode;
+    *n_fit = 0;
+    return fl_obs_plan(kind, o, d, max_nodes, pred_depth, max_depth, tree_pred, label ? &dummy_label : nullptr, record, n_fit);
+}
 
 double fl_algorithmic_bytes_per_agent_step(fl_batch *h, int with_cutils_obs, int tree_depth) {
     if (!h) return 0.0;

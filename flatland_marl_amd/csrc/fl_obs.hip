@@ -1,9 +1,11 @@
 // fl_obs.hip -- host side of the observation kernels: scratch allocation, the choice of what a launch keeps in LDS
-// (obs_pick_config; the carving itself is obs_layout_c in fl_obs_layout.h, shared with the kernels), the fixed launch classes
-// and the three launch entry points.  The kernels are fl_obs_unit.hip, compiled once per unit of build.sh's list (one unit per
-// runtime-carving MODE, per launch class and per split kernel), each instantiating fl_obs_body.h and the phase-level headers it
-// includes (fl_obs_ctx.h, fl_obs_passb.h, fl_obs_trees.h); obs_launch below names them all.
+// (obs_pick_config; the carving itself is obs_layout_c in fl_obs_layout.h, shared with the kernels), the choice of a launch class
+// (obs_class_holds over the rows of OBS_CLASSES, fl_obs_layout.h) and the three launch entry points.  The kernels are fl_obs_unit.hip,
+// compiled once per unit of build.sh's list (one unit per runtime-carving MODE, per launch class and per split kernel), each
+// instantiating fl_obs_body.h and the phase-level headers it includes (fl_obs_ctx.h, fl_obs_passb.h, fl_obs_trees.h); obs_launch
+// below reaches them all: the MODEs by its list, the classes' and split kernels by the table's rows.
 #include <algorithm>
+#include <utility>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -121,76 +123,68 @@ static ObsLayout obs_layout(const FlDev &d, const ObsArgs &P, const ObsOptions &
     return obs_layout_c(ObsDims{d.Rcap, d.A, d.Ucap, d.rkey != nullptr}, ObsShape{P.merged, P.tw_c, P.tw_t, P.tpw_t, P.tree_pred}, o);
 }
 
-// A FIXED launch class (compile-time carving, ObsFixed<k> in fl_obs_layout.h) is taken when the batch fits the class's capacities
-// and the configuration just chosen for it has the class's options and shape; L becomes the class's carving (what the kernel has
-// compiled in) with the next-hop tables, last in the carving, at the batch's size.
-template <int FIX>
-static bool obs_fits_fixed(const FlDev &d, const ObsArgs &P, const ObsOptions &o, ObsLayout &L) {
-    using F = ObsFixed<FIX>;
-    if (F::opt.wl_head && obs_no_wl_head()) return false;
+// ---- the launch classes (OBS_CLASSES in fl_obs_layout.h: one row a class, compile-time carving): does class `c` hold this batch?
+//   OBS_FIT_EXACT  the whole batch fits the class's capacities and the configuration just chosen for it (`own`) has the class's options
+//   OBS_FIT_BIN    (round 6) the whole batch fits, and its own choice only has the class's STRUCTURE (one round / rounds of 32 agents / two
+//                  stages): the class's options then REPLACE the batch's own, in P too -- a compile-time carving with the options of the
+//                  bin's largest shape instead of the runtime carving with options chosen for this one (per shape of the Round-2 table:
+//                  profiles/r06_round2_classes.txt).  FL_OBS_NO_BINS: exact classes only
+//   OBS_FIT_SPLIT  everything but the rail cells of the batch's LARGEST map matches, and the runtime configuration chosen for the batch (L)
+//                  runs the class's MODE, VAR and threads: the class's split kernel serves the envs that fit it (obs_split_count)
+// EXACT and BIN: L becomes the class's carving (what the kernel has compiled in) with the next-hop tables, last in it, at the batch's size.
+enum ObsFit { OBS_FIT_EXACT, OBS_FIT_BIN, OBS_FIT_SPLIT };
+static int obs_var(const ObsLayout &L) { return L.tab_lds ? 1 : L.wl_bytes == 0 ? 2 : 0; }
+static bool obs_class_holds(const ObsClass &c, ObsFit kind, const FlDev &d, ObsArgs &P, const ObsOptions &own, ObsLayout &L) {
+    const ObsLayout &CL = OBS_CLASS_LAYOUTS.L[&c - OBS_CLASSES];
+    if (c.opt.wl_head && obs_no_wl_head()) return false;
     if (P.label) return false;   // (get_many(handles) with a strict subset: the stand-alone kernel's runtime body)
-    if ((FIX == 1 || FIX == 5) && P.keep_mode) return false;   // (the small-env classes carry no row-mask code: FL_OBS_KEEP_TREE_ROWS runs the runtime carving there)
-    const size_t nh_bytes = F::opt.nh ? (((size_t)d.Ucap * d.Rcap * 2 + 15) & ~(size_t)15) : 0;
-    if (!(d.A <= F::dims.A && d.Rcap <= F::dims.Rcap && d.rkey == nullptr && obs_same_options(o, F::opt) && P.merged == F::shape.merged &&
-          P.tw_c == F::shape.tw_c && P.tw_t == F::shape.tw_t && P.tpw_t == F::shape.tpw_t)) return false;
-    if (F::opt.dual && (size_t)d.A * (P.tree_pred + 2) > (size_t)F::L.items2_cap) return false;
+    if (P.keep_mode && !c.keep_rows) return false;   // (FL_OBS_KEEP_TREE_ROWS: the runtime carving instead)
+    if (!P.compact_t || (d.rkey != nullptr) != (c.dims.rkey != 0) || (c.agents != 0 ? d.A != c.agents : d.A > c.dims.A)) return false;
+    if (P.merged != c.shape.merged || P.tw_c != c.shape.tw_c || P.tw_t != c.shape.tw_t || P.tpw_t != c.shape.tpw_t) return false;
     // the class's kernel has the builders' parameters compiled in
-    if (P.max_nodes != F::max_nodes || P.pred_depth != F::pred_depth || P.tree_pred != F::shape.tree_pred || (F::max_depth != 0 && P.max_depth != F::max_depth)) return false;
-    if (F::agents != 0 && d.A != F::agents) return false;
-    // ... and what the launcher derives from the options (the kernel has the class's values: obs_fixed_* in fl_obs_layout.h)
-    if (!P.compact_t || P.bk != obs_fixed_bk<FIX>() || P.wl_occ_div != obs_fixed_wl_occ_div<FIX>() || P.tshift != obs_fixed_tshift<FIX>(d.A)) return false;
-    const size_t total = F::opt.nh ? F::L.off[L_NH] + nh_bytes : F::L.total;
+    if (P.max_nodes != c.max_nodes || P.pred_depth != c.pred_depth || P.tree_pred != c.shape.tree_pred || (c.max_depth != 0 && P.max_depth != c.max_depth)) return false;
+    if (c.opt.dual && (size_t)d.A * (P.tree_pred + 2) > (size_t)CL.items2_cap) return false;
+    const size_t total = c.opt.nh ? CL.off[L_NH] + obs_al16((unsigned long long)d.Ucap * d.Rcap * 2) : CL.total;
     if (total > (size_t)160 * 1024) return false;
-    L = F::L;
+    switch (kind) {
+    case OBS_FIT_SPLIT:   // (no options compared: the class's body has its own compiled in; the rail cells are counted per env)
+        return obs_var(L) == obs_class_var(c) && L.nt == c.opt.nt;
+    case OBS_FIT_EXACT:
+        // ... and what the launcher derives from the options: the kernel has the class's values (obs_class_* in fl_obs_layout.h)
+        if (d.Rcap > c.dims.Rcap || !obs_same_options(own, c.opt)) return false;
+        if (P.bk != obs_class_bk(c) || P.wl_occ_div != obs_class_wl_occ_div(c) || P.tshift != obs_class_tshift(c, d.A)) return false;
+        break;
+    case OBS_FIT_BIN:
+        if (d.Rcap > c.dims.Rcap) return false;
+        // the large-map bins have no LDS successor table: not for a batch that affords one itself (Test_12: 200 agents on 2 745 rail cells --
+        // same box, its envs beyond class 4 on the runtime carving WITH the table 435 us, on class 14 without 442)
+        if (!c.opt.snext && c.dims.rkey == 0 && own.snext) return false;
+        if (c.shape.tw_t != 0 && (P.max_depth < 1 || P.max_depth > 3)) return false;
+        if (c.shape.merged != 0 && (long long)d.A * (P.pred_depth + 2) >= 65536) return false;
+        P.use_tmask = c.opt.tmask; P.dual_index = c.opt.dual; P.bk = obs_class_bk(c);
+        P.bk_nb = c.shape.merged != 0 ? OBS_FB_NB : OBS_BK_NB; P.bk_shift = c.shape.merged != 0 ? OBS_FB_SHIFT : OBS_BK_SHIFT;
+        P.wl_occ_div = obs_class_wl_occ_div(c); P.tshift = obs_class_tshift(c, d.A);
+        break;
+    }
+    L = CL;
     L.total = (unsigned)total;
     return true;
 }
-// A BIN class (round 6): the batch fits the class's capacities, the call has the class's builder parameters (the depth is the call's) and the
-// batch's own choice has the class's STRUCTURE (one round / rounds of 32 agents / two stages) -- the class's options then replace the batch's
-// own: a compile-time carving with the options of the bin's largest shape instead of the runtime carving with options chosen for this one
-// (per shape of the Round-2 table: profiles/r06_round2_classes.txt).  FL_OBS_NO_BINS: exact classes only.
-template <int FIX> static int obs_split_fits(const FlDev &d, const ObsArgs &P, const int *h_R);
-template <int FIX>
-static bool obs_fits_bin(const FlDev &d, ObsArgs &P, const ObsOptions &own, ObsLayout &L) {
-    using F = ObsFixed<FIX>;
-    if (F::opt.wl_head && obs_no_wl_head()) return false;
-    // the large-map bins have no LDS successor table: not for a batch that affords one itself (Test_12: 200 agents on 2 745 rail cells --
-    // same box, its envs beyond class 4 on the runtime carving WITH the table 435 us, on class 14 without 442)
-    if (!F::opt.snext && F::dims.rkey == 0 && own.snext) return false;
-    if (P.label || !P.compact_t || (d.rkey != nullptr) != (F::dims.rkey != 0) || d.A > F::dims.A || d.Rcap > F::dims.Rcap) return false;
-    if (P.merged != F::shape.merged || P.tw_c != F::shape.tw_c || P.tw_t != F::shape.tw_t || P.tpw_t != F::shape.tpw_t) return false;
-    if (P.max_nodes != F::max_nodes || P.pred_depth != F::pred_depth || P.tree_pred != F::shape.tree_pred || (F::max_depth != 0 && P.max_depth != F::max_depth)) return false;
-    if (F::shape.tw_t != 0 && (P.max_depth < 1 || P.max_depth > 3)) return false;
-    if (FIX == 11 && P.keep_mode) return false;   // (class 1's code: no row masks)
-    if (F::opt.dual && (size_t)d.A * (P.tree_pred + 2) > (size_t)F::L.items2_cap) return false;
-    if (F::shape.merged != 0 && (long long)d.A * (P.pred_depth + 2) >= 65536) return false;
-    const size_t nh_bytes = F::opt.nh ? (((size_t)d.Ucap * d.Rcap * 2 + 15) & ~(size_t)15) : 0;
-    const size_t total = F::opt.nh ? F::L.off[L_NH] + nh_bytes : F::L.total;
-    if (total > (size_t)160 * 1024) return false;
-    // what the launcher derives from the options: the class's values (its kernel has them compiled in)
-    P.use_tmask = F::opt.tmask; P.dual_index = F::opt.dual; P.bk = obs_fixed_bk<FIX>();
-    P.bk_nb = F::shape.merged != 0 ? OBS_FB_NB : OBS_BK_NB; P.bk_shift = F::shape.merged != 0 ? OBS_FB_SHIFT : OBS_BK_SHIFT;
-    P.wl_occ_div = obs_fixed_wl_occ_div<FIX>(); P.tshift = obs_fixed_tshift<FIX>(d.A);
-    L = F::L;
-    L.total = (unsigned)total;
-    return true;
+// the envs that class `c`'s split kernel would serve with the class's body, the others running the carving L (h_R: the host's copy of
+// the envs' rail cells, null: unknown, no split); 0: no split launch of this class
+static int obs_split_count(const ObsClass &c, const FlDev &d, ObsArgs &P, const ObsLayout &L, const int *h_R) {
+    ObsLayout cur = L;
+    if (!h_R || !obs_class_holds(c, OBS_FIT_SPLIT, d, P, ObsOptions(), cur)) return 0;
+    int n = 0;
+    for (int b = 0; b < d.B; b++) n += h_R[b] <= c.dims.Rcap;
+    return n;
 }
-// an exact class's SPLIT launch (its body for the envs that fit, the runtime carving for the few larger maps) goes before a bin class for the
-// whole batch when at least half the envs fit the exact class
-template <int FIX>
-static bool exact_split_covers_most(const FlDev &d, ObsArgs &P, const ObsLayout &L) {
-    if (obs_no_split() || !P.h_R) return false;
-    const ObsLayout keep = P.L;
-    P.L = L;
-    const int n = obs_split_fits<FIX>(d, P, P.h_R);
-    P.L = keep;
-    return 2 * n >= d.B;
+// the first class of `ids` (an OBS_ORDER_* list) that holds the batch becomes P.fix
+static bool obs_take_first(const int *ids, ObsFit kind, const FlDev &d, ObsArgs &P, const ObsOptions &o, ObsLayout &L) {
+    for (; *ids; ids++)
+        if (obs_class_holds(OBS_CLASSES[obs_class_index(*ids)], kind, d, P, o, L)) { P.fix = *ids; return true; }
+    return false;
 }
-// the first class of K... (in this order) that holds the batch becomes P.fix
-template <int... K>
-static bool obs_take_exact(const FlDev &d, ObsArgs &P, const ObsOptions &o, ObsLayout &L) { return ((obs_fits_fixed<K>(d, P, o, L) && (P.fix = K) != 0) || ...); }
-template <int... K>
-static bool obs_take_bin(const FlDev &d, ObsArgs &P, const ObsOptions &o, ObsLayout &L) { return ((obs_fits_bin<K>(d, P, o, L) && (P.fix = K) != 0) || ...); }
 static void obs_take_fixed_class(const FlDev &d, ObsArgs &P, const ObsOptions &o, ObsLayout &L, bool allowed) {
     // diagnostic: exact classes only (the launcher of rounds 4 and 5).  A bin class REPLACES the batch's own options, so the switches that shape those options
     // (what a same-box experiment wants to measure) rule the bins out as well; an exact class only ever matches options it dominates.
@@ -201,64 +195,45 @@ static void obs_take_fixed_class(const FlDev &d, ObsArgs &P, const ObsOptions &o
     }();
     P.fix = 0; P.split = 0;
     if (obs_no_fix() || !allowed) return;
-    if (P.tw_t == 0) {   // the flatland_cutils builder alone: classes 6 .. 10 (the counterparts of 1 .. 5)
-        if (obs_take_exact<6, 7, 8, 9, 10, 21>(d, P, o, L) || no_bins || !P.cutils_alone) return;   // (FL_OBS_NO_CUTILS_MERGE: the stand-alone kernel as it ran before round 6)
-        obs_take_bin<21, 17, 8, 18, 9, 19, 20>(d, P, o, L);
+    if (P.tw_t == 0) {   // the flatland_cutils builder alone
+        // (FL_OBS_NO_CUTILS_MERGE, !P.cutils_alone: no bin -- but the exact classes are tried all the same, so class 9, the stand-alone kernel's, is still taken)
+        if (obs_take_first(OBS_ORDER_ALONE_EXACT, OBS_FIT_EXACT, d, P, o, L) || no_bins || !P.cutils_alone) return;
+        obs_take_first(OBS_ORDER_ALONE_BIN, OBS_FIT_BIN, d, P, o, L);
         return;
     }
-    if (obs_take_exact<1, 2, 3, 4, 5>(d, P, o, L) || no_bins) return;
-    if (exact_split_covers_most<2>(d, P, L) || exact_split_covers_most<3>(d, P, L)) return;   // (obs_take_split_class takes it)
-    obs_take_bin<11, 12, 13, 15, 4, 14, 16>(d, P, o, L);
+    if (obs_take_first(OBS_ORDER_BOTH_EXACT, OBS_FIT_EXACT, d, P, o, L) || no_bins) return;
+    // an exact class's SPLIT launch (its body for the envs that fit, the runtime carving L for the few larger maps) goes before a bin class for
+    // the whole batch when at least half the envs fit the exact class: no class here, obs_take_split_class takes it
+    if (!obs_no_split() && P.h_R)
+        for (const int *k = OBS_ORDER_BOTH_SPLIT_FIRST; *k; k++)
+            if (2 * obs_split_count(OBS_CLASSES[obs_class_index(*k)], d, P, L, P.h_R) >= d.B) return;
+    obs_take_first(OBS_ORDER_BOTH_BIN, OBS_FIT_BIN, d, P, o, L);
 }
 
-// (ObsArgs::fix_allowed: this launch's configuration was chosen without the diagnostic overrides that rule the fixed launch classes out)
-// A batch whose LARGEST map exceeds a class's rail cells still has the class's kind of envs in it (the levels of a Round-2 test differ
-// by a few per cent in rail cells; the classes are the BASELINE maps' own sizes): when everything but the rail-cell capacity matches
-// -- agents, builder parameters, and the runtime configuration just chosen for the batch runs the class's MODE and VAR -- the launch
-// takes the class's SPLIT kernel: per workgroup the class's body for an env that fits, the runtime-carving body (P.L, unchanged) for
-// the others.  h_R: the host's copy of the envs' rail cells (null: unknown, no split).  Returns the number of envs that fit.
-static int obs_var(const ObsArgs &P);
-template <int FIX>
-static int obs_split_fits(const FlDev &d, const ObsArgs &P, const int *h_R) {
-    using F = ObsFixed<FIX>;
-    if (F::opt.wl_head && obs_no_wl_head()) return 0;
-    if (!h_R || F::opt.nh) return 0;   // (class 1 keeps the next-hop tables, sized by the batch, behind its carving: not split)
-    if ((F::agents != 0 ? d.A != F::agents : d.A > F::dims.A) || d.rkey != nullptr || !P.compact_t) return 0;
-    if (P.max_nodes != F::max_nodes || P.pred_depth != F::pred_depth || P.tree_pred != F::shape.tree_pred || (F::max_depth != 0 && P.max_depth != F::max_depth)) return 0;
-    if (P.merged != F::shape.merged || obs_var(P) != obs_fixed_var<FIX>() || P.L.nt != F::opt.nt) return 0;
-    if (P.tw_c != F::shape.tw_c || P.tw_t != F::shape.tw_t || P.tpw_t != F::shape.tpw_t) return 0;
-    if (F::opt.dual && (size_t)d.A * (P.tree_pred + 2) > (size_t)F::L.items2_cap) return 0;
-    if (F::L.total > (size_t)160 * 1024) return 0;
-    int n = 0;
-    for (int b = 0; b < d.B; b++) n += h_R[b] <= F::dims.Rcap;
-    return n;
-}
+// The split launch of a configured batch (P.L, P.fix; ObsArgs::fix_allowed: chosen without the diagnostic overrides that rule the launch
+// classes out).  Per workgroup the class's body for an env that fits its rail cells (d.R[b] <= dims.Rcap) and for the others
+//   split 1: the runtime-carving body (P.L, unchanged) -- for a batch that no class holds whole
+//   split 2: the body of the class's larger partner (`split2`: no LDS successor table), which was taken because of the batch's largest map --
+//            one kernel, every env on a compile-time carving
+// Returns the number of envs that fit (0: no split launch).
 static int obs_take_split_class(const FlDev &d, ObsArgs &P, const int *h_R) {
     if (obs_no_fix() || obs_no_split() || !P.fix_allowed) return 0;
-    if (P.fix == 14 || P.fix == 19) {
-        // the larger large-map bin (no LDS successor table) was taken because of the batch's largest map: the envs that fit the smaller class
-        // (with the table) run ITS body, the others the bin's -- one kernel, every env on a compile-time carving (split 2)
-        const int fix2 = P.fix;
-        P.fix = 0;
-        const int n2 = fix2 == 14 ? obs_split_fits<4>(d, P, h_R) : obs_split_fits<9>(d, P, h_R);
-        const unsigned t2 = fix2 == 14 ? ObsFixed<4>::L.total : ObsFixed<9>::L.total;
-        if (n2 > 0) { P.fix = fix2 == 14 ? 4 : 9; P.split = 2; if (t2 > P.L.total) P.L.total = t2; return n2; }
-        P.fix = fix2;
+    auto take = [&](const ObsClass &c, int split) {
+        const int n = obs_split_count(c, d, P, P.L, h_R);
+        if (n > 0) {
+            P.fix = c.id; P.split = split;
+            P.L.total = std::max(P.L.total, OBS_CLASS_LAYOUTS.L[&c - OBS_CLASSES].total);   // dynamic LDS of the launch: the larger of the two carvings
+        }
+        return n;
+    };
+    if (P.fix != 0) {
+        for (const ObsClass &c : OBS_CLASSES)
+            if (c.split2 == P.fix) return take(c, 2);
         return 0;
     }
-    if (P.fix != 0) return 0;
-    int n = 0, k = 0;
-    unsigned total = 0;
-    if (P.tw_t == 0) {   // the flatland_cutils builder alone: the large-map class has a split kernel (the levels of cfg5's row differ by 13 % in rail cells)
-        if ((n = obs_split_fits<9>(d, P, h_R)) > 0) { k = 9; total = ObsFixed<9>::L.total; }
-    } else
-    if ((n = obs_split_fits<2>(d, P, h_R)) > 0) { k = 2; total = ObsFixed<2>::L.total; }
-    else if ((n = obs_split_fits<3>(d, P, h_R)) > 0) { k = 3; total = ObsFixed<3>::L.total; }
-    else if ((n = obs_split_fits<4>(d, P, h_R)) > 0) { k = 4; total = ObsFixed<4>::L.total; }
-    if (k == 0) return 0;
-    P.fix = k; P.split = 1;
-    if (total > P.L.total) P.L.total = total;   // dynamic LDS of the launch: the larger of the two carvings
-    return n;
+    for (const int *k = P.tw_t == 0 ? OBS_ORDER_SPLIT_ALONE : OBS_ORDER_SPLIT_BOTH; *k; k++)
+        if (const int n = take(OBS_CLASSES[obs_class_index(*k)], 1)) return n;
+    return 0;
 }
 
 // Choose what lives in LDS so that the workgroup fits 160 KiB.  `accepted`: the options of the configuration chosen (what the launch's
@@ -451,37 +426,38 @@ static void obs_verbose(const ObsArgs &P) {
                 P.fix, P.split ? " (split: the envs that fit it)" : "", L.nt, L.total, L.tab_lds, L.off[L_NH] != L_ABSENT, L.off[L_SNEXT] != L_ABSENT, L.wl_bytes, P.use_tmask, P.dual_index, L.off[L_ITEMS] != L_ABSENT, P.merged, P.compact_t, P.bk);
     }
 }
-static int obs_var(const ObsArgs &P) { return P.L.tab_lds ? 1 : P.L.wl_bytes == 0 ? 2 : 0; }
 // one pass B (P.merged 1 / 2 / 3): MODE 3 / 4 / 5 for both builders, 6 / 7 / 8 for the flatland_cutils builder alone; else the builders of the launch
 static int obs_mode(const ObsArgs &P) { return P.merged ? (P.tw_t ? 2 : 5) + P.merged : P.tw_c == 0 ? 1 : P.tw_t ? 2 : 0; }
 
 // The kernel of a launch: the split kernel of (P.split, P.fix), the kernel of class P.fix, or else the runtime-carving kernel of the launch's
-// MODE; FL_ERR_ARG for a (split, class) pair that has no kernel.  The lists are build.sh's units.
-template <int FIX2, int... K>
-static int obs_launch_class(const FlDev &d, const FlObsScratch &u, const ObsArgs &P, hipStream_t s) {
+// MODE; FL_ERR_ARG for a (split, class) pair that has no kernel.  The kernels a row of OBS_CLASSES names are build.sh's units fK, sK and sKb.
+template <int ROW>
+static int obs_launch_row(const FlDev &d, const FlObsScratch &u, const ObsArgs &P, hipStream_t s) {
+    constexpr ObsClass c = OBS_CLASSES[ROW];
+    if (P.split == 2) { if constexpr (c.split2 != 0) return fl_obs_launch_class<c.id, c.split2>(d, u, P, s); else return FL_ERR_ARG; }
+    if (P.split) { if constexpr (c.split_rt != 0) return fl_obs_launch_class<c.id, 0>(d, u, P, s); else return FL_ERR_ARG; }
+    return fl_obs_launch_class<c.id>(d, u, P, s);
+}
+template <int... ROW>
+static int obs_launch_class(std::integer_sequence<int, ROW...>, const FlDev &d, const FlObsScratch &u, const ObsArgs &P, hipStream_t s) {
     int rc = FL_ERR_ARG;
-    (void)((P.fix == K && (rc = fl_obs_launch_class<K, FIX2>(d, u, P, s), true)) || ...);
+    (void)((P.fix == OBS_CLASSES[ROW].id && (rc = obs_launch_row<ROW>(d, u, P, s), true)) || ...);
     return rc;
 }
 template <int... M>
 static int obs_launch_mode(int mode, const FlDev &d, const FlObsScratch &u, const ObsArgs &P, hipStream_t s) {
     int rc = FL_ERR_ARG;
-    (void)((mode == M && (rc = fl_obs_launch_mode<M>(obs_var(P), d, u, P, s), true)) || ...);
+    (void)((mode == M && (rc = fl_obs_launch_mode<M>(obs_var(P.L), d, u, P, s), true)) || ...);
     return rc;
 }
 static int obs_launch(const FlDev &d, const FlObsScratch &u, const ObsArgs &P, hipStream_t s) {
-    if (P.split == 2) return P.fix == 4 ? fl_obs_launch_class<4, 14>(d, u, P, s) : P.fix == 9 ? fl_obs_launch_class<9, 19>(d, u, P, s) : FL_ERR_ARG;
-    if (P.split) return obs_launch_class<0, 2, 3, 4, 9>(d, u, P, s);
-    if (P.fix) return obs_launch_class<-1, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21>(d, u, P, s);
-    return obs_launch_mode<0, 1, 2, 3, 4, 5, 6, 7, 8>(obs_mode(P), d, u, P, s);
+    if (P.fix) return obs_launch_class(std::make_integer_sequence<int, OBS_N_CLASSES>(), d, u, P, s);
+    return P.split ? FL_ERR_ARG : obs_launch_mode<0, 1, 2, 3, 4, 5, 6, 7, 8>(obs_mode(P), d, u, P, s);
 }
 // the record of a launch (fl_obs.h lists the words): the ObsArgs that were launched and the options `q` the preference walk accepted for them
-template <int... K>
-static void obs_class_kernel(int fix, int &mode, int &var) { (void)((fix == K && (mode = obs_fixed_mode<K>(), var = obs_fixed_var<K>(), true)) || ...); }
 static void obs_record_launch(const ObsArgs &P, const ObsOptions &q, int record[FL_OBS_LAUNCH_WORDS]) {
-    int mode = obs_mode(P), var = obs_var(P);
-    if (P.fix) obs_class_kernel<1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21>(P.fix, mode, var);
-    const int rec[FL_OBS_LAUNCH_WORDS] = {mode, var, P.fix, P.split, P.split == 2 ? (P.fix == 4 ? 14 : 19) : 0, P.L.nt, (int)P.L.total,
+    const ObsClass *c = P.fix ? &OBS_CLASSES[obs_class_index(P.fix)] : nullptr;
+    const int rec[FL_OBS_LAUNCH_WORDS] = {c ? obs_class_mode(*c) : obs_mode(P), c ? obs_class_var(*c) : obs_var(P.L), P.fix, P.split, P.split == 2 ? c->split2 : 0, P.L.nt, (int)P.L.total,
                                           q.wl_bytes, q.tab, q.nh, q.tmask, q.dual, q.items, q.items_cap, q.snext, q.partial, q.bk_room, q.own_filter, q.fb, q.raw, q.wl_head,
                                           P.bk, P.tshift, P.compact_t, P.label != nullptr};
     memcpy(record, rec, sizeof rec);
@@ -523,18 +499,58 @@ static int obs_configure(const FlDev &d, ObsArgs &P, ObsOptions &accepted, const
     return P.split ? n_split : P.fix ? d.B : 0;
 }
 
-// ---- the three launches: obs_begin, their own limits and arguments, obs_run
+// ---- the three launches, each in two halves: the PLAN (obs_begin, the launch's own limits and arguments, obs_configure -- host decisions
+// only, what the diagnostic fl_obs_plan shares with the real launch) and obs_enqueue (output pointers, row masks, env order, the kernel)
+struct ObsPlan {
+    ObsArgs P;
+    ObsOptions accepted;   // the options the preference walk accepted (the record's words 7 .. 20)
+    int n_fit;             // envs on a launch class's body (obs_configure)
+};
 // voids the record (MODE -1: nothing ran -- what every failing return leaves) and checks the limits every launch has
 static bool obs_begin(const FlObsScratch &o, const FlDev &d, int pred_depth, int record[FL_OBS_LAUNCH_WORDS]) {
     memset(record, 0, FL_OBS_LAUNCH_WORDS * sizeof record[0]);
     record[0] = -1;
     return d.A <= 1024 && pred_depth + 2 <= o.pred_cap && pred_depth <= 510;
 }
-static int obs_run(FlObsScratch &o, const FlDev &d, ObsArgs &P, const int *h_R, hipStream_t s, int record[FL_OBS_LAUNCH_WORDS]) {
-    ObsOptions accepted = {};
-    const int n_fit = obs_configure(d, P, accepted, h_R);
-    if (n_fit < 0) return FL_ERR_ARG;
-    o.last_fix = P.fix; o.last_split = P.split; o.last_fit = n_fit;
+static int obs_plan_end(const FlDev &d, ObsPlan &pl, const int *h_R) {
+    pl.accepted = ObsOptions();
+    pl.n_fit = obs_configure(d, pl.P, pl.accepted, h_R);
+    return pl.n_fit < 0 ? FL_ERR_ARG : FL_OK;
+}
+static int obs_plan_cutils(const FlObsScratch &o, const FlDev &d, int max_nodes, int pred_depth, const int16_t *label_dev, int record[FL_OBS_LAUNCH_WORDS], ObsPlan &pl) {
+    if (!obs_begin(o, d, pred_depth, record) || max_nodes > FL_OBS_MAX_NODES) return FL_ERR_ARG;
+    pl.P = ObsArgs();
+    pl.P.label = label_dev;
+    obs_cutils_args(pl.P, max_nodes, pred_depth, obs_batch_is_wide(d.B, o.n_cu));
+    obs_alone_args(d, pl.P);
+    return obs_plan_end(d, pl, pl.P.label ? nullptr : o.h_R);   // (a handle subset: no split class)
+}
+static int obs_plan_both(const FlObsScratch &o, const FlDev &d, int max_nodes, int pred_depth, int max_depth, int tree_pred, double *tree_out,
+                         int record[FL_OBS_LAUNCH_WORDS], ObsPlan &pl) {
+    if (!obs_begin(o, d, pred_depth, record) || max_nodes > OBS_CAP_C) return FL_ERR_ARG;   // (the fused kernels: 32-lane teams)
+    if (max_depth > 3 || tree_pred > pred_depth || tree_pred < 0) return FL_ERR_ARG;  // the upstream path must be a prefix
+    pl.P = ObsArgs();
+    obs_cutils_args(pl.P, max_nodes, pred_depth, obs_batch_is_wide(d.B, o.n_cu));
+    obs_tree_args(d, pl.P, max_depth, tree_pred, tree_out);
+    pl.P.keep_mode = o.keep_rows;
+    pl.P.h_R = o.h_R;
+    return obs_plan_end(d, pl, o.h_R);
+}
+static int obs_plan_tree(const FlObsScratch &o, const FlDev &d, int max_depth, int pred_depth, double *out, const int16_t *label_dev,
+                         int record[FL_OBS_LAUNCH_WORDS], ObsPlan &pl) {
+    if (!obs_begin(o, d, pred_depth, record) || max_depth > FL_MAX_TREE_DEPTH) return FL_ERR_ARG;
+    // depth 4: compact node tables only (level L of the tree has at most 2^L nodes when no direction of a cell has more than two
+    // transitions -- every Flatland rail cell type): 30 slots; the DFS-slot tables of other grids stop at depth 3 (85 slots)
+    if (max_depth > 3 && d.max_branch > 2) return FL_ERR_ARG;
+    pl.P = ObsArgs();
+    pl.P.label = label_dev;
+    obs_tree_args(d, pl.P, max_depth, pred_depth, out);
+    if (max_depth > 3 && !pl.P.compact_t) return FL_ERR_ARG;   // (FL_OBS_NO_COMPACT)
+    return obs_plan_end(d, pl, nullptr);   // (no split class has the upstream builder alone)
+}
+static int obs_enqueue(FlObsScratch &o, const FlDev &d, ObsPlan &pl, hipStream_t s, int record[FL_OBS_LAUNCH_WORDS]) {
+    ObsArgs &P = pl.P;
+    o.last_fix = P.fix; o.last_split = P.split; o.last_fit = pl.n_fit;
     // FL_OBS_KEEP_TREE_ROWS: the row masks of the previous launch describe this very buffer at this depth -> no pre-fill of the slab
     uint4 *const rowmask = o.rowmask;
     struct Restore { FlObsScratch &o; uint4 *m; ~Restore() { o.rowmask = m; } } restore{o, rowmask};
@@ -553,47 +569,51 @@ static int obs_run(FlObsScratch &o, const FlDev &d, ObsArgs &P, const int *h_R, 
     if (P.merged == 1) u.order = nullptr;   // small envs, one round: workgroup k builds env k
     else u = fl_obs_env_order(o, d, s);
     const int rc = obs_launch(d, u, P, s);
-    if (rc == FL_OK) obs_record_launch(P, accepted, record);
+    if (rc == FL_OK) obs_record_launch(P, pl.accepted, record);
     return rc;
 }
 
 int fl_launch_obs_cutils(FlObsScratch &o, const FlDev &d, int max_nodes, int pred_depth, const FlObsCutilsOut &out, hipStream_t s,
                          int record[FL_OBS_LAUNCH_WORDS], const int16_t *label_dev, int out64) {
-    if (!obs_begin(o, d, pred_depth, record) || max_nodes > FL_OBS_MAX_NODES) return FL_ERR_ARG;
-    ObsArgs P = {};
-    P.label = label_dev;
-    P.out64 = out64;
-    obs_out_args(P, o, out);
-    obs_cutils_args(P, max_nodes, pred_depth, obs_batch_is_wide(d.B, o.n_cu));
-    obs_alone_args(d, P);
-    return obs_run(o, d, P, P.label ? nullptr : o.h_R, s, record);   // (a handle subset: no split class)
+    ObsPlan pl;
+    const int rc = obs_plan_cutils(o, d, max_nodes, pred_depth, label_dev, record, pl);
+    if (rc != FL_OK) return rc;
+    pl.P.out64 = out64;
+    obs_out_args(pl.P, o, out);
+    return obs_enqueue(o, d, pl, s, record);
 }
 
 int fl_launch_obs_both(FlObsScratch &o, const FlDev &d, int max_nodes, int pred_depth, const FlObsCutilsOut &out, int max_depth, int tree_pred,
                        double *tree_out, hipStream_t s, int record[FL_OBS_LAUNCH_WORDS]) {
-    if (!obs_begin(o, d, pred_depth, record) || max_nodes > OBS_CAP_C) return FL_ERR_ARG;   // (the fused kernels: 32-lane teams)
-    if (max_depth > 3 || tree_pred > pred_depth || tree_pred < 0) return FL_ERR_ARG;  // the upstream path must be a prefix
-    ObsArgs P = {};
-    obs_out_args(P, o, out);
-    obs_cutils_args(P, max_nodes, pred_depth, obs_batch_is_wide(d.B, o.n_cu));
-    obs_tree_args(d, P, max_depth, tree_pred, tree_out);
-    P.keep_mode = o.keep_rows;
-    P.h_R = o.h_R;
-    return obs_run(o, d, P, o.h_R, s, record);
+    ObsPlan pl;
+    const int rc = obs_plan_both(o, d, max_nodes, pred_depth, max_depth, tree_pred, tree_out, record, pl);
+    if (rc != FL_OK) return rc;
+    obs_out_args(pl.P, o, out);
+    return obs_enqueue(o, d, pl, s, record);
 }
 
 int fl_launch_obs_tree(FlObsScratch &o, const FlDev &d, int max_depth, int pred_depth, double *out, hipStream_t s, int record[FL_OBS_LAUNCH_WORDS],
                        const int16_t *label_dev) {
-    if (!obs_begin(o, d, pred_depth, record) || max_depth > FL_MAX_TREE_DEPTH) return FL_ERR_ARG;
-    // depth 4: compact node tables only (level L of the tree has at most 2^L nodes when no direction of a cell has more than two
-    // transitions -- every Flatland rail cell type): 30 slots; the DFS-slot tables of other grids stop at depth 3 (85 slots)
-    if (max_depth > 3 && d.max_branch > 2) return FL_ERR_ARG;
-    ObsArgs P = {};
-    P.dbg = o.dbg;
-    P.label = label_dev;
-    obs_tree_args(d, P, max_depth, pred_depth, out);
-    if (max_depth > 3 && !P.compact_t) return FL_ERR_ARG;   // (FL_OBS_NO_COMPACT)
-    return obs_run(o, d, P, nullptr, s, record);   // (no split class has the upstream builder alone)
+    ObsPlan pl;
+    const int rc = obs_plan_tree(o, d, max_depth, pred_depth, out, label_dev, record, pl);
+    if (rc != FL_OK) return rc;
+    pl.P.dbg = o.dbg;
+    return obs_enqueue(o, d, pl, s, record);
+}
+
+// diagnostic, no GPU needed: the plan half of the launch `kind` (0 fl_launch_obs_cutils, 1 _both, 2 _tree: each takes of the parameters what its
+// launch takes -- the tree launch's predictor depth is tree_pred) and the record that launch would leave; o: n_cu, h_R, keep_rows and pred_cap
+// as the handle has them.  *n_fit: envs on a launch class's body.  FL_ERR_ARG (record voided) where the launch returns it.
+int fl_obs_plan(int kind, const FlObsScratch &o, const FlDev &d, int max_nodes, int pred_depth, int max_depth, int tree_pred, const int16_t *label,
+                int record[FL_OBS_LAUNCH_WORDS], int *n_fit) {
+    ObsPlan pl;
+    const int rc = kind == 0 ? obs_plan_cutils(o, d, max_nodes, pred_depth, label, record, pl)
+                 : kind == 1 ? obs_plan_both(o, d, max_nodes, pred_depth, max_depth, tree_pred, nullptr, record, pl)
+                 : kind == 2 ? obs_plan_tree(o, d, max_depth, tree_pred, nullptr, label, record, pl) : FL_ERR_ARG;
+    if (rc != FL_OK) return rc;
+    obs_record_launch(pl.P, pl.accepted, record);
+    *n_fit = pl.n_fit;
+    return FL_OK;
 }
 
 // diagnostic: the configuration obs_pick_config chooses for the fused launch (cutils + upstream tree of max_depth):

@@ -113,7 +113,7 @@ struct ObsLayout {
 };
 
 // ---- the carving of the dynamic LDS, one function for the host (obs_pick_config: any env size) and for the kernels whose layout
-// is a compile-time constant (FIXED launch classes below: every LDS base is an immediate instead of a scalar register)
+// is a compile-time constant (the launch classes below: every LDS base is an immediate instead of a scalar register)
 // what a launch may keep in LDS besides the arrays every launch needs
 struct ObsOptions { int nt, wl_bytes, tab, nh, tmask, dual, items, snext, partial, bk_room, own_filter, fb, raw, items_cap, wl_head; };
 struct ObsDims { int Rcap, A, Ucap, rkey; };                   // capacities of the batch (rkey: colliding prediction keys, H > W)
@@ -183,214 +183,178 @@ __host__ __device__ constexpr ObsLayout obs_layout_c(const ObsDims &d, const Obs
     return L;
 }
 
-// FIXED launch classes: the pinned configurations of the small-env kernels with every capacity rounded up to a class value, so that
-// the whole carving is a compile-time constant -- an LDS base is an immediate of the ds_* instruction instead of one of ~50 scalar
-// registers the kernel cannot keep (311-373 spilled SGPRs before, every one a v_readlane / v_writelane in the hot loops).  The
-// host (obs_pick_config) takes a class when the batch fits its capacities AND its own choice of options is the class's; any
-// other batch runs the same kernel with the runtime layout (FIX 0).  The next-hop tables (sized by the unique targets) come last
-// in the carving: their base is fixed, their size is the batch's.
-// A class is a BASELINE configuration: besides the capacities it fixes the builders' parameters (31 nodes, predictor depths 500 / 30,
-// the upstream tree's depth) and, for the larger ones, the exact number of agents -- all constants in its kernel.
-//   FIX 1: one round of trees for both builders (MODE 3): at most 32 agents, 256 rail cells, depth 2 -- cfg1, cfg2 (BASELINE configs[0..1])
-#define OBS_FIX3_RCAP 680
-#define OBS_FIX4_RCAP 2816   // classes 4 / 9 (round 6: bins): cfg5 (2 680 rail cells) and, with the LDS successor table still fitting, Test_12 (2 745) and
-#define OBS_FIX4_A 432       // the first level of Test_14 (2 807 cells, 425 agents)
-#define OBS_FIX3_WL_HEAD (10 * 1024)
 #ifndef OBS_WL_HEAD_MAX
 #define OBS_WL_HEAD_MAX (32 * 1024)   // (round 6: 16 -> 32 KB, the builder alone at cfg4 0.243 -> 0.240 ms same box; both builders never have that much left)
 #endif
 // LDS head of HBM work lists: whatever the carving leaves, in KB steps, at most this, at least OBS_WL_HEAD_MIN
 #define OBS_WL_HEAD_MIN (4 * 1024)
 #define OBS_ALONE_LDS_LISTS_RCAP 320   // the flatland_cutils builder alone, rounds of 32 agents: LDS work lists up to this many rail cells, HBM lists with an LDS head beyond
-template <int FIX> struct ObsFixed;
-// EXACT classes (1, 2, 3, 5, 6, 7, 10) are BASELINE configurations down to the number of agents and the upstream depth -- constants in their
-// kernels.  BIN classes (round 6) keep the compile-time carving but take the agents as an upper bound (dims.A, `agents` 0) and the depth from
-// the call (`max_depth` 0): same-box cost against the exact class 3 % at cfg3, 1.7 % at cfg4, nothing measurable at cfg5 and for the builder
-// alone (runtime carving: 7 - 8 %) -- so 4, 8, 9 are bins themselves and 2, 3, 7 have bin twins (12, 13, 17); 11 = class 1 at any depth;
-// 14 / 19 = the large-map classes without the LDS successor table: 432 agents / 3 072 rail cells (Test_14; the larger levels of cfg5's row).
-// options of the classes of the flatland_cutils builder alone: what obs_pick_config chooses at the classes' capacities (tests/test_obs_config.py)
-//                      nt, wl_bytes, tab, nh, tmask, dual, items, snext, partial, bk_room, own_filter, fb, raw, items_cap, wl_head
-#define OBS_FIX7_OPT  {OBS_NT, 36 * 1024, 0, 0, 1, 0, 1, 1, 1, 0, 1, 1, 1, OBS_ITEMS_LDS_CAP, 0}
-#define OBS_FIX8_OPT  {OBS_NT, 0, 0, 0, 1, 0, 0, 1, 1, 0, 1, 1, 1, OBS_ITEMS_LDS_CAP, OBS_WL_HEAD_MAX}
-#define OBS_FIX9_OPT  {OBS_NT, 0, 0, 0, 1, 0, 0, 1, 1, 1, 0, 0, 0, 0, 0}
-#define OBS_FIX10_OPT {512, 16 * 1024, 0, 1, 1, 0, 1, 1, 1, 0, 1, 0, 1, OBS_ITEMS_LDS_CAP, 0}
-template <> struct ObsFixed<1> {
-    static constexpr int max_nodes = 31, pred_depth = 500, max_depth = 2;   // the builders' parameters of the class (tree_pred: shape)
-    static constexpr int agents = 0;   // agents per env, exactly (0 = any number up to dims.A)
-    static constexpr ObsDims dims = {256, 32, 0, 0};
-    static constexpr ObsShape shape = {1, N_WORDS_C * OBS_CAP_C, N_WORDS_T * OBS_CAP_T_COMPACT, 4, 30};
-    //                                  nt, wl_bytes, tab, nh, tmask, dual, items, snext, partial, bk_room, own_filter, fb, raw, items_cap
-    static constexpr ObsOptions opt = {OBS_NT, 24 * 1024, 0, 1, 1, 1, 1, 1, 1, 0, 1, 0, 1, OBS_ITEMS_LDS_CAP};
-    static constexpr ObsLayout L = obs_layout_c(dims, shape, opt);
+
+// ---- LAUNCH CLASSES.  A class is a pinned configuration of the small-env kernels with every capacity rounded up to a class value, so that
+// the whole carving is a compile-time constant -- an LDS base is an immediate of the ds_* instruction instead of one of ~50 scalar
+// registers the kernel cannot keep (311-373 spilled SGPRs before, every one a v_readlane / v_writelane in the hot loops).  The next-hop
+// tables (sized by the unique targets) come last in the carving: their base is fixed, their size is the batch's.  A batch that no class
+// holds runs the same kernel code with the runtime layout (class 0).  A class is ONE ROW of OBS_CLASSES: what its kernel has compiled in
+// (fl_obs_body.h reads the row as ObsFixed<id>), what the host compares a batch with (fl_obs.hip: obs_class_holds, one function), and its
+// relations to other classes.  To retire a class: its row, its id in the OBS_ORDER_* arrays behind the table, its unit in build.sh.
+//   bin 0      an EXACT class: a BASELINE configuration down to the upstream depth (max_depth) and, for 2, 3 and 7, the number of agents,
+//              taken when the batch's own choice of options (obs_pick_config) is the class's (obs_same_options).  The LDS of 2 - 4 is full
+//              to the last few hundred bytes -- that is how obs_pick_config chose their options -- so their capacities are the BASELINE
+//              maps' own sizes rounded up to 8 / 16 rail cells; tests/test_obs_config.py: each class IS the choice at its capacities
+//   bin 1      a BIN class (round 6): the agents are an upper bound, the upstream depth is the call's (1 .. 3), and the batch's own choice
+//              only needs the class's STRUCTURE (shape): the class's options then replace the batch's own.  Same-box cost against the exact
+//              class 3 % at cfg3, 1.7 % at cfg4, nothing measurable at cfg5 and for the builder alone (runtime carving: 7 - 8 %).  A bin
+//              whose options a batch chooses by itself is taken as an exact class first (4, 8, 9 and 21 are in both orders)
+//   shape      obs_shape_both / _alone(merged): both builders, or the flatland_cutils builder ALONE -- what the reference's solution launches
+//              (solution/eval_env.py:15-17); no second index, no upstream tables.  merged (-> the kernel's MODE, obs_class_mode): 1 one round
+//              of trees, 2 rounds of 32 agents, 3 rounds of 16 agents on 512 threads in at most 80 KB of LDS -- TWO workgroups a CU, for
+//              batches of several envs per CU (obs_batch_is_wide; profiles/r05_cfg2_bsweep.json) --, 0 two stages
+//   split_rt   the class has a split kernel (P.split 1, unit sK of build.sh): its body for the envs of a batch that fit its rail cells, the
+//              runtime carving's for the others (the levels of a Round-2 test differ by a few per cent in rail cells)
+//   split2     ... and one whose second body is this larger class's, every env on a compile-time carving (P.split 2, unit sKb)
+//   keep_rows  the host takes the class under FL_OBS_KEEP_TREE_ROWS.  The kernels of 1 and 5 carry no row-mask code; class 11's kernel DOES
+//              (fl_obs_body.h hands it the row masks) and the host refuses it all the same: such a batch runs the runtime carving
+struct ObsClass {
+    int id, bin;
+    int max_nodes = 31, pred_depth = 500;   // the builders' parameters: the solution's in every class (the upstream predictor's 30: shape.tree_pred)
+    int max_depth;                          // ... 0: the call's depth
+    int agents;                             // agents per env, exactly (0 = any number up to dims.A)
+    ObsDims dims;
+    ObsShape shape;
+    int split2 = 0, split_rt = 0, keep_rows = 1;
+    ObsOptions opt;
 };
-//   FIX 2: rounds of 32 agents, work lists in LDS (MODE 4, VAR 0): 80 agents, at most 232 rail cells, depth 3 -- cfg3 (BASELINE configs[2])
-//   FIX 3: rounds of 32 agents, work lists in HBM scratch with an LDS head (MODE 4, VAR 2): 80 agents, at most 680 rail cells -- every
-//          level of the Round-2 row (Test_8: 603 .. 677) --, depth 2 -- cfg4 (configs[3]).  No LDS copy of the items: every cfg4 env has
-//          more items than the 4 096 entries that fitted (round 4: the copy was dead weight); its 16 KB are the larger maps and the head.
-//   FIX 4: two stages, hundreds of agents (MODE 2, VAR 2): at most 432 agents / 2816 rail cells, any depth (a bin since round 6) -- cfg5 (configs[4]), Test_12, Test_14
-// The LDS of these three is full to the last few hundred bytes (that is how obs_pick_config chose their options), so the classes
-// are the BASELINE maps' own sizes rounded up to a multiple of 8 / 16 rail cells; tests/test_obs_config.py checks that each class
-// IS what obs_pick_config chooses at the class's capacities.
-template <> struct ObsFixed<2> {
-    static constexpr int max_nodes = 31, pred_depth = 500, max_depth = 3;   // the builders' parameters of the class (tree_pred: shape)
-    static constexpr int agents = 80;   // agents per env, exactly (0 = any number up to dims.A)
-    static constexpr ObsDims dims = {232, 80, 0, 0};
-    static constexpr ObsShape shape = {2, N_WORDS_C * OBS_CAP_C, N_WORDS_T * OBS_CAP_T_COMPACT, 4, 30};
-    static constexpr ObsOptions opt = {OBS_NT, 36 * 1024, 0, 0, 1, 1, 1, 1, 1, 0, 1, 1, 1, 4096};
-    static constexpr ObsLayout L = obs_layout_c(dims, shape, opt);
+__host__ __device__ constexpr ObsShape obs_shape_both(int merged) { return {merged, N_WORDS_C * OBS_CAP_C, N_WORDS_T * OBS_CAP_T_COMPACT, 4, 30}; }
+__host__ __device__ constexpr ObsShape obs_shape_alone(int merged) { return {merged, N_WORDS_C * OBS_CAP_C, 0, 0, 0}; }
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wc++20-designator"
+inline constexpr ObsClass OBS_CLASSES[] = {
+    // 1 .. 5, both builders.  1: one round -- cfg1, cfg2 (BASELINE configs[0..1]).  2: rounds, work lists in LDS -- cfg3 (configs[2]).  3: rounds, work
+    // lists in HBM scratch behind an LDS head -- cfg4 (configs[3]; every level of the Round-2 row, Test_8: 603 .. 677 rail cells); no LDS copy of the items:
+    // every cfg4 env has more than the 4 096 that fitted.  4: two stages, hundreds of agents -- cfg5 (configs[4]: 2 680 rail cells) and, the LDS successor
+    // table still fitting, Test_12 (2 745) and the first level of Test_14 (2 807 cells, 425 agents).  5: class 1's envs two workgroups a CU
+    {.id = 1, .bin = 0, .max_depth = 2, .agents = 0, .dims = {.Rcap = 256, .A = 32}, .shape = obs_shape_both(1), .keep_rows = 0,
+     .opt = {.nt = OBS_NT, .wl_bytes = 24 * 1024, .tab = 0, .nh = 1, .tmask = 1, .dual = 1, .items = 1, .snext = 1, .partial = 1, .bk_room = 0, .own_filter = 1, .fb = 0, .raw = 1, .items_cap = OBS_ITEMS_LDS_CAP, .wl_head = 0}},
+    {.id = 2, .bin = 0, .max_depth = 3, .agents = 80, .dims = {.Rcap = 232, .A = 80}, .shape = obs_shape_both(2), .split_rt = 1,
+     .opt = {.nt = OBS_NT, .wl_bytes = 36 * 1024, .tab = 0, .nh = 0, .tmask = 1, .dual = 1, .items = 1, .snext = 1, .partial = 1, .bk_room = 0, .own_filter = 1, .fb = 1, .raw = 1, .items_cap = 4096, .wl_head = 0}},
+    {.id = 3, .bin = 0, .max_depth = 2, .agents = 80, .dims = {.Rcap = 680, .A = 80}, .shape = obs_shape_both(2), .split_rt = 1,
+     .opt = {.nt = OBS_NT, .wl_bytes = 0, .tab = 0, .nh = 0, .tmask = 1, .dual = 1, .items = 0, .snext = 1, .partial = 1, .bk_room = 0, .own_filter = 1, .fb = 1, .raw = 1, .items_cap = OBS_ITEMS_LDS_CAP, .wl_head = 10 * 1024}},
+    {.id = 4, .bin = 1, .max_depth = 0, .agents = 0, .dims = {.Rcap = 2816, .A = 432}, .shape = obs_shape_both(0), .split2 = 14, .split_rt = 1,
+     .opt = {.nt = OBS_NT, .wl_bytes = 0, .tab = 0, .nh = 0, .tmask = 1, .dual = 0, .items = 0, .snext = 1, .partial = 1, .bk_room = 1, .own_filter = 0, .fb = 0, .raw = 0, .items_cap = 0, .wl_head = 0}},
+    {.id = 5, .bin = 0, .max_depth = 2, .agents = 0, .dims = {.Rcap = 256, .A = 32}, .shape = obs_shape_both(3), .keep_rows = 0,
+     .opt = {.nt = 512, .wl_bytes = 16 * 1024, .tab = 0, .nh = 0, .tmask = 1, .dual = 1, .items = 1, .snext = 1, .partial = 1, .bk_room = 0, .own_filter = 1, .fb = 0, .raw = 0, .items_cap = 2048, .wl_head = 0}},
+    // 6 .. 10: the flatland_cutils builder alone, the counterparts of 1 .. 5 on the same machinery (8: the largest LDS head; 9: the stand-alone kernel,
+    // MODE 0, with its carving compiled in -- the levels of cfg5's row differ by 13 % in rail cells, hence its split kernels)
+    {.id = 6, .bin = 0, .max_depth = 0, .agents = 0, .dims = {.Rcap = 256, .A = 32}, .shape = obs_shape_alone(1),
+     .opt = {.nt = OBS_NT, .wl_bytes = 24 * 1024, .tab = 0, .nh = 1, .tmask = 1, .dual = 0, .items = 1, .snext = 1, .partial = 1, .bk_room = 0, .own_filter = 1, .fb = 0, .raw = 1, .items_cap = OBS_ITEMS_LDS_CAP, .wl_head = 0}},
+    {.id = 7, .bin = 0, .max_depth = 0, .agents = 80, .dims = {.Rcap = 232, .A = 80}, .shape = obs_shape_alone(2),
+     .opt = {.nt = OBS_NT, .wl_bytes = 36 * 1024, .tab = 0, .nh = 0, .tmask = 1, .dual = 0, .items = 1, .snext = 1, .partial = 1, .bk_room = 0, .own_filter = 1, .fb = 1, .raw = 1, .items_cap = OBS_ITEMS_LDS_CAP, .wl_head = 0}},
+    {.id = 8, .bin = 1, .max_depth = 0, .agents = 0, .dims = {.Rcap = 680, .A = 80}, .shape = obs_shape_alone(2),
+     .opt = {.nt = OBS_NT, .wl_bytes = 0, .tab = 0, .nh = 0, .tmask = 1, .dual = 0, .items = 0, .snext = 1, .partial = 1, .bk_room = 0, .own_filter = 1, .fb = 1, .raw = 1, .items_cap = OBS_ITEMS_LDS_CAP, .wl_head = OBS_WL_HEAD_MAX}},
+    {.id = 9, .bin = 1, .max_depth = 0, .agents = 0, .dims = {.Rcap = 2816, .A = 432}, .shape = obs_shape_alone(0), .split2 = 19, .split_rt = 1,
+     .opt = {.nt = OBS_NT, .wl_bytes = 0, .tab = 0, .nh = 0, .tmask = 1, .dual = 0, .items = 0, .snext = 1, .partial = 1, .bk_room = 1, .own_filter = 0, .fb = 0, .raw = 0, .items_cap = 0, .wl_head = 0}},
+    {.id = 10, .bin = 0, .max_depth = 0, .agents = 0, .dims = {.Rcap = 256, .A = 32}, .shape = obs_shape_alone(3),
+     .opt = {.nt = 512, .wl_bytes = 16 * 1024, .tab = 0, .nh = 1, .tmask = 1, .dual = 0, .items = 1, .snext = 1, .partial = 1, .bk_room = 0, .own_filter = 1, .fb = 0, .raw = 1, .items_cap = OBS_ITEMS_LDS_CAP, .wl_head = 0}},
+    // 11, 12, 13 (and 17): the bin twins of 1, 2, 3 (and 7) -- their dims, shape and options at any depth and any number of agents up to dims.A
+    {.id = 11, .bin = 1, .max_depth = 0, .agents = 0, .dims = {.Rcap = 256, .A = 32}, .shape = obs_shape_both(1), .keep_rows = 0,
+     .opt = {.nt = OBS_NT, .wl_bytes = 24 * 1024, .tab = 0, .nh = 1, .tmask = 1, .dual = 1, .items = 1, .snext = 1, .partial = 1, .bk_room = 0, .own_filter = 1, .fb = 0, .raw = 1, .items_cap = OBS_ITEMS_LDS_CAP, .wl_head = 0}},
+    {.id = 12, .bin = 1, .max_depth = 0, .agents = 0, .dims = {.Rcap = 232, .A = 80}, .shape = obs_shape_both(2),
+     .opt = {.nt = OBS_NT, .wl_bytes = 36 * 1024, .tab = 0, .nh = 0, .tmask = 1, .dual = 1, .items = 1, .snext = 1, .partial = 1, .bk_room = 0, .own_filter = 1, .fb = 1, .raw = 1, .items_cap = 4096, .wl_head = 0}},
+    {.id = 13, .bin = 1, .max_depth = 0, .agents = 0, .dims = {.Rcap = 680, .A = 80}, .shape = obs_shape_both(2),
+     .opt = {.nt = OBS_NT, .wl_bytes = 0, .tab = 0, .nh = 0, .tmask = 1, .dual = 1, .items = 0, .snext = 1, .partial = 1, .bk_room = 0, .own_filter = 1, .fb = 1, .raw = 1, .items_cap = OBS_ITEMS_LDS_CAP, .wl_head = 10 * 1024}},
+    // 14 (and 19, the builder alone): class 4's (9's) kind of env on larger maps, without the LDS successor table (Test_14; the larger levels of cfg5's
+    // row) -- not for a batch that affords the table itself (obs_class_holds)
+    {.id = 14, .bin = 1, .max_depth = 0, .agents = 0, .dims = {.Rcap = 3200, .A = 432}, .shape = obs_shape_both(0),
+     .opt = {.nt = OBS_NT, .wl_bytes = 0, .tab = 0, .nh = 0, .tmask = 1, .dual = 0, .items = 0, .snext = 0, .partial = 1, .bk_room = 1, .own_filter = 0, .fb = 0, .raw = 0, .items_cap = 0, .wl_head = 0}},
+    // 15 (and 18, the builder alone): rounds of 32 agents on maps beyond class 3's (Test_10: 1 265 / 1 319 rail cells), HBM work lists behind an LDS head;
+    // both builders without the LDS copy of the items (a hundred paths across a 100 x 80 map are more items than any copy that fits)
+    {.id = 15, .bin = 1, .max_depth = 0, .agents = 0, .dims = {.Rcap = 1344, .A = 100}, .shape = obs_shape_both(2),
+     .opt = {.nt = OBS_NT, .wl_bytes = 0, .tab = 0, .nh = 0, .tmask = 1, .dual = 1, .items = 0, .snext = 1, .partial = 1, .bk_room = 0, .own_filter = 0, .fb = 0, .raw = 0, .items_cap = 0, .wl_head = 8 * 1024}},
+    // 16 (and 20, the builder alone): maps TALLER than wide (dims.rkey: the reference's prediction key col * W + row collides there, tool.h:391-398 --
+    // compact keys in LDS, L_RKEY; never the one-pass kernels): Test_3 (35 x 30), Test_6 (60 x 40), Test_9 (120 x 80), two stages
+    {.id = 16, .bin = 1, .max_depth = 0, .agents = 0, .dims = {.Rcap = 1280, .A = 100, .rkey = 1}, .shape = obs_shape_both(0),
+     .opt = {.nt = OBS_NT, .wl_bytes = 24 * 1024, .tab = 0, .nh = 0, .tmask = 1, .dual = 1, .items = 1, .snext = 0, .partial = 0, .bk_room = 0, .own_filter = 0, .fb = 0, .raw = 0, .items_cap = 0, .wl_head = 0}},
+    {.id = 17, .bin = 1, .max_depth = 0, .agents = 0, .dims = {.Rcap = 232, .A = 80}, .shape = obs_shape_alone(2),
+     .opt = {.nt = OBS_NT, .wl_bytes = 36 * 1024, .tab = 0, .nh = 0, .tmask = 1, .dual = 0, .items = 1, .snext = 1, .partial = 1, .bk_room = 0, .own_filter = 1, .fb = 1, .raw = 1, .items_cap = OBS_ITEMS_LDS_CAP, .wl_head = 0}},
+    {.id = 18, .bin = 1, .max_depth = 0, .agents = 0, .dims = {.Rcap = 1344, .A = 100}, .shape = obs_shape_alone(2),
+     .opt = {.nt = OBS_NT, .wl_bytes = 0, .tab = 0, .nh = 0, .tmask = 1, .dual = 0, .items = 0, .snext = 1, .partial = 1, .bk_room = 0, .own_filter = 1, .fb = 1, .raw = 1, .items_cap = OBS_ITEMS_LDS_CAP, .wl_head = 4 * 1024}},
+    {.id = 19, .bin = 1, .max_depth = 0, .agents = 0, .dims = {.Rcap = 3200, .A = 432}, .shape = obs_shape_alone(0),
+     .opt = {.nt = OBS_NT, .wl_bytes = 0, .tab = 0, .nh = 0, .tmask = 1, .dual = 0, .items = 0, .snext = 0, .partial = 1, .bk_room = 1, .own_filter = 0, .fb = 0, .raw = 0, .items_cap = 0, .wl_head = 0}},
+    {.id = 20, .bin = 1, .max_depth = 0, .agents = 0, .dims = {.Rcap = 1280, .A = 100, .rkey = 1}, .shape = obs_shape_alone(0),
+     .opt = {.nt = OBS_NT, .wl_bytes = 24 * 1024, .tab = 0, .nh = 0, .tmask = 1, .dual = 0, .items = 1, .snext = 1, .partial = 1, .bk_room = 0, .own_filter = 0, .fb = 0, .raw = 0, .items_cap = 0, .wl_head = 0}},
+    // 21: class 7's envs (any number of agents up to 80) two workgroups a CU -- the builder alone leaves the LDS that the two-a-CU kernel of both
+    // builders lacked (round 4: cfg3 0.715 -> 0.81 ms): same box, runtime carving both sides, cfg3 at 1 024 envs 0.467 -> 0.419 ms
+    {.id = 21, .bin = 1, .max_depth = 0, .agents = 0, .dims = {.Rcap = 232, .A = 80}, .shape = obs_shape_alone(3),
+     .opt = {.nt = 512, .wl_bytes = 16 * 1024, .tab = 0, .nh = 0, .tmask = 1, .dual = 0, .items = 1, .snext = 1, .partial = 1, .bk_room = 0, .own_filter = 1, .fb = 1, .raw = 1, .items_cap = 4096, .wl_head = 0}},
 };
-template <> struct ObsFixed<3> {
-    static constexpr int max_nodes = 31, pred_depth = 500, max_depth = 2;   // the builders' parameters of the class (tree_pred: shape)
-    static constexpr int agents = 80;   // agents per env, exactly (0 = any number up to dims.A)
-    static constexpr ObsDims dims = {OBS_FIX3_RCAP, 80, 0, 0};
-    static constexpr ObsShape shape = {2, N_WORDS_C * OBS_CAP_C, N_WORDS_T * OBS_CAP_T_COMPACT, 4, 30};
-    static constexpr ObsOptions opt = {OBS_NT, 0, 0, 0, 1, 1, 0, 1, 1, 0, 1, 1, 1, OBS_ITEMS_LDS_CAP, OBS_FIX3_WL_HEAD};
-    static constexpr ObsLayout L = obs_layout_c(dims, shape, opt);
-};
-template <> struct ObsFixed<4> {
-    static constexpr int max_nodes = 31, pred_depth = 500, max_depth = 0;   // (a bin: the call's depth, 1 .. 3)
-    static constexpr int agents = 0;   // agents per env, exactly (0 = any number up to dims.A)
-    static constexpr ObsDims dims = {OBS_FIX4_RCAP, OBS_FIX4_A, 0, 0};
-    static constexpr ObsShape shape = {0, N_WORDS_C * OBS_CAP_C, N_WORDS_T * OBS_CAP_T_COMPACT, 4, 30};
-    static constexpr ObsOptions opt = {OBS_NT, 0, 0, 0, 1, 0, 0, 1, 1, 1, 0, 0, 0, 0};
-    static constexpr ObsLayout L = obs_layout_c(dims, shape, opt);
-};
-//   FIX 5: class 1's envs (at most 32 agents, 256 rail cells, depth 2) in rounds of 16 agents on 512 threads and at most 80 KB of LDS
-//   (MODE 5): TWO workgroups a CU.  For batches of several envs per CU -- there one env's barriers and round trips are filled by the
-//   other's issue (same-box sweep at the cfg2 shape, profiles/r05_cfg2_bsweep.json); a batch of at most one env per CU keeps class 1.
-template <> struct ObsFixed<5> {
-    static constexpr int max_nodes = 31, pred_depth = 500, max_depth = 2;
-    static constexpr int agents = 0;
-    static constexpr ObsDims dims = {256, 32, 0, 0};
-    static constexpr ObsShape shape = {3, N_WORDS_C * OBS_CAP_C, N_WORDS_T * OBS_CAP_T_COMPACT, 4, 30};
-    static constexpr ObsOptions opt = {512, 16 * 1024, 0, 0, 1, 1, 1, 1, 1, 0, 1, 0, 0, 2048};
-    static constexpr ObsLayout L = obs_layout_c(dims, shape, opt);
-};
-// ---- classes 6 .. 10: the flatland_cutils builder ALONE (fl_obs_cutils / fl_step_obs without a tree -- the launch the reference's
-// solution makes: solution/eval_env.py:15-17, demo.py:39 build TreeCutils(31, 500) only), the counterparts of classes 1 .. 5 on the same
-// machinery without the second index and the upstream tables (shape.tw_t = 0; MODE 6 / 7 / 8 = MODE 3 / 4 / 5 with UP = false, class 9: MODE 0)
-template <> struct ObsFixed<6> {   // at most 32 agents / 256 rail cells, one round (cfg1, cfg2)
-    static constexpr int max_nodes = 31, pred_depth = 500, max_depth = 0;
-    static constexpr int agents = 0;
-    static constexpr ObsDims dims = {256, 32, 0, 0};
-    static constexpr ObsShape shape = {1, N_WORDS_C * OBS_CAP_C, 0, 0, 0};
-    static constexpr ObsOptions opt = {OBS_NT, 24 * 1024, 0, 1, 1, 0, 1, 1, 1, 0, 1, 0, 1, OBS_ITEMS_LDS_CAP};
-    static constexpr ObsLayout L = obs_layout_c(dims, shape, opt);
-};
-template <> struct ObsFixed<7> {   // 80 agents, at most 232 rail cells, rounds of 32 agents, work lists in LDS (cfg3)
-    static constexpr int max_nodes = 31, pred_depth = 500, max_depth = 0;
-    static constexpr int agents = 80;
-    static constexpr ObsDims dims = {232, 80, 0, 0};
-    static constexpr ObsShape shape = {2, N_WORDS_C * OBS_CAP_C, 0, 0, 0};
-    static constexpr ObsOptions opt = OBS_FIX7_OPT;
-    static constexpr ObsLayout L = obs_layout_c(dims, shape, opt);
-};
-template <> struct ObsFixed<8> {   // 80 agents, at most 680 rail cells, rounds of 32 agents (cfg4: every level of the Round-2 row)
-    static constexpr int max_nodes = 31, pred_depth = 500, max_depth = 0;
-    static constexpr int agents = 0;
-    static constexpr ObsDims dims = {OBS_FIX3_RCAP, 80, 0, 0};
-    static constexpr ObsShape shape = {2, N_WORDS_C * OBS_CAP_C, 0, 0, 0};
-    static constexpr ObsOptions opt = OBS_FIX8_OPT;
-    static constexpr ObsLayout L = obs_layout_c(dims, shape, opt);
-};
-template <> struct ObsFixed<9> {   // at most 432 agents / 2816 rail cells: the stand-alone kernel (MODE 0, VAR 2) with its carving compiled in (cfg5)
-    static constexpr int max_nodes = 31, pred_depth = 500, max_depth = 0;
-    static constexpr int agents = 0;
-    static constexpr ObsDims dims = {OBS_FIX4_RCAP, OBS_FIX4_A, 0, 0};
-    static constexpr ObsShape shape = {0, N_WORDS_C * OBS_CAP_C, 0, 0, 0};
-    static constexpr ObsOptions opt = OBS_FIX9_OPT;
-    static constexpr ObsLayout L = obs_layout_c(dims, shape, opt);
-};
-template <> struct ObsFixed<10> {   // class 6's envs in rounds of 16 agents on 512 threads, two workgroups a CU (batches of several envs per CU)
-    static constexpr int max_nodes = 31, pred_depth = 500, max_depth = 0;
-    static constexpr int agents = 0;
-    static constexpr ObsDims dims = {256, 32, 0, 0};
-    static constexpr ObsShape shape = {3, N_WORDS_C * OBS_CAP_C, 0, 0, 0};
-    static constexpr ObsOptions opt = OBS_FIX10_OPT;
-    static constexpr ObsLayout L = obs_layout_c(dims, shape, opt);
-};
-// ---- bin classes (see above): twins of exact classes with the agents as an upper bound and the call's depth, and the larger large-map classes
-template <> struct ObsFixed<11> : ObsFixed<1> { static constexpr int max_depth = 0; };
-template <> struct ObsFixed<12> : ObsFixed<2> { static constexpr int max_depth = 0, agents = 0; };
-template <> struct ObsFixed<13> : ObsFixed<3> { static constexpr int max_depth = 0, agents = 0; };
-template <> struct ObsFixed<17> : ObsFixed<7> { static constexpr int agents = 0; };
-#define OBS_FIXB_RCAP 3200
-#define OBS_FIXB_A 432
-template <> struct ObsFixed<14> {   // both builders, two stages, no LDS successor table: at most 432 agents / 3 072 rail cells, any depth
-    static constexpr int max_nodes = 31, pred_depth = 500, max_depth = 0;
-    static constexpr int agents = 0;
-    static constexpr ObsDims dims = {OBS_FIXB_RCAP, OBS_FIXB_A, 0, 0};
-    static constexpr ObsShape shape = {0, N_WORDS_C * OBS_CAP_C, N_WORDS_T * OBS_CAP_T_COMPACT, 4, 30};
-    static constexpr ObsOptions opt = {OBS_NT, 0, 0, 0, 1, 0, 0, 0, 1, 1, 0, 0, 0, 0};
-    static constexpr ObsLayout L = obs_layout_c(dims, shape, opt);
-};
-// 21: class 7's envs (the builder alone, at most 80 agents / 232 rail cells) in rounds of 16 agents on 512 threads and at most 80 KB of LDS, TWO
-// workgroups a CU, for batches of several envs per CU (obs_batch_is_wide) -- the builder alone leaves the LDS that the two-a-CU kernel of both
-// builders lacked (round 4: cfg3 0.715 -> 0.81 ms): same box, runtime carving both sides, cfg3 at 1 024 envs 0.467 -> 0.419 ms
-template <> struct ObsFixed<21> {
-    static constexpr int max_nodes = 31, pred_depth = 500, max_depth = 0;
-    static constexpr int agents = 0;
-    static constexpr ObsDims dims = {232, 80, 0, 0};
-    static constexpr ObsShape shape = {3, N_WORDS_C * OBS_CAP_C, 0, 0, 0};
-    static constexpr ObsOptions opt = {512, 16 * 1024, 0, 0, 1, 0, 1, 1, 1, 0, 1, 1, 1, 4096, 0};
-    static constexpr ObsLayout L = obs_layout_c(dims, shape, opt);
-};
-// 15 / 18: rounds of 32 agents on maps beyond class 3's: at most 100 agents / 1 344 rail cells (Test_10: 1 265 / 1 319), HBM work lists with an
-// LDS head, no LDS copy of the items (a hundred paths across a 100 x 80 map are more items than any copy that fits)
-#define OBS_FIX15_RCAP 1344
-template <> struct ObsFixed<15> {
-    static constexpr int max_nodes = 31, pred_depth = 500, max_depth = 0;
-    static constexpr int agents = 0;
-    static constexpr ObsDims dims = {OBS_FIX15_RCAP, 100, 0, 0};
-    static constexpr ObsShape shape = {2, N_WORDS_C * OBS_CAP_C, N_WORDS_T * OBS_CAP_T_COMPACT, 4, 30};
-    static constexpr ObsOptions opt = {OBS_NT, 0, 0, 0, 1, 1, 0, 1, 1, 0, 0, 0, 0, 0, 8 * 1024};
-    static constexpr ObsLayout L = obs_layout_c(dims, shape, opt);
-};
-template <> struct ObsFixed<18> {
-    static constexpr int max_nodes = 31, pred_depth = 500, max_depth = 0;
-    static constexpr int agents = 0;
-    static constexpr ObsDims dims = {OBS_FIX15_RCAP, 100, 0, 0};
-    static constexpr ObsShape shape = {2, N_WORDS_C * OBS_CAP_C, 0, 0, 0};
-    static constexpr ObsOptions opt = {OBS_NT, 0, 0, 0, 1, 0, 0, 1, 1, 0, 1, 1, 1, OBS_ITEMS_LDS_CAP, 4 * 1024};
-    static constexpr ObsLayout L = obs_layout_c(dims, shape, opt);
-};
-// 16 / 20: maps TALLER than wide (the reference's prediction key col * W + row collides there, tool.h:391-398: compact keys in LDS, L_RKEY;
-// never the one-pass kernels) -- Test_3 (35 x 30), Test_6 (60 x 40), Test_9 (120 x 80): two stages, at most 100 agents / 1 280 rail cells
-template <> struct ObsFixed<16> {
-    static constexpr int max_nodes = 31, pred_depth = 500, max_depth = 0;
-    static constexpr int agents = 0;
-    static constexpr ObsDims dims = {1280, 100, 0, 1};
-    static constexpr ObsShape shape = {0, N_WORDS_C * OBS_CAP_C, N_WORDS_T * OBS_CAP_T_COMPACT, 4, 30};
-    static constexpr ObsOptions opt = {OBS_NT, 24 * 1024, 0, 0, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0, 0};
-    static constexpr ObsLayout L = obs_layout_c(dims, shape, opt);
-};
-template <> struct ObsFixed<20> {
-    static constexpr int max_nodes = 31, pred_depth = 500, max_depth = 0;
-    static constexpr int agents = 0;
-    static constexpr ObsDims dims = {1280, 100, 0, 1};
-    static constexpr ObsShape shape = {0, N_WORDS_C * OBS_CAP_C, 0, 0, 0};
-    static constexpr ObsOptions opt = {OBS_NT, 24 * 1024, 0, 0, 1, 0, 1, 1, 1, 0, 0, 0, 0, 0, 0};
-    static constexpr ObsLayout L = obs_layout_c(dims, shape, opt);
-};
-template <> struct ObsFixed<19> {   // the flatland_cutils builder alone, the same capacities
-    static constexpr int max_nodes = 31, pred_depth = 500, max_depth = 0;
-    static constexpr int agents = 0;
-    static constexpr ObsDims dims = {OBS_FIXB_RCAP, OBS_FIXB_A, 0, 0};
-    static constexpr ObsShape shape = {0, N_WORDS_C * OBS_CAP_C, 0, 0, 0};
-    static constexpr ObsOptions opt = {OBS_NT, 0, 0, 0, 1, 0, 0, 0, 1, 1, 0, 0, 0, 0, 0};
-    static constexpr ObsLayout L = obs_layout_c(dims, shape, opt);
-};
-// what obs_pick_config derives from a class's options for ObsArgs: ONE definition for the kernel (which has them as constants) and
-// for the host (obs_fits_fixed only takes the class when its own derivation for the batch gives the same values)
-template <int FIX> __host__ __device__ constexpr int obs_fixed_bk() { return ObsFixed<FIX>::shape.merged != 0 ? (ObsFixed<FIX>::opt.fb ? 2 : 0) : ObsFixed<FIX>::opt.bk_room; }
-template <int FIX> __host__ __device__ constexpr int obs_fixed_wl_occ_div() { return (ObsFixed<FIX>::shape.merged != 0 && ObsFixed<FIX>::dims.A > 32) ? 3 : OBS_WL_OCC_DIV; }
-template <int FIX> __host__ __device__ constexpr int obs_fixed_tshift(int A) { return (ObsFixed<FIX>::shape.merged != 0 && ObsFixed<FIX>::dims.A <= 32) ? (A <= 31 ? 2 : OBS_TSHIFT) : OBS_TSHIFT; }
-// kernel of a class: MODE 3 (one round) / 4 (rounds of 32 agents) / 2 (two stages), VAR 1 (static tables in LDS) / 2 (work lists in HBM scratch) / 0
-// (the flatland_cutils builder alone, shape.tw_t == 0: MODE 6 / 7 / 8 for the one-pass shapes, MODE 0 else)
-template <int FIX> __host__ __device__ constexpr int obs_fixed_mode() {
-    return (ObsFixed<FIX>::shape.merged == 1 ? 3 : ObsFixed<FIX>::shape.merged == 2 ? 4 : ObsFixed<FIX>::shape.merged == 3 ? 5 : ObsFixed<FIX>::shape.tw_t == 0 ? -3 : 2) + (ObsFixed<FIX>::shape.tw_t == 0 ? 3 : 0);
+#pragma clang diagnostic pop
+#define OBS_N_CLASSES ((int)(sizeof OBS_CLASSES / sizeof OBS_CLASSES[0]))
+// The orders in which the host tries the classes (0 ends a list; obs_take_fixed_class and obs_take_split_class of fl_obs.hip): the first that
+// holds the batch wins.  The flatland_cutils builder alone: exact, then bin.  Both builders: exact; then the split launch of an exact class
+// that at least half the envs fit (SPLIT_FIRST); then bin.  Then, for a batch that no class holds whole, the split launch of the first
+// class of OBS_ORDER_SPLIT_* that some env fits.
+inline constexpr int OBS_ORDER_ALONE_EXACT[] = {6, 7, 8, 9, 10, 21, 0}, OBS_ORDER_ALONE_BIN[] = {21, 17, 8, 18, 9, 19, 20, 0}, OBS_ORDER_SPLIT_ALONE[] = {9, 0};
+inline constexpr int OBS_ORDER_BOTH_EXACT[] = {1, 2, 3, 4, 5, 0}, OBS_ORDER_BOTH_SPLIT_FIRST[] = {2, 3, 0}, OBS_ORDER_BOTH_BIN[] = {11, 12, 13, 15, 4, 14, 16, 0},
+                     OBS_ORDER_SPLIT_BOTH[] = {2, 3, 4, 0};
+
+__host__ __device__ constexpr int obs_class_index(int id) {   // row of class `id`, -1: no such class
+    for (int i = 0; i < OBS_N_CLASSES; i++) if (OBS_CLASSES[i].id == id) return i;
+    return -1;
 }
-template <int FIX> __host__ __device__ constexpr int obs_fixed_var() { return ObsFixed<FIX>::opt.tab ? 1 : ObsFixed<FIX>::opt.wl_bytes == 0 ? 2 : 0; }
+// every class's carving, computed once (the host copies a row's; a kernel has its class's folded into its instructions)
+struct ObsClassLayouts { ObsLayout L[OBS_N_CLASSES]; };
+__host__ __device__ constexpr ObsClassLayouts obs_class_layouts() {
+    ObsClassLayouts t = {};
+    for (int i = 0; i < OBS_N_CLASSES; i++) t.L[i] = obs_layout_c(OBS_CLASSES[i].dims, OBS_CLASSES[i].shape, OBS_CLASSES[i].opt);
+    return t;
+}
+inline constexpr ObsClassLayouts OBS_CLASS_LAYOUTS = obs_class_layouts();
+// what obs_pick_config derives from a class's options for ObsArgs, and the class's kernel: ONE definition for the kernel (constants: obs_fixed_*
+// below) and for the host (by row: an exact class is only taken when the host's own derivation for the batch gives the same values).
+// MODE 3 (one round) / 4 (rounds of 32 agents) / 5 (of 16) / 2 (two stages), the flatland_cutils builder alone (shape.tw_t == 0) 6 / 7 / 8 / 0;
+// VAR 1 (static tables in LDS) / 2 (work lists in HBM scratch) / 0
+__host__ __device__ constexpr int obs_class_bk(const ObsClass &c) { return c.shape.merged != 0 ? (c.opt.fb ? 2 : 0) : c.opt.bk_room; }
+__host__ __device__ constexpr int obs_class_wl_occ_div(const ObsClass &c) { return (c.shape.merged != 0 && c.dims.A > 32) ? 3 : OBS_WL_OCC_DIV; }
+__host__ __device__ constexpr int obs_class_tshift(const ObsClass &c, int A) { return (c.shape.merged != 0 && c.dims.A <= 32) ? (A <= 31 ? 2 : OBS_TSHIFT) : OBS_TSHIFT; }
+__host__ __device__ constexpr int obs_class_mode(const ObsClass &c) {
+    return (c.shape.merged == 1 ? 3 : c.shape.merged == 2 ? 4 : c.shape.merged == 3 ? 5 : c.shape.tw_t == 0 ? -3 : 2) + (c.shape.tw_t == 0 ? 3 : 0);
+}
+__host__ __device__ constexpr int obs_class_var(const ObsClass &c) { return c.opt.tab ? 1 : c.opt.wl_bytes == 0 ? 2 : 0; }
+
+// a class as the kernels read it: ObsFixed<id>::L is the compile-time carving
+template <int FIX> struct ObsFixed {
+    static_assert(obs_class_index(FIX) >= 0, "no row of OBS_CLASSES has this id");
+    static constexpr ObsClass row = OBS_CLASSES[obs_class_index(FIX)];
+    static constexpr int max_nodes = row.max_nodes, pred_depth = row.pred_depth, max_depth = row.max_depth, agents = row.agents;
+    static constexpr ObsDims dims = row.dims;
+    static constexpr ObsShape shape = row.shape;
+    static constexpr ObsOptions opt = row.opt;
+    static constexpr ObsLayout L = OBS_CLASS_LAYOUTS.L[obs_class_index(FIX)];
+};
+// (each through a constant of its own: a kernel must not read the row from memory)
+template <int FIX> __host__ __device__ constexpr int obs_fixed_bk() { constexpr int v = obs_class_bk(ObsFixed<FIX>::row); return v; }
+template <int FIX> __host__ __device__ constexpr int obs_fixed_wl_occ_div() { constexpr int v = obs_class_wl_occ_div(ObsFixed<FIX>::row); return v; }
+template <int FIX> __host__ __device__ constexpr int obs_fixed_tshift(int A) {
+    constexpr int few = obs_class_tshift(ObsFixed<FIX>::row, 31), more = obs_class_tshift(ObsFixed<FIX>::row, 32);
+    return A <= 31 ? few : more;
+}
+template <int FIX> __host__ __device__ constexpr int obs_fixed_mode() { constexpr int v = obs_class_mode(ObsFixed<FIX>::row); return v; }
+template <int FIX> __host__ __device__ constexpr int obs_fixed_var() { constexpr int v = obs_class_var(ObsFixed<FIX>::row); return v; }
+// what obs_class_holds takes for granted: every id of an order is a row; a bin order holds bins (no exact agents or depth); an exact or split
+// class has keys = rail indices; a class with a split kernel keeps nothing sized by the batch behind its carving (the next-hop tables) and has
+// a row-mask kernel
+__host__ __device__ constexpr bool obs_order_ok(const int *k, bool bins, bool split) {
+    for (; *k; k++) {
+        if (obs_class_index(*k) < 0) return false;
+        const ObsClass &c = OBS_CLASSES[obs_class_index(*k)];
+        if (bins ? !c.bin || c.agents != 0 || c.max_depth != 0 : c.dims.rkey != 0 || c.agents > c.dims.A) return false;
+        if (split && (!c.split_rt || c.opt.nh || !c.keep_rows || (c.split2 != 0 && obs_class_index(c.split2) < 0))) return false;
+    }
+    return true;
+}
+static_assert(obs_order_ok(OBS_ORDER_ALONE_EXACT, false, false) && obs_order_ok(OBS_ORDER_BOTH_EXACT, false, false) && obs_order_ok(OBS_ORDER_ALONE_BIN, true, false) &&
+              obs_order_ok(OBS_ORDER_BOTH_BIN, true, false) && obs_order_ok(OBS_ORDER_BOTH_SPLIT_FIRST, false, true) && obs_order_ok(OBS_ORDER_SPLIT_ALONE, false, true) &&
+              obs_order_ok(OBS_ORDER_SPLIT_BOTH, false, true), "OBS_CLASSES / OBS_ORDER_*: see obs_order_ok");
 // The batch's own choice `a` (obs_pick_config's preference walk at the batch's sizes) is the class's kind of configuration: the same
 // structure, and of everything that is "whatever LDS the carving leaves" -- the next-hop tables, the agents' raw words, the
 // capacity of the items' copy, the head of HBM work lists -- at least what the class `b` has (a smaller batch inside the class's
@@ -429,8 +393,8 @@ struct ObsArgs {
     const int16_t *label;  // flatland_cutils get_many(handles) with a strict subset (MODE 0 only; null: every agent): label[i] = position of agent i in
                        // the list or -1.  Only the listed agents' predictions enter the index, under their list POSITION -- the conflict test
                        // then leaves out position `handle` and reads the state of agent `position` (treeobs.cpp:50-62, 393-465, tool.h:428-434)
-    int keep_mode;     // host side: FL_OBS_KEEP_TREE_ROWS is on for this handle (the kernels keep row masks; classes 1 and 5 -- the headline
-                       // kernels, which carry no code for it -- are not taken)
+    int keep_mode;     // host side: FL_OBS_KEEP_TREE_ROWS is on for this handle (the kernels keep row masks; the classes whose row says
+                       // keep_rows 0 are not taken)
     int keep_rows;     // upstream tree: the output buffer still holds the previous launch's rows (FL_OBS_KEEP_TREE_ROWS and the same buffer and
                        // depth as that launch): no -inf pre-fill of the slab, only the rows that were real nodes then and are not now
     int out64;         // launches of the flatland_cutils builder alone: adjacency / node_order / edge_order point to int64 buffers and are written as
