@@ -74,6 +74,14 @@ _ABI = {
 _DEBUG_ABI = {
     "fl_debug_last_obs_class": ([vp, vp], i32),
     "fl_debug_last_obs_launch": ([vp, vp, i32], i32),
+    # the host half of a handle alone (csrc/fl_static.h), no GPU needed: new(B, A, H, W), free, load (fl_load_env's arguments after the
+    # handle), reserve, commit, read(name, env or -1, out, capacity in bytes) -> bytes
+    "fl_debug_static_new": ([i32, i32, i32, i32], vp),
+    "fl_debug_static_free": ([vp], None),
+    "fl_debug_static_load": ([vp, i32] + [vp] * 7 + [i32, u64, i32, i32, vp, i32], i32),
+    "fl_debug_static_reserve": ([vp, i32, i32], i32),
+    "fl_debug_static_commit": ([vp], i32),
+    "fl_debug_static_read": ([vp, C.c_char_p, i32, vp, C.c_longlong], C.c_longlong),
 }
 # name -> (argtypes, restype) of every function include/flatland_policy.h declares, in the header's order
 _POLICY_ABI = {
