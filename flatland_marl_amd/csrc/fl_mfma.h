@@ -13,7 +13,7 @@ __device__ __forceinline__ fl_f32x16 fl_mfma(float a, float b, fl_f32x16 c) {
 // bf16 instruction of fl_bf16.h has the same accumulator)
 __device__ __forceinline__ int fl_acc_row(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }
 
-// 16 consecutive floats (16-byte aligned) -> a[0 .. 15]: a lane's operands of one chunk
+// 16 consecutive floats (16-byte aligned) -> a[0 .. 15]: a lane's operands of one chunk.  Every product of those kernels unpacks with it.
 __device__ __forceinline__ void fl_ld16(const float *src, float (&a)[16]) {
 #pragma unroll
     for (int q = 0; q < 4; q++) {

@@ -59,17 +59,25 @@ static float *fph_fill(FphArgs &a, int n_envs, int n_agents, const float *attr_d
     return f;
 }
 
+// workgroups of the row-tile kernels (tiles of 32 rows) and of the attention kernels (an env's tiles of 32 agents, every env)
+struct FphGrid { int tiles, qtiles; };
+static FphGrid fph_grid(int n_envs, int n_agents) {
+    return {(n_envs * n_agents + FPH_ROWS - 1) / FPH_ROWS, n_envs * ((n_agents + FPH_ROWS - 1) / FPH_ROWS)};
+}
+
+// more than 64 KiB of dynamic LDS needs the attribute
+template <class K>
+static int fph_allow_lds(const char *fn, K kernel, size_t bytes) {
+    if (hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess) return FL_OK;
+    fl_set_error("%s: hipFuncSetAttribute failed: %s", fn, hipGetErrorString(hipGetLastError()));
+    return FL_ERR_HIP;
+}
+
 // the forward's launches; block i's attention output goes to ao[i], its q k v are read from qkv[i]
 static int fph_launch(const char *fn, FphArgs a, float *const (&ao)[3], float *const (&qkv)[3], hipStream_t s) {
-    // more than 64 KiB of dynamic LDS needs the attribute
-    if (hipFuncSetAttribute((const void *)k_ph_embed, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FPH_LDS_EMBED) != hipSuccess ||
-        hipFuncSetAttribute((const void *)k_ph_block<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FPH_LDS_BLOCK) != hipSuccess ||
-        hipFuncSetAttribute((const void *)k_ph_block<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FPH_LDS_LAST) != hipSuccess) {
-        fl_set_error("%s: hipFuncSetAttribute failed: %s", fn, hipGetErrorString(hipGetLastError()));
-        return FL_ERR_HIP;
-    }
-    const int tiles = (a.R + FPH_ROWS - 1) / FPH_ROWS;
-    const int qtiles = a.B * ((a.A + FPH_ROWS - 1) / FPH_ROWS);
+    if (fph_allow_lds(fn, k_ph_embed, FPH_LDS_EMBED) != FL_OK || fph_allow_lds(fn, k_ph_block<false>, FPH_LDS_BLOCK) != FL_OK ||
+        fph_allow_lds(fn, k_ph_block<true>, FPH_LDS_LAST) != FL_OK) return FL_ERR_HIP;
+    const auto [tiles, qtiles] = fph_grid(a.B, a.A);
     a.qkv = qkv[0];
     hipLaunchKernelGGL(k_ph_embed, dim3(tiles), dim3(FPH_THREADS), FPH_LDS_EMBED, s, a);
     const float *xin[3] = {a.emb, a.xa, a.xb};
@@ -184,15 +192,9 @@ int fl_policy_head_backward(int n_envs, int n_agents, const float *attr_dev, con
     a.stats = (float *)workspace_dev;
 
     hipStream_t s = (hipStream_t)hip_stream;
-    if (hipFuncSetAttribute((const void *)k_pb_heads, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FPB_LDS_HEADS) != hipSuccess ||
-        hipFuncSetAttribute((const void *)k_pb_block, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FPB_LDS_BLOCK) != hipSuccess ||
-        hipFuncSetAttribute((const void *)k_pb_inproj, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FPB_LDS_INPROJ) != hipSuccess ||
-        hipFuncSetAttribute((const void *)k_pb_attr, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FPB_LDS_ATTR) != hipSuccess) {
-        fl_set_error("%s: hipFuncSetAttribute failed: %s", fn, hipGetErrorString(hipGetLastError()));
-        return FL_ERR_HIP;
-    }
-    const int tiles = (a.R + FPH_ROWS - 1) / FPH_ROWS;
-    const int qtiles = n_envs * ((n_agents + FPH_ROWS - 1) / FPH_ROWS);
+    if (fph_allow_lds(fn, k_pb_heads, FPB_LDS_HEADS) != FL_OK || fph_allow_lds(fn, k_pb_block, FPB_LDS_BLOCK) != FL_OK ||
+        fph_allow_lds(fn, k_pb_inproj, FPB_LDS_INPROJ) != FL_OK || fph_allow_lds(fn, k_pb_attr, FPB_LDS_ATTR) != FL_OK) return FL_ERR_HIP;
+    const auto [tiles, qtiles] = fph_grid(n_envs, n_agents);
     hipLaunchKernelGGL(k_pb_heads, dim3(tiles), dim3(FPH_THREADS), FPB_LDS_HEADS, s, a);
     for (int blk = 2; blk >= 0; blk--) {
         hipLaunchKernelGGL(k_pb_block, dim3(tiles), dim3(FPH_THREADS), FPB_LDS_BLOCK, s, a, blk);
@@ -260,8 +262,7 @@ int fl_policy_head_bf16(int n_envs, int n_agents, const float *attr_dev, const f
     a.packed = (const __bf16 *)packed_dev;
 
     hipStream_t s = (hipStream_t)hip_stream;
-    const int tiles = (a.R + FPH_ROWS - 1) / FPH_ROWS;
-    const int qtiles = a.B * ((a.A + FPH_ROWS - 1) / FPH_ROWS);
+    const auto [tiles, qtiles] = fph_grid(a.B, a.A);
     hipLaunchKernelGGL(k_ph16_embed, dim3(tiles), dim3(FPH_THREADS), 0, s, a);
     const float *xin[3] = {a.emb, a.xa, a.xb};
     float *xout[3] = {a.xa, a.xb, nullptr};

@@ -1,7 +1,8 @@
 // fl_policy_head_bf16.h -- the policy head of fl_policy_head.h with 16 of its 19 matrices on the bf16 matrix instruction
 // (v_mfma_f32_32x32x16_bf16, gfx950), for inference.  Included by fl_policy_head.hip behind fl_policy_head.h, whose first layer
-// (fph_mm_attr), float32 product (fph_mm), GELU (fph_gelu), action choice (fph_choose) and value kernel (k_ph_value) it calls.  The
-// entry points are those of include/flatland_policy_head_bf16.h.
+// (fph_load_attr, fph_mm_attr), float32 product (fph_mm), GELU (fph_gelu), a head's last layer (fph_head_out), the tail of the last
+// block (fph_put_logits, fph_put_val, fph_act with the action choice fph_choose) and value kernel (k_ph_value) it calls, on that header's FphLane / FphRows /
+// FphAttnTile coordinates.  The entry points are those of include/flatland_policy_head_bf16.h.
 //
 // Launches: k_ph16_embed, (k_ph16_attn, k_ph16_block) x 3, k_ph_value -- the structure of fl_policy_head.h, a workgroup of 4 waves
 // on a tile of 32 rows, a wave per head in the attention.
@@ -59,37 +60,46 @@ struct Fph16Args : FphArgs {
 };
 
 // this lane's A row of a tile: row `col`, column c0, its k half of a step
-__device__ __forceinline__ const __bf16 *fph16_arow(const unsigned char *tile, int stride, int c0, int col, int hh) {
-    return (const __bf16 *)(tile + col * stride) + c0 + 8 * hh;
+__device__ __forceinline__ const __bf16 *fph16_arow(const unsigned char *tile, int stride, int c0, const FphLane L) {
+    return (const __bf16 *)(tile + L.col * stride) + c0 + 8 * L.hh;
 }
 
 // a layer of 256 outputs: the wave's two blocks 2 wave, 2 wave + 1 of a packed matrix of K columns over a tile's columns c0 .. c0 + K
 __device__ __forceinline__ void fph16_layer256(const unsigned char *tile, int stride, int c0, int K, const __bf16 *w, fl_f32x16 (&acc)[2],
-                                               int wave, int lane) {
-    const __bf16 *const ws[2] = {fl_bf16_block(w, K, 2 * wave, lane), fl_bf16_block(w, K, 2 * wave + 1, lane)};
-    fl_bf16_mm<2>(fph16_arow(tile, stride, c0, lane & 31, lane >> 5), K / 16, ws, acc);
+                                               const FphLane L) {
+    const __bf16 *const ws[2] = {fl_bf16_block(w, K, 2 * L.wave, L.lane), fl_bf16_block(w, K, 2 * L.wave + 1, L.lane)};
+    fl_bf16_mm<2>(fph16_arow(tile, stride, c0, L), K / 16, ws, acc);
 }
 
-// (acc + bias) [GELU] of one 32 x 32 block: rounded to bf16 -> tile columns c0 + col; the float32 value -> g[row][col] of the
-// rows below `rows` where g is given (g = the block's first column of row 0, ld floats a row)
+// (acc + bias) [GELU] of the 32 x 32 block of features j0 .. j0 + 31 of a layer: rounded to bf16 -> tile columns c0 + j0 ..; the
+// float32 value -> g[row][j0 ..] of the rows below `rows` where g is given (g = the layer's first feature of row 0, ld floats a row)
 template <bool GELU>
-__device__ __forceinline__ void fph16_to_lds(const fl_f32x16 &acc, float bias, unsigned char *tile, int stride, int c0, int col, int hh,
-                                             float *g = nullptr, int ld = 0, int rows = 0) {
+__device__ __forceinline__ void fph16_to_lds(const fl_f32x16 &acc, const float *bias, int j0, unsigned char *tile, int stride, int c0,
+                                             const FphLane L, float *g = nullptr, int ld = 0, int rows = 0) {
+    const float b = bias[j0 + L.col];
 #pragma unroll
     for (int r = 0; r < 16; r++) {
-        const int row = fl_acc_row(r, hh);
-        float v = acc[r] + bias;
+        const int row = fl_acc_row(r, L.hh);
+        float v = acc[r] + b;
         if (GELU) v = fph_gelu(v);
-        *((__bf16 *)(tile + row * stride) + c0 + col) = (__bf16)v;
-        if (g && row < rows) g[(size_t)row * ld + col] = v;
+        *((__bf16 *)(tile + row * stride) + c0 + j0 + L.col) = (__bf16)v;
+        if (g && row < rows) g[(size_t)row * ld + j0 + L.col] = v;
     }
+}
+
+// a 256-wide layer: the wave's two blocks, features 64 wave .. 64 wave + 63
+template <bool GELU>
+__device__ __forceinline__ void fph16_to_lds(const fl_f32x16 (&acc)[2], const float *bias, unsigned char *tile, int stride, int c0,
+                                             const FphLane L, float *g = nullptr, int ld = 0, int rows = 0) {
+    fph16_to_lds<GELU>(acc[0], bias, 64 * L.wave, tile, stride, c0, L, g, ld, rows);
+    fph16_to_lds<GELU>(acc[1], bias, 64 * L.wave + 32, tile, stride, c0, L, g, ld, rows);
 }
 
 // rows [0, rows) x n8 groups of 8 floats of global rows of ld floats -> bf16 columns c0 .. of a tile (rows past `rows`: zero); the
 // float32 values are copied to copy[row][8 q ..] (ldc floats a row) where copy is given
-__device__ __forceinline__ void fph16_load_tile(unsigned char *tile, int stride, int c0, const float *src, int ld, int n8, int rows, int tid,
+__device__ __forceinline__ void fph16_load_tile(unsigned char *tile, int stride, int c0, const float *src, int ld, int n8, int rows, const FphLane L,
                                                 float *copy = nullptr, int ldc = 0) {
-    for (int i = tid; i < FPH_ROWS * n8; i += FPH_THREADS) {
+    for (int i = L.tid; i < FPH_ROWS * n8; i += FPH_THREADS) {
         const int r = i / n8, q = i % n8;
         fl_bf16x8 o = {};
         if (r < rows) {
@@ -106,19 +116,19 @@ __device__ __forceinline__ void fph16_load_tile(unsigned char *tile, int stride,
 
 // q, k, v of the next block from a tile's columns c0 .. c0 + 255: bf16((X in_proj^T) + bias) -> out[rows][768] (6 blocks a wave, in pairs)
 __device__ __forceinline__ void fph16_qkv(const unsigned char *tile, int stride, int c0, const __bf16 *w, const float *bias, __bf16 *out,
-                                          int rows, int wave, int lane) {
-    const int col = lane & 31, hh = lane >> 5;
-    const __bf16 *arow = fph16_arow(tile, stride, c0, col, hh);
+                                          int rows, const FphLane L) {
+    const int col = L.col;
+    const __bf16 *arow = fph16_arow(tile, stride, c0, L);
 #pragma unroll 1
     for (int pr = 0; pr < 3; pr++) {
-        const int b0 = 6 * wave + 2 * pr, j0 = 32 * b0, j1 = j0 + 32;
-        const __bf16 *const ws[2] = {fl_bf16_block(w, FPH_E, b0, lane), fl_bf16_block(w, FPH_E, b0 + 1, lane)};
+        const int b0 = 6 * L.wave + 2 * pr, j0 = 32 * b0, j1 = j0 + 32;
+        const __bf16 *const ws[2] = {fl_bf16_block(w, FPH_E, b0, L.lane), fl_bf16_block(w, FPH_E, b0 + 1, L.lane)};
         fl_f32x16 acc[2] = {};
         fl_bf16_mm<2>(arow, FPH_E / 16, ws, acc);
         const float bb0 = bias[j0 + col], bb1 = bias[j1 + col];
 #pragma unroll
         for (int r = 0; r < 16; r++) {
-            const int row = fl_acc_row(r, hh);
+            const int row = fl_acc_row(r, L.hh);
             if (row < rows) {
                 out[(size_t)row * (3 * FPH_E) + j0 + col] = (__bf16)(acc[0][r] + bb0);
                 out[(size_t)row * (3 * FPH_E) + j1 + col] = (__bf16)(acc[1][r] + bb1);
@@ -131,50 +141,44 @@ __device__ __forceinline__ void fph16_qkv(const unsigned char *tile, int stride,
 __global__ void __launch_bounds__(FPH_THREADS) k_ph16_embed(Fph16Args p) {
     __shared__ __attribute__((aligned(16))) float s_attr[FPH_ROWS * FPH16_ASTRIDE];
     __shared__ __attribute__((aligned(16))) unsigned char s_t[2][FPH_ROWS * FPH16_STRIDE];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, hh = lane >> 5;
-    const int row0 = blockIdx.x * FPH_ROWS, rows = min(FPH_ROWS, p.R - row0);
+    const FphLane L{};
+    const FphRows T{p.R};
 
-    for (int i = tid; i < FPH_ROWS * FPH_ATTR_PAD; i += FPH_THREADS) {
-        const int r = i / FPH_ATTR_PAD, c = i % FPH_ATTR_PAD;
-        s_attr[r * FPH16_ASTRIDE + c] = (r < rows && c < FPH_ATTR) ? p.attr[(size_t)(row0 + r) * FPH_ATTR + c] : 0.f;
-    }
+    fph_load_attr(s_attr, FPH16_ASTRIDE, p.attr, T, L);
     __syncthreads();
     const float *const *w = p.p + FPH_P_ATTR;
     {                                                            // 83 -> 256, exact float32: -> tile 0
         fl_f32x16 acc[2] = {};
-        fph_mm_attr(s_attr + col * FPH16_ASTRIDE, w[0] + (size_t)(64 * wave + col) * FPH_ATTR, w[0] + (size_t)(64 * wave + 32 + col) * FPH_ATTR,
-                    acc[0], acc[1], hh);
-        fph16_to_lds<true>(acc[0], w[1][64 * wave + col], s_t[0], FPH16_STRIDE, 64 * wave, col, hh);
-        fph16_to_lds<true>(acc[1], w[1][64 * wave + 32 + col], s_t[0], FPH16_STRIDE, 64 * wave + 32, col, hh);
+        fph_mm_attr(s_attr + L.col * FPH16_ASTRIDE, w[0] + (size_t)(64 * L.wave + L.col) * FPH_ATTR, w[0] + (size_t)(64 * L.wave + 32 + L.col) * FPH_ATTR, acc, L);
+        fph16_to_lds<true>(acc, w[1], s_t[0], FPH16_STRIDE, 0, L);
     }
     __syncthreads();
     for (int l = 1; l <= 2; l++) {                               // 256 -> 256 twice: tile 0 -> 1 -> 0
         fl_f32x16 acc[2] = {};
-        fph16_layer256(s_t[l - 1], FPH16_STRIDE, 0, FPH_E, p.packed + (l == 1 ? FPH16_ATTR2 : FPH16_ATTR4), acc, wave, lane);
-        fph16_to_lds<true>(acc[0], w[2 * l + 1][64 * wave + col], s_t[l & 1], FPH16_STRIDE, 64 * wave, col, hh);
-        fph16_to_lds<true>(acc[1], w[2 * l + 1][64 * wave + 32 + col], s_t[l & 1], FPH16_STRIDE, 64 * wave + 32, col, hh);
+        fph16_layer256(s_t[l - 1], FPH16_STRIDE, 0, FPH_E, p.packed + (l == 1 ? FPH16_ATTR2 : FPH16_ATTR4), acc, L);
+        fph16_to_lds<true>(acc, w[2 * l + 1], s_t[l & 1], FPH16_STRIDE, 0, L);
         __syncthreads();
     }
-    float *emb = p.emb + (size_t)row0 * FPH_E;
+    float *emb = p.emb + (size_t)T.row0 * FPH_E;
     {                                                            // 256 -> 128: tile 0 -> tile 1[:, :128] and emb; the tree embedding beside it
         fl_f32x16 acc = {};
-        fl_bf16_mm(fph16_arow(s_t[0], FPH16_STRIDE, 0, col, hh), FPH_E / 16, fl_bf16_block(p.packed + FPH16_ATTR6, FPH_E, wave, lane), acc);
-        fph16_to_lds<true>(acc, w[7][32 * wave + col], s_t[1], FPH16_STRIDE, 32 * wave, col, hh, emb + 32 * wave, FPH_E, rows);
-        fph16_load_tile(s_t[1], FPH16_STRIDE, FPH_H, p.tree + (size_t)row0 * FPH_H, FPH_H, FPH_H / 8, rows, tid, emb + FPH_H, FPH_E);
+        fl_bf16_mm(fph16_arow(s_t[0], FPH16_STRIDE, 0, L), FPH_E / 16, fl_bf16_block(p.packed + FPH16_ATTR6, FPH_E, L.wave, L.lane), acc);
+        fph16_to_lds<true>(acc, w[7], 32 * L.wave, s_t[1], FPH16_STRIDE, 0, L, emb, FPH_E, T.rows);
+        fph16_load_tile(s_t[1], FPH16_STRIDE, FPH_H, p.tree + (size_t)T.row0 * FPH_H, FPH_H, FPH_H / 8, T.rows, L, emb + FPH_H, FPH_E);
     }
     __syncthreads();
-    fph16_qkv(s_t[1], FPH16_STRIDE, 0, p.packed + FPH16_BLOCK, p.p[FPH_P_BLOCK + 1], p.qkv16 + (size_t)row0 * (3 * FPH_E), rows, wave, lane);
+    fph16_qkv(s_t[1], FPH16_STRIDE, 0, p.packed + FPH16_BLOCK, p.p[FPH_P_BLOCK + 1], p.qkv16 + (size_t)T.row0 * (3 * FPH_E), T.rows, L);
 }
 
 // ---- attention of one block: workgroup = (env, tile of 32 queries), wave = head; see the head of this file.  Two passes over the
 // keys in chunks of 32: the maxima, then e, its sums and e v.  Keys past the env's last agent take no part: their e and their v are 0.
 __global__ void __launch_bounds__(FPH_THREADS) k_ph16_attn(Fph16Args p) {
     __shared__ __attribute__((aligned(16))) unsigned char s_vt[FPH_HEADS][FPH_D * FPH16_VSTRIDE];
-    const int tid = threadIdx.x, lane = tid & 63, head = tid >> 6, col = lane & 31, hh = lane >> 5;
-    const int A = p.A, tiles = (A + FPH_ROWS - 1) / FPH_ROWS;
-    const int env = blockIdx.x / tiles, q0 = (blockIdx.x % tiles) * FPH_ROWS;
-    const size_t base = (size_t)env * A;
-    const __bf16 *qkv = p.qkv16 + base * (3 * FPH_E);
+    const FphLane L{};
+    const int A = p.A, lane = L.lane, head = L.wave, col = L.col, hh = L.hh;
+    const FphAttnTile T{A};
+    const int q0 = T.first;
+    const __bf16 *qkv = p.qkv16 + T.base * (3 * FPH_E);
     unsigned char *vt = s_vt[head];
 
     fl_bf16x8 qb[4];                                             // the B operand: q of query q0 + col (the last one repeated past the env)
@@ -241,7 +245,7 @@ __global__ void __launch_bounds__(FPH_THREADS) k_ph16_attn(Fph16Args p) {
         if (pass == 0) mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
         else sum = sum + __shfl_xor(sum, 32, 64);
     }
-    float *out = p.ao + base * FPH_E + head * FPH_D;
+    float *out = p.ao + T.base * FPH_E + head * FPH_D;
 #pragma unroll
     for (int r = 0; r < 16; r++) {
         const int row = fl_acc_row(r, hh), qi = q0 + row;
@@ -257,35 +261,26 @@ __global__ void __launch_bounds__(FPH_THREADS) k_ph16_attn(Fph16Args p) {
 // the result of rows x n_out in wave 0's registers, bias added.  h: 32 rows of 528 bytes, bf16 [256] then float32 [128].  Every
 // wave calls it (barriers inside).
 __device__ __forceinline__ void fph16_head(const unsigned char *tile, unsigned char *h, const __bf16 *w0, const __bf16 *w2, const float *const *p,
-                                           int n_out, fl_f32x16 &out, int wave, int lane) {
-    const int col = lane & 31, hh = lane >> 5;
+                                           int n_out, fl_f32x16 &out, const FphLane L) {
+    const int wave = L.wave, col = L.col;
     {
         fl_f32x16 acc[2] = {};
-        fph16_layer256(tile, FPH16_STRIDE2, 0, 2 * FPH_E, w0, acc, wave, lane);
+        fph16_layer256(tile, FPH16_STRIDE2, 0, 2 * FPH_E, w0, acc, L);
         __syncthreads();                                         // (h may still be read by the head before this one)
-        fph16_to_lds<true>(acc[0], p[1][64 * wave + col], h, FPH16_STRIDE, 64 * wave, col, hh);
-        fph16_to_lds<true>(acc[1], p[1][64 * wave + 32 + col], h, FPH16_STRIDE, 64 * wave + 32, col, hh);
+        fph16_to_lds<true>(acc, p[1], h, FPH16_STRIDE, 0, L);
     }
     __syncthreads();
     float *hf = (float *)h;
     {
         fl_f32x16 acc = {};
-        fl_bf16_mm(fph16_arow(h, FPH16_STRIDE, 0, col, hh), FPH_E / 16, fl_bf16_block(w2, FPH_E, wave, lane), acc);
+        fl_bf16_mm(fph16_arow(h, FPH16_STRIDE, 0, L), FPH_E / 16, fl_bf16_block(w2, FPH_E, wave, L.lane), acc);
         __syncthreads();
         const float b = p[3][32 * wave + col];
 #pragma unroll
-        for (int r = 0; r < 16; r++) hf[fl_acc_row(r, hh) * FPH16_HSTRIDE + 32 * wave + col] = fph_gelu(acc[r] + b);
+        for (int r = 0; r < 16; r++) hf[fl_acc_row(r, L.hh) * FPH16_HSTRIDE + 32 * wave + col] = fph_gelu(acc[r] + b);
     }
     __syncthreads();
-    if (wave == 0) {
-        const int j = min(col, n_out - 1);                       // (columns past n_out repeat the last feature and are dropped)
-        const float *const ws[1] = {p[4] + (size_t)j * FPH_H};
-        fl_f32x16 acc[1] = {};
-        fph_mm<1>(hf + col * FPH16_HSTRIDE, FPH_H, ws, acc, hh);
-        const float b = p[5][j];
-#pragma unroll
-        for (int r = 0; r < 16; r++) out[r] = acc[0][r] + b;
-    }
+    fph_head_out(hf, FPH16_HSTRIDE, p[4], p[5], n_out, out, L);
 }
 
 // ---- the rest of a block per row tile; LAST: the heads and the action instead of the next block's q k v.  The tile is [x | a]:
@@ -295,58 +290,40 @@ __global__ void __launch_bounds__(FPH_THREADS) k_ph16_block(Fph16Args p, int blk
     __shared__ __attribute__((aligned(16))) unsigned char s_t[FPH_ROWS * FPH16_STRIDE2];
     __shared__ __attribute__((aligned(16))) unsigned char s_h[LAST ? FPH_ROWS * FPH16_STRIDE : 16];
     __shared__ float s_lg[FPH_ROWS][FPH_ACT + 1];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, hh = lane >> 5;
-    const int row0 = blockIdx.x * FPH_ROWS, rows = min(FPH_ROWS, p.R - row0);
+    const FphLane L{};
+    const FphRows T{p.R};
     const float *const *w = p.p + FPH_P_BLOCK + 6 * blk;
     const __bf16 *pk = p.packed + FPH16_BLOCK + (size_t)blk * FPH16_BLOCK_SIZE;
+    const size_t t0 = (size_t)T.row0 * FPH_E;
 
-    fph16_load_tile(s_t, FPH16_STRIDE2, 0, xin + (size_t)row0 * FPH_E, FPH_E, FPH_E / 8, rows, tid);
-    fph16_load_tile(s_t, FPH16_STRIDE2, FPH_E, p.ao + (size_t)row0 * FPH_E, FPH_E, FPH_E / 8, rows, tid);
+    fph16_load_tile(s_t, FPH16_STRIDE2, 0, xin + t0, FPH_E, FPH_E / 8, T.rows, L);
+    fph16_load_tile(s_t, FPH16_STRIDE2, FPH_E, p.ao + t0, FPH_E, FPH_E / 8, T.rows, L);
     __syncthreads();
     {                                                            // out_proj, over the attention output
         fl_f32x16 acc[2] = {};
-        fph16_layer256(s_t, FPH16_STRIDE2, FPH_E, FPH_E, pk + FPH16_OUT_PROJ, acc, wave, lane);
+        fph16_layer256(s_t, FPH16_STRIDE2, FPH_E, FPH_E, pk + FPH16_OUT_PROJ, acc, L);
         __syncthreads();
-        fph16_to_lds<false>(acc[0], w[3][64 * wave + col], s_t, FPH16_STRIDE2, FPH_E + 64 * wave, col, hh);
-        fph16_to_lds<false>(acc[1], w[3][64 * wave + 32 + col], s_t, FPH16_STRIDE2, FPH_E + 64 * wave + 32, col, hh);
+        fph16_to_lds<false>(acc, w[3], s_t, FPH16_STRIDE2, FPH_E, L);
     }
     __syncthreads();
     {                                                            // att_mlp on [input | attention], over the attention's half
         fl_f32x16 acc[2] = {};
-        fph16_layer256(s_t, FPH16_STRIDE2, 0, 2 * FPH_E, pk + FPH16_ATT_MLP, acc, wave, lane);
+        fph16_layer256(s_t, FPH16_STRIDE2, 0, 2 * FPH_E, pk + FPH16_ATT_MLP, acc, L);
         __syncthreads();
-        float *g = LAST ? nullptr : xout + (size_t)row0 * FPH_E + 64 * wave;
-        fph16_to_lds<true>(acc[0], w[5][64 * wave + col], s_t, FPH16_STRIDE2, FPH_E + 64 * wave, col, hh, g, FPH_E, rows);
-        fph16_to_lds<true>(acc[1], w[5][64 * wave + 32 + col], s_t, FPH16_STRIDE2, FPH_E + 64 * wave + 32, col, hh, LAST ? nullptr : g + 32,
-                           FPH_E, rows);
-        if (LAST) fph16_load_tile(s_t, FPH16_STRIDE2, 0, p.emb + (size_t)row0 * FPH_E, FPH_E, FPH_E / 8, rows, tid);
+        fph16_to_lds<true>(acc, w[5], s_t, FPH16_STRIDE2, FPH_E, L, LAST ? nullptr : xout + t0, FPH_E, T.rows);
+        if (LAST) fph16_load_tile(s_t, FPH16_STRIDE2, 0, p.emb + t0, FPH_E, FPH_E / 8, T.rows, L);
     }
     __syncthreads();
     if (!LAST) {
-        fph16_qkv(s_t, FPH16_STRIDE2, FPH_E, pk + FPH16_BLOCK_SIZE, w[7], p.qkv16 + (size_t)row0 * (3 * FPH_E), rows, wave, lane);
+        fph16_qkv(s_t, FPH16_STRIDE2, FPH_E, pk + FPH16_BLOCK_SIZE, w[7], p.qkv16 + (size_t)T.row0 * (3 * FPH_E), T.rows, L);
         return;
     }
     fl_f32x16 out = {};
-    fph16_head(s_t, s_h, p.packed + FPH16_ACTOR0, p.packed + FPH16_ACTOR2, p.p + FPH_P_ACTOR, FPH_ACT, out, wave, lane);
-    if (wave == 0 && col < FPH_ACT) {
-#pragma unroll
-        for (int r = 0; r < 16; r++) {
-            const int row = fl_acc_row(r, hh);
-            s_lg[row][col] = out[r];
-            if (row < rows) p.logits[(size_t)(row0 + row) * FPH_ACT + col] = out[r];
-        }
-    }
+    fph16_head(s_t, s_h, p.packed + FPH16_ACTOR0, p.packed + FPH16_ACTOR2, p.p + FPH_P_ACTOR, FPH_ACT, out, L);
+    fph_put_logits(out, s_lg, p.logits, T, L);
     if (p.value) {
-        fph16_head(s_t, s_h, p.packed + FPH16_CRITIC0, p.packed + FPH16_CRITIC2, p.p + FPH_P_CRITIC, 1, out, wave, lane);
-        if (wave == 0 && col == 0) {
-#pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const int row = fl_acc_row(r, hh);
-                if (row < rows) p.val[row0 + row] = out[r];
-            }
-        }
+        fph16_head(s_t, s_h, p.packed + FPH16_CRITIC0, p.packed + FPH16_CRITIC2, p.p + FPH_P_CRITIC, 1, out, L);
+        fph_put_val(out, p.val, T, L);
     }
-    __syncthreads();
-    if (p.select && tid < rows)
-        p.actions[row0 + tid] = (unsigned char)fph_choose(s_lg[tid], p.valid + (size_t)(row0 + tid) * FPH_ACT, p.select, p.u);
+    fph_act(s_lg, p, T, L);
 }

@@ -67,13 +67,8 @@ __device__ __forceinline__ void ftl_gemm1(const float *arow, const float *w0, fl
 #pragma unroll 2
     for (int kc = 0; kc < K; kc += 32) {
         float a[16], b[16];
-        const float4 *ap = (const float4 *)(arow + kc + 16 * hh), *bp = (const float4 *)(w0 + kc + 16 * hh);
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            float4 av = ap[q], bv = bp[q];
-            a[4 * q] = av.x; a[4 * q + 1] = av.y; a[4 * q + 2] = av.z; a[4 * q + 3] = av.w;
-            b[4 * q] = bv.x; b[4 * q + 1] = bv.y; b[4 * q + 2] = bv.z; b[4 * q + 3] = bv.w;
-        }
+        fl_ld16(arow + kc + 16 * hh, a);
+        fl_ld16(w0 + kc + 16 * hh, b);
 #pragma unroll
         for (int s = 0; s < 16; s++) acc = fl_mfma(a[s], b[s], acc);
     }
@@ -87,15 +82,10 @@ __device__ __forceinline__ void ftl_gemm3(const float *arow, const float *w0, co
     for (int kc = 0; kc < K; kc += 32) {
         float a[16], b0[16], b1[16], b2[16];
         const int o = kc + 16 * hh;
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            float4 av = ((const float4 *)(arow + o))[q];
-            float4 v0 = ((const float4 *)(w0 + o))[q], v1 = ((const float4 *)(w1 + o))[q], v2 = ((const float4 *)(w2 + o))[q];
-            a[4 * q] = av.x; a[4 * q + 1] = av.y; a[4 * q + 2] = av.z; a[4 * q + 3] = av.w;
-            b0[4 * q] = v0.x; b0[4 * q + 1] = v0.y; b0[4 * q + 2] = v0.z; b0[4 * q + 3] = v0.w;
-            b1[4 * q] = v1.x; b1[4 * q + 1] = v1.y; b1[4 * q + 2] = v1.z; b1[4 * q + 3] = v1.w;
-            b2[4 * q] = v2.x; b2[4 * q + 1] = v2.y; b2[4 * q + 2] = v2.z; b2[4 * q + 3] = v2.w;
-        }
+        fl_ld16(arow + o, a);
+        fl_ld16(w0 + o, b0);
+        fl_ld16(w1 + o, b1);
+        fl_ld16(w2 + o, b2);
 #pragma unroll
         for (int s = 0; s < 16; s++) {
             c0 = fl_mfma(a[s], b0[s], c0);

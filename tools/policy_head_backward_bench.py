@@ -13,10 +13,15 @@ allocator, warm after the warmup.
   module_fwd         Network.head with grad mode on                   module_bwd       backward() behind it
   module_fwd_bwd     both                                             torch_fwd / torch_bwd / torch_fwd_bwd   head_torch likewise
 
+--parent-lib PARENT.so: fl_policy_head_forward_saved and fl_policy_head_backward of that library (the parent commit's build) and of
+this build on the same buffers, --rounds times interleaved: every round's medians, the spread (max - min) of the parent's, and
+whether this build's median is behind the parent's by no more than that spread.
+
 --inference-libs A.so B.so ...: the inference forward (fl_policy_head through the C entry point, select = soft) of each library
 in turn, --rounds times interleaved: the medians of every round per library, for an A/B of two builds on the same box.
 
 Usage:  python tools/policy_head_backward_bench.py [--launches 20] [--warmup 5] [--inference-libs parent.so new.so]
+                                                   [--parent-lib parent.so] [--rounds 5]
                                                    [--out profiles/policy_head_backward_bench.json]
 """
 import argparse
@@ -79,6 +84,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--inference-libs", nargs="*", default=[])
+    ap.add_argument("--parent-lib", default=None, help="libflatland_hip.so of the parent commit, for the A/B of the training entry points")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
@@ -94,6 +100,12 @@ def main():
     vp = hb.vp
     fwd_saved, bwd = hb._sym("fl_policy_head_forward_saved"), hb._sym("fl_policy_head_backward")
     rows_out, ab = [], {}
+    train = {"this": (fwd_saved, bwd)}
+    if args.parent_lib:
+        P = C.CDLL(os.path.abspath(args.parent_lib))
+        for name, (argtypes, restype) in hb._POLICY_TRAIN_ABI.items():
+            getattr(P, name).argtypes, getattr(P, name).restype = argtypes, restype
+        train["parent"] = (P.fl_policy_head_forward_saved, P.fl_policy_head_backward)
     libs = [(p, C.CDLL(os.path.abspath(p))) for p in args.inference_libs]
     for label, B, A in SHAPES:
         attr, tree, valid = (torch.from_numpy(x).to(dev) for x in synth_inputs(B, A, 11))
@@ -115,12 +127,12 @@ def main():
         s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         inf = [inference_call(hb.lib(), vp, c["attr"], c["tree"], plist, None, 0) for c in parts]
 
-        def saved_forward():
+        def saved_forward(fwd_saved=fwd_saved):
             for c in parts:
                 hb._chk(fwd_saved(c["nb"], A, c["attr"].data_ptr(), c["tree"].data_ptr(), ptrs, c["logits"].data_ptr(), c["value"].data_ptr(),
                                   c["saved"].data_ptr(), c["saved"].numel() * 4, s))
 
-        def backward_kernels():
+        def backward_kernels(bwd=bwd):
             for c in parts:
                 hb._chk(bwd(c["nb"], A, c["attr"].data_ptr(), c["tree"].data_ptr(), ptrs, c["saved"].data_ptr(), c["gl"].data_ptr(),
                             c["gv"].data_ptr(), c["gtree"].data_ptr(), c["rows"].data_ptr(), c["rows"].numel() * 4, c["ws"].data_ptr(),
@@ -134,6 +146,18 @@ def main():
         r["saved_fwd_ms"] = median_events(saved_forward, args.warmup, args.launches)
         r["backward_kernels_ms"] = median_events(backward_kernels, args.warmup, args.launches)
         r["products_ms"] = median_events(products, args.warmup, args.launches)
+        if args.parent_lib:                                      # the training entry points of both builds, interleaved
+            us = {"%s_%s" % (who, what): [] for who in ("parent", "this") for what in ("saved_fwd", "backward")}
+            for _ in range(args.rounds):
+                for who in ("parent", "this"):
+                    us[who + "_saved_fwd"].append(round(median_events(lambda: saved_forward(train[who][0]), args.warmup, args.launches) * 1e3, 2))
+                    us[who + "_backward"].append(round(median_events(lambda: backward_kernels(train[who][1]), args.warmup, args.launches) * 1e3, 2))
+            mid = {k: sorted(v)[len(v) // 2] for k, v in us.items()}
+            r["parent_ab"] = dict(us_rounds=us, us_median=mid)
+            for what in ("saved_fwd", "backward"):
+                spread = round(max(us["parent_" + what]) - min(us["parent_" + what]), 2)
+                r["parent_ab"][what] = dict(parent_spread_us=spread, behind_parent_us=round(mid["this_" + what] - mid["parent_" + what], 2),
+                                            not_behind_by_more_than_parent_spread=bool(mid["this_" + what] - mid["parent_" + what] <= spread))
         del parts, inf
         torch.cuda.empty_cache()
         # ---- through the module, and torch's eager autograd
@@ -173,7 +197,7 @@ def main():
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
             json.dump(dict(tool="tools/policy_head_backward_bench.py", device=torch.cuda.get_device_name(0), launches=args.launches,
-                           warmup=args.warmup, results=rows_out, inference_forward_us_by_library=ab), f, indent=1)
+                           warmup=args.warmup, rounds=args.rounds, parent_lib=bool(args.parent_lib), results=rows_out, inference_forward_us_by_library=ab), f, indent=1)
 
 
 if __name__ == "__main__":
