@@ -12,7 +12,7 @@ HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 # the units, longest compile first.  fl_obs_mK / fl_obs_fK / fl_obs_sK are fl_obs_unit.hip compiled with the defines of unit_source_and_defines
 # (the runtime-carving MODE K / launch class K / class K's split kernel; NAME:K2 = the split kernel whose second body is class K2); every
 # other unit is its own source.  The object of a unit is $OBJDIR/NAME.o.
-UNITS=(fl_obs_s4b:14 fl_obs_f21 fl_obs_f16 fl_obs_f20 fl_obs_f14 fl_obs_s9b:19 fl_obs_f19 fl_obs_f15 fl_obs_f13 fl_obs_f12 fl_obs_f18 fl_obs_f17 fl_obs_f11 fl_obs_f5 fl_obs_f10 fl_obs_f9 fl_obs_s9 fl_obs_f8 fl_obs_f7 fl_obs_m7 fl_obs_m8 fl_obs_m6 fl_obs_f6 fl_obs_s4 fl_obs_s3 fl_obs_s2 fl_obs_m2 fl_obs_m4 fl_obs_m5 fl_obs_f4 fl_obs_f3 fl_obs_f2 fl_obs_m3 fl_obs_m0 fl_obs_m1 fl_obs_f1 fl_policy_head fl_tree_lstm fl_host fl_step fl_dmap fl_obs)
+UNITS=(fl_obs_s4b:14 fl_obs_f21 fl_obs_f16 fl_obs_f20 fl_obs_f14 fl_obs_s9b:19 fl_obs_f19 fl_obs_f15 fl_obs_f13 fl_obs_f12 fl_obs_f18 fl_obs_f17 fl_obs_f11 fl_obs_f5 fl_obs_f10 fl_obs_f9 fl_obs_s9 fl_obs_f8 fl_obs_f7 fl_obs_m7 fl_obs_m8 fl_obs_m6 fl_obs_f6 fl_obs_s4 fl_obs_s3 fl_obs_s2 fl_obs_m2 fl_obs_m4 fl_obs_m5 fl_obs_f4 fl_obs_f3 fl_obs_f2 fl_obs_m3 fl_obs_m0 fl_obs_m1 fl_obs_f1 fl_policy_head fl_tree_lstm fl_param_grads fl_host fl_step fl_dmap fl_obs)
 unit_source_and_defines() {   # $1: an entry of UNITS -> name, src, defs
   name=${1%%:*}; src="$HERE/fl_obs_unit.hip"
   local k=${name#fl_obs_?} k2=0

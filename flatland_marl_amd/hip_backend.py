@@ -124,6 +124,13 @@ _POLICY_HEAD_BF16_ABI = {
     "fl_policy_head_bf16_workspace_bytes": ([i32, i32], C.c_size_t),
     "fl_policy_head_bf16": ([i32, i32, vp, vp, C.POINTER(vp), vp, C.c_size_t, vp, i32, C.c_double, vp, vp, vp, vp, C.c_size_t, vp], i32),
 }
+# ... of every function include/flatland_param_grads.h declares
+_PARAM_GRADS_ABI = {
+    "fl_policy_head_param_grads_workspace_bytes": ([i32, i32], C.c_size_t),
+    "fl_policy_head_param_grads": ([i32, i32, vp, vp, vp, i32, i32, C.POINTER(vp), i32, vp, C.c_size_t, vp], i32),
+    "fl_tree_lstm_param_grads_workspace_bytes": ([i32, i32], C.c_size_t),
+    "fl_tree_lstm_param_grads": ([i32] + [vp] * 8 + [C.POINTER(vp), i32, vp, C.c_size_t, vp], i32),
+}
 SYMBOLS = tuple(_ABI)      # every symbol include/flatland_hip.h declares
 POLICY_SYMBOLS = tuple(_POLICY_ABI)      # ... and include/flatland_policy.h
 TRAIN_SYMBOLS = tuple(_TRAIN_ABI)      # ... and include/flatland_train.h
@@ -132,7 +139,9 @@ PREDICT_SYMBOLS = tuple(_PREDICT_ABI)      # ... and include/flatland_predict.h
 WRAPPERS_SYMBOLS = tuple(_WRAPPERS_ABI)      # ... and include/flatland_wrappers.h
 POLICY_BF16_SYMBOLS = tuple(_POLICY_BF16_ABI)      # ... and include/flatland_policy_bf16.h
 POLICY_HEAD_BF16_SYMBOLS = tuple(_POLICY_HEAD_BF16_ABI)      # ... and include/flatland_policy_head_bf16.h
+PARAM_GRADS_SYMBOLS = tuple(_PARAM_GRADS_ABI)      # ... and include/flatland_param_grads.h
 POLICY_HEAD_NPARAMS = 38
+PARAM_GRADS_MAX_SLICES = 32      # FL_PARAM_GRADS_MAX_SLICES
 # the 16 matrices fl_policy_head_pack_bf16 rounds, as indices into the 38 parameters, in the packed buffer's order
 POLICY_HEAD_BF16_MATRICES = (2, 4, 6, 8, 10, 12, 14, 16, 18, 20, 22, 24, 26, 28, 32, 34)
 POLICY_SELECT = {None: 0, "soft": 1, "hard": 2}
@@ -171,7 +180,7 @@ def lib():
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
         for name, (args, res) in {**_ABI, **_DEBUG_ABI, **_POLICY_ABI, **_TRAIN_ABI, **_POLICY_TRAIN_ABI, **_PREDICT_ABI,
-                                  **_WRAPPERS_ABI, **_POLICY_BF16_ABI, **_POLICY_HEAD_BF16_ABI}.items():
+                                  **_WRAPPERS_ABI, **_POLICY_BF16_ABI, **_POLICY_HEAD_BF16_ABI, **_PARAM_GRADS_ABI}.items():
             fn = getattr(L, name, None)        # (a library from bench.py --lib or a tool's LIB_PATH may predate the newer ones)
             if fn is not None:
                 fn.argtypes, fn.restype = args, res
@@ -488,6 +497,68 @@ def policy_head_backward(agents_attr, tree_embedding, params, saved, grad_logits
           B, A, agents_attr.data_ptr(), tree_embedding.data_ptr(), ptrs, saved.data_ptr(), _opt(grad_logits), _opt(grad_value),
           grad_tree.data_ptr(), rows.data_ptr(), rows.numel() * 4)
     return grad_tree
+
+
+# [out, in] of the 38 head parameters and of the encoder's 8, in the kernels' order (a bias: (out,))
+POLICY_HEAD_PARAM_SHAPES = tuple(
+    [s for o, k in ((256, 83), (256, 256), (256, 256), (128, 256)) for s in ((o, k), (o,))]
+    + [s for _ in range(3) for o, k in ((768, 256), (256, 256), (256, 512)) for s in ((o, k), (o,))]
+    + [s for last in (5, 1) for o, k in ((256, 512), (128, 256), (last, 128)) for s in ((o, k), (o,))])
+TREE_LSTM_PARAM_SHAPES = ((384, 12), (384,), (384, 384), (128, 384), (128,), (128, 12), (128,), (128, 128))
+
+
+def _param_grads_call(what, dev, rows, shapes, on, slices, workspace, *args):
+    """fl_<what>(*args, grads, slices, workspace, its bytes, stream) with new output tensors of `shapes` (None where `on` is False)
+    and the caller's workspace (a tensor of at least fl_<what>_workspace_bytes bytes) or one from torch's allocator"""
+    import torch
+    if not 0 <= slices <= PARAM_GRADS_MAX_SLICES:
+        raise ValueError("%s: slices must be 0 (automatic) or in [1, %d], got %r" % (what, PARAM_GRADS_MAX_SLICES, slices))
+    fn, need = _sym("fl_" + what), _sym("fl_%s_workspace_bytes" % what)(rows, slices)
+    if workspace is not None and (workspace.device != dev or not workspace.is_contiguous()
+                                  or workspace.numel() * workspace.element_size() < need):
+        raise ValueError("%s: workspace must be a contiguous tensor of at least %d bytes on %s" % (what, need, dev))
+    with torch.cuda.device(dev):
+        grads = [torch.empty(s, dtype=torch.float32, device=dev) if k else None for s, k in zip(shapes, on)]
+        if workspace is None and need:
+            workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+        ptrs = (vp * len(shapes))(*[_opt(g) for g in grads])
+        _chk(fn(*args, ptrs, slices, _opt(workspace), 0 if workspace is None else workspace.numel() * workspace.element_size(),
+                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    return grads
+
+
+def policy_head_param_grads(agents_attr, saved, rows, actor=True, critic=True, slices=0, workspace=None):
+    """The 38 gradients of the head's parameters (fl_policy_head_param_grads, include/flatland_param_grads.h) on torch's current
+    stream of the inputs' device: agents_attr f32 [B, A, 83], saved / rows as policy_head_forward_saved / policy_head_backward left
+    them for the same envs.  Returns a list of 38 new tensors in the parameters' order and shapes; actor / critic False: that head's
+    six are None (its rows are not read).  slices: 0 = the library's choice, else the forced count; workspace: a tensor of at least
+    fl_policy_head_param_grads_workspace_bytes(B * A, slices) bytes, None = from torch's allocator."""
+    import torch
+    B, A = agents_attr.shape[:2]
+    dev = agents_attr.device
+    _check_tensors("policy_head_param_grads", dev,
+                   (("agents_attr", agents_attr, torch.float32, B * A * 83), ("saved", saved, torch.float32, policy_saved_floats(B, A)),
+                    ("rows", rows, torch.float32, B * A * POLICY_ROW_FLOATS)))
+    on = [True] * 26 + [bool(actor)] * 6 + [bool(critic)] * 6
+    return _param_grads_call("policy_head_param_grads", dev, B * A, POLICY_HEAD_PARAM_SHAPES, on, int(slices), workspace,
+                             B, A, agents_attr.data_ptr(), saved.data_ptr(), rows.data_ptr(), int(bool(actor)), int(bool(critic)))
+
+
+def tree_lstm_param_grads(x, node_order, h, da, dc, dg, q, child, slices=0, workspace=None):
+    """The 8 gradients of the tree encoder's parameters (fl_tree_lstm_param_grads, include/flatland_param_grads.h) on torch's
+    current stream of the inputs' device: x f32 [n, 12], node_order i64 [n], h f32 [n, 128] and the rows tree_lstm_backward wrote
+    for the same n nodes (da [n, 384], dc [n, 128], dg [n, 3, 128], q [n, 384], child i32 [n, 3]).  Returns a list of 8 new tensors
+    in the parameters' order and shapes.  slices, workspace: as for policy_head_param_grads."""
+    import torch
+    n = node_order.numel()
+    dev = x.device
+    _check_tensors("tree_lstm_param_grads", dev,
+                   (("x", x, torch.float32, n * 12), ("node_order", node_order, torch.int64, n), ("h", h, torch.float32, n * 128),
+                    ("da", da, torch.float32, n * 384), ("dc", dc, torch.float32, n * 128), ("dg", dg, torch.float32, n * 384),
+                    ("q", q, torch.float32, n * 384), ("child", child, torch.int32, n * 3)))
+    return _param_grads_call("tree_lstm_param_grads", dev, n, TREE_LSTM_PARAM_SHAPES, [True] * 8, int(slices), workspace,
+                             n, x.data_ptr(), node_order.data_ptr(), h.data_ptr(), da.data_ptr(), dc.data_ptr(), dg.data_ptr(),
+                             q.data_ptr(), child.data_ptr())
 
 
 class BatchedRailEnv:

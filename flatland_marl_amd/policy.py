@@ -33,6 +33,12 @@ layers -- and the attention's two products on the bf16 matrix instruction with f
 and sums stay float32, q k v are kept in bf16.  The module packs the 16 matrices on first use and again whenever one of them changed.
 Inference only, as the encoder's.  A whole bf16 roll-out is Network(precision="bf16", head_precision="bf16").
 
+TreeLSTM(param_grads="hip") / Network(param_grads="hip") (or the attribute param_grads of either, or from_module(m,
+param_grads="hip")) take the parameter gradients from the library as well: fl_tree_lstm_param_grads and fl_policy_head_param_grads
+(include/flatland_param_grads.h), one grouped MFMA kernel per chunk with _tn's summation order fixed in the kernel, so that the
+gradients of a chunk are the same bits from call to call whatever the BLAS library does.  "torch", the default, is the products
+below.  Network's value governs the head, its tree_lstm keeps its own; Network(param_grads="hip") sets both.
+
 Swap it into the reference's Network:  net.tree_lstm = TreeLSTM.from_module(net.tree_lstm)
 or take the whole network:              net = Network.from_module(net)
 """
@@ -44,6 +50,7 @@ from . import hip_backend
 IN_FEATURES = 12      # FeatureParserConfig.node_sz
 OUT_FEATURES = 128    # NetworkConfig.tree_embedding_sz
 PRECISIONS = ("f32", "bf16")
+PARAM_GRADS = ("torch", "hip")
 PARAM_ORDER = ("W_iou.weight", "W_iou.bias", "U_iou.weight", "W_c.weight", "W_c.bias", "W_f.weight", "W_f.bias", "U_f.weight")
 
 
@@ -95,13 +102,13 @@ class _TrainForward(torch.autograd.Function):
     """fl_tree_lstm on every node with c kept, fl_tree_lstm_backward + the parameter products behind it"""
 
     @staticmethod
-    def forward(ctx, forest, adjacency, node_order, edge_order, roots_only, status, *weights):
+    def forward(ctx, forest, adjacency, node_order, edge_order, roots_only, status, hip_grads, *weights):
         B, A, N = forest.shape[:3]
         T = B * A
         h = torch.empty((T * N, OUT_FEATURES), dtype=torch.float32, device=forest.device)
         c = torch.empty_like(h)
         hip_backend.tree_lstm(forest, adjacency, node_order, edge_order, weights, False, h, c, status=status)
-        ctx.roots_only = roots_only
+        ctx.roots_only, ctx.hip_grads = roots_only, hip_grads
         ctx.save_for_backward(forest, adjacency, node_order, edge_order, h, c, *weights)
         return h.view(T, N, OUT_FEATURES)[:, 0].contiguous() if roots_only else h
 
@@ -133,10 +140,11 @@ class _TrainForward(torch.autograd.Function):
             hc = hv[t0:t1].reshape(n, M)
             hip_backend.tree_lstm_backward(x[t0:t1], a, no[t0:t1], eo[t0:t1], weights, hc, cv[t0:t1].reshape(n, M),
                                            gv[t0:t1].reshape(-1, M), ctx.roots_only, da, dc, dg, q, child)
-            part = tree_lstm_param_grads(x[t0:t1].reshape(n, IN_FEATURES), no[t0:t1].reshape(n), hc, da, dc, dg, q, child)
+            grads = hip_backend.tree_lstm_param_grads if ctx.hip_grads else tree_lstm_param_grads
+            part = grads(x[t0:t1].reshape(n, IN_FEATURES), no[t0:t1].reshape(n), hc, da, dc, dg, q, child)
             total = part if total is None else tuple(u + v for u, v in zip(total, part))
-        need = ctx.needs_input_grad[6:]
-        return (None,) * 6 + tuple(g if k else None for g, k in zip(total, need))
+        need = ctx.needs_input_grad[7:]
+        return (None,) * 7 + tuple(g if k else None for g, k in zip(total, need))
 
 
 class _Forward(torch.autograd.Function):
@@ -164,6 +172,12 @@ class _Forward(torch.autograd.Function):
 def _precision(value, what="TreeLSTM: precision"):
     if value not in PRECISIONS:
         raise ValueError("%s must be 'f32' or 'bf16', got %r" % (what, value))
+    return value
+
+
+def _param_grads(value, what):
+    if value not in PARAM_GRADS:
+        raise ValueError("%s: param_grads must be 'torch' or 'hip', got %r" % (what, value))
     return value
 
 
@@ -196,11 +210,14 @@ class TreeLSTM(nn.Module):
     are differentiable with respect to the parameters (fl_tree_lstm_backward), their values the same bits as the inference path's.
     precision (a plain attribute, settable): "f32" = fl_tree_lstm; "bf16" = fl_tree_lstm_bf16, the recurrent products with bf16
     operands and float32 sums, inference only -- together with trainable it runs under torch.no_grad() and raises ValueError under
-    grad mode (training stays float32: the backward recomputes float32 gates from the saved h / c)."""
+    grad mode (training stays float32: the backward recomputes float32 gates from the saved h / c).
+    param_grads (a plain attribute, settable): "torch" = the eight parameter gradients as torch products (tree_lstm_param_grads);
+    "hip" = fl_tree_lstm_param_grads, the same sums in one deterministic kernel."""
 
-    def __init__(self, in_features=IN_FEATURES, out_features=OUT_FEATURES, trainable=False, precision="f32"):
+    def __init__(self, in_features=IN_FEATURES, out_features=OUT_FEATURES, trainable=False, precision="f32", param_grads="torch"):
         super().__init__()
         _switches(self, trainable, "precision", precision, "TreeLSTM: precision")
+        self.param_grads = _param_grads(param_grads, "TreeLSTM")
         if (in_features, out_features) != (IN_FEATURES, OUT_FEATURES):
             raise ValueError("TreeLSTM: only in_features=%d, out_features=%d exist here, got %d, %d"
                              % (IN_FEATURES, OUT_FEATURES, in_features, out_features))
@@ -213,7 +230,7 @@ class TreeLSTM(nn.Module):
         self.U_f = nn.Linear(out_features, out_features, bias=False)
 
     @classmethod
-    def from_module(cls, m, trainable=False, precision="f32"):
+    def from_module(cls, m, trainable=False, precision="f32", param_grads="torch"):
         """a TreeLSTM that shares m's parameters (m: the reference's TreeLSTM or one of these)"""
         if (m.in_features, m.out_features) != (IN_FEATURES, OUT_FEATURES):
             raise ValueError("TreeLSTM.from_module: only in_features=%d, out_features=%d exist here, got %d, %d"
@@ -222,6 +239,7 @@ class TreeLSTM(nn.Module):
         nn.Module.__init__(obj)
         obj.in_features, obj.out_features = m.in_features, m.out_features
         _switches(obj, trainable, "precision", precision, "TreeLSTM: precision")
+        obj.param_grads = _param_grads(param_grads, "TreeLSTM")
         for name in ("W_iou", "U_iou", "W_c", "W_f", "U_f"):
             setattr(obj, name, getattr(m, name))
         return obj
@@ -277,7 +295,8 @@ class TreeLSTM(nn.Module):
             raise ValueError("TreeLSTM: the forest gets no gradient (fl_tree_lstm_backward differentiates with respect to the "
                              "parameters only): detach it")
         if train:
-            out = _TrainForward.apply(forest, adjacency, node_order, edge_order, roots_only, status, *ws)
+            hip_grads = _param_grads(self.param_grads, "TreeLSTM") == "hip"
+            out = _TrainForward.apply(forest, adjacency, node_order, edge_order, roots_only, status, hip_grads, *ws)
         else:                                        # U_iou, W_c and U_f (items 2, 3, 7) are the packed ones
             packed = _packed_bf16(self, hip_backend.tree_lstm_pack_bf16, ws, (2, 3, 7), forest.device) if bf16 else None
             out = _Forward.apply(forest, adjacency, node_order, edge_order, roots_only, status, packed, *ws)
@@ -406,10 +425,11 @@ class _HeadTrain(torch.autograd.Function):
     fl_policy_head_backward + the parameter products, the chunks' gradients added in order"""
 
     @staticmethod
-    def forward(ctx, agents_attr, tree_embedding, valid_actions, mode, u, with_value, *weights):
+    def forward(ctx, agents_attr, tree_embedding, valid_actions, mode, u, with_value, hip_grads, *weights):
         B, A = agents_attr.shape[:2]
         dev = agents_attr.device
         chunks = head_chunks(B, A)
+        ctx.hip_grads = hip_grads
         logits, values, saved = [], [], []
         for e0, e1 in chunks:
             lg = torch.empty((e1 - e0, A, ACTIONS), dtype=torch.float32, device=dev)
@@ -438,7 +458,7 @@ class _HeadTrain(torch.autograd.Function):
         B, A = agents_attr.shape[:2]
         dev = agents_attr.device
         g_value = more[0] if ctx.with_value else None
-        nothing = (None,) * (6 + len(weights))
+        nothing = (None,) * (7 + len(weights))
         if g_logits is None and g_value is None:
             return nothing
         if g_logits is not None:
@@ -454,14 +474,17 @@ class _HeadTrain(torch.autograd.Function):
             hip_backend.policy_head_backward(attr, tree_embedding[e0:e1], weights, sv,
                                              None if g_logits is None else _aligned(g_logits[e0:e1]),
                                              None if g_value is None else _aligned(g_value[e0:e1]), gt, rows)
-            part = policy_head_param_grads(attr.view(R, AGENT_ATTR), hip_backend.policy_views(sv, hip_backend.POLICY_SAVED_LAYOUT, R),
-                                           hip_backend.policy_views(rows, hip_backend.POLICY_ROWS_LAYOUT, R),
-                                           g_logits is not None, g_value is not None)
+            if ctx.hip_grads:
+                part = hip_backend.policy_head_param_grads(attr, sv, rows, g_logits is not None, g_value is not None)
+            else:
+                part = policy_head_param_grads(attr.view(R, AGENT_ATTR), hip_backend.policy_views(sv, hip_backend.POLICY_SAVED_LAYOUT, R),
+                                               hip_backend.policy_views(rows, hip_backend.POLICY_ROWS_LAYOUT, R),
+                                               g_logits is not None, g_value is not None)
             total = part if total is None else [None if v is None else w + v for w, v in zip(total, part)]
             gtree.append(gt)
         gtree = gtree[0] if len(gtree) == 1 else torch.cat(gtree)
         need = ctx.needs_input_grad
-        return (None, gtree if need[1] else None, None, None, None, None) + tuple(g if k else None for g, k in zip(total, need[6:]))
+        return (None, gtree if need[1] else None) + (None,) * 5 + tuple(g if k else None for g, k in zip(total, need[7:]))
 
 
 class Network(nn.Module):
@@ -475,27 +498,35 @@ class Network(nn.Module):
     stays float32 under it.
     head_precision (a plain attribute, settable): "f32" = fl_policy_head; "bf16" = fl_policy_head_bf16 in head, forward and act: 16
     of the head's 19 matrices and the attention's products with bf16 operands and float32 sums, inference only -- together with
-    trainable it runs under torch.no_grad() and raises ValueError under grad mode (training stays float32)."""
+    trainable it runs under torch.no_grad() and raises ValueError under grad mode (training stays float32).
+    param_grads (a plain attribute, settable): "torch" = the head's 38 parameter gradients as torch products
+    (policy_head_param_grads); "hip" = fl_policy_head_param_grads.  It governs the head; tree_lstm.param_grads stays settable on its
+    own, and the constructor's value sets both."""
 
-    def __init__(self, trainable=False, precision="f32", head_precision="f32"):
+    def __init__(self, trainable=False, precision="f32", head_precision="f32", param_grads="torch"):
         super().__init__()
         _switches(self, trainable, "head_precision", head_precision, "Network: head_precision")
-        self.tree_lstm = TreeLSTM(IN_FEATURES, OUT_FEATURES, precision=precision)
+        self.param_grads = _param_grads(param_grads, "Network")
+        self.tree_lstm = TreeLSTM(IN_FEATURES, OUT_FEATURES, precision=precision, param_grads=param_grads)
         self.attr_embedding = _mlp((AGENT_ATTR, 2 * HIDDEN, 2 * HIDDEN, 2 * HIDDEN, HIDDEN), True)
         self.transformer = nn.Sequential(*[Transformer(EMBED, HEADS) for _ in range(3)])
         self.actor_net = _mlp((2 * EMBED, 2 * HIDDEN, HIDDEN, ACTIONS), False)
         self.critic_net = _mlp((2 * EMBED, 2 * HIDDEN, HIDDEN, 1), False)
 
     @classmethod
-    def from_module(cls, m, trainable=False, precision=None, head_precision=None):
+    def from_module(cls, m, trainable=False, precision=None, head_precision=None, param_grads=None):
         """a Network that shares m's parameters (m: the reference's Network or one of these); precision: the tree encoder's, None =
-        m.tree_lstm's own ("f32" for the reference's); head_precision: None = m's own ("f32" for the reference's)"""
+        m.tree_lstm's own ("f32" for the reference's); head_precision: None = m's own ("f32" for the reference's); param_grads: the
+        head's and the encoder's, None = m's and m.tree_lstm's own ("torch" for the reference's)"""
         obj = cls.__new__(cls)
         nn.Module.__init__(obj)
         _switches(obj, trainable, "head_precision", getattr(m, "head_precision", "f32") if head_precision is None else head_precision,
                   "Network: head_precision")
+        obj.param_grads = _param_grads(getattr(m, "param_grads", "torch") if param_grads is None else param_grads, "Network")
         obj.tree_lstm = TreeLSTM.from_module(m.tree_lstm, trainable=getattr(m.tree_lstm, "trainable", False),
-                                             precision=getattr(m.tree_lstm, "precision", "f32") if precision is None else precision)
+                                             precision=getattr(m.tree_lstm, "precision", "f32") if precision is None else precision,
+                                             param_grads=getattr(m.tree_lstm, "param_grads", "torch") if param_grads is None
+                                             else param_grads)
         obj.attr_embedding = m.attr_embedding
         blocks = []
         for b in m.transformer:
@@ -591,7 +622,7 @@ class Network(nn.Module):
                              "parameters and the tree embedding only): detach it")
         args = (agents_attr, tree_embedding, valid_actions if mode is not None else None, mode, u, bool(value))
         if train:
-            out = list(_HeadTrain.apply(*args, *ws))
+            out = list(_HeadTrain.apply(*args, _param_grads(self.param_grads, "Network") == "hip", *ws))
         else:
             packed = _packed_bf16(self, hip_backend.policy_head_pack_bf16, ws, hip_backend.POLICY_HEAD_BF16_MATRICES,
                                   agents_attr.device) if bf16 else None

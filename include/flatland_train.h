@@ -28,7 +28,8 @@
  * The eight parameter gradients are sums over the nodes of products of these rows (x = the node's features, hk = [h_k1|h_k2|h_k3]):
  *   dW_iou = sum da x^T   db_iou = sum da   dU_iou = sum da hk^T   dW_c = sum dc q^T   db_c = sum dc (height > 0 only)
  *   dW_f = sum (dg_1+dg_2+dg_3) x^T   db_f = sum (dg_1+dg_2+dg_3)   dU_f = sum_j sum dg_j h_kj^T
- * and are left to the caller (batch-wide matrix products); this call writes none of them.
+ * and are left to the caller (batch-wide matrix products); this call writes none of them.  fl_tree_lstm_param_grads of
+ * include/flatland_param_grads.h forms them from these very rows.
  *
  * Deterministic: no float atomics, every address has one writer, a node adds its parents' hand-downs in increasing (parent id,
  * slot).  Two calls on the same inputs give the same bits.
