@@ -1,13 +1,19 @@
 // fl_policy_head.hip -- entry points of include/flatland_policy.h and include/flatland_policy_train.h: the checks (all before any
 // HIP call) and the launches of the kernels in fl_policy_head.h and fl_policy_head_bwd.h; behind them those of
-// include/flatland_policy_head_bf16.h and fl_policy_head_bf16.h.
+// include/flatland_policy_head_bf16.h and fl_policy_head_bf16.h, and those of include/flatland_ppo.h and fl_ppo.h (whose draw is this
+// unit's fph_choose).
+#include <algorithm>
+#include <cmath>
+
 #include "../../include/flatland_policy.h"
 #include "../../include/flatland_policy_train.h"
 #include "../../include/flatland_policy_head_bf16.h"
+#include "../../include/flatland_ppo.h"
 #include "fl_policy_head.h"
 #include "fl_policy_head_bf16.h"
 #include "fl_policy_head_bwd.h"
 #include "fl_policy_host.h"
+#include "fl_ppo.h"
 
 size_t fl_policy_head_workspace_bytes(int n_envs, int n_agents) {
     if (n_envs <= 0 || n_agents <= 0) return 0;
@@ -272,5 +278,97 @@ int fl_policy_head_bf16(int n_envs, int n_agents, const float *attr_dev, const f
         else hipLaunchKernelGGL(k_ph16_block<true>, dim3(tiles), dim3(FPH_THREADS), 0, s, a, blk, xin[blk], xout[blk]);
     }
     if (a.value) hipLaunchKernelGGL(k_ph_value, dim3(a.B), dim3(64), 0, s, (FphArgs)a);
+    return fl_launched(fn);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- PPO (include/flatland_ppo.h)
+static int fpp_groups(int n) { return (n + FPP_THREADS - 1) / FPP_THREADS; }
+static bool fpp_size(int n) { return n >= 1 && n <= FL_PPO_MAX_ROWS; }      // (a lane's row index and its strides stay inside an int)
+
+// workgroups of k_ppo_rows (a workgroup takes 256 rows and 256 values) and of k_ppo_count
+struct FppGrid { int groups, count_groups; };
+static FppGrid fpp_grid(int n_rows, int n_envs) {
+    const int row_groups = fpp_groups(n_rows), groups = n_envs > 0 ? std::max(row_groups, fpp_groups(n_envs)) : row_groups;
+    return {groups, std::min(row_groups, FPP_COUNT_GROUPS)};
+}
+
+size_t fl_ppo_loss_workspace_bytes(int n_rows, int n_envs) {
+    if (!fpp_size(n_rows) || (n_envs != 0 && !fpp_size(n_envs))) return 0;
+    const auto [groups, count_groups] = fpp_grid(n_rows, n_envs);
+    return ((size_t)groups * FPP_SUMS * sizeof(double) + (size_t)count_groups * 2 * sizeof(int) + 15) / 16 * 16;
+}
+
+int fl_policy_sample(int n_rows, const float *logits_dev, const uint8_t *valid_dev, const double *u_dev, uint8_t *actions_dev,
+                     float *logp_dev, float *entropy_dev, void *hip_stream) {
+    const char *fn = "fl_policy_sample";
+    if (!fpp_size(n_rows)) { fl_set_error("%s: bad sizes (n_rows %d; 1 <= n_rows <= %d)", fn, n_rows, FL_PPO_MAX_ROWS); return FL_ERR_ARG; }
+    const FlPtr tab[] = {{logits_dev, "logits", 16}, {valid_dev, "valid", 1}, {u_dev, "u", 16}, {actions_dev, "actions", 1},
+                         {logp_dev, "logp", 16, true}, {entropy_dev, "entropy", 16, true}};
+    if (fl_check_ptrs(fn, tab, 6) != FL_OK) return FL_ERR_ARG;
+    hipLaunchKernelGGL(k_policy_sample, dim3(fpp_groups(n_rows)), dim3(FPP_THREADS), 0, (hipStream_t)hip_stream, n_rows, logits_dev,
+                       valid_dev, u_dev, actions_dev, logp_dev, entropy_dev);
+    return fl_launched(fn);
+}
+
+int fl_ppo_loss(int n_rows, int n_envs, const float *logits_dev, const uint8_t *valid_dev, const uint8_t *actions_dev,
+                const float *old_logp_dev, const float *adv_dev, const uint8_t *mask_dev, const float *value_dev,
+                const float *returns_dev, double clip_eps, double vf_coef, double ent_coef, float *grad_logits_dev,
+                float *grad_value_dev, double *stats_dev, void *workspace_dev, size_t workspace_bytes, void *hip_stream) {
+    const char *fn = "fl_ppo_loss";
+    const int critic = (value_dev != nullptr) + (returns_dev != nullptr) + (grad_value_dev != nullptr);
+    if (critic != 0 && critic != 3) {
+        fl_set_error("%s: value, returns and grad_value are all three NULL or all three given (value %s, returns %s, grad_value %s)", fn,
+                     value_dev ? "given" : "NULL", returns_dev ? "given" : "NULL", grad_value_dev ? "given" : "NULL");
+        return FL_ERR_ARG;
+    }
+    if (!fpp_size(n_rows) || (n_envs != 0 && !fpp_size(n_envs)) || (n_envs == 0 && critic)) {
+        fl_set_error("%s: bad sizes (n_rows %d, n_envs %d; 1 <= n_rows <= %d, 1 <= n_envs <= %d, n_envs 0 only without value, returns and "
+                     "grad_value)", fn, n_rows, n_envs, FL_PPO_MAX_ROWS, FL_PPO_MAX_ROWS);
+        return FL_ERR_ARG;
+    }
+    const FlPtr tab[] = {{logits_dev, "logits", 16}, {valid_dev, "valid", 1}, {actions_dev, "actions", 1}, {old_logp_dev, "old_logp", 16},
+                         {adv_dev, "adv", 16}, {mask_dev, "mask", 1, true}, {value_dev, "value", 16, true},
+                         {returns_dev, "returns", 16, true}, {grad_logits_dev, "grad_logits", 16}, {grad_value_dev, "grad_value", 16, true},
+                         {stats_dev, "stats", 16}, {workspace_dev, "workspace", 16}};
+    if (fl_check_ptrs(fn, tab, 12) != FL_OK) return FL_ERR_ARG;
+    const struct { double v; const char *name; } coef[] = {{clip_eps, "clip_eps"}, {vf_coef, "vf_coef"}, {ent_coef, "ent_coef"}};
+    for (const auto &c : coef)
+        if (!std::isfinite(c.v)) { fl_set_error("%s: %s must be finite, got %g", fn, c.name, c.v); return FL_ERR_ARG; }
+    if (clip_eps < 0.0) { fl_set_error("%s: clip_eps must be >= 0, got %g", fn, clip_eps); return FL_ERR_ARG; }
+    const int n_values = critic ? n_envs : 0;
+    if (fl_check_bytes(fn, "workspace", workspace_bytes, fl_ppo_loss_workspace_bytes(n_rows, n_values), "fl_ppo_loss_workspace_bytes") != FL_OK)
+        return FL_ERR_ARG;
+
+    FppLossArgs a;
+    a.R = n_rows; a.B = n_values;
+    const auto [groups, count_groups] = fpp_grid(n_rows, n_values);
+    a.groups = groups; a.count_groups = count_groups;
+    a.logits = logits_dev; a.valid = valid_dev; a.actions = actions_dev; a.mask = mask_dev;
+    a.old_logp = old_logp_dev; a.adv = adv_dev; a.value = value_dev; a.returns = returns_dev;
+    a.clip_eps = clip_eps; a.vf_coef = vf_coef; a.ent_coef = ent_coef;
+    a.grad_logits = grad_logits_dev; a.grad_value = grad_value_dev; a.stats = stats_dev;
+    a.sums = (double *)workspace_dev;
+    a.counts = (int *)(a.sums + (size_t)groups * FPP_SUMS);
+    hipStream_t s = (hipStream_t)hip_stream;
+    hipLaunchKernelGGL(k_ppo_count, dim3(count_groups), dim3(FPP_THREADS), 0, s, a);
+    hipLaunchKernelGGL(k_ppo_rows, dim3(groups), dim3(FPP_THREADS), 0, s, a);
+    hipLaunchKernelGGL(k_ppo_final, dim3(1), dim3(FPP_THREADS), 0, s, a);
+    return fl_launched(fn);
+}
+
+int fl_gae(int n_steps, int n_cols, const float *rewards_dev, const float *values_dev, const uint8_t *dones_dev, double gamma,
+           double lam, float *adv_dev, float *returns_dev, void *hip_stream) {
+    const char *fn = "fl_gae";
+    if (n_steps <= 0 || !fpp_size(n_cols)) {
+        fl_set_error("%s: bad sizes (n_steps %d, n_cols %d; 1 <= n_steps, 1 <= n_cols <= %d)", fn, n_steps, n_cols, FL_PPO_MAX_ROWS);
+        return FL_ERR_ARG;
+    }
+    const FlPtr tab[] = {{rewards_dev, "rewards", 16}, {values_dev, "values", 16}, {dones_dev, "dones", 1}, {adv_dev, "adv", 16},
+                         {returns_dev, "returns", 16}};
+    if (fl_check_ptrs(fn, tab, 5) != FL_OK) return FL_ERR_ARG;
+    if (!(gamma >= 0.0 && gamma <= 1.0)) { fl_set_error("%s: gamma must be in [0, 1], got %g", fn, gamma); return FL_ERR_ARG; }
+    if (!(lam >= 0.0 && lam <= 1.0)) { fl_set_error("%s: lam must be in [0, 1], got %g", fn, lam); return FL_ERR_ARG; }
+    hipLaunchKernelGGL(k_gae, dim3(fpp_groups(n_cols)), dim3(FPP_THREADS), 0, (hipStream_t)hip_stream, n_steps, n_cols, rewards_dev,
+                       values_dev, dones_dev, gamma, lam, adv_dev, returns_dev);
     return fl_launched(fn);
 }

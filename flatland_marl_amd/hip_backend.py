@@ -131,6 +131,13 @@ _PARAM_GRADS_ABI = {
     "fl_tree_lstm_param_grads_workspace_bytes": ([i32, i32], C.c_size_t),
     "fl_tree_lstm_param_grads": ([i32] + [vp] * 8 + [C.POINTER(vp), i32, vp, C.c_size_t, vp], i32),
 }
+# ... of every function include/flatland_ppo.h declares
+_PPO_ABI = {
+    "fl_policy_sample": ([i32, vp, vp, vp, vp, vp, vp, vp], i32),
+    "fl_ppo_loss_workspace_bytes": ([i32, i32], C.c_size_t),
+    "fl_ppo_loss": ([i32, i32] + [vp] * 8 + [C.c_double] * 3 + [vp, vp, vp, vp, C.c_size_t, vp], i32),
+    "fl_gae": ([i32, i32, vp, vp, vp, C.c_double, C.c_double, vp, vp, vp], i32),
+}
 SYMBOLS = tuple(_ABI)      # every symbol include/flatland_hip.h declares
 POLICY_SYMBOLS = tuple(_POLICY_ABI)      # ... and include/flatland_policy.h
 TRAIN_SYMBOLS = tuple(_TRAIN_ABI)      # ... and include/flatland_train.h
@@ -140,6 +147,8 @@ WRAPPERS_SYMBOLS = tuple(_WRAPPERS_ABI)      # ... and include/flatland_wrappers
 POLICY_BF16_SYMBOLS = tuple(_POLICY_BF16_ABI)      # ... and include/flatland_policy_bf16.h
 POLICY_HEAD_BF16_SYMBOLS = tuple(_POLICY_HEAD_BF16_ABI)      # ... and include/flatland_policy_head_bf16.h
 PARAM_GRADS_SYMBOLS = tuple(_PARAM_GRADS_ABI)      # ... and include/flatland_param_grads.h
+PPO_SYMBOLS = tuple(_PPO_ABI)      # ... and include/flatland_ppo.h
+PPO_STATS = 8      # FL_PPO_STATS
 POLICY_HEAD_NPARAMS = 38
 PARAM_GRADS_MAX_SLICES = 32      # FL_PARAM_GRADS_MAX_SLICES
 # the 16 matrices fl_policy_head_pack_bf16 rounds, as indices into the 38 parameters, in the packed buffer's order
@@ -180,7 +189,7 @@ def lib():
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
         for name, (args, res) in {**_ABI, **_DEBUG_ABI, **_POLICY_ABI, **_TRAIN_ABI, **_POLICY_TRAIN_ABI, **_PREDICT_ABI,
-                                  **_WRAPPERS_ABI, **_POLICY_BF16_ABI, **_POLICY_HEAD_BF16_ABI, **_PARAM_GRADS_ABI}.items():
+                                  **_WRAPPERS_ABI, **_POLICY_BF16_ABI, **_POLICY_HEAD_BF16_ABI, **_PARAM_GRADS_ABI, **_PPO_ABI}.items():
             fn = getattr(L, name, None)        # (a library from bench.py --lib or a tool's LIB_PATH may predate the newer ones)
             if fn is not None:
                 fn.argtypes, fn.restype = args, res
@@ -559,6 +568,57 @@ def tree_lstm_param_grads(x, node_order, h, da, dc, dg, q, child, slices=0, work
     return _param_grads_call("tree_lstm_param_grads", dev, n, TREE_LSTM_PARAM_SHAPES, [True] * 8, int(slices), workspace,
                              n, x.data_ptr(), node_order.data_ptr(), h.data_ptr(), da.data_ptr(), dc.data_ptr(), dg.data_ptr(),
                              q.data_ptr(), child.data_ptr())
+
+
+def policy_sample(logits, valid_actions, u, actions, logp=None, entropy=None):
+    """An action per (env, agent) row with that row's own uniform number, its log-probability and entropy (fl_policy_sample,
+    include/flatland_ppo.h) on torch's current stream of the inputs' device.  logits f32 [..., 5], valid_actions u8 [..., 5], u f64
+    [...] in [0, 1); actions u8 [...] (out), logp / entropy f32 [...] or None (out)."""
+    import torch
+    R = logits.numel() // 5
+    dev = logits.device
+    _check_tensors("policy_sample", dev, (("logits", logits, torch.float32, R * 5), ("valid_actions", valid_actions, torch.uint8, R * 5),
+                                          ("u", u, torch.float64, R), ("actions", actions, torch.uint8, R),
+                                          ("logp", logp, torch.float32, R), ("entropy", entropy, torch.float32, R)))
+    _call(_sym("fl_policy_sample"), dev, None, R, logits.data_ptr(), valid_actions.data_ptr(), u.data_ptr(), actions.data_ptr(),
+          _opt(logp), _opt(entropy))
+    return actions
+
+
+def ppo_loss(logits, valid_actions, actions, old_logp, advantages, mask, value, returns, clip, vf_coef, ent_coef, grad_logits,
+             grad_value, stats):
+    """The clipped-surrogate loss, its gradients and statistics (fl_ppo_loss, include/flatland_ppo.h) on torch's current stream of
+    the inputs' device, with a workspace from torch's allocator.  logits f32 [R, 5], valid_actions u8 [R, 5], actions u8 [R],
+    old_logp / advantages f32 [R], mask u8 [R] or None; value / returns f32 [B] and grad_value f32 [B] (out), or all three None;
+    grad_logits f32 [R, 5] (out), stats f64 [8] (out)."""
+    import torch
+    R = logits.numel() // 5
+    B = 0 if value is None else value.numel()
+    dev = logits.device
+    _check_tensors("ppo_loss", dev, (("logits", logits, torch.float32, R * 5), ("valid_actions", valid_actions, torch.uint8, R * 5),
+                                     ("actions", actions, torch.uint8, R), ("old_logp", old_logp, torch.float32, R),
+                                     ("advantages", advantages, torch.float32, R), ("mask", mask, torch.uint8, R),
+                                     ("value", value, torch.float32, B), ("returns", returns, torch.float32, B),
+                                     ("grad_logits", grad_logits, torch.float32, R * 5), ("grad_value", grad_value, torch.float32, B),
+                                     ("stats", stats, torch.float64, PPO_STATS)))
+    _call(_sym("fl_ppo_loss"), dev, _sym("fl_ppo_loss_workspace_bytes")(R, B), R, B, logits.data_ptr(), valid_actions.data_ptr(),
+          actions.data_ptr(), old_logp.data_ptr(), advantages.data_ptr(), _opt(mask), _opt(value), _opt(returns), float(clip),
+          float(vf_coef), float(ent_coef), grad_logits.data_ptr(), _opt(grad_value), stats.data_ptr())
+    return stats
+
+
+def gae(rewards, values, dones, gamma, lam, advantages, returns):
+    """Generalised advantage estimation (fl_gae, include/flatland_ppo.h) on torch's current stream of the inputs' device: rewards
+    f32 [T, N], values f32 [T + 1, N], dones u8 [T, N]; advantages / returns f32 [T, N] (out)."""
+    import torch
+    T, N = rewards.shape
+    dev = rewards.device
+    _check_tensors("gae", dev, (("rewards", rewards, torch.float32, T * N), ("values", values, torch.float32, (T + 1) * N),
+                                ("dones", dones, torch.uint8, T * N), ("advantages", advantages, torch.float32, T * N),
+                                ("returns", returns, torch.float32, T * N)))
+    _call(_sym("fl_gae"), dev, None, T, N, rewards.data_ptr(), values.data_ptr(), dones.data_ptr(), float(gamma), float(lam),
+          advantages.data_ptr(), returns.data_ptr())
+    return advantages, returns
 
 
 class BatchedRailEnv:

@@ -39,6 +39,13 @@ param_grads="hip")) take the parameter gradients from the library as well: fl_tr
 gradients of a chunk are the same bits from call to call whatever the BLAS library does.  "torch", the default, is the products
 below.  Network's value governs the head, its tree_lstm keeps its own; Network(param_grads="hip") sets both.
 
+What PPO needs per step is here too (include/flatland_ppo.h): sample_actions / Network.rollout draw an action per agent with that
+agent's own uniform number and return its log-probability and entropy (fl_policy_sample: the draw is fl_policy_head's "soft" draw,
+so the reference's constant u reproduces Network.act); gae forms advantages and returns (fl_gae); ppo_loss is the clipped
+surrogate with the value and entropy terms as an autograd.Function over fl_ppo_loss, so loss.backward() through
+Network(trainable=True).forward runs no torch eager op between the HIP forward and the HIP backward.  The loop, the roll-out buffer
+and the optimiser are the caller's.
+
 Swap it into the reference's Network:  net.tree_lstm = TreeLSTM.from_module(net.tree_lstm)
 or take the whole network:              net = Network.from_module(net)
 """
@@ -653,6 +660,17 @@ class Network(nn.Module):
             tree = self.tree_lstm.roots(forest, adjacency, node_order, edge_order)
             return self.head(agents_attr, tree, valid_actions, mode, u, value=False)[2]
 
+    def rollout(self, agents_attr, forest, adjacency, node_order, edge_order, valid_actions, u=None, generator=None):
+        """One on-policy step: forward and sample_actions under torch.no_grad(), with either precision of the encoder and of the
+        head.  Returns (actions u8 [B, A] ready for BatchedRailEnv.step(actions, filter_required=True), logp f32 [B, A], entropy f32
+        [B, A], value f32 [B], logits f32 [B, A, 5]); the inputs as for forward (adjacency already modified), valid_actions u8
+        [B, A, 5]; u, generator: as for sample_actions (None: a uniform number per agent from torch's generator).  act stays the
+        reference's draw."""
+        with torch.no_grad():
+            logits, value = self.forward(agents_attr, forest, adjacency, node_order, edge_order)
+            actions, logp, entropy = sample_actions(logits[0], valid_actions, u, generator)
+        return actions, logp, entropy, value, logits[0]
+
     def head_torch(self, agents_attr, tree_embedding):
         """head() through torch's eager ops on the same parameters, with autograd: ([logits], value)"""
         embedding = torch.cat([self.attr_embedding(agents_attr), tree_embedding], dim=2)
@@ -670,3 +688,118 @@ class Network(nn.Module):
             with torch.no_grad():
                 tree = self.tree_lstm.roots(forest, adjacency, node_order, edge_order)
         return self.head_torch(agents_attr, tree)
+
+
+def _rows(name, t, like, dtype):
+    """t as a contiguous tensor of dtype with like's leading shape (the rows), on like's device"""
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.device != like.device or tuple(t.shape) != tuple(like.shape[:-1]):
+        raise ValueError("%s must be a %s tensor of shape %s on %s" % (name, dtype, tuple(like.shape[:-1]), like.device))
+    return t.detach().contiguous()
+
+
+def _check_logits(what, logits, valid_actions):
+    if not isinstance(logits, torch.Tensor) or logits.dtype != torch.float32 or logits.device.type != "cuda" or logits.dim() < 1 \
+            or logits.shape[-1] != ACTIONS or logits.numel() == 0:
+        raise ValueError("%s: logits must be a float32 [..., %d] tensor on a GPU" % (what, ACTIONS))
+    if not isinstance(valid_actions, torch.Tensor) or valid_actions.dtype != torch.uint8 or valid_actions.device != logits.device \
+            or tuple(valid_actions.shape) != tuple(logits.shape):
+        raise ValueError("%s: valid_actions must be a uint8 tensor of shape %s on %s" % (what, tuple(logits.shape), logits.device))
+
+
+def sample_actions(logits, valid_actions, u=None, generator=None):
+    """(actions u8 [B, A], logp f32 [B, A], entropy f32 [B, A]) of logits f32 [B, A, 5] under the mask valid_actions u8 [B, A, 5]
+    (fl_policy_sample, include/flatland_ppo.h): the reference actor's soft draw per agent with that agent's own uniform number, the
+    log-probability of the drawn action and the entropy of the masked softmax, both evaluated in float64.  u: a float64 [B, A] tensor
+    in [0, 1), used as given; a Python float, that value for every agent (hip_backend.POLICY_U_REFERENCE reproduces mode "soft");
+    None: torch.rand in float64 on the logits' device from `generator`.  No gradient flows through it."""
+    _check_logits("sample_actions", logits, valid_actions)
+    dev, shape = logits.device, tuple(logits.shape[:-1])
+    if u is None:
+        u = torch.rand(shape, dtype=torch.float64, device=dev, generator=generator)
+    elif isinstance(u, torch.Tensor):
+        u = _rows("sample_actions: u", u, logits, torch.float64)
+    else:
+        if not 0.0 <= float(u) < 1.0:
+            raise ValueError("sample_actions: u must be in [0, 1), got %r" % (u,))
+        u = torch.full(shape, float(u), dtype=torch.float64, device=dev)
+    actions = torch.empty(shape, dtype=torch.uint8, device=dev)
+    logp = torch.empty(shape, dtype=torch.float32, device=dev)
+    entropy = torch.empty(shape, dtype=torch.float32, device=dev)
+    hip_backend.policy_sample(logits.detach().contiguous(), valid_actions.contiguous(), u, actions, logp, entropy)
+    return actions, logp, entropy
+
+
+class _PpoLoss(torch.autograd.Function):
+    """fl_ppo_loss: the loss with its gradients in one call; backward scales them by the upstream scalar on the device"""
+
+    @staticmethod
+    def forward(ctx, logits, value, valid_actions, actions, old_logp, advantages, returns, mask, clip, vf_coef, ent_coef):
+        dev = logits.device
+        grad_logits = torch.empty(logits.shape, dtype=torch.float32, device=dev)
+        grad_value = None if value is None else torch.empty(value.shape, dtype=torch.float32, device=dev)
+        stats = torch.empty(hip_backend.PPO_STATS, dtype=torch.float64, device=dev)
+        hip_backend.ppo_loss(logits.detach().contiguous(), valid_actions, actions, old_logp, advantages, mask,
+                             None if value is None else value.detach().contiguous(), returns, clip, vf_coef, ent_coef, grad_logits,
+                             grad_value, stats)
+        ctx.save_for_backward(grad_logits, grad_value)
+        ctx.mark_non_differentiable(stats)
+        return stats[3].clone(), stats
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_loss, _g_stats):
+        grad_logits, grad_value = ctx.saved_tensors
+        g = g_loss.to(torch.float32)
+        need = ctx.needs_input_grad
+        return (grad_logits * g if need[0] else None, grad_value * g if grad_value is not None and need[1] else None) + (None,) * 9
+
+
+def ppo_loss(logits, value, valid_actions, actions, old_logp, advantages, returns, mask=None, clip=0.2, vf_coef=0.5, ent_coef=0.01):
+    """(loss, stats) of PPO's clipped surrogate with the value and entropy terms (fl_ppo_loss, include/flatland_ppo.h, which states
+    the formulas): logits f32 [B, A, 5] and value f32 [B] as Network.forward returns them (value None, with returns None: no critic
+    terms), valid_actions u8 [B, A, 5], actions u8 [B, A], old_logp f32 [B, A] and advantages f32 [B, A] of the roll-out, returns f32
+    [B], mask u8 [B, A] or None (0 = the agent's step does not count).  loss: a 0-dim float64 tensor = stats[3]; loss.backward()
+    hands the kernel's gradients, times the upstream scalar, to logits and value.  stats: the float64 [8] device tensor (L_pi, L_v,
+    mean entropy, total, mean old_logp - logp, clipped share, counted rows, rows whose action is not valid)."""
+    _check_logits("ppo_loss", logits, valid_actions)
+    actions = _rows("ppo_loss: actions", actions, logits, torch.uint8)
+    old_logp = _rows("ppo_loss: old_logp", old_logp, logits, torch.float32)
+    advantages = _rows("ppo_loss: advantages", advantages, logits, torch.float32)
+    if mask is not None:
+        mask = _rows("ppo_loss: mask", mask, logits, torch.uint8)
+    if (value is None) != (returns is None):
+        raise ValueError("ppo_loss: value and returns are both given or both None")
+    if value is not None:
+        if not isinstance(value, torch.Tensor) or value.dtype != torch.float32 or value.device != logits.device or value.numel() == 0:
+            raise ValueError("ppo_loss: value must be a float32 tensor on %s" % logits.device)
+        if not isinstance(returns, torch.Tensor) or returns.dtype != torch.float32 or returns.device != logits.device \
+                or tuple(returns.shape) != tuple(value.shape):
+            raise ValueError("ppo_loss: returns must be a float32 tensor of shape %s on %s" % (tuple(value.shape), logits.device))
+        returns = returns.detach().contiguous()
+    for name, c in (("clip", clip), ("vf_coef", vf_coef), ("ent_coef", ent_coef)):
+        if not float("-inf") < float(c) < float("inf") or (name == "clip" and float(c) < 0):
+            raise ValueError("ppo_loss: %s must be finite%s, got %r" % (name, " and >= 0" if name == "clip" else "", c))
+    return _PpoLoss.apply(logits, value, valid_actions.contiguous(), actions, old_logp, advantages, returns, mask, float(clip),
+                          float(vf_coef), float(ent_coef))
+
+
+def gae(rewards, values, dones, gamma=0.99, lam=0.95):
+    """(advantages f32 [T, N], returns f32 [T, N]) of rewards f32 [T, N], values f32 [T + 1, N] (the last row bootstraps) and dones
+    u8 [T, N] (non-zero: the episode of that column ended with step t) by generalised advantage estimation in float64 (fl_gae,
+    include/flatland_ppo.h).  N is whatever the caller estimates per column: envs, or (env, agent) pairs."""
+    if not isinstance(rewards, torch.Tensor) or rewards.dtype != torch.float32 or rewards.dim() != 2 or rewards.numel() == 0 \
+            or rewards.device.type != "cuda":
+        raise ValueError("gae: rewards must be a float32 [T, N] tensor on a GPU")
+    T, N = rewards.shape
+    if not isinstance(values, torch.Tensor) or values.dtype != torch.float32 or values.device != rewards.device \
+            or tuple(values.shape) != (T + 1, N):
+        raise ValueError("gae: values must be a float32 tensor of shape %s on %s" % ((T + 1, N), rewards.device))
+    if not isinstance(dones, torch.Tensor) or dones.dtype != torch.uint8 or dones.device != rewards.device \
+            or tuple(dones.shape) != (T, N):
+        raise ValueError("gae: dones must be a uint8 tensor of shape %s on %s" % ((T, N), rewards.device))
+    if not (0.0 <= float(gamma) <= 1.0 and 0.0 <= float(lam) <= 1.0):
+        raise ValueError("gae: gamma and lam must be in [0, 1], got %r and %r" % (gamma, lam))
+    adv = torch.empty((T, N), dtype=torch.float32, device=rewards.device)
+    ret = torch.empty((T, N), dtype=torch.float32, device=rewards.device)
+    hip_backend.gae(rewards.detach().contiguous(), values.detach().contiguous(), dones.contiguous(), gamma, lam, adv, ret)
+    return adv, ret
