@@ -11,6 +11,7 @@
 
 #include "../../include/flatland_hip.h"
 #include "fl_internal.h"
+#include "fl_policy_layout.h"
 #include "fl_static.h"
 #include "fl_obs.h"
 #include "fl_global.h"
@@ -924,6 +925,20 @@ extern "C" long long fl_debug_static_read(FlStatic *s, const char *name, int b, 
     array("max_branch", std::vector<int>(s->B, fl_static_max_branch(*s)));
     array("Ucap", std::vector<int>(s->B, s->Ucap)); array("Rcap", std::vector<int>(s->B, s->Rcap));
     return n;
+}
+
+// diagnostic, no HIP call: a window on the constexpr tables of fl_policy_layout.h.  table 0 = saved_dev's arrays, 1 = rows_dev's: name,
+// *a = floats a row, *b = floats a row before it; table 2 = the head's parameters: *a = out, *b = in (0: a bias), name "bf16" for a matrix
+// fl_policy_head_pack_bf16 rounds, else "".  i < 0: returns the table's entries; else fills entry i and returns 0; -1: no such table or entry.
+extern "C" int fl_debug_policy_layout(int table, int i, char *name, int name_cap, int *a, int *b) {
+    const int count = table == 0 ? FPL_S_COUNT : table == 1 ? FPL_R_COUNT : table == 2 ? FPH_NPARAMS : -1;
+    if (i < 0 || count < 0) return count;
+    if (i >= count || !name || name_cap < 1 || !a || !b) return -1;
+    const FplArray *t = table == 0 ? FPL_SAVED : FPL_ROWS;
+    if (table == 2) { *a = FPL_PARAMS[i].out; *b = FPL_PARAMS[i].in; }
+    else { *a = t[i].floats; *b = fpl_before(t, i); }
+    snprintf(name, (size_t)name_cap, "%s", table == 2 ? (FPL_PARAMS[i].bf16 ? "bf16" : "") : t[i].name);
+    return 0;
 }
 
 double fl_algorithmic_bytes_per_agent_step(fl_batch *h, int with_cutils_obs, int tree_depth) {

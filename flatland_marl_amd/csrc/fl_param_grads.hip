@@ -4,20 +4,11 @@
 #include "fl_param_grads.h"
 #include "fl_policy_host.h"
 
-// the head's sizes (fl_policy_head.h; that header's kernels belong to another unit)
-#define FPH_ATTR 83
-#define FPH_H 128
-#define FPH_E 256
-#define FPH_ACT 5
-#define FPH_NPARAMS 38
-#define FPH_MAX_A 1024
-
 static_assert(FL_PARAM_GRADS_MAX_SLICES == FPG_MAX_SLICES && FL_PARAM_GRADS_BLOCK == FPG_BLOCK, "the header's constants are the kernel's");
 
 #define FPG_HEAD_AUTO 2          // slices = 0: at most this many for the head (106 tiles) ...
 #define FPG_TREE_AUTO 15         // ... and for the encoder (17 tiles): at most 256 workgroups, one a compute unit (the kernel's registers)
-#define FPG_HEAD_DOUBLES 1698694 // the float64 partials of a slice: sum of P * (Q + 1) over the head's matrices
-#define FPG_TREE_DOUBLES 219776  // ... over the encoder's
+                                 // (FPG_HEAD_DOUBLES, FPG_TREE_DOUBLES, the float64 partials of a slice: fl_policy_layout.h)
 
 // a table under construction: problems in launch order, tiles and workspace offsets counted as they are added
 struct FpgTable {
@@ -95,14 +86,42 @@ static int fpg_launch(const char *fn, FpgTable &tb, int slices, void *workspace_
     return fl_launched(fn);
 }
 
+// the head's 19 gradient problems in launch order (include/flatland_policy_train.h): dW of parameter `param` = sum over the rows of
+// dZ^T [X0 | X1] and db of parameter `param` + 1 = sum dZ, where dZ is array dz of the rows and an X is attr, a saved array or an
+// array of the rows.  padded: dZ's rows are wider than the layer (the last layers' 5 / 1 columns in rows of 8 / 4 floats)
+struct FpgX { enum { NONE, ATTR, SAVED, ROWS } from; int k; };
+struct FpgHeadProblem { int param, dz; FpgX x0, x1; bool padded; };
+#define S(k) {FpgX::SAVED, FPL_S_##k}
+#define R(k) {FpgX::ROWS, FPL_R_##k}
+static constexpr FpgHeadProblem FPG_HEAD[19] = {
+    {0, FPL_R_ATTR_DZ0, {FpgX::ATTR}}, {2, FPL_R_ATTR_DZ2, R(ATTR_H1)}, {4, FPL_R_ATTR_DZ4, R(ATTR_H2)}, {6, FPL_R_ATTR_DZ6, R(ATTR_H3)},
+    {8, FPL_R_DQKV0, S(EMB)}, {10, FPL_R_DO0, S(C0)}, {12, FPL_R_DZ0, S(EMB), R(O0)},
+    {14, FPL_R_DQKV1, S(Y1)}, {16, FPL_R_DO1, S(C1)}, {18, FPL_R_DZ1, S(Y1), R(O1)},
+    {20, FPL_R_DQKV2, S(Y2)}, {22, FPL_R_DO2, S(C2)}, {24, FPL_R_DZ2, S(Y2), R(O2)},
+    {26, FPL_R_ACTOR_DZ0, S(EMB), S(Y3)}, {28, FPL_R_ACTOR_DZ2, R(ACTOR_U1)}, {30, FPL_R_ACTOR_DZ4, R(ACTOR_U2), {}, true},
+    {32, FPL_R_CRITIC_DZ0, S(EMB), S(Y3)}, {34, FPL_R_CRITIC_DZ2, R(CRITIC_U1)}, {36, FPL_R_CRITIC_DZ4, R(CRITIC_U2), {}, true},
+};
+#undef R
+#undef S
+constexpr int fpg_width(FpgX x) {
+    return x.from == FpgX::ATTR ? FPH_ATTR : x.from == FpgX::SAVED ? FPL_SAVED[x.k].floats : x.from == FpgX::ROWS ? FPL_ROWS[x.k].floats : 0;
+}
+// every matrix once, in the parameters' order; [X0 | X1] as wide as the matrix; dZ as wide as the layer, or padded and said so
+constexpr bool fpg_head_fits() {
+    for (int n = 0; n < 19; n++) {
+        const FpgHeadProblem &h = FPG_HEAD[n];
+        const int out = FPL_PARAMS[h.param].out, ldz = FPL_ROWS[h.dz].floats;
+        if (h.param != 2 * n || fpg_width(h.x0) + fpg_width(h.x1) != FPL_PARAMS[h.param].in || (h.padded ? ldz <= out : ldz != out)) return false;
+    }
+    return true;
+}
+static_assert(fpg_head_fits(), "the problems' arrays have the parameters' shapes");
+
 int fl_policy_head_param_grads(int n_envs, int n_agents, const float *attr_dev, const void *saved_dev, const void *rows_dev,
                                int actor, int critic, float *const *grads, int slices, void *workspace_dev, size_t workspace_bytes,
                                void *hip_stream) {
     const char *fn = "fl_policy_head_param_grads";
-    if (n_envs <= 0 || n_agents < 1 || n_agents > FPH_MAX_A || (long long)n_envs * n_agents > INT32_MAX / (3 * FPH_E)) {
-        fl_set_error("%s: bad sizes (n_envs %d, n_agents %d; 1 <= n_envs, 1 <= n_agents <= %d)", fn, n_envs, n_agents, FPH_MAX_A);
-        return FL_ERR_ARG;
-    }
+    if (fph_check_sizes(fn, n_envs, n_agents) != FL_OK) return FL_ERR_ARG;
     if ((actor != 0 && actor != 1) || (critic != 0 && critic != 1)) {
         fl_set_error("%s: actor and critic must be 0 or 1, got %d, %d", fn, actor, critic);
         return FL_ERR_ARG;
@@ -117,43 +136,18 @@ int fl_policy_head_param_grads(int n_envs, int n_agents, const float *attr_dev, 
                          fl_policy_head_param_grads_workspace_bytes(R, slices), "fl_policy_head_param_grads_workspace_bytes") != FL_OK)
         return FL_ERR_ARG;
 
-    const size_t Rs = (size_t)R;
-    const float *sv = (const float *)saved_dev, *rw = (const float *)rows_dev;
-    const float *y[4], *c[3];
-    for (int i = 0; i < 4; i++) y[i] = sv + i * Rs * FPH_E;
-    for (int i = 0; i < 3; i++) c[i] = sv + (4 + i) * Rs * FPH_E;
-    const auto take = [&](size_t n) { const float *q = rw; rw += Rs * n; return q; };      // the order of include/flatland_policy_train.h
-    const float *a_dz[4], *a_h[3];
-    for (int i = 0; i < 3; i++) a_dz[i] = take(FPH_E);
-    a_dz[3] = take(FPH_H);
-    for (int i = 0; i < 3; i++) a_h[i] = take(FPH_E);
-
     FpgTable tb;
-    const float *a_x[4] = {attr_dev, a_h[0], a_h[1], a_h[2]};
-    for (int i = 0; i < 4; i++)
-        tb.place(tb.add(R, a_dz[i], i < 3 ? FPH_E : FPH_H, i < 3 ? FPH_E : FPH_H, a_x[i], i ? FPH_E : FPH_ATTR, i ? FPH_E : FPH_ATTR,
-                        grads[2 * i], grads[2 * i + 1]));
-    for (int i = 0; i < 3; i++) {
-        const float *dqkv = take(3 * FPH_E), *dout = take(FPH_E), *dz = take(FPH_E), *o = take(FPH_E);
-        take(FPH_E); take(FPH_E);                                                          // (dc_i, dy_i)
-        float *const *g = grads + 8 + 6 * i;
-        tb.place(tb.add(R, dqkv, 3 * FPH_E, 3 * FPH_E, y[i], FPH_E, FPH_E, g[0], g[1]));
-        tb.place(tb.add(R, dout, FPH_E, FPH_E, c[i], FPH_E, FPH_E, g[2], g[3]));
-        FpgProblem &m = tb.add(R, dz, FPH_E, FPH_E, y[i], FPH_E, FPH_E, g[4], g[5]);
-        tb.second(m, o, FPH_E, FPH_E);
-        tb.place(m);
-    }
-    take(FPH_E);                                                                           // (dy_3)
-    for (int hd = 0; hd < 2; hd++) {
-        const int last = hd ? 1 : FPH_ACT, last_ld = hd ? 4 : 8;
-        const float *dz0 = take(FPH_E), *dz2 = take(FPH_H), *dz4 = take(last_ld), *u1 = take(FPH_E), *u2 = take(FPH_H);
-        if (!(hd ? critic : actor)) continue;
-        float *const *g = grads + 26 + 6 * hd;
-        FpgProblem &m = tb.add(R, dz0, FPH_E, FPH_E, y[0], FPH_E, FPH_E, g[0], g[1]);
-        tb.second(m, y[3], FPH_E, FPH_E);
-        tb.place(m);
-        tb.place(tb.add(R, dz2, FPH_H, FPH_H, u1, FPH_E, FPH_E, g[2], g[3]));
-        tb.place(tb.add(R, dz4, last_ld, last, u2, FPH_H, FPH_H, g[4], g[5]));
+    const auto at = [&](FpgX x) -> const float * {
+        return x.from == FpgX::ATTR ? attr_dev : x.from == FpgX::SAVED ? fpl_saved((const float *)saved_dev, (size_t)R, x.k)
+                                                                       : fpl_rows((const float *)rows_dev, (size_t)R, x.k);
+    };
+    for (const FpgHeadProblem &h : FPG_HEAD) {
+        if (!on[h.param]) continue;
+        const FpgX dz = {FpgX::ROWS, h.dz};
+        FpgProblem &p = tb.add(R, at(dz), fpg_width(dz), FPL_PARAMS[h.param].out, at(h.x0), fpg_width(h.x0), fpg_width(h.x0), grads[h.param],
+                               grads[h.param + 1]);
+        if (h.x1.from != FpgX::NONE) tb.second(p, at(h.x1), fpg_width(h.x1), fpg_width(h.x1));
+        tb.place(p);
     }
     return fpg_launch(fn, tb, fpg_slices(R, slices, FPG_HEAD_AUTO), workspace_dev, (hipStream_t)hip_stream);
 }
@@ -162,7 +156,7 @@ int fl_tree_lstm_param_grads(int n_rows, const float *x_dev, const int64_t *node
                              const float *dc_dev, const float *dg_dev, const float *q_dev, const int32_t *child_dev,
                              float *const *grads, int slices, void *workspace_dev, size_t workspace_bytes, void *hip_stream) {
     const char *fn = "fl_tree_lstm_param_grads";
-    constexpr int M = 128, IN = 12;
+    constexpr int M = FTL_M, IN = FTL_F;
     if (n_rows <= 0 || n_rows > INT32_MAX / (3 * M)) {
         fl_set_error("%s: bad size (n_rows %d; 1 <= n_rows <= %d)", fn, n_rows, INT32_MAX / (3 * M));
         return FL_ERR_ARG;

@@ -25,20 +25,15 @@
 #pragma once
 #include "fl_internal.h"
 #include "fl_mfma.h"
+#include "fl_policy_layout.h"       // FPH_ATTR, FPH_H, FPH_E, FPH_ACT, FPH_NPARAMS, FPH_MAX_A
 
-#define FPH_ATTR 83
 #define FPH_ATTR_PAD 96             // K of the first layer in LDS, zero filled
-#define FPH_H 128                   // hidden_sz = tree_embedding_sz
-#define FPH_E 256                   // embedding
 #define FPH_HEADS 4
 #define FPH_D 64                    // head size
-#define FPH_ACT 5
 #define FPH_THREADS 256
 #define FPH_ROWS 32
 #define FPH_STRIDE 260
 #define FPH_PSTRIDE 36              // a wave's tile of attention probabilities: 32 x 32, row stride 36
-#define FPH_NPARAMS 38
-#define FPH_MAX_A 1024
 #define FPH_ROW_FLOATS (4 * FPH_E + 3 * FPH_E + 1)   // workspace floats a row: embedding, two block outputs, attention, q k v, value
 
 // parameter indices: the Network's state_dict without tree_lstm.*, in state_dict order

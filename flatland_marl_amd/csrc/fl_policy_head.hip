@@ -23,10 +23,7 @@ size_t fl_policy_head_workspace_bytes(int n_envs, int n_agents) {
 
 // sizes, NULLs and alignment of what the forward's entry points share; `fn` names the caller in the message
 static int fph_check(const char *fn, int n_envs, int n_agents, const float *const *params, const FlPtr *tab, int n) {
-    if (n_envs <= 0 || n_agents < 1 || n_agents > FPH_MAX_A || (long long)n_envs * n_agents > INT32_MAX / (3 * FPH_E)) {
-        fl_set_error("%s: bad sizes (n_envs %d, n_agents %d; 1 <= n_envs, 1 <= n_agents <= %d)", fn, n_envs, n_agents, FPH_MAX_A);
-        return FL_ERR_ARG;
-    }
+    if (fph_check_sizes(fn, n_envs, n_agents) != FL_OK) return FL_ERR_ARG;
     if (!params) { fl_set_error("%s: params is NULL", fn); return FL_ERR_ARG; }
     if (fl_check_ptrs(fn, tab, n) != FL_OK) return FL_ERR_ARG;
     for (int i = 0; i < FPH_NPARAMS; i++)
@@ -48,20 +45,23 @@ static int fph_check_choice(const char *fn, const float *value_dev, const uint8_
     return FL_OK;
 }
 
-// what the three forwards' arguments share; emb, xa, xb are the first three [R][256] arrays of `buf` (the workspace, or the saved
-// buffer).  Returns buf as floats: the caller places the rest (ao, qkv, val, y3) behind them
-static float *fph_fill(FphArgs &a, int n_envs, int n_agents, const float *attr_dev, const float *tree_dev, const float *const *params,
-                       const uint8_t *valid_actions_dev, int select, double u, float *logits_dev, float *value_dev, uint8_t *actions_dev,
-                       void *buf) {
+// what the three forwards' arguments share; the caller places the arrays (emb, xa, xb, ao, qkv, val, y3)
+static void fph_fill(FphArgs &a, int n_envs, int n_agents, const float *attr_dev, const float *tree_dev, const float *const *params,
+                     const uint8_t *valid_actions_dev, int select, double u, float *logits_dev, float *value_dev, uint8_t *actions_dev) {
     a.B = n_envs; a.A = n_agents; a.R = n_envs * n_agents;
     a.select = select; a.u = u;
     a.attr = attr_dev; a.tree = tree_dev;
     for (int i = 0; i < FPH_NPARAMS; i++) a.p[i] = params[i];
     a.valid = valid_actions_dev; a.logits = logits_dev; a.value = value_dev; a.actions = actions_dev;
-    const size_t R = (size_t)a.R;
-    float *f = (float *)buf;
-    a.emb = f; a.xa = f + R * FPH_E; a.xb = f + 2 * R * FPH_E;
     a.ao = nullptr; a.qkv = nullptr; a.y3 = nullptr;
+}
+
+// emb, xa, xb = the first three [R][256] arrays of an inference workspace.  Returns the workspace as floats: the caller places the
+// rest (ao, qkv, val) behind them
+static float *fph_workspace(FphArgs &a, void *workspace_dev) {
+    const size_t R = (size_t)a.R;
+    float *f = (float *)workspace_dev;
+    a.emb = f; a.xa = f + R * FPH_E; a.xb = f + 2 * R * FPH_E;
     return f;
 }
 
@@ -113,8 +113,8 @@ int fl_policy_head(int n_envs, int n_agents, const float *attr_dev, const float 
                        "fl_policy_head_workspace_bytes") != FL_OK) return FL_ERR_ARG;
 
     FphArgs a;
-    float *ws = fph_fill(a, n_envs, n_agents, attr_dev, tree_dev, params, valid_actions_dev, select, u, logits_dev, value_dev, actions_dev,
-                         workspace_dev);
+    fph_fill(a, n_envs, n_agents, attr_dev, tree_dev, params, valid_actions_dev, select, u, logits_dev, value_dev, actions_dev);
+    float *ws = fph_workspace(a, workspace_dev);
     const size_t R = (size_t)a.R;
     a.val = ws + 7 * R * FPH_E;
     float *ao1 = ws + 3 * R * FPH_E, *qkv1 = ws + 4 * R * FPH_E;          // the three blocks share one array of each
@@ -148,13 +148,39 @@ int fl_policy_head_forward_saved(int n_envs, int n_agents, const float *attr_dev
         fl_check_bytes(fn, "saved buffer", saved_bytes, fl_policy_head_saved_bytes(n_envs, n_agents), "fl_policy_head_saved_bytes") != FL_OK)
         return FL_ERR_ARG;
     FphArgs a;
-    float *sv = fph_fill(a, n_envs, n_agents, attr_dev, tree_dev, params, nullptr, 0, 0.0, logits_dev, value_dev, nullptr, saved_dev);
-    const size_t R = (size_t)a.R;
-    a.y3 = sv + 3 * R * FPH_E;
-    float *const ao[3] = {sv + 4 * R * FPH_E, sv + 5 * R * FPH_E, sv + 6 * R * FPH_E};
-    float *const qkv[3] = {sv + 7 * R * FPH_E, sv + 10 * R * FPH_E, sv + 13 * R * FPH_E};
-    a.val = sv + 16 * R * FPH_E;
+    fph_fill(a, n_envs, n_agents, attr_dev, tree_dev, params, nullptr, 0, 0.0, logits_dev, value_dev, nullptr);
+    const auto sv = [&](int k) { return fpl_saved((float *)saved_dev, (size_t)a.R, k); };
+    a.emb = sv(FPL_S_EMB); a.xa = sv(FPL_S_Y1); a.xb = sv(FPL_S_Y2); a.y3 = sv(FPL_S_Y3); a.val = sv(FPL_S_VAL);
+    float *const ao[3] = {sv(FPL_S_C0), sv(FPL_S_C1), sv(FPL_S_C2)}, *const qkv[3] = {sv(FPL_S_QKV0), sv(FPL_S_QKV1), sv(FPL_S_QKV2)};
     return fph_launch(fn, a, ao, qkv, (hipStream_t)hip_stream);
+}
+
+// the backward's arguments: the saved arrays and the rows by name (fl_policy_layout.h)
+static void fpb_fill(FpbArgs &a, int n_envs, int n_agents, const float *attr_dev, const float *const *params, const float *saved,
+                     const float *grad_logits_dev, const float *grad_value_dev, float *grad_tree_dev, float *rows, float *stats) {
+    a.B = n_envs; a.A = n_agents; a.R = n_envs * n_agents;
+    a.attr = attr_dev;
+    for (int i = 0; i < FPH_NPARAMS; i++) a.p[i] = params[i];
+    a.gl = grad_logits_dev; a.gv = grad_value_dev; a.gtree = grad_tree_dev;
+    a.stats = stats;
+    const size_t R = (size_t)a.R;
+    const auto sv = [&](int k) { return fpl_saved(saved, R, k); };
+    const auto rw = [&](int k) { return fpl_rows(rows, R, k); };
+    for (int i = 0; i < 4; i++) a.y[i] = sv(FPL_S_EMB + i);
+    for (int i = 0; i < 3; i++) { a.ao[i] = sv(FPL_S_C0 + i); a.qkv[i] = sv(FPL_S_QKV0 + i); }
+    for (int i = 0; i < 4; i++) a.a_dz[i] = rw(FPL_R_ATTR_DZ0 + i);
+    for (int i = 0; i < 3; i++) a.a_h[i] = rw(FPL_R_ATTR_H1 + i);
+    for (int i = 0; i < 3; i++) {
+        const int b = i * FPL_R_PER_BLOCK;
+        a.dqkv[i] = rw(FPL_R_DQKV0 + b); a.dout[i] = rw(FPL_R_DO0 + b); a.dz[i] = rw(FPL_R_DZ0 + b);
+        a.o[i] = rw(FPL_R_O0 + b); a.dc[i] = rw(FPL_R_DC0 + b); a.dy[i] = rw(FPL_R_DY0 + b);
+    }
+    a.dy[3] = rw(FPL_R_DY3);
+    for (int hd = 0; hd < 2; hd++) {
+        const int h = hd * FPL_R_PER_HEAD;
+        a.h_dz[hd][0] = rw(FPL_R_ACTOR_DZ0 + h); a.h_dz[hd][1] = rw(FPL_R_ACTOR_DZ2 + h); a.h_dz[hd][2] = rw(FPL_R_ACTOR_DZ4 + h);
+        a.h_h[hd][0] = rw(FPL_R_ACTOR_U1 + h); a.h_h[hd][1] = rw(FPL_R_ACTOR_U2 + h);
+    }
 }
 
 int fl_policy_head_backward(int n_envs, int n_agents, const float *attr_dev, const float *tree_dev, const float *const *params,
@@ -173,29 +199,8 @@ int fl_policy_head_backward(int n_envs, int n_agents, const float *attr_dev, con
                        "fl_policy_head_backward_workspace_bytes") != FL_OK) return FL_ERR_ARG;
 
     FpbArgs a;
-    a.B = n_envs; a.A = n_agents; a.R = n_envs * n_agents;
-    a.attr = attr_dev;
-    for (int i = 0; i < FPH_NPARAMS; i++) a.p[i] = params[i];
-    const size_t R = (size_t)a.R;
-    const float *sv = (const float *)saved_dev;
-    for (int i = 0; i < 4; i++) a.y[i] = sv + i * R * FPH_E;
-    for (int i = 0; i < 3; i++) { a.ao[i] = sv + (4 + i) * R * FPH_E; a.qkv[i] = sv + (7 + 3 * i) * R * FPH_E; }
-    a.gl = grad_logits_dev; a.gv = grad_value_dev; a.gtree = grad_tree_dev;
-    float *rw = (float *)rows_dev;
-    const auto take = [&](size_t n) { float *q = rw; rw += R * n; return q; };     // the order of include/flatland_policy_train.h
-    for (int i = 0; i < 3; i++) a.a_dz[i] = take(FPH_E);
-    a.a_dz[3] = take(FPH_H);
-    for (int i = 0; i < 3; i++) a.a_h[i] = take(FPH_E);
-    for (int i = 0; i < 3; i++) {
-        a.dqkv[i] = take(3 * FPH_E); a.dout[i] = take(FPH_E); a.dz[i] = take(FPH_E);
-        a.o[i] = take(FPH_E); a.dc[i] = take(FPH_E); a.dy[i] = take(FPH_E);
-    }
-    a.dy[3] = take(FPH_E);
-    for (int hd = 0; hd < 2; hd++) {
-        a.h_dz[hd][0] = take(FPH_E); a.h_dz[hd][1] = take(FPH_H); a.h_dz[hd][2] = take(hd ? 4 : 8);
-        a.h_h[hd][0] = take(FPH_E); a.h_h[hd][1] = take(FPH_H);
-    }
-    a.stats = (float *)workspace_dev;
+    fpb_fill(a, n_envs, n_agents, attr_dev, params, (const float *)saved_dev, grad_logits_dev, grad_value_dev, grad_tree_dev,
+             (float *)rows_dev, (float *)workspace_dev);
 
     hipStream_t s = (hipStream_t)hip_stream;
     if (fph_allow_lds(fn, k_pb_heads, FPB_LDS_HEADS) != FL_OK || fph_allow_lds(fn, k_pb_block, FPB_LDS_BLOCK) != FL_OK ||
@@ -221,12 +226,8 @@ size_t fl_policy_head_bf16_workspace_bytes(int n_envs, int n_agents) {
     return (R * FPH16_ROW_BYTES + 15) / 16 * 16;
 }
 
-// the parameter index and K of the 16 packed matrices, in state_dict order
-static const int FPH16_SRC[FPH16_NMAT] = {2, 4, 6, 8, 10, 12, 14, 16, 18, 20, 22, 24, 26, 28, 32, 34};
-static constexpr int FPH16_K[FPH16_NMAT] = {256, 256, 256, 256, 256, 512, 256, 256, 512, 256, 256, 512, 512, 256, 512, 256};
-static constexpr int FPH16_ROWS_OF[FPH16_NMAT] = {256, 256, 128, 768, 256, 256, 768, 256, 256, 768, 256, 256, 256, 128, 256, 128};
-constexpr int fph16_elements(int m = 0) { return m == FPH16_NMAT ? 0 : FPH16_ROWS_OF[m] * FPH16_K[m] + fph16_elements(m + 1); }
-static_assert(fph16_elements() == FPH16_PACKED, "the pack kernel writes as many elements as fl_policy_head_bf16_packed_bytes counts");
+static_assert(fpl_bf16_param(FPH16_NMAT - 1) >= 0 && fpl_bf16_param(FPH16_NMAT) < 0, "the parameter table marks the 16 packed matrices");
+static_assert(fpl_bf16_before(FPH16_NMAT) == FPH16_PACKED, "the pack kernel writes as many elements as fl_policy_head_bf16_packed_bytes counts");
 
 static int fph16_check_packed(const char *fn, size_t packed_bytes) {
     return fl_check_bytes(fn, "packed buffer", packed_bytes, fl_policy_head_bf16_packed_bytes(), "fl_policy_head_bf16_packed_bytes");
@@ -236,12 +237,16 @@ int fl_policy_head_pack_bf16(const float *const *params, void *packed_dev, size_
     const char *fn = "fl_policy_head_pack_bf16";
     if (!params) { fl_set_error("%s: params is NULL", fn); return FL_ERR_ARG; }
     for (int m = 0; m < FPH16_NMAT; m++)
-        if (fl_check_param(fn, params, FPH16_SRC[m]) != FL_OK) return FL_ERR_ARG;
+        if (fl_check_param(fn, params, fpl_bf16_param(m)) != FL_OK) return FL_ERR_ARG;
     const FlPtr packed = {packed_dev, "packed", 16};
     if (fl_check_ptrs(fn, &packed, 1) != FL_OK || fph16_check_packed(fn, packed_bytes) != FL_OK) return FL_ERR_ARG;
     FlBf16Pack<FPH16_NMAT> a;
-    for (int m = 0; m < FPH16_NMAT; m++) { a.src[m] = params[FPH16_SRC[m]]; a.K[m] = FPH16_K[m]; }
-    fl_launch_bf16_pack(a, FPH16_ROWS_OF, packed_dev, (hipStream_t)hip_stream);       // (a.off[16] = FPH16_PACKED)
+    int rows[FPH16_NMAT];
+    for (int m = 0; m < FPH16_NMAT; m++) {
+        const int i = fpl_bf16_param(m);
+        a.src[m] = params[i]; a.K[m] = FPL_PARAMS[i].in; rows[m] = FPL_PARAMS[i].out;
+    }
+    fl_launch_bf16_pack(a, rows, packed_dev, (hipStream_t)hip_stream);                // (a.off[16] = FPH16_PACKED)
     return fl_launched(fn);
 }
 
@@ -259,8 +264,8 @@ int fl_policy_head_bf16(int n_envs, int n_agents, const float *attr_dev, const f
         fph16_check_packed(fn, packed_bytes) != FL_OK) return FL_ERR_ARG;
 
     Fph16Args a;
-    float *ws = fph_fill(a, n_envs, n_agents, attr_dev, tree_dev, params, valid_actions_dev, select, u, logits_dev, value_dev, actions_dev,
-                         workspace_dev);
+    fph_fill(a, n_envs, n_agents, attr_dev, tree_dev, params, valid_actions_dev, select, u, logits_dev, value_dev, actions_dev);
+    float *ws = fph_workspace(a, workspace_dev);
     const size_t R = (size_t)a.R;
     a.ao = ws + 3 * R * FPH_E;
     a.qkv16 = (__bf16 *)(ws + 4 * R * FPH_E);

@@ -53,6 +53,12 @@ enum {
     FPH16_ACTOR0 = 1343488, FPH16_ACTOR2 = 1474560, FPH16_CRITIC0 = 1507328, FPH16_CRITIC2 = 1638400,
     FPH16_PACKED = 1671168,             // bf16 elements: 3 342 336 bytes
 };
+// (literals, as the kernels use them: each is the running sum of out * in over the packed matrices of fl_policy_layout.h's table)
+static_assert(FPH16_ATTR2 == fpl_bf16_before(0) && FPH16_ATTR4 == fpl_bf16_before(1) && FPH16_ATTR6 == fpl_bf16_before(2) &&
+              FPH16_BLOCK == fpl_bf16_before(3) && FPH16_OUT_PROJ == fpl_bf16_before(4) - FPH16_BLOCK &&
+              FPH16_ATT_MLP == fpl_bf16_before(5) - FPH16_BLOCK && FPH16_BLOCK_SIZE == fpl_bf16_before(6) - FPH16_BLOCK &&
+              FPH16_ACTOR0 == fpl_bf16_before(12) && FPH16_ACTOR2 == fpl_bf16_before(13) && FPH16_CRITIC0 == fpl_bf16_before(14) &&
+              FPH16_CRITIC2 == fpl_bf16_before(15), "the packed buffer's offsets (FPH16_PACKED: fl_policy_head.hip)");
 
 struct Fph16Args : FphArgs {
     const __bf16 *packed;               // fl_policy_head_pack_bf16's buffer

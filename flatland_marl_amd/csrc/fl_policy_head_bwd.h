@@ -28,8 +28,7 @@
 
 #define FPB_QSTRIDE 772             // LDS row stride of a [32][768] tile (4 mod 32, as 260)
 #define FPB_STATS 12                // workspace floats a row: (max, sum, D) of the row's query in each of the 4 heads
-#define FPB_SAVED_FLOATS (4 * FPH_E + 3 * FPH_E + 9 * FPH_E + 1)
-#define FPB_ROW_FLOATS (1664 + 3 * 2048 + 256 + 776 + 772)
+                                    // (FPB_SAVED_FLOATS, FPB_ROW_FLOATS: fl_policy_layout.h)
 
 struct FpbArgs {
     int B, A, R;

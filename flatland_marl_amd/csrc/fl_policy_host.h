@@ -4,6 +4,16 @@
 #include <stdio.h>
 
 #include "fl_internal.h"
+#include "fl_policy_layout.h"
+
+// (n_envs, n_agents) of the head's entry points: a row index times an array's width stays inside an int
+static inline int fph_check_sizes(const char *fn, int n_envs, int n_agents) {
+    if (n_envs <= 0 || n_agents < 1 || n_agents > FPH_MAX_A || (long long)n_envs * n_agents > INT32_MAX / (3 * FPH_E)) {
+        fl_set_error("%s: bad sizes (n_envs %d, n_agents %d; 1 <= n_envs, 1 <= n_agents <= %d)", fn, n_envs, n_agents, FPH_MAX_A);
+        return FL_ERR_ARG;
+    }
+    return FL_OK;
+}
 
 struct FlPtr {
     const void *p;

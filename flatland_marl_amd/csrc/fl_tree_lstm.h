@@ -26,9 +26,8 @@
 #pragma once
 #include "fl_internal.h"
 #include "fl_mfma.h"
+#include "fl_policy_layout.h"       // FTL_F, FTL_M
 
-#define FTL_F 12
-#define FTL_M 128
 #define FTL_THREADS 256
 #define FTL_ROWS 32                 // nodes a tile (the MFMA's 32 rows)
 #define FTL_STRIDE 420              // floats a staged row: 12 + 3 * 128 = 396 used

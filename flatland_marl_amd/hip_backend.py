@@ -82,6 +82,9 @@ _DEBUG_ABI = {
     "fl_debug_static_reserve": ([vp, i32, i32], i32),
     "fl_debug_static_commit": ([vp], i32),
     "fl_debug_static_read": ([vp, C.c_char_p, i32, vp, C.c_longlong], C.c_longlong),
+    # the library's copy of POLICY_SAVED_LAYOUT (table 0), POLICY_ROWS_LAYOUT (1) and POLICY_HEAD_PARAM_SHAPES (2), csrc/fl_policy_layout.h:
+    # (table, entry or -1 for the count, name out, its capacity, a out, b out)
+    "fl_debug_policy_layout": ([i32, i32, C.c_char_p, i32, C.POINTER(i32), C.POINTER(i32)], i32),
 }
 # name -> (argtypes, restype) of every function include/flatland_policy.h declares, in the header's order
 _POLICY_ABI = {

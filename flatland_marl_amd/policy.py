@@ -548,7 +548,7 @@ class Network(nn.Module):
 
     def _head_weights(self, device):
         sd = dict(self.named_parameters())
-        ref = Network._shapes()
+        ref = dict(zip(HEAD_PARAM_ORDER, hip_backend.POLICY_HEAD_PARAM_SHAPES))
         ws = []
         for name in HEAD_PARAM_ORDER:
             if name not in sd or tuple(sd[name].shape) != ref[name]:
@@ -560,22 +560,6 @@ class Network(nn.Module):
                                 % (name, device, w.dtype, w.device, "" if w.is_contiguous() else ", not contiguous"))
             ws.append(w)
         return ws
-
-    @staticmethod
-    def _shapes():
-        E, H = EMBED, HIDDEN
-        out = {}
-        for i, (o, k) in zip((0, 2, 4, 6), ((2 * H, AGENT_ATTR), (2 * H, 2 * H), (2 * H, 2 * H), (H, 2 * H))):
-            out["attr_embedding.%d.weight" % i], out["attr_embedding.%d.bias" % i] = tuple((o, k)), tuple((o,))
-        for i in range(3):
-            t = "transformer.%d." % i
-            out[t + "attention.in_proj_weight"], out[t + "attention.in_proj_bias"] = tuple((3 * E, E)), tuple((3 * E,))
-            out[t + "attention.out_proj.weight"], out[t + "attention.out_proj.bias"] = tuple((E, E)), tuple((E,))
-            out[t + "att_mlp.0.weight"], out[t + "att_mlp.0.bias"] = tuple((E, 2 * E)), tuple((E,))
-        for n, last in (("actor_net", ACTIONS), ("critic_net", 1)):
-            for i, (o, k) in zip((0, 2, 4), ((2 * H, 2 * E), (H, 2 * H), (last, H))):
-                out["%s.%d.weight" % (n, i)], out["%s.%d.bias" % (n, i)] = tuple((o, k)), tuple((o,))
-        return out
 
     @staticmethod
     def _check_head_inputs(agents_attr, tree_embedding, valid_actions):

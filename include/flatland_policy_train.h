@@ -49,6 +49,7 @@
  *     actor_net        dZ of layer 0 [256], 2 [128], 4 [8: Gl, three zeros];  u1 [256], u2 [128]
  *     critic_net       dZ of layer 0 [256], 2 [128], 4 [4: Gv[e] / A, three zeros];  u1 [256], u2 [128]
  * With Gl NULL the actor's five arrays are not written, with Gv NULL the critic's; everything else always is.
+ * (The library's own copy of both layouts and of the parameters' shapes: flatland_marl_amd/csrc/fl_policy_layout.h.)
  * The 38 parameter gradients are sums over the rows, dW = sum dZ^T X and db = sum dZ, and are left to the caller
  * (fl_policy_head_param_grads of include/flatland_param_grads.h forms them from these very buffers):
  *     attr_embedding.0: X = attr   .2: h1   .4: h2   .6: h3

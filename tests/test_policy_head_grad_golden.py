@@ -262,7 +262,7 @@ def test_parameter_products_from_hand_made_rows(R):
     from flatland_marl_amd import policy
     attr, sv, rw = _hand_rows(R, 3)
     got, want, S = policy.policy_head_param_grads(attr, sv, rw), _expected(attr, sv, rw), _expected(*_abs(attr, sv, rw))
-    shapes = policy.Network._shapes()
+    shapes = dict(zip(policy.HEAD_PARAM_ORDER, hb.POLICY_HEAD_PARAM_SHAPES))
     assert len(got) == 38
     for name, g, w, s in zip(policy.HEAD_PARAM_ORDER, got, want, S):
         assert tuple(g.shape) == shapes[name] and g.dtype == torch.float32, name
