@@ -17,7 +17,21 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "csrc", "gen", "libflatland_gen.so")
-SYMBOLS = ("flg_last_error", "flg_city_positions", "flg_generate", "flg_generate_seeded_rail", "flg_timetable")
+vp, i32, pi32 = C.c_void_p, C.c_int, C.POINTER(C.c_int)
+_mt = [vp, pi32]                                                   # an MT19937 state: key, position
+_generate_in = [i32] * 7 + [vp, vp, i32, vp, vp]                   # flg_generate: width .. speed_probs
+_generate_out = [vp] * 4 + [i32] + [vp] * 6 + [pi32]               # ... grid .. max_episode_steps
+# header file name (include/) -> {name: (argtypes, restype)} of every function it declares, in the header's order
+ABI = {
+    "flatland_gen.h": {
+        "flg_last_error": ([], C.c_char_p),
+        "flg_city_positions": ([i32] * 6 + _mt + [pi32, vp], i32),
+        "flg_generate": (_generate_in + _mt + _generate_out, i32),
+        "flg_generate_seeded_rail": (_generate_in + _mt + _mt + _generate_out, i32),
+        "flg_timetable": ([i32, i32, vp, i32, i32, vp, vp, vp, vp] + _mt + [vp, vp, pi32], i32),
+    },
+}
+SYMBOLS = tuple(ABI["flatland_gen.h"])
 _lib = None
 
 
@@ -35,13 +49,9 @@ def lib():
         if not os.path.exists(LIB_PATH):
             raise FileNotFoundError("%s is missing: build it with flatland_marl_amd/csrc/gen/build.sh" % LIB_PATH)
         L = C.CDLL(LIB_PATH)
-        vp, i32 = C.c_void_p, C.c_int
-        L.flg_last_error.restype = C.c_char_p
-        L.flg_city_positions.argtypes = [i32] * 6 + [vp, C.POINTER(i32), C.POINTER(i32), vp]
-        L.flg_generate.argtypes = [i32] * 7 + [vp, vp, i32, vp, vp, vp, C.POINTER(i32), vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, C.POINTER(i32)]
-        L.flg_generate_seeded_rail.argtypes = [i32] * 7 + [vp, vp, i32, vp, vp, vp, C.POINTER(i32), vp, C.POINTER(i32), vp, vp, vp, vp, i32, vp, vp, vp,
-                                               vp, vp, vp, C.POINTER(i32)]
-        L.flg_timetable.argtypes = [i32, i32, vp, i32, i32, vp, vp, vp, vp, vp, C.POINTER(i32), vp, vp, C.POINTER(i32)]
+        for name, (args, res) in ABI["flatland_gen.h"].items():
+            fn = getattr(L, name)
+            fn.argtypes, fn.restype = args, res
         _lib = L
     return _lib
 

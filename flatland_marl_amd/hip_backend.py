@@ -17,61 +17,120 @@ LIB_PATH = os.path.join(HERE, "csrc", "libflatland_hip.so")
 FL_OK = 0
 ERR_NAMES = {1: "FL_ERR_ARG", 2: "FL_ERR_HIP", 3: "FL_ERR_EPISODE_DONE", 4: "FL_ERR_STATE_SYNC",
              5: "FL_ERR_ZERO_TRANSITION", 6: "FL_ERR_CAPACITY"}
+# the public headers' constants, restated (tests/test_cabi_headers.py holds each to its header); POLICY_SAVED_FLOATS and POLICY_ROW_FLOATS
+# (FL_POLICY_HEAD_SAVED_FLOATS, FL_POLICY_HEAD_ROW_FLOATS) follow from the layout tables below
+FL_STEP_AUTO_RESET, FL_STEP_FILTER_REQUIRED = 1, 2
+FL_OBS_KEEP_TREE_ROWS = 1
 ACTION_ABSENT = 255
 STATE_COLS = 12
 AUX_COLS = 4
+PPO_STATS = 8
+PARAM_GRADS_MAX_SLICES = 32
+POLICY_HEAD_NPARAMS = 38
+POLICY_SELECT = {None: 0, "soft": 1, "hard": 2}      # FL_POLICY_SELECT_NONE, _SOFT, _HARD
+POLICY_U_REFERENCE = 0.3745401188473625      # numpy.random.RandomState(42).random_sample(): the reference seeds before every draw
+# the 16 matrices fl_policy_head_pack_bf16 rounds, as indices into the 38 parameters, in the packed buffer's order
+POLICY_HEAD_BF16_MATRICES = (2, 4, 6, 8, 10, 12, 14, 16, 18, 20, 22, 24, 26, 28, 32, 34)
 STATE_NAMES = ("row", "col", "dir", "state", "malf", "nmalf", "scount", "saved", "arrival",
                "old_row", "old_col", "old_dir")
 
 vp, i32, u32, u64 = C.c_void_p, C.c_int, C.c_uint32, C.c_uint64
 _cutils7 = [vp] * 7        # attr, forest, adjacency, node_order, edge_order, valid_actions, props
 _tree3 = [i32, i32, vp]    # tree_max_depth, tree_pred_depth, tree_out
-# name -> (argtypes, restype) of every function include/flatland_hip.h declares, in the header's order
-_ABI = {
-    "fl_last_error": ([], C.c_char_p),
-    "fl_version": ([], i32),
-    "fl_device_count": ([], i32),
-    "fl_create": ([i32, i32, i32, i32, i32, C.POINTER(vp)], i32),
-    "fl_destroy": ([vp], None),
-    "fl_set_stream": ([vp, vp], i32),
-    "fl_sync": ([vp], i32),
-    "fl_load_env": ([vp, i32] + [vp] * 7 + [i32, u64, i32, i32, vp, i32], i32),
-    "fl_reserve": ([vp, i32, i32], i32),
-    "fl_commit": ([vp], i32),
-    "fl_set_rng": ([vp, vp, vp], i32),
-    "fl_get_rng": ([vp, vp, vp], i32),
-    "fl_reset": ([vp, vp, i32], i32),
-    "fl_reset_dev": ([vp, vp, i32], i32),
-    "fl_step": ([vp, vp, vp, vp, vp, i32], i32),
-    "fl_step_synth": ([vp, u32, u32, i32, vp, vp, vp, i32], i32),
-    "fl_step_obs": ([vp, vp, u32, u32, i32, vp, vp, vp, i32, i32, i32] + _cutils7 + _tree3, i32),
-    "fl_obs_cutils_tree": ([vp, i32, i32] + _cutils7 + _tree3, i32),
-    "fl_metrics": ([vp, vp, i32], i32),
-    "fl_scores": ([vp, vp, i32], i32),
-    "fl_check": ([vp], i32),
-    "fl_obs_cutils": ([vp, i32, i32] + _cutils7, i32),
-    "fl_obs_cutils_handles": ([vp, i32, i32, vp, i32] + _cutils7, i32),
-    "fl_obs_cutils_policy": ([vp, i32, i32] + _cutils7, i32),
-    "fl_obs_tree": ([vp, i32, i32, vp], i32),
-    "fl_obs_tree_handles": ([vp, i32, i32, vp, i32, vp], i32),
-    "fl_obs_global": ([vp, i32, i32, i32, vp, vp, vp], i32),
-    "fl_obs_set_mode": ([vp, i32], i32),
-    "fl_info": ([vp, vp, vp, vp, vp], i32),
-    "fl_policy_pack": ([i32, i32, i32] + [vp] * 7, i32),
-    "fl_tree_lstm_workspace_bytes": ([i32, i32, i32], C.c_size_t),
-    "fl_tree_lstm": ([i32, i32] + [vp] * 12 + [i32, vp, vp, vp, vp, C.c_size_t, vp], i32),
-    "fl_get_state": ([vp, vp, vp], i32),
-    "fl_get_state_aux": ([vp, vp], i32),
-    "fl_set_state": ([vp, vp, vp, vp, vp], i32),
-    "fl_motion_check": ([i32, i32, vp, vp, vp, vp], i32),
-    "fl_distance_map": ([vp, i32, C.POINTER(i32), vp, vp], i32),
-    "fl_distance_map_rebuild": ([vp], i32),
-    "fl_distance_map_rebuild_masked": ([vp, vp], i32),
-    "fl_positions_map": ([vp, i32, vp], i32),
-    "fl_algorithmic_bytes_per_agent_step": ([vp, i32, i32], C.c_double),
+# header file name (include/) -> {name: (argtypes, restype)} of every function it declares, in the header's order
+ABI = {
+    "flatland_hip.h": {
+        "fl_last_error": ([], C.c_char_p),
+        "fl_version": ([], i32),
+        "fl_device_count": ([], i32),
+        "fl_create": ([i32, i32, i32, i32, i32, C.POINTER(vp)], i32),
+        "fl_destroy": ([vp], None),
+        "fl_set_stream": ([vp, vp], i32),
+        "fl_sync": ([vp], i32),
+        "fl_load_env": ([vp, i32] + [vp] * 7 + [i32, u64, i32, i32, vp, i32], i32),
+        "fl_reserve": ([vp, i32, i32], i32),
+        "fl_commit": ([vp], i32),
+        "fl_set_rng": ([vp, vp, vp], i32),
+        "fl_get_rng": ([vp, vp, vp], i32),
+        "fl_reset": ([vp, vp, i32], i32),
+        "fl_reset_dev": ([vp, vp, i32], i32),
+        "fl_step": ([vp, vp, vp, vp, vp, i32], i32),
+        "fl_step_synth": ([vp, u32, u32, i32, vp, vp, vp, i32], i32),
+        "fl_step_obs": ([vp, vp, u32, u32, i32, vp, vp, vp, i32, i32, i32] + _cutils7 + _tree3, i32),
+        "fl_obs_cutils_tree": ([vp, i32, i32] + _cutils7 + _tree3, i32),
+        "fl_metrics": ([vp, vp, i32], i32),
+        "fl_scores": ([vp, vp, i32], i32),
+        "fl_check": ([vp], i32),
+        "fl_obs_cutils": ([vp, i32, i32] + _cutils7, i32),
+        "fl_obs_cutils_handles": ([vp, i32, i32, vp, i32] + _cutils7, i32),
+        "fl_obs_cutils_policy": ([vp, i32, i32] + _cutils7, i32),
+        "fl_obs_tree": ([vp, i32, i32, vp], i32),
+        "fl_obs_tree_handles": ([vp, i32, i32, vp, i32, vp], i32),
+        "fl_obs_global": ([vp, i32, i32, i32, vp, vp, vp], i32),
+        "fl_obs_set_mode": ([vp, i32], i32),
+        "fl_info": ([vp, vp, vp, vp, vp], i32),
+        "fl_policy_pack": ([i32, i32, i32] + [vp] * 7, i32),
+        "fl_tree_lstm_workspace_bytes": ([i32, i32, i32], C.c_size_t),
+        "fl_tree_lstm": ([i32, i32] + [vp] * 12 + [i32, vp, vp, vp, vp, C.c_size_t, vp], i32),
+        "fl_get_state": ([vp, vp, vp], i32),
+        "fl_get_state_aux": ([vp, vp], i32),
+        "fl_set_state": ([vp, vp, vp, vp, vp], i32),
+        "fl_motion_check": ([i32, i32, vp, vp, vp, vp], i32),
+        "fl_distance_map": ([vp, i32, C.POINTER(i32), vp, vp], i32),
+        "fl_distance_map_rebuild": ([vp], i32),
+        "fl_distance_map_rebuild_masked": ([vp, vp], i32),
+        "fl_positions_map": ([vp, i32, vp], i32),
+        "fl_algorithmic_bytes_per_agent_step": ([vp, i32, i32], C.c_double),
+    },
+    "flatland_policy.h": {
+        "fl_policy_head_workspace_bytes": ([i32, i32], C.c_size_t),
+        "fl_policy_head": ([i32, i32, vp, vp, C.POINTER(vp), vp, i32, C.c_double, vp, vp, vp, vp, C.c_size_t, vp], i32),
+    },
+    "flatland_train.h": {
+        "fl_tree_lstm_backward_workspace_bytes": ([i32, i32], C.c_size_t),
+        "fl_tree_lstm_backward": ([i32, i32] + [vp] * 15 + [i32] + [vp] * 7 + [C.c_size_t, vp], i32),
+    },
+    "flatland_policy_train.h": {
+        "fl_policy_head_saved_bytes": ([i32, i32], C.c_size_t),
+        "fl_policy_head_forward_saved": ([i32, i32, vp, vp, C.POINTER(vp), vp, vp, vp, C.c_size_t, vp], i32),
+        "fl_policy_head_backward_rows_bytes": ([i32, i32], C.c_size_t),
+        "fl_policy_head_backward_workspace_bytes": ([i32, i32], C.c_size_t),
+        "fl_policy_head_backward": ([i32, i32, vp, vp, C.POINTER(vp), vp, vp, vp, vp, vp, C.c_size_t, vp, C.c_size_t, vp], i32),
+    },
+    "flatland_predict.h": {
+        "fl_predict": ([vp, i32, i32, i32, i32, vp, vp, vp], i32),
+    },
+    "flatland_wrappers.h": {
+        "fl_action_space": ([vp, i32, i32, i32, vp, vp, vp, vp, vp, vp], i32),
+        "fl_decision_cells": ([vp, i32, i32, vp], i32),
+    },
+    "flatland_policy_bf16.h": {
+        "fl_tree_lstm_bf16_packed_bytes": ([], C.c_size_t),
+        "fl_tree_lstm_pack_bf16": ([vp, vp, vp, vp, C.c_size_t, vp], i32),
+        "fl_tree_lstm_bf16_workspace_bytes": ([i32, i32, i32], C.c_size_t),
+        "fl_tree_lstm_bf16": ([i32, i32] + [vp] * 10 + [C.c_size_t, i32, vp, vp, vp, vp, C.c_size_t, vp], i32),
+    },
+    "flatland_policy_head_bf16.h": {
+        "fl_policy_head_bf16_packed_bytes": ([], C.c_size_t),
+        "fl_policy_head_pack_bf16": ([C.POINTER(vp), vp, C.c_size_t, vp], i32),
+        "fl_policy_head_bf16_workspace_bytes": ([i32, i32], C.c_size_t),
+        "fl_policy_head_bf16": ([i32, i32, vp, vp, C.POINTER(vp), vp, C.c_size_t, vp, i32, C.c_double, vp, vp, vp, vp, C.c_size_t, vp], i32),
+    },
+    "flatland_param_grads.h": {
+        "fl_policy_head_param_grads_workspace_bytes": ([i32, i32], C.c_size_t),
+        "fl_policy_head_param_grads": ([i32, i32, vp, vp, vp, i32, i32, C.POINTER(vp), i32, vp, C.c_size_t, vp], i32),
+        "fl_tree_lstm_param_grads_workspace_bytes": ([i32, i32], C.c_size_t),
+        "fl_tree_lstm_param_grads": ([i32] + [vp] * 8 + [C.POINTER(vp), i32, vp, C.c_size_t, vp], i32),
+    },
+    "flatland_ppo.h": {
+        "fl_policy_sample": ([i32, vp, vp, vp, vp, vp, vp, vp], i32),
+        "fl_ppo_loss_workspace_bytes": ([i32, i32], C.c_size_t),
+        "fl_ppo_loss": ([i32, i32] + [vp] * 8 + [C.c_double] * 3 + [vp, vp, vp, vp, C.c_size_t, vp], i32),
+        "fl_gae": ([i32, i32, vp, vp, vp, C.c_double, C.c_double, vp, vp, vp], i32),
+    },
 }
-# diagnostics the library exports beside the public header
-_DEBUG_ABI = {
+# diagnostics the library exports beside the public headers
+DEBUG_ABI = {
     "fl_debug_last_obs_class": ([vp, vp], i32),
     "fl_debug_last_obs_launch": ([vp, vp, i32], i32),
     # the host half of a handle alone (csrc/fl_static.h), no GPU needed: new(B, A, H, W), free, load (fl_load_env's arguments after the
@@ -86,79 +145,6 @@ _DEBUG_ABI = {
     # (table, entry or -1 for the count, name out, its capacity, a out, b out)
     "fl_debug_policy_layout": ([i32, i32, C.c_char_p, i32, C.POINTER(i32), C.POINTER(i32)], i32),
 }
-# name -> (argtypes, restype) of every function include/flatland_policy.h declares, in the header's order
-_POLICY_ABI = {
-    "fl_policy_head_workspace_bytes": ([i32, i32], C.c_size_t),
-    "fl_policy_head": ([i32, i32, vp, vp, C.POINTER(vp), vp, i32, C.c_double, vp, vp, vp, vp, C.c_size_t, vp], i32),
-}
-# name -> (argtypes, restype) of every function include/flatland_train.h declares, in the header's order
-_TRAIN_ABI = {
-    "fl_tree_lstm_backward_workspace_bytes": ([i32, i32], C.c_size_t),
-    "fl_tree_lstm_backward": ([i32, i32] + [vp] * 15 + [i32] + [vp] * 7 + [C.c_size_t, vp], i32),
-}
-# name -> (argtypes, restype) of every function include/flatland_policy_train.h declares, in the header's order
-_POLICY_TRAIN_ABI = {
-    "fl_policy_head_saved_bytes": ([i32, i32], C.c_size_t),
-    "fl_policy_head_forward_saved": ([i32, i32, vp, vp, C.POINTER(vp), vp, vp, vp, C.c_size_t, vp], i32),
-    "fl_policy_head_backward_rows_bytes": ([i32, i32], C.c_size_t),
-    "fl_policy_head_backward_workspace_bytes": ([i32, i32], C.c_size_t),
-    "fl_policy_head_backward": ([i32, i32, vp, vp, C.POINTER(vp), vp, vp, vp, vp, vp, C.c_size_t, vp, C.c_size_t, vp], i32),
-}
-# name -> (argtypes, restype) of every function include/flatland_predict.h declares, in the header's order
-_PREDICT_ABI = {
-    "fl_predict": ([vp, i32, i32, i32, i32, vp, vp, vp], i32),
-}
-# ... of every function include/flatland_wrappers.h declares
-_WRAPPERS_ABI = {
-    "fl_action_space": ([vp, i32, i32, i32, vp, vp, vp, vp, vp, vp], i32),
-    "fl_decision_cells": ([vp, i32, i32, vp], i32),
-}
-# ... of every function include/flatland_policy_bf16.h declares
-_POLICY_BF16_ABI = {
-    "fl_tree_lstm_bf16_packed_bytes": ([], C.c_size_t),
-    "fl_tree_lstm_pack_bf16": ([vp, vp, vp, vp, C.c_size_t, vp], i32),
-    "fl_tree_lstm_bf16_workspace_bytes": ([i32, i32, i32], C.c_size_t),
-    "fl_tree_lstm_bf16": ([i32, i32] + [vp] * 10 + [C.c_size_t, i32, vp, vp, vp, vp, C.c_size_t, vp], i32),
-}
-# ... of every function include/flatland_policy_head_bf16.h declares
-_POLICY_HEAD_BF16_ABI = {
-    "fl_policy_head_bf16_packed_bytes": ([], C.c_size_t),
-    "fl_policy_head_pack_bf16": ([C.POINTER(vp), vp, C.c_size_t, vp], i32),
-    "fl_policy_head_bf16_workspace_bytes": ([i32, i32], C.c_size_t),
-    "fl_policy_head_bf16": ([i32, i32, vp, vp, C.POINTER(vp), vp, C.c_size_t, vp, i32, C.c_double, vp, vp, vp, vp, C.c_size_t, vp], i32),
-}
-# ... of every function include/flatland_param_grads.h declares
-_PARAM_GRADS_ABI = {
-    "fl_policy_head_param_grads_workspace_bytes": ([i32, i32], C.c_size_t),
-    "fl_policy_head_param_grads": ([i32, i32, vp, vp, vp, i32, i32, C.POINTER(vp), i32, vp, C.c_size_t, vp], i32),
-    "fl_tree_lstm_param_grads_workspace_bytes": ([i32, i32], C.c_size_t),
-    "fl_tree_lstm_param_grads": ([i32] + [vp] * 8 + [C.POINTER(vp), i32, vp, C.c_size_t, vp], i32),
-}
-# ... of every function include/flatland_ppo.h declares
-_PPO_ABI = {
-    "fl_policy_sample": ([i32, vp, vp, vp, vp, vp, vp, vp], i32),
-    "fl_ppo_loss_workspace_bytes": ([i32, i32], C.c_size_t),
-    "fl_ppo_loss": ([i32, i32] + [vp] * 8 + [C.c_double] * 3 + [vp, vp, vp, vp, C.c_size_t, vp], i32),
-    "fl_gae": ([i32, i32, vp, vp, vp, C.c_double, C.c_double, vp, vp, vp], i32),
-}
-SYMBOLS = tuple(_ABI)      # every symbol include/flatland_hip.h declares
-POLICY_SYMBOLS = tuple(_POLICY_ABI)      # ... and include/flatland_policy.h
-TRAIN_SYMBOLS = tuple(_TRAIN_ABI)      # ... and include/flatland_train.h
-POLICY_TRAIN_SYMBOLS = tuple(_POLICY_TRAIN_ABI)      # ... and include/flatland_policy_train.h
-PREDICT_SYMBOLS = tuple(_PREDICT_ABI)      # ... and include/flatland_predict.h
-WRAPPERS_SYMBOLS = tuple(_WRAPPERS_ABI)      # ... and include/flatland_wrappers.h
-POLICY_BF16_SYMBOLS = tuple(_POLICY_BF16_ABI)      # ... and include/flatland_policy_bf16.h
-POLICY_HEAD_BF16_SYMBOLS = tuple(_POLICY_HEAD_BF16_ABI)      # ... and include/flatland_policy_head_bf16.h
-PARAM_GRADS_SYMBOLS = tuple(_PARAM_GRADS_ABI)      # ... and include/flatland_param_grads.h
-PPO_SYMBOLS = tuple(_PPO_ABI)      # ... and include/flatland_ppo.h
-PPO_STATS = 8      # FL_PPO_STATS
-POLICY_HEAD_NPARAMS = 38
-PARAM_GRADS_MAX_SLICES = 32      # FL_PARAM_GRADS_MAX_SLICES
-# the 16 matrices fl_policy_head_pack_bf16 rounds, as indices into the 38 parameters, in the packed buffer's order
-POLICY_HEAD_BF16_MATRICES = (2, 4, 6, 8, 10, 12, 14, 16, 18, 20, 22, 24, 26, 28, 32, 34)
-POLICY_SELECT = {None: 0, "soft": 1, "hard": 2}
-POLICY_U_REFERENCE = 0.3745401188473625      # numpy.random.RandomState(42).random_sample(): the reference seeds before every draw
-
 _lib = None
 
 
@@ -180,6 +166,22 @@ def build(force=False):
     return LIB_PATH
 
 
+def symbols(header=None):
+    """the names one header declares, in its order (None: those of all ten, in the table's order)"""
+    return tuple(name for h in ([header] if header else ABI) for name in ABI[h])
+
+
+def bind(L, groups=None):
+    """argtypes and restype of every function of the groups (keys of ABI or "debug"; None: all of them) on the ctypes.CDLL L,
+    which it returns.  No torch, no GPU."""
+    for g in (*ABI, "debug") if groups is None else groups:
+        for name, (args, res) in (DEBUG_ABI if g == "debug" else ABI[g]).items():
+            fn = getattr(L, name, None)        # (a library from bench.py --lib or a tool's LIB_PATH may predate the newer ones)
+            if fn is not None:
+                fn.argtypes, fn.restype = args, res
+    return L
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -190,13 +192,7 @@ def lib():
         # torch ships its own HIP runtime (same soname as /opt/rocm's): it has to be the one this process loads first,
         # otherwise torch.cuda finds no device once the library below has pulled in the system runtime
         import torch  # noqa: F401
-        L = C.CDLL(LIB_PATH)
-        for name, (args, res) in {**_ABI, **_DEBUG_ABI, **_POLICY_ABI, **_TRAIN_ABI, **_POLICY_TRAIN_ABI, **_PREDICT_ABI,
-                                  **_WRAPPERS_ABI, **_POLICY_BF16_ABI, **_POLICY_HEAD_BF16_ABI, **_PARAM_GRADS_ABI, **_PPO_ABI}.items():
-            fn = getattr(L, name, None)        # (a library from bench.py --lib or a tool's LIB_PATH may predate the newer ones)
-            if fn is not None:
-                fn.argtypes, fn.restype = args, res
-        _lib = L
+        _lib = bind(C.CDLL(LIB_PATH))
     return _lib
 
 
@@ -724,8 +720,8 @@ class BatchedRailEnv:
         """actions: uint8 tensor [B, A] on the device (255 = agent not in the action dict).
         filter_required: ignore the actions of agents without action_required (eval_env.parse_actions)."""
         actions = self._actions(actions)
-        _chk(lib().fl_step(self.h, actions.data_ptr(), self.rewards.data_ptr(), self.dones.data_ptr(),
-                           self.done_all.data_ptr(), int(bool(auto_reset)) | (2 if filter_required else 0)))
+        _chk(lib().fl_step(self.h, actions.data_ptr(), self.rewards.data_ptr(), self.dones.data_ptr(), self.done_all.data_ptr(),
+                           FL_STEP_AUTO_RESET * bool(auto_reset) | FL_STEP_FILTER_REQUIRED * bool(filter_required)))
         return self.rewards, self.dones, self.done_all
 
     def info(self):
@@ -753,8 +749,8 @@ class BatchedRailEnv:
         tree = self._tree_buffer(tree_depth) if tree_depth > 0 else None
         _chk(lib().fl_step_obs(self.h, None if actions is None else actions.data_ptr(), int(seed), int(stream_base), int(kind),
                                self.rewards.data_ptr(), self.dones.data_ptr(), self.done_all.data_ptr(),
-                               int(bool(auto_reset)) | (2 if filter_required else 0), self.max_nodes, self.pred_depth,
-                               *self._cutils_ptrs(o), int(tree_depth), int(tree_pred), None if tree is None else tree.data_ptr()))
+                               FL_STEP_AUTO_RESET * bool(auto_reset) | FL_STEP_FILTER_REQUIRED * bool(filter_required), self.max_nodes,
+                               self.pred_depth, *self._cutils_ptrs(o), int(tree_depth), int(tree_pred), None if tree is None else tree.data_ptr()))
         return self.rewards, self.dones, self.done_all, o, tree
 
     def step_synth(self, seed, stream_base=0, kind=0, auto_reset=True):
@@ -855,7 +851,7 @@ class BatchedRailEnv:
         HAZARD: obs_tree / obs_both / step_obs hand out that very tensor; an in-place op on it (replacing -inf before a network, say) breaks
         the promise silently -- clone it first.  FL_OBS_KEEP_VERIFY=1 (environment, diagnostic) checks the promise before every such launch
         and latches an error for check() when a constant row is no longer -inf or a real row is."""
-        _chk(_sym("fl_obs_set_mode")(self.h, 1 if on else 0))
+        _chk(_sym("fl_obs_set_mode")(self.h, FL_OBS_KEEP_TREE_ROWS if on else 0))
 
     def policy_inputs(self, obs=None):
         """(agents_attr f32[B,A,83], forest f32[B,A,N,12], adjacency i64[B,A,N-1,3], node_order i64[B,A,N],

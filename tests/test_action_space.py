@@ -3,9 +3,7 @@ find_all_cells_where_agent_can_choose :145-176, on_decision_cell :197-198).  The
 every array the real reference recorded (tests/golden/action_space_*.npz, tools/capture_action_space.py), bit for bit; the fixtures
 hold every property a transcription gets wrong easily; fl_action_space and fl_decision_cells are declared, exported and bound; the
 shim has flatland.contrib.wrappers.flatland_wrappers."""
-import ctypes
 import os
-import re
 import subprocess
 import sys
 
@@ -14,6 +12,7 @@ import pytest
 
 from flatland_marl_amd import hip_backend as hb
 from tests import action_space_np as an
+from tests import cabi
 from tests import util
 
 
@@ -140,26 +139,16 @@ def test_the_fixtures_hold_the_map(prop):
 
 
 def test_the_entry_points_are_declared_exported_and_bound():
-    """include/flatland_wrappers.h (a header of its own, like flatland_predict.h: include/flatland_hip.h and its table stay the list
-    tests/test_cabi_symbols.py pins) against its ctypes table and the built library"""
-    hdr = open(os.path.join(util.ROOT, "include", "flatland_wrappers.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
-    hdr = re.sub(r"//[^\n]*", " ", hdr)
-    decls = re.findall(r"([A-Za-z_][A-Za-z_0-9 ]*?[ *]+)(fl_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", hdr)
-    assert [name for _, name, _ in decls] == list(hb.WRAPPERS_SYMBOLS) == ["fl_action_space", "fl_decision_cells"]
-    assert not set(hb.WRAPPERS_SYMBOLS) & (set(hb.SYMBOLS) | set(hb.POLICY_SYMBOLS) | set(hb.TRAIN_SYMBOLS) | set(hb.PREDICT_SYMBOLS))
-    assert '#include "flatland_hip.h"' in hdr
-    params = {name: [" ".join(p.split()) for p in ps.split(",")] for _, name, ps in decls}
+    """include/flatland_wrappers.h (a header of its own, like flatland_predict.h) against its ctypes table: what is this header's own;
+    the types, the counts and the exports are tests/test_cabi_headers.py's"""
+    decls = cabi.declarations("flatland_wrappers.h")
+    assert [name for _, name, _ in decls] == list(hb.symbols("flatland_wrappers.h")) == ["fl_action_space", "fl_decision_cells"]
+    assert '#include "flatland_hip.h"' in cabi.text("flatland_wrappers.h")
+    params = {name: ps for _, name, ps in decls}
     assert params["fl_action_space"] == ["fl_batch *h", "int b0", "int nb", "int elem_kind", "uint8_t *sp_action_dev", "void *sp_dist_dev",
                                          "uint8_t *sp_count_dev", "uint8_t *on_decision_dev", "const uint8_t *reduced_dev",
                                          "uint8_t *actions_dev"]
     assert params["fl_decision_cells"] == ["fl_batch *h", "int b0", "int nb", "uint8_t *cells_dev"]
-    L = ctypes.CDLL(hb.build())
-    for ret, name, _ in decls:
-        assert " ".join(ret.split()) == "int"
-        assert hasattr(L, name), name
-        fn = getattr(hb.lib(), name)
-        assert len(fn.argtypes) == len(params[name]) and fn.restype is ctypes.c_int, name
     for cls, names in ((hb.BatchedRailEnv, ("shortest_path_actions", "on_decision_cell", "decision_cells", "reduced_actions",
                                             "step_shortest_path")),
                        (hb.MixedBatch, ("shortest_path_actions", "on_decision_cell", "decision_cells", "reduced_actions",

@@ -1,7 +1,6 @@
 """CPU: the parameter-gradient entry points (include/flatland_param_grads.h) -- the header, the binding and the library agree; the
 byte functions; the param_grads switch of policy.TreeLSTM / policy.Network; and the numpy restatement of the summation scheme
 (tests/param_grads_np.py) inside its a-priori bound.  The kernels themselves: tests/test_gpu_param_grads.py."""
-import ctypes as C
 import os
 import re
 
@@ -9,8 +8,8 @@ import numpy as np
 import pytest
 
 from flatland_marl_amd import hip_backend as hb
+from tests import cabi
 from tests import param_grads_np as pn
-from tests import util
 
 NAMES = ["fl_policy_head_param_grads_workspace_bytes", "fl_policy_head_param_grads", "fl_tree_lstm_param_grads_workspace_bytes",
          "fl_tree_lstm_param_grads"]
@@ -19,29 +18,13 @@ HEAD_AUTO, TREE_AUTO = 2, 15      # the automatic rule's ceilings, as the header
 TREE_DOUBLES = 384 * 13 + 384 * 384 + 128 * 385 + 128 * 13 + 128 * 128       # W_iou + b, U_iou, W_c + b, W_f + b, U_f
 
 
-def _declarations():
-    hdr = open(os.path.join(util.ROOT, "include", "flatland_param_grads.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
-    hdr = re.sub(r"//[^\n]*", " ", hdr)
-    return hdr, re.findall(r"([A-Za-z_][A-Za-z_0-9 ]*?[ *]+)(fl_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", hdr)
-
-
 def test_header_binding_and_library_agree():
-    hdr, decls = _declarations()
-    assert [n for _, n, _ in decls] == list(hb.PARAM_GRADS_SYMBOLS) == NAMES
-    others = [getattr(hb, k) for k in dir(hb) if k.endswith("_SYMBOLS") and k != "PARAM_GRADS_SYMBOLS"] + [tuple(hb._DEBUG_ABI)]
-    assert len(others) >= 8
-    for group in others:
-        assert not set(hb.PARAM_GRADS_SYMBOLS) & set(group)
+    """what is this header's own; names in order against the table, types, counts, exports: tests/test_cabi_headers.py"""
+    hb.build()                                                             # (the tests below call the library)
+    hdr, decls = cabi.text("flatland_param_grads.h"), cabi.declarations("flatland_param_grads.h")
+    assert [n for _, n, _ in decls] == list(hb.symbols("flatland_param_grads.h")) == NAMES
     assert '#include "flatland_policy_train.h"' in hdr and '#include "flatland_train.h"' in hdr
-    restypes = {"size_t": C.c_size_t, "int": C.c_int}
-    raw = C.CDLL(hb.build())
-    for res, name, params in decls:
-        args, restype = hb._PARAM_GRADS_ABI[name]
-        assert restypes[res.strip()] is restype, name
-        assert len([p for p in params.split(",") if p.strip()]) == len(args), name
-        assert hasattr(raw, name), name
-    params = {n: [" ".join(p.split()) for p in ps.split(",")] for _, n, ps in decls}
+    params = {n: ps for _, n, ps in decls}
     assert params["fl_policy_head_param_grads"] == [
         "int n_envs", "int n_agents", "const float *attr_dev", "const void *saved_dev", "const void *rows_dev", "int actor", "int critic",
         "float *const *grads", "int slices", "void *workspace_dev", "size_t workspace_bytes", "void *hip_stream"]
@@ -49,19 +32,14 @@ def test_header_binding_and_library_agree():
         "int n_rows", "const float *x_dev", "const int64_t *node_order_dev", "const float *h_dev", "const float *da_dev",
         "const float *dc_dev", "const float *dg_dev", "const float *q_dev", "const int32_t *child_dev", "float *const *grads",
         "int slices", "void *workspace_dev", "size_t workspace_bytes", "void *hip_stream"]
-    consts = dict(re.findall(r"#define (FL_PARAM_GRADS_[A-Z_]+) (\d+)", hdr))
-    assert int(consts["FL_PARAM_GRADS_MAX_SLICES"]) == hb.PARAM_GRADS_MAX_SLICES
-    assert int(consts["FL_PARAM_GRADS_BLOCK"]) == pn.REDUCE_BLOCK
     assert callable(hb.policy_head_param_grads) and callable(hb.tree_lstm_param_grads)
 
 
 def test_the_existing_headers_declare_what_they_did():
-    for header, symbols in (("flatland_policy_train.h", hb.POLICY_TRAIN_SYMBOLS), ("flatland_train.h", hb.TRAIN_SYMBOLS)):
-        hdr = open(os.path.join(util.ROOT, "include", header)).read()
-        assert "flatland_param_grads.h" in hdr                                   # the pointer, in the comment
-        code = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
-        assert "param_grads" not in code
-        assert re.findall(r"\b(fl_[a-z_0-9]+)\s*\(", code) == list(symbols)
+    for header in ("flatland_policy_train.h", "flatland_train.h"):
+        assert "flatland_param_grads.h" in open(os.path.join(cabi.INCLUDE, header)).read()      # the pointer, in the comment
+        assert "param_grads" not in cabi.text(header)
+        assert re.findall(r"\b(fl_[a-z_0-9]+)\s*\(", cabi.text(header)) == list(hb.symbols(header))
 
 
 def test_shapes_and_orders_are_the_modules():

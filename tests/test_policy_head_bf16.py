@@ -6,12 +6,12 @@ tests/policy_head_bf16_bounds.py, the head_precision switch of policy.Network, a
 import ctypes as C
 import json
 import os
-import re
 
 import pytest
 import torch
 
 from flatland_marl_amd import hip_backend as hb
+from tests import cabi
 from tests import policy_head_bf16_bounds as pb16
 from tests import policy_head_bf16_torch as ph16
 from tests import policy_head_bounds as pb
@@ -25,19 +25,15 @@ HEADER = os.path.join(util.ROOT, "include", "flatland_policy_head_bf16.h")
 
 
 def test_header_table_and_library_agree():
-    hdr = re.sub(r"/\*.*?\*/", " ", open(HEADER).read(), flags=re.S)
-    decls = re.findall(r"([A-Za-z_][A-Za-z_0-9 ]*?[ *]+)(fl_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", hdr)
-    assert [name for _, name, _ in decls] == list(hb.POLICY_HEAD_BF16_SYMBOLS) == NAMES
-    others = (set(hb.SYMBOLS) | set(hb.POLICY_SYMBOLS) | set(hb.TRAIN_SYMBOLS) | set(hb.POLICY_TRAIN_SYMBOLS) | set(hb.PREDICT_SYMBOLS)
-              | set(hb.WRAPPERS_SYMBOLS) | set(hb.POLICY_BF16_SYMBOLS))
-    assert not set(hb.POLICY_HEAD_BF16_SYMBOLS) & others
-    assert [" ".join(r.split()) for r, _, _ in decls] == ["size_t", "int", "size_t", "int"]
-    nargs = [0 if " ".join(p.split()) == "void" else len(p.split(",")) for _, _, p in decls]
-    assert nargs == [len(hb._POLICY_HEAD_BF16_ABI[n][0]) for n in NAMES] == [0, 4, 2, 16]
-    assert nargs[3] == len(hb._POLICY_ABI["fl_policy_head"][0]) + 2                  # fl_policy_head's, and packed / packed_bytes
-    assert '#include "flatland_hip.h"' in hdr
-    L = C.CDLL(hb.build())
-    assert all(hasattr(L, n) for n in NAMES)
+    """what is this header's own; names in order against the table, types, counts, exports: tests/test_cabi_headers.py"""
+    decls = cabi.declarations("flatland_policy_head_bf16.h")
+    assert [name for _, name, _ in decls] == list(hb.symbols("flatland_policy_head_bf16.h")) == NAMES
+    assert [r for r, _, _ in decls] == ["size_t", "int", "size_t", "int"]
+    nargs = [len(p) for _, _, p in decls]
+    assert nargs == [len(hb.ABI["flatland_policy_head_bf16.h"][n][0]) for n in NAMES] == [0, 4, 2, 16]
+    assert nargs[3] == len(hb.ABI["flatland_policy.h"]["fl_policy_head"][0]) + 2     # fl_policy_head's, and packed / packed_bytes
+    assert '#include "flatland_hip.h"' in cabi.text("flatland_policy_head_bf16.h")
+    hb.build()
     fn = hb.lib().fl_policy_head_bf16
     assert len(fn.argtypes) == 16 and fn.restype is C.c_int and hb.lib().fl_policy_head_bf16_packed_bytes.restype is C.c_size_t
     assert callable(hb.policy_head_pack_bf16) and callable(hb.policy_head_bf16)

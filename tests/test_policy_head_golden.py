@@ -14,6 +14,7 @@ import pytest
 import torch
 
 from flatland_marl_amd import hip_backend as hb
+from tests import cabi
 from tests import policy_head_torch as ph
 from tests import util
 
@@ -48,28 +49,13 @@ def golden_params(g, s):
 
 
 # ---------------------------------------------------------------------------------------------------------------- the C-ABI
-def _declarations():
-    hdr = open(os.path.join(util.ROOT, "include", "flatland_policy.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
-    hdr = re.sub(r"//[^\n]*", " ", hdr)
-    return re.findall(r"([A-Za-z_][A-Za-z_0-9 ]*?[ *]+)(fl_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", hdr)
-
-
 def test_header_binding_and_library_agree():
-    decls = _declarations()
-    assert [name for _, name, _ in decls] == list(hb.POLICY_SYMBOLS) == ["fl_policy_head_workspace_bytes", "fl_policy_head"]
-    assert not set(hb.POLICY_SYMBOLS) & set(hb.SYMBOLS)
-    restypes = {"size_t": C.c_size_t, "int": C.c_int}
-    raw = C.CDLL(hb.build())
-    L = hb.lib()
-    for ret, name, params in decls:
-        assert hasattr(raw, name), name
-        fn = getattr(L, name)
-        assert len(fn.argtypes) == len(params.split(",")), (name, len(fn.argtypes), params)
-        assert fn.restype is restypes[" ".join(ret.split())], (name, ret)
-    hdr = open(os.path.join(util.ROOT, "include", "flatland_policy.h")).read()
-    assert int(re.search(r"#define FL_POLICY_HEAD_NPARAMS (\d+)", hdr).group(1)) == hb.POLICY_HEAD_NPARAMS == len(ph.head_shapes())
-    assert float(re.search(r"#define FL_POLICY_U_REFERENCE ([0-9.]+)", hdr).group(1)) == hb.POLICY_U_REFERENCE == ph.U_REFERENCE
+    """what is this header's own; names in order against the table, types, counts, exports: tests/test_cabi_headers.py"""
+    hb.build()                                                             # (the tests below call the library)
+    names = [name for _, name, _ in cabi.declarations("flatland_policy.h")]
+    assert names == list(hb.symbols("flatland_policy.h")) == ["fl_policy_head_workspace_bytes", "fl_policy_head"]
+    hdr = open(os.path.join(cabi.INCLUDE, "flatland_policy.h")).read()
+    assert hb.POLICY_HEAD_NPARAMS == len(ph.head_shapes()) and hb.POLICY_U_REFERENCE == ph.U_REFERENCE      # (both are the header's)
     assert np.random.RandomState(42).random_sample() == ph.U_REFERENCE
     # the header lists every parameter, in order, with its shape
     for i, (name, shape) in enumerate(ph.head_shapes()):

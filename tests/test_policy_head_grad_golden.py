@@ -2,16 +2,15 @@
 reference Network's own float64 autograd (tests/golden/grad_policy_head_*.npz, tools/capture_policy_head_grads.py); the C-ABI of
 include/flatland_policy_train.h: header, ctypes table and library agree, the byte functions, every refusal; the trainable switch
 of policy.Network; the parameter products from hand-made rows; the chunking arithmetic."""
-import ctypes as C
 import glob
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 from flatland_marl_amd import hip_backend as hb
+from tests import cabi
 from tests import policy_head_grad_torch as pg
 from tests import policy_head_torch as ph
 from tests import util
@@ -87,29 +86,15 @@ def test_restatement_gradients_match_the_reference(name):
 
 
 # ---------------------------------------------------------------------------------------------------------------- the C-ABI
-def _declarations():
-    hdr = open(os.path.join(util.ROOT, "include", "flatland_policy_train.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
-    hdr = re.sub(r"//[^\n]*", " ", hdr)
-    return hdr, re.findall(r"([A-Za-z_][A-Za-z_0-9 ]*?[ *]+)(fl_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", hdr)
-
-
 def test_header_binding_and_library_agree():
-    hdr, decls = _declarations()
-    assert [n for _, n, _ in decls] == list(hb.POLICY_TRAIN_SYMBOLS) == [
+    """what is this header's own; names in order against the table, types, counts, exports: tests/test_cabi_headers.py"""
+    hb.build()                                                             # (the tests below call the library)
+    decls = cabi.declarations("flatland_policy_train.h")
+    assert [n for _, n, _ in decls] == list(hb.symbols("flatland_policy_train.h")) == [
         "fl_policy_head_saved_bytes", "fl_policy_head_forward_saved", "fl_policy_head_backward_rows_bytes",
         "fl_policy_head_backward_workspace_bytes", "fl_policy_head_backward"]
-    others = set(hb.SYMBOLS) | set(hb.POLICY_SYMBOLS) | set(hb.TRAIN_SYMBOLS) | set(hb.PREDICT_SYMBOLS) | set(hb.WRAPPERS_SYMBOLS)
-    assert not set(hb.POLICY_TRAIN_SYMBOLS) & others
-    assert '#include "flatland_policy.h"' in hdr
-    restypes = {"size_t": C.c_size_t, "int": C.c_int}
-    raw = C.CDLL(hb.build())
-    for ret, name, params in decls:
-        assert hasattr(raw, name), name
-        fn = getattr(hb.lib(), name)
-        assert fn.restype is restypes[" ".join(ret.split())], name
-        assert len(fn.argtypes) == len(params.split(",")), name
-    params = {n: [" ".join(p.split()) for p in ps.split(",")] for _, n, ps in decls}
+    assert '#include "flatland_policy.h"' in cabi.text("flatland_policy_train.h")
+    params = {n: ps for _, n, ps in decls}
     assert params["fl_policy_head_backward"] == [
         "int n_envs", "int n_agents", "const float *attr_dev", "const float *tree_dev", "const float *const *params",
         "const void *saved_dev", "const float *grad_logits_dev", "const float *grad_value_dev", "float *grad_tree_dev", "void *rows_dev",
@@ -117,9 +102,6 @@ def test_header_binding_and_library_agree():
     assert params["fl_policy_head_forward_saved"] == [
         "int n_envs", "int n_agents", "const float *attr_dev", "const float *tree_dev", "const float *const *params", "float *logits_dev",
         "float *value_dev", "void *saved_dev", "size_t saved_bytes", "void *hip_stream"]
-    consts = dict(re.findall(r"#define (FL_POLICY_HEAD_[A-Z_]+) (\d+)", hdr))
-    assert int(consts["FL_POLICY_HEAD_SAVED_FLOATS"]) == hb.POLICY_SAVED_FLOATS == 4097
-    assert int(consts["FL_POLICY_HEAD_ROW_FLOATS"]) == hb.POLICY_ROW_FLOATS == 9612
     assert callable(hb.policy_head_forward_saved) and callable(hb.policy_head_backward)
 
 

@@ -1,13 +1,11 @@
 """CPU: the library's layout tables (csrc/fl_policy_layout.h: the arrays of saved_dev and rows_dev, the head's 38 parameters) read
 through fl_debug_policy_layout -- which runs no HIP call -- against hip_backend's literal tables and the public header's constants."""
 import ctypes as C
-import os
-import re
 
 import pytest
 
 from flatland_marl_amd import hip_backend as hb
-from tests import util
+from tests import cabi
 
 SAVED, ROWS, PARAMS = 0, 1, 2
 
@@ -38,9 +36,7 @@ def test_arrays_are_the_python_tables(layout, table, want, total, define):
     got = layout[1](table)
     assert [(n, k) for n, k, _ in got] == list(want)                          # names and widths, in order
     assert [b for _, _, b in got] == _running([k for _, k in want])           # the floats a row before each array
-    hdr = open(os.path.join(util.ROOT, "include", "flatland_policy_train.h")).read()
-    consts = dict(re.findall(r"#define (FL_POLICY_HEAD_[A-Z_]+) (\d+)", hdr))
-    assert got[-1][1] + got[-1][2] == total == int(consts[define])
+    assert got[-1][1] + got[-1][2] == total == int(cabi.define("flatland_policy_train.h", define))
 
 
 def test_array_counts():

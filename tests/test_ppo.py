@@ -2,16 +2,15 @@
 through ctypes without a device (the refusals come before any HIP call); the byte function; and the numpy restatements of
 tests/ppo_np.py pinned: the draw to the reference actor's actions of the fixtures, the closed-form gradients to torch's float64
 autograd of the plain formula, GAE to an independent evaluation.  The kernels themselves: tests/test_gpu_ppo.py."""
-import ctypes as C
 import glob
 import math
 import os
-import re
 
 import numpy as np
 import pytest
 
 from flatland_marl_amd import hip_backend as hb
+from tests import cabi
 from tests import policy_head_torch as pht
 from tests import ppo_np as pn
 from tests import util
@@ -23,29 +22,13 @@ MAX_ROWS = 1 << 28    # FL_PPO_MAX_ROWS
 FIXTURES = sorted(glob.glob(os.path.join(util.ROOT, "tests", "golden", "policy_head_*.npz")))
 
 
-def _declarations():
-    hdr = open(os.path.join(util.ROOT, "include", "flatland_ppo.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
-    hdr = re.sub(r"//[^\n]*", " ", hdr)
-    return hdr, re.findall(r"([A-Za-z_][A-Za-z_0-9 ]*?[ *]+)(fl_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", hdr)
-
-
 def test_header_binding_and_library_agree():
-    hdr, decls = _declarations()
-    assert [n for _, n, _ in decls] == list(hb.PPO_SYMBOLS) == NAMES
-    others = [getattr(hb, k) for k in dir(hb) if k.endswith("_SYMBOLS") and k != "PPO_SYMBOLS"] + [tuple(hb._DEBUG_ABI)]
-    assert len(others) >= 9
-    for group in others:
-        assert not set(hb.PPO_SYMBOLS) & set(group)
-    assert '#include "flatland_policy.h"' in hdr
-    restypes = {"size_t": C.c_size_t, "int": C.c_int}
-    raw = C.CDLL(hb.build())
-    for res, name, params in decls:
-        args, restype = hb._PPO_ABI[name]
-        assert restypes[res.strip()] is restype, name
-        assert len([p for p in params.split(",") if p.strip()]) == len(args), name
-        assert hasattr(raw, name), name
-    params = {n: [" ".join(p.split()) for p in ps.split(",")] for _, n, ps in decls}
+    """what is this header's own; names in order against the table, types, counts, exports: tests/test_cabi_headers.py"""
+    hb.build()                                                             # (the tests below call the library)
+    decls = cabi.declarations("flatland_ppo.h")
+    assert [n for _, n, _ in decls] == list(hb.symbols("flatland_ppo.h")) == NAMES
+    assert '#include "flatland_policy.h"' in cabi.text("flatland_ppo.h")
+    params = {n: ps for _, n, ps in decls}
     assert params["fl_policy_sample"] == [
         "int n_rows", "const float *logits_dev", "const uint8_t *valid_dev", "const double *u_dev", "uint8_t *actions_dev",
         "float *logp_dev", "float *entropy_dev", "void *hip_stream"]
@@ -57,12 +40,6 @@ def test_header_binding_and_library_agree():
     assert params["fl_gae"] == [
         "int n_steps", "int n_cols", "const float *rewards_dev", "const float *values_dev", "const uint8_t *dones_dev", "double gamma",
         "double lam", "float *adv_dev", "float *returns_dev", "void *hip_stream"]
-    # the positions of the doubles in the binding are the header's
-    for name in ("fl_ppo_loss", "fl_gae"):
-        doubles = [i for i, p in enumerate(params[name]) if p.startswith("double ") and "*" not in p]
-        assert [i for i, t in enumerate(hb._PPO_ABI[name][0]) if t is C.c_double] == doubles, name
-    assert int(re.search(r"#define FL_PPO_STATS (\d+)", hdr).group(1)) == hb.PPO_STATS == 8
-    assert re.search(r"#define FL_PPO_MAX_ROWS \(1 << 28\)", hdr)
     assert callable(hb.policy_sample) and callable(hb.ppo_loss) and callable(hb.gae)
     from flatland_marl_amd import policy
     for name in ("sample_actions", "ppo_loss", "gae"):

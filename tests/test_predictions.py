@@ -2,17 +2,13 @@
 The numpy restatement (tests/predictions_np.py) equals every array the real reference recorded (tests/golden/predictions_*.npz,
 tools/capture_predictions.py), bit for bit; the fixtures hold every property a transcription gets wrong easily; fl_predict is declared,
 exported and bound."""
-import ctypes
-import os
-import re
-
 import numpy as np
 import pytest
 
 from flatland_marl_amd import hip_backend as hb
+from tests import cabi
 from tests import predictions_cases as pc
 from tests import predictions_np as pn
-from tests import util
 
 
 def test_every_source_is_there():
@@ -95,20 +91,11 @@ def test_get_handle_keys():
 
 
 def test_fl_predict_is_declared_exported_and_bound():
-    """include/flatland_predict.h (a header of its own, like flatland_policy.h and flatland_train.h: include/flatland_hip.h and its
-    table stay the list tests/test_cabi_symbols.py pins) against its ctypes table and the built library"""
-    hdr = open(os.path.join(util.ROOT, "include", "flatland_predict.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
-    decls = re.findall(r"([A-Za-z_][A-Za-z_0-9 ]*?[ *]+)(fl_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", hdr)
-    assert [name for _, name, _ in decls] == list(hb.PREDICT_SYMBOLS) == ["fl_predict"]
-    assert not set(hb.PREDICT_SYMBOLS) & (set(hb.SYMBOLS) | set(hb.POLICY_SYMBOLS) | set(hb.TRAIN_SYMBOLS))
-    ret, _, params = decls[0]
-    assert " ".join(ret.split()) == "int"
-    assert [" ".join(p.split()) for p in params.split(",")] == [
+    """include/flatland_predict.h (a header of its own, like flatland_policy.h and flatland_train.h) against its ctypes table: what is
+    this header's own; the types, the counts and the exports are tests/test_cabi_headers.py's"""
+    decls = cabi.declarations("flatland_predict.h")
+    assert [name for _, name, _ in decls] == list(hb.symbols("flatland_predict.h")) == ["fl_predict"]
+    assert decls[0][2] == [
         "fl_batch *h", "int b0", "int nb", "int max_depth", "int elem_kind", "void *pred_dev", "int32_t *path_dev", "int32_t *path_len_dev"]
-    assert '#include "flatland_hip.h"' in hdr
-    L = ctypes.CDLL(hb.build())
-    assert hasattr(L, "fl_predict")
-    fn = hb.lib().fl_predict
-    assert len(fn.argtypes) == 8 and fn.restype is ctypes.c_int
+    assert '#include "flatland_hip.h"' in cabi.text("flatland_predict.h")
     assert callable(getattr(hb.BatchedRailEnv, "predictions")) and callable(getattr(hb.MixedBatch, "predictions"))

@@ -26,13 +26,7 @@ STAGED = ("T", "mt_pos", "mt", "malf_thr", "malf_min", "malf_max", "U", "R", "in
 
 
 def _lib():
-    L = ctypes.CDLL(hb.LIB_PATH)       # plain dlopen: no torch, no GPU
-    for name, (args, res) in hb._DEBUG_ABI.items():
-        if name.startswith("fl_debug_static_"):
-            fn = getattr(L, name)
-            fn.argtypes, fn.restype = args, res
-    L.fl_last_error.restype = ctypes.c_char_p
-    return L
+    return hb.bind(ctypes.CDLL(hb.LIB_PATH), ("flatland_hip.h", "debug"))       # plain dlopen: no torch, no GPU
 
 
 class Static:

@@ -5,13 +5,13 @@ call), the precision switch of policy.TreeLSTM / policy.Network, the emulation t
 import ctypes as C
 import json
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 from flatland_marl_amd import hip_backend as hb
+from tests import cabi
 from tests import test_gpu_tree_lstm_bf16 as gpu
 from tests import tree_lstm_bf16_torch as tl16
 from tests import tree_lstm_forests as tf
@@ -23,19 +23,14 @@ NAMES = ["fl_tree_lstm_bf16_packed_bytes", "fl_tree_lstm_pack_bf16", "fl_tree_ls
 
 
 def test_header_table_and_library_agree():
-    hdr = open(os.path.join(util.ROOT, "include", "flatland_policy_bf16.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
-    decls = re.findall(r"([A-Za-z_][A-Za-z_0-9 ]*?[ *]+)(fl_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", hdr)
-    assert [name for _, name, _ in decls] == list(hb.POLICY_BF16_SYMBOLS) == NAMES
-    others = (set(hb.SYMBOLS) | set(hb.POLICY_SYMBOLS) | set(hb.TRAIN_SYMBOLS) | set(hb.POLICY_TRAIN_SYMBOLS) | set(hb.PREDICT_SYMBOLS)
-              | set(hb.WRAPPERS_SYMBOLS))
-    assert not set(hb.POLICY_BF16_SYMBOLS) & others
-    assert [" ".join(r.split()) for r, _, _ in decls] == ["size_t", "int", "size_t", "int"]
-    nargs = [0 if " ".join(p.split()) == "void" else len(p.split(",")) for _, _, p in decls]
-    assert nargs == [len(hb._POLICY_BF16_ABI[n][0]) for n in NAMES] == [0, 6, 3, 20]
-    assert '#include "flatland_hip.h"' in hdr
-    L = C.CDLL(hb.build())
-    assert all(hasattr(L, n) for n in NAMES)
+    """what is this header's own; names in order against the table, types, counts, exports: tests/test_cabi_headers.py"""
+    decls = cabi.declarations("flatland_policy_bf16.h")
+    assert [name for _, name, _ in decls] == list(hb.symbols("flatland_policy_bf16.h")) == NAMES
+    assert [r for r, _, _ in decls] == ["size_t", "int", "size_t", "int"]
+    nargs = [len(p) for _, _, p in decls]
+    assert nargs == [len(hb.ABI["flatland_policy_bf16.h"][n][0]) for n in NAMES] == [0, 6, 3, 20]
+    assert '#include "flatland_hip.h"' in cabi.text("flatland_policy_bf16.h")
+    hb.build()
     fn = hb.lib().fl_tree_lstm_bf16
     assert len(fn.argtypes) == 20 and fn.restype is C.c_int
     assert hb.lib().fl_tree_lstm_bf16_packed_bytes() == 2 * (384 * 384 + 128 * 384 + 128 * 128) == 425984

@@ -9,13 +9,13 @@ to <= 8e-16 of each gradient's max-abs on the weird / chain / rand / mixpad fore
 import ctypes as C
 import glob
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 from flatland_marl_amd import hip_backend as hb
+from tests import cabi
 from tests import tree_lstm_grad_torch as tg
 from tests import util
 from tests.test_tree_lstm_golden import golden_inputs
@@ -101,27 +101,12 @@ def test_float32_restatement_is_close():
 
 
 # ---------------------------------------------------------------------------------------------------------------- the C-ABI
-def _declarations():
-    hdr = open(os.path.join(util.ROOT, "include", "flatland_train.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
-    hdr = re.sub(r"//[^\n]*", " ", hdr)
-    return re.findall(r"([A-Za-z_][A-Za-z_0-9 ]*?[ *]+)(fl_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", hdr)
-
-
 def test_header_binding_and_library_agree():
-    decls = _declarations()
-    assert [name for _, name, _ in decls] == list(hb.TRAIN_SYMBOLS) == ["fl_tree_lstm_backward_workspace_bytes", "fl_tree_lstm_backward"]
-    assert not set(hb.TRAIN_SYMBOLS) & (set(hb.SYMBOLS) | set(hb.POLICY_SYMBOLS))
-    restypes = {"size_t": C.c_size_t, "int": C.c_int}
-    raw = C.CDLL(hb.build())
-    L = hb.lib()
-    for ret, name, params in decls:
-        assert hasattr(raw, name), name
-        fn = getattr(L, name)
-        assert len(fn.argtypes) == len(params.split(",")), (name, len(fn.argtypes), params)
-        assert fn.restype is restypes[" ".join(ret.split())], (name, ret)
-    hdr = open(os.path.join(util.ROOT, "include", "flatland_train.h")).read()
-    assert "solution/nn/TreeLSTM.py:33-154" in hdr
+    """what is this header's own; names in order against the table, types, counts, exports: tests/test_cabi_headers.py"""
+    hb.build()                                                             # (the tests below call the library)
+    names = [name for _, name, _ in cabi.declarations("flatland_train.h")]
+    assert names == list(hb.symbols("flatland_train.h")) == ["fl_tree_lstm_backward_workspace_bytes", "fl_tree_lstm_backward"]
+    assert "solution/nn/TreeLSTM.py:33-154" in open(os.path.join(cabi.INCLUDE, "flatland_train.h")).read()
 
 
 FAKE = 0x10000      # 16-byte aligned, never dereferenced

@@ -205,9 +205,7 @@ def main():
     dev = torch.device("cuda:0")
     parent = None
     if args.parent_lib:
-        parent = C.CDLL(os.path.abspath(args.parent_lib))
-        for name in ("fl_tree_lstm", "fl_tree_lstm_workspace_bytes"):
-            getattr(parent, name).argtypes, getattr(parent, name).restype = hb._ABI[name]
+        parent = hb.bind(C.CDLL(os.path.abspath(args.parent_lib)))
     t0, results, skipped = time.perf_counter(), dict(head=[], tree=[]), []
     jobs = [("head", s) for s in HEAD_SHAPES] + [("tree", s) for s in TREE_SHAPES]
     for kind, shape in jobs:

@@ -55,13 +55,9 @@ def median_events(fn, warmup, n, before=None):
 
 
 def inference_call(L, vp, attr, tree, plist, valid, mode):
-    """a closure that enqueues fl_policy_head of library L on the current stream with buffers allocated here"""
+    """a closure that enqueues fl_policy_head of library L (bound: hip_backend.bind) on the current stream with buffers allocated here"""
     import torch
     B, A = attr.shape[:2]
-    L.fl_policy_head_workspace_bytes.restype = C.c_size_t
-    L.fl_policy_head_workspace_bytes.argtypes = [C.c_int, C.c_int]
-    L.fl_policy_head.argtypes = [C.c_int, C.c_int, vp, vp, C.POINTER(vp), vp, C.c_int, C.c_double, vp, vp, vp, vp, C.c_size_t, vp]
-    L.fl_policy_head.restype = C.c_int
     n = L.fl_policy_head_workspace_bytes(B, A)
     ws = torch.empty(n, dtype=torch.uint8, device=attr.device)
     logits = torch.empty((B, A, 5), device=attr.device)
@@ -102,11 +98,9 @@ def main():
     rows_out, ab = [], {}
     train = {"this": (fwd_saved, bwd)}
     if args.parent_lib:
-        P = C.CDLL(os.path.abspath(args.parent_lib))
-        for name, (argtypes, restype) in hb._POLICY_TRAIN_ABI.items():
-            getattr(P, name).argtypes, getattr(P, name).restype = argtypes, restype
+        P = hb.bind(C.CDLL(os.path.abspath(args.parent_lib)))
         train["parent"] = (P.fl_policy_head_forward_saved, P.fl_policy_head_backward)
-    libs = [(p, C.CDLL(os.path.abspath(p))) for p in args.inference_libs]
+    libs = [(p, hb.bind(C.CDLL(os.path.abspath(p)))) for p in args.inference_libs]
     for label, B, A in SHAPES:
         attr, tree, valid = (torch.from_numpy(x).to(dev) for x in synth_inputs(B, A, 11))
         g = torch.Generator().manual_seed(3)

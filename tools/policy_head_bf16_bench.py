@@ -77,12 +77,9 @@ def outputs(B, A, dev):
 
 
 def f32_call(L, x, w):
-    """a closure that enqueues fl_policy_head of library L on the current stream with buffers allocated here"""
+    """a closure that enqueues fl_policy_head of library L (bound: hip_backend.bind) on the current stream with buffers allocated here"""
     import torch
     vp = C.c_void_p
-    L.fl_policy_head_workspace_bytes.restype, L.fl_policy_head_workspace_bytes.argtypes = C.c_size_t, [C.c_int] * 2
-    L.fl_policy_head.restype = C.c_int
-    L.fl_policy_head.argtypes = [C.c_int, C.c_int, vp, vp, C.POINTER(vp), vp, C.c_int, C.c_double, vp, vp, vp, vp, C.c_size_t, vp]
     B, A = x[0].shape[:2]
     ws = torch.empty(max(L.fl_policy_head_workspace_bytes(B, A), 16), dtype=torch.uint8, device=x[0].device)
     out = outputs(B, A, x[0].device)
@@ -96,12 +93,10 @@ def f32_call(L, x, w):
     return call, out
 
 
-def bf16_call(hb, L, x, w):
+def bf16_call(L, x, w):
     """the same for fl_policy_head_bf16 of library L, on the buffer that L's own fl_policy_head_pack_bf16 packs here"""
     import torch
     vp = C.c_void_p
-    for name, (argtypes, restype) in hb._POLICY_HEAD_BF16_ABI.items():
-        getattr(L, name).argtypes, getattr(L, name).restype = argtypes, restype
     fn = L.fl_policy_head_bf16
     B, A = x[0].shape[:2]
     ws = torch.empty(max(L.fl_policy_head_bf16_workspace_bytes(B, A), 16), dtype=torch.uint8, device=x[0].device)
@@ -125,7 +120,7 @@ def kernels_only(args):
     from flatland_marl_amd import hip_backend as hb
     for label, B, A in SHAPES:
         x, w = setup(B, A)
-        for call, _ in (f32_call(hb.lib(), x, w), bf16_call(hb, hb.lib(), x, w)):
+        for call, _ in (f32_call(hb.lib(), x, w), bf16_call(hb.lib(), x, w)):
             for _ in range(args.warmup + args.launches):
                 call()
             torch.cuda.synchronize()
@@ -181,7 +176,7 @@ def main():
         kernels_only(args)
         return
     from flatland_marl_amd import hip_backend as hb
-    parent = C.CDLL(os.path.abspath(args.parent_lib)) if args.parent_lib else None
+    parent = hb.bind(C.CDLL(os.path.abspath(args.parent_lib))) if args.parent_lib else None
     parent_has_bf16 = parent is not None and hasattr(parent, "fl_policy_head_bf16")
     rows, pack_us = [], None
     for label, B, A in SHAPES:
@@ -195,8 +190,8 @@ def main():
         if parent is not None:
             calls.append(("parent_f32", f32_call(parent, x, w)))
         if parent_has_bf16:
-            calls.append(("parent_bf16", bf16_call(hb, parent, x, w)))
-        calls += [("f32", f32_call(hb.lib(), x, w)), ("bf16", bf16_call(hb, hb.lib(), x, w))]
+            calls.append(("parent_bf16", bf16_call(parent, x, w)))
+        calls += [("f32", f32_call(hb.lib(), x, w)), ("bf16", bf16_call(hb.lib(), x, w))]
         med = {k: [] for k, _ in calls}
         for _ in range(args.rounds):
             for k, (call, _) in calls:

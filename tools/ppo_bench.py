@@ -152,7 +152,7 @@ def main():
     from flatland_marl_amd import hip_backend as hb
     assert torch.cuda.is_available(), "tools/ppo_bench.py needs a GPU"
     dev = torch.device("cuda:0")
-    parent = C.CDLL(os.path.abspath(args.parent_lib)) if args.parent_lib else None
+    parent = hb.bind(C.CDLL(os.path.abspath(args.parent_lib))) if args.parent_lib else None
     hb.lib()
     results = []
     for label, B, A in SHAPES:

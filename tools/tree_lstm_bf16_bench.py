@@ -68,12 +68,9 @@ def inner_tiles(node_order, G):
 
 
 def f32_call(L, x, w, roots_only):
-    """a closure that enqueues fl_tree_lstm of library L on the current stream with buffers allocated here"""
+    """a closure that enqueues fl_tree_lstm of library L (bound: hip_backend.bind) on the current stream with buffers allocated here"""
     import torch
     vp = C.c_void_p
-    L.fl_tree_lstm_workspace_bytes.restype, L.fl_tree_lstm_workspace_bytes.argtypes = C.c_size_t, [C.c_int] * 3
-    L.fl_tree_lstm.restype = C.c_int
-    L.fl_tree_lstm.argtypes = [C.c_int, C.c_int] + [vp] * 12 + [C.c_int, vp, vp, vp, vp, C.c_size_t, vp]
     N = x[0].shape[-2]
     T = x[0].numel() // (N * 12)
     n = L.fl_tree_lstm_workspace_bytes(T, N, roots_only)
@@ -88,12 +85,10 @@ def f32_call(L, x, w, roots_only):
     return call, h
 
 
-def bf16_call(hb, L, x, w, roots_only):
+def bf16_call(L, x, w, roots_only):
     """the same for fl_tree_lstm_bf16 of library L, on the buffer that L's own fl_tree_lstm_pack_bf16 packs here"""
     import torch
     vp = C.c_void_p
-    for name, (argtypes, restype) in hb._POLICY_BF16_ABI.items():
-        getattr(L, name).argtypes, getattr(L, name).restype = argtypes, restype
     fn = L.fl_tree_lstm_bf16
     N = x[0].shape[-2]
     T = x[0].numel() // (N * 12)
@@ -168,7 +163,7 @@ def main():
     cu = torch.cuda.get_device_properties(0).multi_processor_count
     params = seeded_params(7)
     w = [params[k].to(dev).contiguous() for k in PARAM_ORDER]
-    parent = C.CDLL(os.path.abspath(args.parent_lib)) if args.parent_lib else None
+    parent = hb.bind(C.CDLL(os.path.abspath(args.parent_lib))) if args.parent_lib else None
     parent_has_bf16 = parent is not None and hasattr(parent, "fl_tree_lstm_bf16")
     rows = []
     for label, wl_name, B, N in SHAPES:
@@ -183,8 +178,8 @@ def main():
             if parent is not None:
                 calls.append(("parent_f32", f32_call(parent, x, w, ro)))
             if parent_has_bf16:
-                calls.append(("parent_bf16", bf16_call(hb, parent, x, w, ro)))
-            calls += [("f32", f32_call(hb.lib(), x, w, ro)), ("bf16", bf16_call(hb, hb.lib(), x, w, ro))]
+                calls.append(("parent_bf16", bf16_call(parent, x, w, ro)))
+            calls += [("f32", f32_call(hb.lib(), x, w, ro)), ("bf16", bf16_call(hb.lib(), x, w, ro))]
             med = {k: [] for k, _ in calls}
             for _ in range(args.rounds):
                 for k, (call, _) in calls:
