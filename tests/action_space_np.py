@@ -60,12 +60,7 @@ def wrapped_episode(name="wrapped_episode"):
 def static_of(g, agents=None):
     """a static description BatchedRailEnv loads: the group's map and its agents (`agents`: a subset of them); what the action space
     does not read (timetable, malfunction parameters, the RNG) is filled in"""
-    sel = slice(None) if agents is None else list(agents)
-    A = len(g["slot"][sel])
-    return dict(grid=g["grid"], init_pos=g["init_pos"][sel], init_dir=g["init_dir"][sel], target=g["target"][sel], speed=g["speed"][sel],
-                earliest=np.zeros(A, dtype=np.int32), latest=np.full(A, 1000, dtype=np.int32), T=np.int32(2000),
-                malf_rate=np.float64(0.0), malf_min=np.int32(0), malf_max=np.int32(0),
-                mt_key=np.arange(624, dtype=np.uint32), mt_pos=np.int32(624))
+    return util.group_static(g, agents)
 
 
 # ---- the restatement

@@ -18,7 +18,7 @@ it copy none of the launcher's arithmetic.
 """
 import numpy as np
 
-from tests import handmaps
+from tests import handmaps, util
 
 WAITING, READY, MALF_OFF, MOVING, STOPPED, MALF, DONE = range(7)
 KINDS = (WAITING, MOVING, READY, STOPPED, MALF_OFF, MALF, DONE)
@@ -29,12 +29,8 @@ SWEEPS = [(H, W, A) for H, W in ((2, 3), (3, 5), (5, 5)) for A in (1, 2, 5, 27)]
 
 
 def _static(grid, ip, idir, tg, speed):
-    A = len(idir)
     W = grid.shape[1]
-    return dict(grid=grid, init_pos=np.stack([ip // W, ip % W], axis=1).astype(np.int32), init_dir=idir.astype(np.int32),
-                target=np.stack([tg // W, tg % W], axis=1).astype(np.int32), speed=speed.astype(np.float64),
-                earliest=np.zeros(A, dtype=np.int32), latest=np.full(A, 200, dtype=np.int32), T=400, malf_rate=0.0, malf_min=0, malf_max=0,
-                mt_key=np.arange(624, dtype=np.uint32), mt_pos=624)
+    return util.plain_static(grid, np.stack([ip // W, ip % W, idir, tg // W, tg % W], axis=1), speed)
 
 
 def _rows(W, kind, cell, dr, malf):

@@ -47,7 +47,7 @@ import os
 
 import numpy as np
 
-from tests import handmaps
+from tests import handmaps, util
 
 WAITING, READY, MALF_OFF, MOVING, STOPPED, MALF, DONE = range(7)
 N, E, S, W = 0, 1, 2, 3
@@ -117,16 +117,12 @@ VARIANTS = {
 
 def static_of(map_name, set_name, variant):
     """the static description BatchedRailEnv / OracleEnv take (no malfunctions are drawn, a long episode)"""
-    a = np.array(AGENTS[map_name][set_name], dtype=np.int32)
     v = VARIANTS[(map_name, set_name)][variant]
-    m = MAPS[map_name]()
-    target = np.array(v["target"], dtype=np.int32) if v["target"] is not None else a[:, 3:5].copy()
-    for (r, c, d, _, _), (tr, tc) in zip(a, target):
-        assert handmaps.nibble(m["grid"][r, c], d) != 0 and m["grid"][tr, tc] != 0
-    A = len(a)
-    return dict(grid=m["grid"], init_pos=a[:, 0:2].copy(), init_dir=a[:, 2].copy(), target=target, speed=np.array(v["speed"], dtype=np.float64),
-                earliest=np.zeros(A, dtype=np.int32), latest=np.full(A, 200, dtype=np.int32), T=400, malf_rate=0.0, malf_min=0, malf_max=0,
-                mt_key=np.arange(624, dtype=np.uint32), mt_pos=624)
+    grid = MAPS[map_name]()["grid"]
+    static = util.plain_static(grid, AGENTS[map_name][set_name], v["speed"], target=v["target"])
+    for (r, c), d, (tr, tc) in zip(static["init_pos"], static["init_dir"], static["target"]):
+        assert handmaps.nibble(grid[r, c], d) != 0 and grid[tr, tc] != 0
+    return static
 
 
 # ---- constructors

@@ -44,8 +44,4 @@ def all_groups():
 def static_of(g):
     """a static description BatchedRailEnv loads: the group's map and agents; what the prediction does not read (timetable, malfunction
     parameters, the RNG) is filled in"""
-    A = len(g["slot"])
-    return dict(grid=g["grid"], init_pos=g["init_pos"], init_dir=g["init_dir"], target=g["target"], speed=g["speed"],
-                earliest=np.zeros(A, dtype=np.int32), latest=np.full(A, 1000, dtype=np.int32), T=np.int32(2000),
-                malf_rate=np.float64(0.0), malf_min=np.int32(0), malf_max=np.int32(0),
-                mt_key=np.arange(624, dtype=np.uint32), mt_pos=np.int32(624))
+    return util.group_static(g)

@@ -20,20 +20,16 @@ def test_every_source_is_there():
     assert an.files() == sorted(an.SOURCES)
 
 
-def _same(mine, ref):
-    return mine.dtype == ref.dtype and mine.shape == ref.shape and mine.tobytes() == ref.tobytes()
-
-
 @pytest.mark.parametrize("source", an.SOURCES)
 def test_restatement_equals_the_reference(source):
     n = 0
     for g in an.groups(source):
         cells = an.decision_cells(g["grid"])
-        assert _same(cells, g["cells"]), g["name"]
+        assert util.same_bits(cells, g["cells"]), g["name"]
         for s in range(len(g["steps"])):
             got = an.action_space(g["grid"], g["dm"], g["slot"], g["init_pos"], g["state"][s], cells)
             for k, mine in zip(an.KINDS, got):
-                assert _same(mine, g[k][s]), (g["name"], int(g["steps"][s]), k)
+                assert util.same_bits(mine, g[k][s]), (g["name"], int(g["steps"][s]), k)
             n += 1
     assert n > 0
 

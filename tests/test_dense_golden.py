@@ -16,13 +16,6 @@ CUTILS = (("attr", "agent_attr", "o_attr"), ("forest", "forest", "o_forest"), ("
           ("node_order", "node_order", "o_node_order"), ("edge_order", "edge_order", "o_edge_order"), ("valid", "valid_actions", "o_valid"))
 
 
-def _same(got, exp, msg):
-    got = np.asarray(got)
-    if not np.array_equal(got, exp):
-        bad = np.argwhere(got != exp)
-        raise AssertionError(f"{msg}: {len(bad)} mismatches, first {bad[0].tolist()}: {got[tuple(bad[0])]} vs {exp[tuple(bad[0])]}")
-
-
 @pytest.mark.parametrize("name", DENSE)
 def test_dense_fixture_is_dense_and_shares_the_head_fixture_env(name):
     fx, head = util.load(name), util.load(HEAD[name])
@@ -46,33 +39,28 @@ def test_oracle_replays_dense_reference_episode(name):
         o = e.obs_cutils(31, 500)          # every step: the deadlock flags are sticky
         T = t + 1
         if T in ss:
-            _same(e.state(), fx["states"][ss[T]], f"{name} T={T} state")
-            _same(rew, fx["rewards"][ss[T]], f"{name} T={T} rewards")
-            _same(done, fx["dones"][ss[T]], f"{name} T={T} dones")
+            util.same(e.state(), fx["states"][ss[T]], f"{name} T={T} state")
+            util.same(rew, fx["rewards"][ss[T]], f"{name} T={T} rewards")
+            util.same(done, fx["dones"][ss[T]], f"{name} T={T} dones")
         if T in os_:
             k = os_[T]
             for ok, _, fk in CUTILS:
-                _same(o[ok], fx[fk][k], f"{name} T={T} {ok}")
-            _same(o["props"][:, 0], fx["o_p_dist_target"][k], f"{name} T={T} dist_target")
-            _same(o["props"][:, 1], fx["o_p_deadlocked"][k], f"{name} T={T} deadlocked")
-            _same(o["props"][:, 2], fx["o_p_ready"][k], f"{name} T={T} ready")
-            _same(e.obs_pytree(3, 30), fx["py_d3_p30"][k], f"{name} T={T} py_d3_p30")
+                util.same(o[ok], fx[fk][k], f"{name} T={T} {ok}")
+            util.same(o["props"][:, 0], fx["o_p_dist_target"][k], f"{name} T={T} dist_target")
+            util.same(o["props"][:, 1], fx["o_p_deadlocked"][k], f"{name} T={T} deadlocked")
+            util.same(o["props"][:, 2], fx["o_p_ready"][k], f"{name} T={T} ready")
+            util.same(e.obs_pytree(3, 30), fx["py_d3_p30"][k], f"{name} T={T} py_d3_p30")
             n += 1
     assert n >= 3
 
 
-def _env(envs, **kw):
-    from flatland_marl_amd.hip_backend import BatchedRailEnv
-    return BatchedRailEnv(envs, **kw)
-
-
 def _check_cutils(o, fx, k, b, msg):
     for _, gk, fk in CUTILS:
-        _same(o[gk].cpu().numpy()[b], fx[fk][k], f"{msg} {gk}")
+        util.same(o[gk].cpu().numpy()[b], fx[fk][k], f"{msg} {gk}")
     pr = o["props"].cpu().numpy()[b]
-    _same(pr[:, 0], fx["o_p_dist_target"][k], f"{msg} dist_target")
-    _same(pr[:, 1], fx["o_p_deadlocked"][k], f"{msg} deadlocked")
-    _same(pr[:, 2], fx["o_p_ready"][k], f"{msg} ready")
+    util.same(pr[:, 0], fx["o_p_dist_target"][k], f"{msg} dist_target")
+    util.same(pr[:, 1], fx["o_p_deadlocked"][k], f"{msg} deadlocked")
+    util.same(pr[:, 2], fx["o_p_ready"][k], f"{msg} ready")
 
 
 @pytest.mark.gpu
@@ -83,7 +71,7 @@ def test_hip_path_replays_dense_reference_episode(name):
     import torch
     fx, head = util.load(name), util.load(HEAD[name])
     st = util.static_of(fx)
-    e_sep, e_fused = _env([st]), _env([st, st])
+    e_sep, e_fused = util.batched([st]), util.batched([st, st])
     ss = {int(t): k for k, t in enumerate(fx["state_steps"])}
     os_ = {int(t): k for k, t in enumerate(fx["obs_steps"])}
     rebuild_at = int(fx["obs_steps"][1]) - 3
@@ -99,32 +87,32 @@ def test_hip_path_replays_dense_reference_episode(name):
         o = e_sep.obs_cutils()
         of, tf = e_fused.obs_both(3, 30)
         if T in ss:
-            _same(e_sep.state()[0][0], fx["states"][ss[T]], f"{name} T={T} state")
-            _same(e_fused.state()[0][1], fx["states"][ss[T]], f"{name} T={T} state (fused batch)")
-            _same(rew.cpu().numpy()[0], fx["rewards"][ss[T]], f"{name} T={T} rewards")
-            _same(done.cpu().numpy()[0], fx["dones"][ss[T]], f"{name} T={T} dones")
+            util.same(e_sep.state()[0][0], fx["states"][ss[T]], f"{name} T={T} state")
+            util.same(e_fused.state()[0][1], fx["states"][ss[T]], f"{name} T={T} state (fused batch)")
+            util.same(rew.cpu().numpy()[0], fx["rewards"][ss[T]], f"{name} T={T} rewards")
+            util.same(done.cpu().numpy()[0], fx["dones"][ss[T]], f"{name} T={T} dones")
         if T in os_:
             k = os_[T]
             _check_cutils(o, fx, k, 0, f"{name} T={T} separate")
-            _same(e_sep.obs_tree(3, 30).cpu().numpy()[0], fx["py_d3_p30"][k], f"{name} T={T} py_d3_p30 separate")
+            util.same(e_sep.obs_tree(3, 30).cpu().numpy()[0], fx["py_d3_p30"][k], f"{name} T={T} py_d3_p30 separate")
             for b in (0, 1):
                 _check_cutils(of, fx, k, b, f"{name} T={T} fused[{b}]")
-                _same(tf.cpu().numpy()[b], fx["py_d3_p30"][k], f"{name} T={T} py_d3_p30 fused[{b}]")
+                util.same(tf.cpu().numpy()[b], fx["py_d3_p30"][k], f"{name} T={T} py_d3_p30 fused[{b}]")
     e_sep.check(); e_fused.check()
-    _same(e_sep.state_aux()[0], fx["o_aux"][-1], f"{name} aux columns at the last snapshot")
+    util.same(e_sep.state_aux()[0], fx["o_aux"][-1], f"{name} aux columns at the last snapshot")
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", DENSE)
 def test_injected_dense_reference_states_reproduce_the_snapshots(name):
     fx = util.load(name)
-    env = _env([util.static_of(fx)])
+    env = util.batched([util.static_of(fx)])
     ss = {int(t): k for k, t in enumerate(fx["state_steps"])}
     for k, T in enumerate(int(t) for t in fx["obs_steps"]):
         env.set_state(fx["states"][ss[T]][None], fx["o_aux"][k][None], np.array([T], dtype=np.int32))
         of, tf = env.obs_both(3, 30)
         _check_cutils(of, fx, k, 0, f"{name} T={T} injected")
-        _same(tf.cpu().numpy()[0], fx["py_d3_p30"][k], f"{name} T={T} injected py_d3_p30")
+        util.same(tf.cpu().numpy()[0], fx["py_d3_p30"][k], f"{name} T={T} injected py_d3_p30")
     env.check()
 
 
@@ -153,7 +141,7 @@ def test_batched_dense_run_matches_oracle_with_depth3_fused_obs_and_autoreset(he
         if b == 2:
             st["malf_rate"] = 1 / 400.0
         envs.append(st)
-    env = _env(envs)
+    env = util.batched(envs)
     oracles = [orc.OracleEnv(st) for st in envs]
     A = env.A
     tcount, resets, peak = [0, 0, 0], 0, 0
@@ -172,15 +160,15 @@ def test_batched_dense_run_matches_oracle_with_depth3_fused_obs_and_autoreset(he
             if chk:
                 st_o = oe.state()
                 peak = max(peak, int((st_o[:, 0] >= 0).sum()))
-                _same(st_g[b], st_o, f"{head} replica {b} iter {it} state")
-                _same(rew[b], r_o, f"{head} replica {b} iter {it} rewards")
-                _same(done[b], d_o, f"{head} replica {b} iter {it} dones")
+                util.same(st_g[b], st_o, f"{head} replica {b} iter {it} state")
+                util.same(rew[b], r_o, f"{head} replica {b} iter {it} rewards")
+                util.same(done[b], d_o, f"{head} replica {b} iter {it} dones")
                 assert bool(done_all[b]) == da
                 exp = oe.obs_cutils(31, 500)
                 for ok, gk, _ in CUTILS:
-                    _same(o[gk][b], exp[ok], f"{head} replica {b} iter {it} {gk}")
-                _same(o["props"][b], exp["props"], f"{head} replica {b} iter {it} props")
-                _same(tr[b], oe.obs_pytree(3, 30), f"{head} replica {b} iter {it} depth-3 tree")
+                    util.same(o[gk][b], exp[ok], f"{head} replica {b} iter {it} {gk}")
+                util.same(o["props"][b], exp["props"], f"{head} replica {b} iter {it} props")
+                util.same(tr[b], oe.obs_pytree(3, 30), f"{head} replica {b} iter {it} depth-3 tree")
             if da:
                 key, pos = oe.get_rng()
                 oracles[b] = orc.OracleEnv(envs[b])

@@ -14,13 +14,6 @@ pytestmark = pytest.mark.gpu
 I32_INF = np.iinfo(np.int32).max
 
 
-def _same(got, exp, msg):
-    got = np.asarray(got)
-    if got.shape != exp.shape or got.dtype != exp.dtype or got.tobytes() != exp.tobytes():
-        bad = np.argwhere(got != exp) if got.shape == exp.shape else [["shape", got.shape, exp.shape]]
-        raise AssertionError(f"{msg}: {len(bad)} mismatches, first {bad[0] if len(bad) else got.dtype}")
-
-
 def _as_i32(dist):
     return np.where(np.isinf(dist), I32_INF, dist).astype(np.int32)
 
@@ -49,20 +42,20 @@ def _check_state(env, gs, s, pick=None, envs=None, cells=True):
         for b, g in enumerate(gs):
             k = min(s, len(g["steps"]) - 1)
             msg = "%s state %d %s" % (g["name"], k, dtype)
-            _same(pick(act, b), g["sp_action"][k], msg + " actions")
-            _same(pick(dist, b), g["sp_dist"][k] if dtype == torch.float64 else _as_i32(g["sp_dist"][k]), msg + " distances")
-            _same(pick(cnt, b), g["sp_count"][k], msg + " count")
+            util.same(pick(act, b), g["sp_action"][k], msg + " actions", dtype=True, bytes=True)
+            util.same(pick(dist, b), g["sp_dist"][k] if dtype == torch.float64 else _as_i32(g["sp_dist"][k]), msg + " distances", dtype=True, bytes=True)
+            util.same(pick(cnt, b), g["sp_count"][k], msg + " count", dtype=True, bytes=True)
     _poison(env)
     dec = env.on_decision_cell(envs).cpu().numpy()
     for b, g in enumerate(gs):
-        _same(pick(dec, b), g["on_decision"][min(s, len(g["steps"]) - 1)], g["name"] + " on_decision")
+        util.same(pick(dec, b), g["on_decision"][min(s, len(g["steps"]) - 1)], g["name"] + " on_decision", dtype=True, bytes=True)
     if cells:
         _poison(env)
         cl = env.decision_cells(envs).cpu().numpy()
         for b, g in enumerate(gs):
             H, W = g["cells"].shape
             got = pick(cl, b)
-            _same(got[:H, :W], g["cells"], g["name"] + " cells")
+            util.same(got[:H, :W], g["cells"], g["name"] + " cells", dtype=True, bytes=True)
             assert not got[H:].any() and not got[:, W:].any()
 
 
@@ -171,13 +164,13 @@ def test_handmaps_in_one_mixed_batch():
         for i, g in enumerate(gs):
             k = min(s, len(g["steps"]) - 1)
             act, dist, cnt = (x.cpu().numpy() for x in mb.pick(i, out))
-            _same(act, g["sp_action"][k], "mixed %s actions" % g["name"])
-            _same(dist, g["sp_dist"][k], "mixed %s distances" % g["name"])
-            _same(cnt, g["sp_count"][k], "mixed %s count" % g["name"])
-            _same(mb.pick(i, o32)[1].cpu().numpy(), _as_i32(g["sp_dist"][k]), "mixed %s int32" % g["name"])
-            _same(mb.pick(i, dec).cpu().numpy(), g["on_decision"][k], "mixed %s on_decision" % g["name"])
-            _same(mb.pick(i, cells).cpu().numpy(), g["cells"], "mixed %s cells" % g["name"])
-            _same(mb.pick(i, tr).cpu().numpy(), an.translate(reduced[i], g["sp_action"][k], g["sp_count"][k]), "mixed %s translation" % g["name"])
+            util.same(act, g["sp_action"][k], "mixed %s actions" % g["name"], dtype=True, bytes=True)
+            util.same(dist, g["sp_dist"][k], "mixed %s distances" % g["name"], dtype=True, bytes=True)
+            util.same(cnt, g["sp_count"][k], "mixed %s count" % g["name"], dtype=True, bytes=True)
+            util.same(mb.pick(i, o32)[1].cpu().numpy(), _as_i32(g["sp_dist"][k]), "mixed %s int32" % g["name"], dtype=True, bytes=True)
+            util.same(mb.pick(i, dec).cpu().numpy(), g["on_decision"][k], "mixed %s on_decision" % g["name"], dtype=True, bytes=True)
+            util.same(mb.pick(i, cells).cpu().numpy(), g["cells"], "mixed %s cells" % g["name"], dtype=True, bytes=True)
+            util.same(mb.pick(i, tr).cpu().numpy(), an.translate(reduced[i], g["sp_action"][k], g["sp_count"][k]), "mixed %s translation" % g["name"], dtype=True, bytes=True)
     mb.check()
     mb.close()
 
@@ -203,9 +196,9 @@ def test_reduced_actions_against_the_recorded_lists(source):
             for n, red in enumerate(rows):
                 arg = red if n % 2 else torch.as_tensor(red).to(env.device)      # (a host array and a device tensor)
                 _poison(env)
-                _same(env.reduced_actions(arg).cpu().numpy(), an.translate(red, act, cnt), "%s state %d row %d" % (source, s, n))
+                util.same(env.reduced_actions(arg).cpu().numpy(), an.translate(red, act, cnt), "%s state %d row %d" % (source, s, n), dtype=True, bytes=True)
             if B > 1:
-                _same(env.reduced_actions(rows[-1][1:], envs=(1, B)).cpu().numpy(), an.translate(rows[-1][1:], act[1:], cnt[1:]), "a range")
+                util.same(env.reduced_actions(rows[-1][1:], envs=(1, B)).cpu().numpy(), an.translate(rows[-1][1:], act[1:], cnt[1:]), "a range", dtype=True, bytes=True)
         for bad in (np.zeros((B, A + 1), dtype=np.uint8), np.zeros((B, A), dtype=np.float32), np.full((B, A), 256),
                     torch.zeros((B, A), dtype=torch.int32, device=env.device), torch.zeros((B, A + 1), dtype=torch.uint8, device=env.device)):
             with pytest.raises(ValueError):
@@ -229,9 +222,9 @@ def test_step_shortest_path_equals_translate_then_step():
         red = rng.choice(np.array([0, 1, 1, 1, 2, 255], dtype=np.uint8), size=(one.B, one.A))
         r1, d1, a1 = one.step_shortest_path(red, filter_required=bool(t % 2))
         r2, d2, a2 = two.step(two.reduced_actions(red), filter_required=bool(t % 2))
-        _same(one.state()[0], two.state()[0], "state after step %d" % (t + 1))
-        _same(r1.cpu().numpy(), r2.cpu().numpy(), "rewards")
-        _same(d1.cpu().numpy(), d2.cpu().numpy(), "dones")
+        util.same(one.state()[0], two.state()[0], "state after step %d" % (t + 1), dtype=True, bytes=True)
+        util.same(r1.cpu().numpy(), r2.cpu().numpy(), "rewards", dtype=True, bytes=True)
+        util.same(d1.cpu().numpy(), d2.cpu().numpy(), "dones", dtype=True, bytes=True)
     st = one.state()[0]
     assert (st[:, :, 3] >= an.MOVING).any(), "no agent ever left"
     for e in (one, two):
@@ -284,14 +277,14 @@ def test_guarded_buffers_and_null_outputs():
                     if skipped:
                         assert body.tobytes() == np.resize(fill, len(body)).tobytes(), "a NULL output was written"
                     else:
-                        _same(body, want[name], "%s range (%d, %d) kind %d" % (name, b0, nb, kind))
+                        util.same(body, want[name], "%s range (%d, %d) kind %d" % (name, b0, nb, kind), dtype=True, bytes=True)
         cells = buf(nb * H * W, torch.uint8)
         assert L.fl_decision_cells(env.h, b0, nb, ptr(cells)) == 0, L.fl_last_error()
         assert L.fl_sync(env.h) == 0
         body, _ = inner(cells, nb * H * W)
         for b, g in enumerate(gs[b0:b0 + nb]):
             h, w = g["cells"].shape
-            _same(body.reshape(nb, H, W)[b][:h, :w], g["cells"], "cells")
+            util.same(body.reshape(nb, H, W)[b][:h, :w], g["cells"], "cells", dtype=True, bytes=True)
     env.check()
     env.close()
 
@@ -358,7 +351,7 @@ def test_functions_on_rail_env_replaying_a_hand_made_map():
             if t not in steps[::4] + steps[-1:]:
                 continue
             k = steps.index(t)
-            _same(env._batch.state()[0][0], g["state"][k], "%s t=%d state" % (name, t))
+            util.same(env._batch.state()[0][0], g["state"][k], "%s t=%d state" % (name, t), dtype=True, bytes=True)
             for h, agent in enumerate(env.agents):
                 got = re_.possible_actions_sorted_by_distance(top if h % 2 else env, h)
                 n = int(g["sp_count"][k][h])
@@ -409,7 +402,7 @@ def test_wrappers_reproduce_the_wrapped_episode(name):
         assert [int(i["malfunction"][h]) for h in keys] == w["malfunction"][s][keys].tolist(), msg
         assert np.array([i["speed"][h] for h in keys], dtype=np.float64).tobytes() == w["speed"][s][keys].tobytes(), msg
         assert [int(i["state"][h]) for h in keys] == w["info_state"][s][keys].tolist(), msg
-        _same(env._batch.state()[0][0], w["state"][s], msg + " state")
+        util.same(env._batch.state()[0][0], w["state"][s], msg + " state", dtype=True, bytes=True)
     if w["done_all"][-1]:
         with pytest.raises(Exception, match="Episode is done"):
             top.step({0: 1})

@@ -8,25 +8,13 @@ from tests import util
 pytestmark = pytest.mark.gpu
 
 
-def _env(envs, **kw):
-    from flatland_marl_amd.hip_backend import BatchedRailEnv
-    return BatchedRailEnv(envs, **kw)
-
-
-def _same(got, exp, msg):
-    got = np.asarray(got)
-    if not np.array_equal(got, exp):
-        bad = np.argwhere(got != exp)
-        raise AssertionError(f"{msg}: {len(bad)} mismatches, first {bad[0].tolist()}: {got[tuple(bad[0])]} vs {exp[tuple(bad[0])]}")
-
-
 @pytest.mark.parametrize("max_nodes,pred_depth", [(16, 100), (4, 1), (32, 500), (25, 37)])
 def test_cutils_other_sizes_match_oracle(max_nodes, pred_depth):
     from oracle import orc
     from flatland_marl_amd import synth
     fx = util.load("cfg2_spfollow")
     st = util.static_of(fx)
-    env = _env([st, st], max_nodes=max_nodes, pred_depth=pred_depth)
+    env = util.batched([st, st], max_nodes=max_nodes, pred_depth=pred_depth)
     o = orc.OracleEnv(st)
     A = env.A
     for t in range(160):
@@ -36,7 +24,7 @@ def test_cutils_other_sizes_match_oracle(max_nodes, pred_depth):
         exp = o.obs_cutils(max_nodes, pred_depth)
         for g, e in (("agent_attr", "attr"), ("forest", "forest"), ("adjacency", "adjacency"), ("node_order", "node_order"),
                      ("edge_order", "edge_order"), ("valid_actions", "valid")):
-            _same(got[g][0], exp[e], f"t={t} {g} N={max_nodes} P={pred_depth}")
+            util.same(got[g][0], exp[e], f"t={t} {g} N={max_nodes} P={pred_depth}")
         if t % 16 == 5:      # the policy's int64 tensors from the launch itself (fl_obs_cutils_policy) at this tree size == fl_policy_pack of the int32 ones
             import torch
             ref = [x.clone() for x in env.policy_inputs(env._obs)[2:]]
@@ -51,13 +39,13 @@ def test_upstream_tree_variants_match_oracle(depth, pred):
     from flatland_marl_amd import synth
     fx = util.load("cfg0_tall_spfollow")
     st = util.static_of(fx)
-    env = _env([st])
+    env = util.batched([st])
     o = orc.OracleEnv(st)
     for t in range(120):
         env.step_synth(9, 0, 1, auto_reset=True)
         o.step(synth.forward_biased_actions(9, 0, t, env.A))
         if t % 3 == 0:
-            _same(env.obs_tree(depth, pred).cpu().numpy()[0], o.obs_pytree(depth, pred), f"t={t} depth={depth} pred={pred}")
+            util.same(env.obs_tree(depth, pred).cpu().numpy()[0], o.obs_pytree(depth, pred), f"t={t} depth={depth} pred={pred}")
     env.check()
 
 
@@ -68,18 +56,18 @@ def test_single_agent_env():
     st = util.static_of(fx)
     for k in ("init_pos", "init_dir", "target", "speed", "earliest", "latest"):
         st[k] = st[k][2:3]
-    env = _env([st])
+    env = util.batched([st])
     o = orc.OracleEnv(st)
     assert env.A == 1
     for t in range(int(st["T"])):
         rew, done, done_all = env.step_synth(1, 0, 1, auto_reset=False)
         r_o, d_o, da_o = o.step(synth.forward_biased_actions(1, 0, t, 1))
-        _same(env.state()[0][0], o.state(), f"t={t}")
-        _same(rew.cpu().numpy()[0], r_o, f"t={t} reward")
+        util.same(env.state()[0][0], o.state(), f"t={t}")
+        util.same(rew.cpu().numpy()[0], r_o, f"t={t} reward")
         got = {k: v.cpu().numpy() for k, v in env.obs_cutils().items()}
         exp = o.obs_cutils(31, 500)
-        _same(got["forest"][0], exp["forest"], f"t={t} forest")
-        _same(got["agent_attr"][0], exp["attr"], f"t={t} attr")
+        util.same(got["forest"][0], exp["forest"], f"t={t} forest")
+        util.same(got["agent_attr"][0], exp["attr"], f"t={t} attr")
         if da_o:
             break
     env.check()
@@ -99,19 +87,19 @@ def test_largest_supported_agent_count_matches_oracle():
         big[k] = np.ascontiguousarray(np.asarray(st[k])[idx])
     big["earliest"] = (np.arange(A) // 4).astype(np.int32)
     big["malf_rate"] = 1 / 300.0
-    env = _env([big], pred_depth=60)
+    env = util.batched([big], pred_depth=60)
     o = orc.OracleEnv(big)
     for t in range(150):
         rew, done, done_all = env.step_synth(77, 0, 1, auto_reset=True)
         r_o, d_o, da = o.step(synth.forward_biased_actions(77, 0, t, A))
-        _same(env.state()[0][0], o.state(), f"t={t} state")
-        _same(rew.cpu().numpy()[0], r_o, f"t={t} rewards")
+        util.same(env.state()[0][0], o.state(), f"t={t} state")
+        util.same(rew.cpu().numpy()[0], r_o, f"t={t} rewards")
         if t % 25 == 0:
             got = {k: v.cpu().numpy() for k, v in env.obs_cutils().items()}
             exp = o.obs_cutils(31, 60)
             for g, e in (("agent_attr", "attr"), ("forest", "forest"), ("adjacency", "adjacency"), ("valid_actions", "valid"), ("props", "props")):
-                _same(got[g][0], exp[e], f"t={t} {g}")
-            _same(env.obs_tree(2, 30).cpu().numpy()[0], o.obs_pytree(2, 30), f"t={t} tree")
+                util.same(got[g][0], exp[e], f"t={t} {g}")
+            util.same(env.obs_tree(2, 30).cpu().numpy()[0], o.obs_pytree(2, 30), f"t={t} tree")
     env.check()
     key, pos = env.rng_state()
     k_o, p_o = o.get_rng()
@@ -135,20 +123,20 @@ def test_fused_observations_at_the_limits_of_the_one_pass_mode(A, max_nodes, dep
         big[k] = np.ascontiguousarray(np.asarray(st[k])[idx])
     big["earliest"] = (np.arange(A) // 3).astype(np.int32)
     big["malf_rate"] = 1 / 200.0
-    env = _env([big, big], max_nodes=max_nodes, pred_depth=120)
+    env = util.batched([big, big], max_nodes=max_nodes, pred_depth=120)
     o = orc.OracleEnv(big)
     keys = (("agent_attr", "attr"), ("forest", "forest"), ("adjacency", "adjacency"), ("node_order", "node_order"),
             ("edge_order", "edge_order"), ("valid_actions", "valid"), ("props", "props"))
     for t in range(140):
         env.step_synth(91, 0, 1, auto_reset=True)
         o.step(synth.forward_biased_actions(91, 0, t, A))
-        _same(env.state()[0][0], o.state(), f"t={t} state")
+        util.same(env.state()[0][0], o.state(), f"t={t} state")
         if t % 7 == 0:
             got, tree = env.obs_both(depth, 30)
             exp = o.obs_cutils(max_nodes, 120)
             for g, e in keys:
-                _same(got[g].cpu().numpy()[0], exp[e], f"t={t} {g}")
-            _same(tree.cpu().numpy()[0], o.obs_pytree(depth, 30), f"t={t} tree")
+                util.same(got[g].cpu().numpy()[0], exp[e], f"t={t} {g}")
+            util.same(tree.cpu().numpy()[0], o.obs_pytree(depth, 30), f"t={t} tree")
     env.check()
 
 
@@ -166,20 +154,20 @@ def test_fused_observations_of_few_agents_on_other_maps(name, A):
         sub[k] = np.ascontiguousarray(np.asarray(st[k])[:A])
     sub["earliest"] = (np.arange(A) // 3).astype(np.int32)  # everybody on the map soon
     sub["malf_rate"] = 1 / 150.0
-    env = _env([sub], pred_depth=300)
+    env = util.batched([sub], pred_depth=300)
     o = orc.OracleEnv(sub)
     keys = (("agent_attr", "attr"), ("forest", "forest"), ("adjacency", "adjacency"), ("node_order", "node_order"),
             ("edge_order", "edge_order"), ("valid_actions", "valid"), ("props", "props"))
     for t in range(120):
         env.step_synth(5, 0, 1, auto_reset=True)
         o.step(synth.forward_biased_actions(5, 0, t, A))
-        _same(env.state()[0][0], o.state(), f"t={t} state")
+        util.same(env.state()[0][0], o.state(), f"t={t} state")
         if t % 10 == 0:
             got, tree = env.obs_both(2, 30)
             exp = o.obs_cutils(31, 300)
             for g, e in keys:
-                _same(got[g].cpu().numpy()[0], exp[e], f"t={t} {g}")
-            _same(tree.cpu().numpy()[0], o.obs_pytree(2, 30), f"t={t} tree")
+                util.same(got[g].cpu().numpy()[0], exp[e], f"t={t} {g}")
+            util.same(tree.cpu().numpy()[0], o.obs_pytree(2, 30), f"t={t} tree")
     assert (env.state()[0][0][:, 0] >= 0).sum() >= min(A, 3) // 2      # agents are on the map at the end
     env.check()
 
@@ -189,7 +177,7 @@ def test_masked_and_non_fresh_reset():
     import torch
     fx = util.load("cfg1_spfollow")
     st = util.static_of(fx)
-    env = _env([st, st, st])
+    env = util.batched([st, st, st])
     acts = util.actions_of(fx)
     for a in acts:
         env.step(torch.from_numpy(np.stack([a, a, a])).cuda())
@@ -213,14 +201,14 @@ def test_masked_and_non_fresh_reset():
     for t, a in enumerate(acts[:50]):
         env.step(torch.from_numpy(np.stack([a, a, a])).cuda())
         o.step(a)
-        _same(env.state()[0][2], o.state(), f"replay t={t}")
+        util.same(env.state()[0][2], o.state(), f"replay t={t}")
     with pytest.raises(EpisodeDoneError):      # env 1 was finished and not reset: its step raised inside the batch
         env.check()
 
 
 def test_distance_map_rebuild_is_idempotent():
     fx = util.load("cfg4_fwd_head")
-    env = _env([util.static_of(fx)])
+    env = util.batched([util.static_of(fx)])
     dm0, slot0 = env.distance_map(0)
     env.rebuild_distance_maps()
     env.rebuild_distance_maps()
@@ -250,7 +238,7 @@ def test_policy_inputs_match_reference_modify_adjacency():
     np.testing.assert_array_equal(out[1].cpu().numpy(), no.cpu().numpy().astype(np.int64))
     np.testing.assert_array_equal(out[2].cpu().numpy(), eo.cpu().numpy().astype(np.int64))
     # and through the env: same transformation of its own observation
-    env = _env([util.static_of(fx)] * 3)
+    env = util.batched([util.static_of(fx)] * 3)
     attr, forest, adj64, no64, eo64 = env.policy_inputs()
     raw = env.obs_cutils()["adjacency"].cpu().numpy().astype(np.int64)
     exp = raw.copy()
@@ -268,7 +256,7 @@ def test_action_required_filter_info_and_scores_match_reference():
     fl_info gives get_info_dict's tensors and the evaluator's normalized reward of the finished episode."""
     import torch
     fx = util.load("cfg2_filtered")
-    env = _env([util.static_of(fx)])
+    env = util.batched([util.static_of(fx)])
     raw = np.array(fx["actions"], dtype=np.uint8)
     req = np.asarray(fx["action_required"])
     assert (raw[req == 0] != 255).any()                         # the raw stream really contains actions to drop
@@ -299,7 +287,7 @@ def test_action_required_filter_info_and_scores_match_reference():
 def test_fused_observation_launch_equals_separate_launches(name, B, depth, pred):
     fx = util.load(name)
     st = util.static_of(fx)
-    env = _env([st] * B)
+    env = util.batched([st] * B)
     for t in range(90):
         env.step_synth(4, 0, 1, auto_reset=True)
         if t % 6 == 0:
@@ -308,8 +296,8 @@ def test_fused_observation_launch_equals_separate_launches(name, B, depth, pred)
             # the deadlock flags are sticky: a second cutils build in the same step must not change anything either
             fo, ft = env.obs_both(depth, pred)
             for k in sep:
-                _same(fo[k].cpu().numpy(), sep[k].cpu().numpy(), f"{name} t={t} {k}")
-            _same(ft.cpu().numpy(), sep_tree.cpu().numpy(), f"{name} t={t} tree")
+                util.same(fo[k].cpu().numpy(), sep[k].cpu().numpy(), f"{name} t={t} {k}")
+            util.same(ft.cpu().numpy(), sep_tree.cpu().numpy(), f"{name} t={t} tree")
         else:
             env.obs_both(depth, pred)
     env.check()
@@ -322,25 +310,25 @@ def test_fused_step_and_observation_launch_equals_separate_launches(name, B, dep
     dones, RNG and every observation tensor identical on every step, through auto-resets."""
     fx = util.load(name)
     st = util.static_of(fx)
-    e1, e2 = _env([st] * B), _env([st] * B)
+    e1, e2 = util.batched([st] * B), util.batched([st] * B)
     n_steps = min(int(st["T"]) + 25, 260)
     for t in range(n_steps):
         r1, d1, a1 = (x.clone() for x in e1.step_synth(5, 3, kind, auto_reset=True))
         o1 = {k: v.clone() for k, v in e1.obs_cutils().items()}
         t1 = e1.obs_tree(depth, 30).clone() if depth > 0 else None
         r2, d2, a2, o2, t2 = e2.step_obs(None, 5, 3, kind, auto_reset=True, tree_depth=depth, tree_pred=30)
-        _same(r2.cpu().numpy(), r1.cpu().numpy(), f"{name} t={t} rewards")
-        _same(d2.cpu().numpy(), d1.cpu().numpy(), f"{name} t={t} dones")
-        _same(a2.cpu().numpy(), a1.cpu().numpy(), f"{name} t={t} done_all")
+        util.same(r2.cpu().numpy(), r1.cpu().numpy(), f"{name} t={t} rewards")
+        util.same(d2.cpu().numpy(), d1.cpu().numpy(), f"{name} t={t} dones")
+        util.same(a2.cpu().numpy(), a1.cpu().numpy(), f"{name} t={t} done_all")
         if t % 7 == 0 or t > n_steps - 30:
-            _same(e2.state()[0], e1.state()[0], f"{name} t={t} state")
+            util.same(e2.state()[0], e1.state()[0], f"{name} t={t} state")
             for k in o1:
-                _same(o2[k].cpu().numpy(), o1[k].cpu().numpy(), f"{name} t={t} {k}")
+                util.same(o2[k].cpu().numpy(), o1[k].cpu().numpy(), f"{name} t={t} {k}")
             if depth > 0:
-                _same(t2.cpu().numpy(), t1.cpu().numpy(), f"{name} t={t} tree")
+                util.same(t2.cpu().numpy(), t1.cpu().numpy(), f"{name} t={t} tree")
     k1, p1 = e1.rng_state()
     k2, p2 = e2.rng_state()
-    _same(k2, k1, "mt key"); _same(p2, p1, "mt pos")
+    util.same(k2, k1, "mt key"); util.same(p2, p1, "mt pos")
     e1.check(); e2.check()
 
 
@@ -349,16 +337,16 @@ def test_fused_step_with_explicit_actions_and_filter():
     fx = util.load("cfg2_filtered")
     st = util.static_of(fx)
     raw = fx["actions"]                       # RAW action stream of the fixture (the filter drops part of it)
-    e1, e2 = _env([st, st]), _env([st, st])
+    e1, e2 = util.batched([st, st]), util.batched([st, st])
     for t in range(min(len(raw), 150)):
         a = torch.from_numpy(np.stack([raw[t], raw[t]]).astype(np.uint8)).cuda()
         r1, d1, _ = (x.clone() for x in e1.step(a, filter_required=True))
         o1 = {k: v.clone() for k, v in e1.obs_cutils().items()}
         r2, d2, _, o2, _ = e2.step_obs(a, filter_required=True)
-        _same(r2.cpu().numpy(), r1.cpu().numpy(), f"t={t} rewards")
-        _same(d2.cpu().numpy(), d1.cpu().numpy(), f"t={t} dones")
+        util.same(r2.cpu().numpy(), r1.cpu().numpy(), f"t={t} rewards")
+        util.same(d2.cpu().numpy(), d1.cpu().numpy(), f"t={t} dones")
         for k in o1:
-            _same(o2[k].cpu().numpy(), o1[k].cpu().numpy(), f"t={t} {k}")
+            util.same(o2[k].cpu().numpy(), o1[k].cpu().numpy(), f"t={t} {k}")
         if bool(e1.done_all.cpu().numpy().all()):
             break
     e1.check(); e2.check()
@@ -368,7 +356,7 @@ def test_fused_step_after_episode_end_raises_like_the_reference():
     from flatland_marl_amd.hip_backend import EpisodeDoneError
     fx = util.load("cfg1_spfollow")
     st = util.static_of(fx)
-    env = _env([st])
+    env = util.batched([st])
     for a in util.actions_of(fx):
         env.step_obs(np.asarray(a, dtype=np.uint8)[None])
     env.check()
@@ -383,7 +371,7 @@ def test_builder_sizes_beyond_the_limits_are_refused_with_a_message():
     from flatland_marl_amd.hip_backend import FlatlandHipError
     fx = util.load("cfg1_uniform")
     st = util.static_of(fx)
-    env = _env([st])
+    env = util.batched([st])
     env.step_synth(1, 0, 0)
     assert env.obs_tree(4, 30).shape == (1, env.A, 341, 12)
     with pytest.raises(FlatlandHipError, match=r"max_depth must be in \[1,4\]"):
@@ -396,11 +384,11 @@ def test_builder_sizes_beyond_the_limits_are_refused_with_a_message():
     slow["speed"] = np.array(st["speed"], dtype=np.float64)
     slow["speed"][0] = 1.0 / 65.0
     with pytest.raises(FlatlandHipError, match="max_count 64"):
-        _env([slow])
+        util.batched([slow])
     slow["speed"][0] = 1.0 / 64.0            # the slowest train this build takes
-    _env([slow]).step_synth(1, 0, 0)
+    util.batched([slow]).step_synth(1, 0, 0)
     tw = util.load("threeway_cfg2")
-    e3 = _env([util.static_of(tw)])
+    e3 = util.batched([util.static_of(tw)])
     e3.step_synth(1, 0, 0)
     with pytest.raises(FlatlandHipError, match="more than two transitions"):
         e3.obs_tree(4, 30)

@@ -7,17 +7,12 @@ alone, observations included) on picked replicas, and two replicas shadowed by t
 import numpy as np
 import pytest
 
+from tests import util
+
 pytestmark = pytest.mark.gpu
 
 CUTILS = (("agent_attr", "attr"), ("forest", "forest"), ("adjacency", "adjacency"), ("node_order", "node_order"),
           ("edge_order", "edge_order"), ("valid_actions", "valid"), ("props", "props"))
-
-
-def _same(got, exp, msg):
-    got = np.asarray(got)
-    if not np.array_equal(got, exp):
-        bad = np.argwhere(got != exp)
-        raise AssertionError(f"{msg}: {len(bad)} mismatches, first {bad[0].tolist()}: {got[tuple(bad[0])]} vs {exp[tuple(bad[0])]}")
 
 
 # fixed launch class of every case (fl_obs_layout.h ObsFixed<k>; BatchedRailEnv.last_obs_class): `klass` = (class, split) of the full
@@ -79,22 +74,22 @@ def test_full_size_batch_replicas_equal_solo_runs_and_the_oracle(workload, B, st
             s_o, s_tree = s_env.obs_both(depth, 30)
             if rebuild:
                 s_env.rebuild_distance_maps(s_env.done_all)
-            _same(s_env.state()[0][0], st[b], f"replica {b} step {t} state")
-            _same(s_rew.cpu().numpy()[0], rew.cpu().numpy()[b], f"replica {b} step {t} rewards")
+            util.same(s_env.state()[0][0], st[b], f"replica {b} step {t} state")
+            util.same(s_rew.cpu().numpy()[0], rew.cpu().numpy()[b], f"replica {b} step {t} rewards")
             if check_obs:
                 for key, _ in CUTILS:
-                    _same(s_o[key].cpu().numpy()[0], ob[key][b], f"replica {b} step {t} {key}")
-                _same(s_tree.cpu().numpy()[0], tr[b], f"replica {b} step {t} depth-{depth} tree")
+                    util.same(s_o[key].cpu().numpy()[0], ob[key][b], f"replica {b} step {t} {key}")
+                util.same(s_tree.cpu().numpy()[0], tr[b], f"replica {b} step {t} depth-{depth} tree")
         for b, orc_env in oracles.items():
             r_o, d_o, da = orc_env.step(synth.uniform_actions(seed, b, tc[b], A))
             tc[b] += 1
-            _same(st[b], orc_env.state(), f"oracle replica {b} step {t} state")
-            _same(rew.cpu().numpy()[b], r_o, f"oracle replica {b} step {t} rewards")
+            util.same(st[b], orc_env.state(), f"oracle replica {b} step {t} state")
+            util.same(rew.cpu().numpy()[b], r_o, f"oracle replica {b} step {t} rewards")
             exp = orc_env.obs_cutils(31, 500)       # every step: the deadlock flags are sticky
             if check_obs:
                 for key, okey in CUTILS:
-                    _same(ob[key][b], exp[okey], f"oracle replica {b} step {t} {key}")
-                _same(tr[b], orc_env.obs_pytree(depth, 30), f"oracle replica {b} step {t} depth-{depth} tree")
+                    util.same(ob[key][b], exp[okey], f"oracle replica {b} step {t} {key}")
+                util.same(tr[b], orc_env.obs_pytree(depth, 30), f"oracle replica {b} step {t} depth-{depth} tree")
             if da:
                 key, pos = orc_env.get_rng()
                 oracles[b] = orc.OracleEnv(envs[b])
@@ -296,10 +291,10 @@ def test_cutils_alone_full_size_replicas_equal_solo_runs_and_the_oracle(workload
         for b, s_env in solo.items():
             s_rew, _, _ = s_env.step_synth(seed, b, 2 if t % 3 else 0, auto_reset=True)
             s_o = s_env.obs_cutils()
-            _same(s_env.state()[0][0], st[b], f"replica {b} step {t} state")
+            util.same(s_env.state()[0][0], st[b], f"replica {b} step {t} state")
             if check_obs:
                 for key, _ in CUTILS:
-                    _same(s_o[key].cpu().numpy()[0], ob[key][b], f"replica {b} step {t} {key}")
+                    util.same(s_o[key].cpu().numpy()[0], ob[key][b], f"replica {b} step {t} {key}")
         for b, orc_env in oracles.items():
             if t % 3:
                 dm = orc_env.distance_map()
@@ -309,11 +304,11 @@ def test_cutils_alone_full_size_replicas_equal_solo_runs_and_the_oracle(workload
                 acts = synth.uniform_actions(seed, b, tc[b], A)
             r_o, d_o, da = orc_env.step(acts)
             tc[b] += 1
-            _same(st[b], orc_env.state(), f"oracle replica {b} step {t} state")
+            util.same(st[b], orc_env.state(), f"oracle replica {b} step {t} state")
             exp = orc_env.obs_cutils(31, 500)
             if check_obs:
                 for key, okey in CUTILS:
-                    _same(ob[key][b], exp[okey], f"oracle replica {b} step {t} {key}")
+                    util.same(ob[key][b], exp[okey], f"oracle replica {b} step {t} {key}")
             if da:
                 key, pos = orc_env.get_rng()
                 oracles[b] = orc.OracleEnv(envs[b])

@@ -19,21 +19,14 @@ FIXTURES = sorted(os.path.basename(f)[len("global_"):-4] for f in glob.glob(os.p
                   if not os.path.basename(f).startswith("global_states_"))
 
 
-def _same(got, exp, msg):
-    got = np.asarray(got)
-    if got.shape != exp.shape or got.dtype != exp.dtype or not np.array_equal(got, exp):
-        bad = np.argwhere(got != exp) if got.shape == exp.shape else [["shape", got.shape, exp.shape]]
-        raise AssertionError(f"{msg}: {len(bad)} mismatches, first {bad[0] if len(bad) else got.dtype}")
-
-
 def _check_env(ast, tgt, static, state, msg, rail=None):
     """one env's outputs (numpy, float64 or float32) against the restatement"""
     r, a, t = global_obs(static, state)
     dt = ast.dtype
-    _same(ast, a.astype(dt), msg + " agents_state")
-    _same(tgt, t.astype(dt), msg + " targets")
+    util.same(ast, a.astype(dt), msg + " agents_state", dtype=True)
+    util.same(tgt, t.astype(dt), msg + " targets", dtype=True)
     if rail is not None:
-        _same(rail, r.astype(dt), msg + " rail")
+        util.same(rail, r.astype(dt), msg + " rail", dtype=True)
 
 
 @pytest.mark.parametrize("name", FIXTURES)
@@ -50,16 +43,16 @@ def test_batched_replay_equals_the_reference(name):
         if t not in steps:
             continue
         k = steps.index(t)
-        _same(env.state()[0][0], g["state"][k], f"{name} t={t} agent state")
+        util.same(env.state()[0][0], g["state"][k], f"{name} t={t} agent state", dtype=True)
         r, ast, tgt = env.obs_global()
         assert r.dtype == torch.float64 and ast.shape == (1, env.A, env.H, env.W, 5) and tgt.shape == (1, env.A, env.H, env.W, 2)
-        _same(r[0].cpu().numpy(), g["rail"], f"{name} t={t} rail f64")
-        _same(ast[0].cpu().numpy(), g["agents_state"][k], f"{name} t={t} agents_state f64")
-        _same(tgt[0].cpu().numpy(), g["targets"][k], f"{name} t={t} targets f64")
+        util.same(r[0].cpu().numpy(), g["rail"], f"{name} t={t} rail f64", dtype=True)
+        util.same(ast[0].cpu().numpy(), g["agents_state"][k], f"{name} t={t} agents_state f64", dtype=True)
+        util.same(tgt[0].cpu().numpy(), g["targets"][k], f"{name} t={t} targets f64", dtype=True)
         r, ast, tgt = env.obs_global(torch.float32)
-        _same(r[0].cpu().numpy(), g["rail"].astype(np.float32), f"{name} t={t} rail f32")
-        _same(ast[0].cpu().numpy(), g["agents_state"][k].astype(np.float32), f"{name} t={t} agents_state f32")
-        _same(tgt[0].cpu().numpy(), g["targets"][k].astype(np.float32), f"{name} t={t} targets f32")
+        util.same(r[0].cpu().numpy(), g["rail"].astype(np.float32), f"{name} t={t} rail f32", dtype=True)
+        util.same(ast[0].cpu().numpy(), g["agents_state"][k].astype(np.float32), f"{name} t={t} agents_state f32", dtype=True)
+        util.same(tgt[0].cpu().numpy(), g["targets"][k].astype(np.float32), f"{name} t={t} targets f32", dtype=True)
     env.check()
     env.close()
 
@@ -128,7 +121,7 @@ def test_cfg5_map_larger_than_one_band():
         if t + 1 not in (1, len(actions)):
             continue
         st = env.state()[0][0]
-        _same(st, util.golden_state(fx, t), f"cfg5 state t={t + 1}")
+        util.same(st, util.golden_state(fx, t), f"cfg5 state t={t + 1}", dtype=True)
         for dt in (torch.float64, torch.float32):
             r, a, g = env.obs_global(dt)
             _check_env(a[0].cpu().numpy(), g[0].cpu().numpy(), static, st, f"cfg5 t={t + 1} {dt}", rail=r[0].cpu().numpy())
@@ -147,7 +140,7 @@ def test_rail_channels_follow_a_replaced_map():
     for _ in range(5):
         env.step_synth(7, 0, 2)
     r, _, _ = env.obs_global()
-    _same(r[1].cpu().numpy(), rail_obs(bases[0]["grid"]), "rail before the replacement")
+    util.same(r[1].cpu().numpy(), rail_obs(bases[0]["grid"]), "rail before the replacement", dtype=True)
     envs[1] = util.static_of(bases[4], *wl.replica_rng(900))
     env.replace_env(1, envs[1])
     for _ in range(3):
@@ -196,10 +189,10 @@ def test_rail_env_builder_reset_and_step_dicts(name):
         k = steps.index(t)
         assert sorted(obs) == list(range(A))
         assert all(obs[h][0] is obs[0][0] for h in range(A)), "rail_obs is one array for every handle"
-        _same(obs[0][0], g["rail"], f"{name} t={t} rail")
+        util.same(obs[0][0], g["rail"], f"{name} t={t} rail", dtype=True)
         for h in range(A):
-            _same(obs[h][1], g["agents_state"][k][h], f"{name} t={t} handle {h} agents_state")
-            _same(obs[h][2], g["targets"][k][h], f"{name} t={t} handle {h} targets")
+            util.same(obs[h][1], g["agents_state"][k][h], f"{name} t={t} handle {h} agents_state", dtype=True)
+            util.same(obs[h][2], g["targets"][k][h], f"{name} t={t} handle {h} targets", dtype=True)
 
     compare(0, obs)
     for t, row in enumerate(util.actions_of(fx)[:max(steps)], start=1):
@@ -207,7 +200,7 @@ def test_rail_env_builder_reset_and_step_dicts(name):
         if t in steps:
             compare(t, obs)
     one = builder.get(3)
-    _same(one[1], obs[3][1], "get(handle)")
+    util.same(one[1], obs[3][1], "get(handle)", dtype=True)
 
 
 @pytest.mark.parametrize("name,string_states", [("cfg3_spfollow_malf100", False), ("cfg2_slow_trains", True)])
@@ -223,9 +216,9 @@ def test_plugin_on_a_duck_typed_env_replaying_a_reference_episode(name, string_s
         env.goto(int(t))
         out = b.get_many(list(range(A)))
         assert all(out[h][0] is out[0][0] for h in range(A))
-        _same(out[0][0], g["rail"], f"{name} t={t} rail")
-        _same(np.stack([out[h][1] for h in range(A)]), g["agents_state"][k], f"{name} t={t} agents_state")
-        _same(np.stack([out[h][2] for h in range(A)]), g["targets"][k], f"{name} t={t} targets")
+        util.same(out[0][0], g["rail"], f"{name} t={t} rail", dtype=True)
+        util.same(np.stack([out[h][1] for h in range(A)]), g["agents_state"][k], f"{name} t={t} agents_state", dtype=True)
+        util.same(np.stack([out[h][2] for h in range(A)]), g["targets"][k], f"{name} t={t} targets", dtype=True)
     assert b.get_many(None) == {}
 
 

@@ -16,16 +16,6 @@ from tests.test_global_obs_states import SHARED_SEED, SHARED_STEPS
 pytestmark = pytest.mark.gpu
 
 
-def _same(got, exp, msg):
-    got = np.asarray(got)
-    if got.shape != exp.shape or got.dtype != exp.dtype or not np.array_equal(got, exp):
-        if got.shape != exp.shape or got.dtype != exp.dtype:
-            raise AssertionError(f"{msg}: {got.shape} {got.dtype}, expected {exp.shape} {exp.dtype}")
-        bad = np.argwhere(got != exp)
-        k = tuple(bad[0])
-        raise AssertionError(f"{msg}: {len(bad)} mismatches, first at {k}: got {got[k]}, expected {exp[k]}")
-
-
 def _dtypes():
     import torch
     return (torch.float64, np.float64), (torch.float32, np.float32)
@@ -44,9 +34,9 @@ def _check_all(env, pairs, msg, restate=global_obs, **kw):
     for tdt, ndt in _dtypes():
         r, a, t = (x.cpu().numpy() for x in env.obs_global(tdt, **kw))
         for b, (er, ea, et) in enumerate(exp):
-            _same(a[b], ea.astype(ndt), f"{msg} env {b} {ndt.__name__} agents_state")
-            _same(t[b], et.astype(ndt), f"{msg} env {b} {ndt.__name__} targets")
-            _same(r[b], er.astype(ndt), f"{msg} env {b} {ndt.__name__} rail")
+            util.same(a[b], ea.astype(ndt), f"{msg} env {b} {ndt.__name__} agents_state", dtype=True)
+            util.same(t[b], et.astype(ndt), f"{msg} env {b} {ndt.__name__} targets", dtype=True)
+            util.same(r[b], er.astype(ndt), f"{msg} env {b} {ndt.__name__} rail", dtype=True)
 
 
 @pytest.mark.parametrize("name", sorted(handmaps.GLOBAL_STATES))
@@ -55,13 +45,13 @@ def test_reference_fixtures_of_constructed_states(name):
     m, _ = handmaps.GLOBAL_STATES[name]()
     static = handmaps.global_static(m)
     env = _batch([(static, rows) for rows in g["state"]])
-    _same(env.state()[0][..., :5], g["state"][..., :5], f"{name} injected state")
+    util.same(env.state()[0][..., :5], g["state"][..., :5], f"{name} injected state", dtype=True)
     for tdt, ndt in _dtypes():
         r, a, t = (x.cpu().numpy() for x in env.obs_global(tdt))
         for k in range(len(g["state"])):
-            _same(a[k], g["agents_state"][k].astype(ndt), f"{name} state {k} {ndt.__name__} agents_state")
-            _same(t[k], g["targets"][k].astype(ndt), f"{name} state {k} {ndt.__name__} targets")
-            _same(r[k], g["rail"].astype(ndt), f"{name} state {k} {ndt.__name__} rail")
+            util.same(a[k], g["agents_state"][k].astype(ndt), f"{name} state {k} {ndt.__name__} agents_state", dtype=True)
+            util.same(t[k], g["targets"][k].astype(ndt), f"{name} state {k} {ndt.__name__} targets", dtype=True)
+            util.same(r[k], g["rail"].astype(ndt), f"{name} state {k} {ndt.__name__} rail", dtype=True)
     env.check()
     env.close()
 
@@ -150,7 +140,7 @@ def test_accepted_calls_write_all_of_their_buffers_and_nothing_else(H, W, A):
                     assert np.isnan(x[G:G + n]).all()
                 else:
                     assert not np.isnan(x[G:G + n]).any(), f"{ndt.__name__} skip {skip}: buffer {k} has elements left unwritten"
-                    _same(x[G:G + n].reshape(exp[k].shape), exp[k].astype(ndt), f"{ndt.__name__} skip {skip} buffer {k}")
+                    util.same(x[G:G + n].reshape(exp[k].shape), exp[k].astype(ndt), f"{ndt.__name__} skip {skip} buffer {k}", dtype=True)
     env.close()
 
 
@@ -191,9 +181,9 @@ def test_plugin_builder_on_a_duck_typed_env_holding_a_stack():
     A = env.get_num_agents()
     out = b.get_many(list(range(A)))
     assert sorted(out) == list(range(A)) and all(out[h][0] is out[0][0] for h in range(A))
-    _same(out[0][0], g["rail"], "rail")
-    _same(np.stack([out[h][1] for h in range(A)]), g["agents_state"][k], "agents_state")
-    _same(np.stack([out[h][2] for h in range(A)]), g["targets"][k], "targets")
+    util.same(out[0][0], g["rail"], "rail", dtype=True)
+    util.same(np.stack([out[h][1] for h in range(A)]), g["agents_state"][k], "agents_state", dtype=True)
+    util.same(np.stack([out[h][2] for h in range(A)]), g["targets"][k], "targets", dtype=True)
 
 
 def test_rail_env_builder_on_an_injected_stack():
@@ -205,8 +195,8 @@ def test_rail_env_builder_on_an_injected_stack():
     env._batch.set_state(g["state"][k][None])
     A = env.get_num_agents()
     out = builder.get_many(list(range(A)))
-    _same(out[0][0], g["rail"], "rail")
+    util.same(out[0][0], g["rail"], "rail", dtype=True)
     for h in range(A):
-        _same(out[h][1], g["agents_state"][k][h], f"handle {h} agents_state")
-        _same(out[h][2], g["targets"][k][h], f"handle {h} targets")
-    _same(builder.get(7)[1], g["agents_state"][k][7], "get(handle) of the stack's highest handle")
+        util.same(out[h][1], g["agents_state"][k][h], f"handle {h} agents_state", dtype=True)
+        util.same(out[h][2], g["targets"][k][h], f"handle {h} targets", dtype=True)
+    util.same(builder.get(7)[1], g["agents_state"][k][7], "get(handle) of the stack's highest handle", dtype=True)

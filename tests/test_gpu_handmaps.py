@@ -8,8 +8,6 @@ flatland_cutils raised on none of these maps, the mesh included (cutils_raised i
 
 One part of the fixtures is no function of the env: the road type of an agent on a cell of no Flatland type (mesh12 only;
 handmaps.known_cell_type).  There the kernels are held to the oracle's value."""
-import os
-import subprocess
 import sys
 import time
 
@@ -17,6 +15,7 @@ import numpy as np
 import pytest
 
 from tests import handmaps, util
+from tests import obs_switch_runs as sw
 
 CUTILS = (("agent_attr", "attr"), ("forest", "forest"), ("adjacency", "adjacency"), ("node_order", "node_order"),
           ("edge_order", "edge_order"), ("valid_actions", "valid"))
@@ -30,30 +29,22 @@ def _fixture(name):
     return util.load("handmap_" + name)
 
 
-def _same(got, exp, msg):
-    got, exp = np.asarray(got), np.asarray(exp)
-    assert got.shape == exp.shape, f"{msg}: shape {got.shape} vs {exp.shape}"
-    if not np.array_equal(got, exp):
-        bad = np.argwhere(got != exp)
-        raise AssertionError(f"{msg}: {len(bad)} mismatches, first {bad[0].tolist()}: {got[tuple(bad[0])]} vs {exp[tuple(bad[0])]}")
-
-
 def _cutils_equals_golden(got, fx, t, b, tag):
     """the seven flatland_cutils tensors of env b against step t of a fixture"""
     ok = handmaps.defined_attr(fx, t)
     attr = got["agent_attr"][b]
-    _same(attr[ok], fx["o_attr"][t][ok], f"{tag} agent_attr")
+    util.same(attr[ok], fx["o_attr"][t][ok], f"{tag} agent_attr")
     no_type = ~ok[:, handmaps.ROAD_TYPE_COLS].all(axis=1)
     assert (attr[no_type][:, handmaps.ROAD_TYPE_COLS] == [1] + [0] * 10).all(), f"{tag}: road type 0 on a cell of no Flatland type, as the oracle says"
     for g, e in CUTILS[1:]:
-        _same(got[g][b], fx["o_" + e][t], f"{tag} {g}")
+        util.same(got[g][b], fx["o_" + e][t], f"{tag} {g}")
     for col, k in enumerate(PROPS):
-        _same(got["props"][b][:, col], fx["o_" + k][t], f"{tag} {k}")
+        util.same(got["props"][b][:, col], fx["o_" + k][t], f"{tag} {k}")
 
 
 def _cutils_equals_oracle(got, exp, b, tag):
     for g, e in CUTILS + (("props", "props"),):
-        _same(got[g][b], exp[e], f"{tag} {g}")
+        util.same(got[g][b], exp[e], f"{tag} {g}")
 
 
 def _host(o):
@@ -68,15 +59,15 @@ def _replay(fx, fused, steps=None, tag=""):
     assert not fx["cutils_raised"].any()
     env = BatchedRailEnv([util.static_of(fx)])
     dm, slot = env.distance_map(0)
-    _same(dm, fx["dm_u16"], f"{tag} distance map")
-    _same(slot, fx["target_slot"], f"{tag} target slots")
+    util.same(dm, fx["dm_u16"], f"{tag} distance map")
+    util.same(slot, fx["target_slot"], f"{tag} target slots")
     n = len(fx["state"]) if steps is None else min(steps + 1, len(fx["state"]))
     for t in range(n):
         if t > 0:
             rew, done, _ = env.step(torch.from_numpy(fx["actions"][t - 1][None, :].copy()).cuda())
-            _same(rew.cpu().numpy()[0], fx["reward"][t - 1], f"{tag} t={t} reward")
-            _same(done.cpu().numpy()[0], fx["done"][t - 1], f"{tag} t={t} done")
-        _same(env.state()[0][0], fx["state"][t], f"{tag} t={t} state")
+            util.same(rew.cpu().numpy()[0], fx["reward"][t - 1], f"{tag} t={t} reward")
+            util.same(done.cpu().numpy()[0], fx["done"][t - 1], f"{tag} t={t} done")
+        util.same(env.state()[0][0], fx["state"][t], f"{tag} t={t} state")
         env.check()
         got = None
         for d in (2, 3):
@@ -84,7 +75,7 @@ def _replay(fx, fused, steps=None, tag=""):
                 got, tree = env.obs_both(d, 30)
             else:
                 tree = env.obs_tree(d, 30)
-            _same(tree.cpu().numpy()[0], fx["py_d%d_p30" % d][t], f"{tag} t={t} depth-{d} tree")
+            util.same(tree.cpu().numpy()[0], fx["py_d%d_p30" % d][t], f"{tag} t={t} depth-{d} tree")
             if not fused:
                 env.check()
         if not fused:
@@ -110,8 +101,8 @@ def test_distance_map_with_levels_of_five_chunks_and_more_states_than_the_ring()
     fx = _fixture("mesh33")
     env = BatchedRailEnv([util.static_of(fx)])
     dm, slot = env.distance_map(0)
-    _same(dm, fx["dm_u16"], "mesh33 distance map")
-    _same(slot, fx["target_slot"], "mesh33 target slots")
+    util.same(dm, fx["dm_u16"], "mesh33 distance map")
+    util.same(slot, fx["target_slot"], "mesh33 target slots")
     env.check()                                     # (no FL_ERR_CAPACITY: the ring never holds more than two levels)
     env.close()
 
@@ -131,7 +122,7 @@ def test_mixed_batch_of_hand_made_maps_matches_the_oracles():
     env = BatchedRailEnv(envs)
     oracles = [orc.OracleEnv(e) for e in envs]
     for b, o in enumerate(oracles):
-        _same(env.distance_map(b)[0], o.distance_map()[0], f"env {b} distance map")
+        util.same(env.distance_map(b)[0], o.distance_map()[0], f"env {b} distance map")
     for t in range(40):
         env.step_synth(SEED, 0, 1, auto_reset=False)
         if t % 2:
@@ -143,9 +134,9 @@ def test_mixed_batch_of_hand_made_maps_matches_the_oracles():
         for b, o in enumerate(oracles):
             o.step(synth.forward_biased_actions(SEED, b, t, env.A))
             tag = f"{handmaps.SMALL[b]} step {t}"
-            _same(st[b], o.state(), f"{tag} state")
+            util.same(st[b], o.state(), f"{tag} state")
             _cutils_equals_oracle(got, o.obs_cutils(31, 500), b, tag)
-            _same(tree[b], o.obs_pytree(depth, 30), f"{tag} depth-{depth} tree")
+            util.same(tree[b], o.obs_pytree(depth, 30), f"{tag} depth-{depth} tree")
     env.check()
     assert (env.state()[0][:, :, 0] >= 0).any(axis=1).all(), "trains are on every map"
     env.close()
@@ -198,15 +189,15 @@ def test_more_envs_than_a_round_of_the_env_list_and_the_looping_rebuild_grid():
 
     def tables(tag):
         for b in range(B):
-            _same(env.distance_map(b)[0], dms[b], f"{tag}: env {b} distance map")
+            util.same(env.distance_map(b)[0], dms[b], f"{tag}: env {b} distance map")
 
     def observations(tag):
         got, tree = env.obs_both(2, 30)
         got, tree, st = _host(got), tree.cpu().numpy(), env.state()[0]
         for b, o in enumerate(oracles):
-            _same(st[b], o.state(), f"{tag}: env {b} state")
+            util.same(st[b], o.state(), f"{tag}: env {b} state")
             _cutils_equals_oracle(got, o.obs_cutils(31, 500), b, f"{tag}: env {b}")
-            _same(tree[b], o.obs_pytree(2, 30), f"{tag}: env {b} depth-2 tree")
+            util.same(tree[b], o.obs_pytree(2, 30), f"{tag}: env {b} depth-2 tree")
 
     def run(t0, n):
         for t in range(t0, t0 + n):
@@ -261,13 +252,10 @@ def test_launcher_fallbacks_on_cycles_and_unreachable_targets(row_id):
     every launch class, and a split launch would run the class's body on them instead of the fallback."""
     from tests import obs_kernel_cases as cases
     row = cases.BY_ID[row_id]
-    env = {k: v for k, v in os.environ.items() if not k.startswith("FL_OBS_")}
     t0 = time.time()
-    child = subprocess.run([sys.executable, os.path.abspath(__file__), row_id], capture_output=True, text=True, timeout=CHILD_TIMEOUT,
-                           env=dict(env, PYTHONPATH=util.ROOT, **dict(row.switches, FL_OBS_NO_SPLIT="1")))
-    print("%s: %.1f s\n%s" % (row_id, time.time() - t0, "\n".join(ln for ln in child.stdout.splitlines() if ln.startswith("RECORD "))))
-    assert child.returncode == 0, (child.stdout[-1500:], child.stderr[-3000:])
-    assert ("DONE %s" % row_id) in child.stdout.splitlines()
+    lines = sw.fresh_child(__file__, [row_id], dict(row.switches, FL_OBS_NO_SPLIT="1"), CHILD_TIMEOUT)
+    print("%s: %.1f s\n%s" % (row_id, time.time() - t0, "\n".join(ln for ln in lines if ln.startswith("RECORD "))))
+    assert ("DONE %s" % row_id) in lines
 
 
 if __name__ == "__main__":

@@ -17,18 +17,6 @@ CUTILS_KEYS = (("agent_attr", "o_attr"), ("forest", "o_forest"), ("adjacency", "
                ("node_order", "o_node_order"), ("edge_order", "o_edge_order"), ("valid_actions", "o_valid"))
 
 
-def _env(envs, **kw):
-    from flatland_marl_amd.hip_backend import BatchedRailEnv
-    return BatchedRailEnv(envs, **kw)
-
-
-def _same(got, exp, msg):
-    got = np.asarray(got)
-    if not np.array_equal(got, exp):
-        bad = np.argwhere(got != exp)
-        raise AssertionError(f"{msg}: {len(bad)} mismatches, first {bad[0].tolist()}: {got[tuple(bad[0])]} vs {exp[tuple(bad[0])]}")
-
-
 def test_motion_check_known_answers_through_the_step_kernel():
     from flatland_marl_amd import hip_backend as hb
     z = util.load("motioncheck")
@@ -66,7 +54,7 @@ def test_motion_check_wide_case_matches_oracle():
     o_nxt = np.where(nxt < 0, 100000 + np.arange(n), nxt)
     exp = orc.motion_check(o_cur, o_nxt)
     got = hb.motion_check(np.array([0, n]), cur, nxt)
-    _same(got, exp, "wide case")
+    util.same(got, exp, "wide case")
 
 
 def _aux_of(fx, T, k_obs=None):
@@ -89,7 +77,7 @@ def _aux_of(fx, T, k_obs=None):
 @pytest.mark.parametrize("name", ["cfg3_uniform", "cfg3_spfollow_malf100", "cfg2_spfollow", "cfg1_malf20_spfollow", "cfg0_tall_spfollow"])
 def test_injected_reference_states_reproduce_the_observation_snapshots(name):
     fx = util.load(name)
-    env = _env([util.static_of(fx)])
+    env = util.batched([util.static_of(fx)])
     obs_steps = [int(t) for t in fx["obs_steps"]]
     py_steps = {int(t): k for k, t in enumerate(fx["py_steps"])} if "py_steps" in fx.files else {}
     pykeys = [k for k in fx.files if k.startswith("py_d")]
@@ -101,11 +89,11 @@ def test_injected_reference_states_reproduce_the_observation_snapshots(name):
                       np.array([fx["done_all"][T - 1]], dtype=np.uint8))
         o = env.obs_cutils()
         for got, key in CUTILS_KEYS:
-            _same(o[got].cpu().numpy()[0], fx[key][k], f"{name} T={T} {got}")
+            util.same(o[got].cpu().numpy()[0], fx[key][k], f"{name} T={T} {got}")
         pr = o["props"].cpu().numpy()[0]
-        _same(pr[:, 0], fx["o_p_dist_target"][k], f"{name} T={T} dist_target")
-        _same(pr[:, 1], fx["o_p_deadlocked"][k], f"{name} T={T} deadlocked")
-        _same(pr[:, 2], fx["o_p_ready"][k], f"{name} T={T} ready")
+        util.same(pr[:, 0], fx["o_p_dist_target"][k], f"{name} T={T} dist_target")
+        util.same(pr[:, 1], fx["o_p_deadlocked"][k], f"{name} T={T} deadlocked")
+        util.same(pr[:, 2], fx["o_p_ready"][k], f"{name} T={T} ready")
         n += 1
     for T, k in py_steps.items():
         if T == 0:
@@ -113,7 +101,7 @@ def test_injected_reference_states_reproduce_the_observation_snapshots(name):
         env.set_state(util.golden_state(fx, T - 1)[None], _aux_of(fx, T)[None], np.array([T], dtype=np.int32))
         for pk in pykeys:
             depth, pdepth = int(pk.split("_")[1][1:]), int(pk.split("_")[2][1:])
-            _same(env.obs_tree(depth, pdepth).cpu().numpy()[0], fx[pk][k], f"{name} T={T} {pk}")
+            util.same(env.obs_tree(depth, pdepth).cpu().numpy()[0], fx[pk][k], f"{name} T={T} {pk}")
     env.check()
     assert n >= 3
 
@@ -128,7 +116,7 @@ def test_mid_episode_hand_over_to_a_fresh_batch_continues_bit_for_bit():
         st["malf_rate"] = 1 / 80.0
         st["mt_key"], st["mt_pos"] = (lambda s: (np.array(s[1], dtype=np.uint32), int(s[2])))(np.random.RandomState([40 + b]).get_state())
         envs.append(st)
-    e1 = _env(envs)
+    e1 = util.batched(envs)
     for t in range(230):
         e1.step_synth(17, 5, 1, auto_reset=True)
         e1.obs_cutils()
@@ -136,7 +124,7 @@ def test_mid_episode_hand_over_to_a_fresh_batch_continues_bit_for_bit():
     aux = e1.state_aux()
     key, pos = e1.rng_state()
     assert (st[:, :, 0] >= 0).sum() > 20 and aux[:, :, 2].sum() >= 0
-    e2 = _env(envs)
+    e2 = util.batched(envs)
     e2.set_state(st, aux, el, e1.done_all.cpu().numpy())
     e2.set_rng_state(key, pos)
     np.testing.assert_array_equal(e2.state()[0], st)
@@ -146,27 +134,27 @@ def test_mid_episode_hand_over_to_a_fresh_batch_continues_bit_for_bit():
         r1, d1, a1 = (x.clone() for x in e1.step_synth(17, 5, 0, auto_reset=True))
         r2, d2, a2 = e2.step_synth(17, 5, 0, auto_reset=True)
         # the synthetic stream is indexed by the env's own step counter, which the injection carried over
-        _same(r2.cpu().numpy(), r1.cpu().numpy(), f"t={t} rewards")
-        _same(d2.cpu().numpy(), d1.cpu().numpy(), f"t={t} dones")
-        _same(a2.cpu().numpy(), a1.cpu().numpy(), f"t={t} done_all")
+        util.same(r2.cpu().numpy(), r1.cpu().numpy(), f"t={t} rewards")
+        util.same(d2.cpu().numpy(), d1.cpu().numpy(), f"t={t} dones")
+        util.same(a2.cpu().numpy(), a1.cpu().numpy(), f"t={t} done_all")
         o1 = {k: v.clone() for k, v in e1.obs_cutils().items()}
         o2 = e2.obs_cutils()
         if t % 5 == 0:
-            _same(e2.state()[0], e1.state()[0], f"t={t} state")
+            util.same(e2.state()[0], e1.state()[0], f"t={t} state")
             for k in o1:
-                _same(o2[k].cpu().numpy(), o1[k].cpu().numpy(), f"t={t} {k}")
+                util.same(o2[k].cpu().numpy(), o1[k].cpu().numpy(), f"t={t} {k}")
     assert int(e1.metrics().cpu().numpy()[3]) >= 4          # every env finished an episode on the way
     k1, p1 = e1.rng_state()
     k2, p2 = e2.rng_state()
-    _same(k2, k1, "mt key")
-    _same(p2, p1, "mt pos")
+    util.same(k2, k1, "mt key")
+    util.same(p2, p1, "mt pos")
     e1.check(); e2.check()
 
 
 def test_set_state_refuses_a_state_position_mismatch():
     from flatland_marl_amd.hip_backend import FlatlandHipError
     fx = util.load("cfg1_uniform")
-    env = _env([util.static_of(fx)])
+    env = util.batched([util.static_of(fx)])
     st, _ = env.state()
     st[0, 0, 3] = 3          # MOVING without a position (env_utils.py:45-52)
     with pytest.raises(FlatlandHipError, match="FL_ERR_STATE_SYNC"):
@@ -185,7 +173,7 @@ def test_finished_env_inside_a_batch_reports_zero_rewards_and_done():
     st = util.static_of(fx)
     long = dict(st)
     long["T"] = np.int32(int(st["T"]) + 50)
-    env = _env([st, long])
+    env = util.batched([st, long])
     acts = util.actions_of(fx)
     idle = np.zeros_like(acts[0])            # env 1 never departs, so it outlives env 0
     for a in acts:

@@ -6,21 +6,10 @@ import numpy as np
 import pytest
 
 from tests import malf_stream_cases as mc
+from tests import util
 from tests.malf_stream_np import rng_of
 
 pytestmark = pytest.mark.gpu
-
-
-def _env(envs, **kw):
-    from flatland_marl_amd.hip_backend import BatchedRailEnv
-    return BatchedRailEnv(envs, **kw)
-
-
-def _same(got, exp, msg):
-    got, exp = np.asarray(got), np.asarray(exp)
-    if got.shape != exp.shape or not np.array_equal(got, exp):
-        bad = np.argwhere(got != exp)
-        raise AssertionError(f"{msg}: {len(bad)} mismatches, first {bad[0].tolist()}: {got[tuple(bad[0])]} vs {exp[tuple(bad[0])]}")
 
 
 def _advance(env, traces, t, how):
@@ -44,20 +33,20 @@ def _compare(env, traces, t, out, what):
     for b, tr in enumerate(traces):
         w = f"{what} env {b} step {t}"
         # against numpy
-        _same(st[b][:, 4], tr.malf[t], w + " malfunction_down_counter vs numpy")
-        _same(st[b][:, 5], tr.nmalf[t], w + " num_malfunctions vs numpy")
-        _same(info[b], tr.malf[t], w + " info['malfunction'] vs numpy")
+        util.same(st[b][:, 4], tr.malf[t], w + " malfunction_down_counter vs numpy")
+        util.same(st[b][:, 5], tr.nmalf[t], w + " num_malfunctions vs numpy")
+        util.same(info[b], tr.malf[t], w + " info['malfunction'] vs numpy")
         assert pos[b] == tr.pos[t], f"{w} mt_pos {pos[b]} vs numpy {tr.pos[t]}"
-        _same(key[b], tr.key[t], w + " mt_key vs numpy")
+        util.same(key[b], tr.key[t], w + " mt_key vs numpy")
         # against the oracle
-        _same(st[b], tr.state[t], w + " state vs oracle")
-        _same(rew[b], tr.rewards[t], w + " rewards vs oracle")
-        _same(done[b], tr.dones[t], w + " dones vs oracle")
+        util.same(st[b], tr.state[t], w + " state vs oracle")
+        util.same(rew[b], tr.rewards[t], w + " rewards vs oracle")
+        util.same(done[b], tr.dones[t], w + " dones vs oracle")
         assert bool(done_all[b]) == bool(tr.done_all[t]), w + " done_all vs oracle"
 
 
 def _run(traces, how, what, before_step=None, **kw):
-    env = _env([tr.env for tr in traces], **kw)
+    env = util.batched([tr.env for tr in traces], **kw)
     for t in range(len(traces[0].malf)):
         if before_step is not None:
             before_step(env, t)

@@ -12,24 +12,11 @@ CUTILS_KEYS = (("agent_attr", "o_attr"), ("forest", "o_forest"), ("adjacency", "
                ("node_order", "o_node_order"), ("edge_order", "o_edge_order"), ("valid_actions", "o_valid"))
 
 
-def _env(envs, **kw):
-    from flatland_marl_amd.hip_backend import BatchedRailEnv
-    return BatchedRailEnv(envs, **kw)
-
-
-def _assert_same(got, exp, msg):
-    got = np.asarray(got)
-    if not np.array_equal(got, exp):
-        bad = np.argwhere(got != exp)
-        raise AssertionError(f"{msg}: {len(bad)} mismatches, first at {bad[0].tolist()}: got {got[tuple(bad[0])]} "
-                             f"expected {exp[tuple(bad[0])]}")
-
-
 @pytest.mark.parametrize("name", util.episode_fixtures())
 def test_obs_match_reference_golden(name):
     import torch
     fx = util.load(name)
-    env = _env([util.static_of(fx)])
+    env = util.batched([util.static_of(fx)])
     obs_steps = {int(t): k for k, t in enumerate(fx["obs_steps"])}
     py_steps = {int(t): k for k, t in enumerate(fx["py_steps"])} if "py_steps" in fx.files else {}
     pykeys = [k for k in fx.files if k.startswith("py_d")]
@@ -39,17 +26,17 @@ def test_obs_match_reference_golden(name):
         if t in obs_steps:
             k = obs_steps[t]
             for got, key in CUTILS_KEYS:
-                _assert_same(o[got].cpu().numpy()[0], fx[key][k], f"{name} t={t} {got}")
+                util.same(o[got].cpu().numpy()[0], fx[key][k], f"{name} t={t} {got}")
             pr = o["props"].cpu().numpy()[0]
-            _assert_same(pr[:, 0], fx["o_p_dist_target"][k], f"{name} t={t} dist_target")
-            _assert_same(pr[:, 1], fx["o_p_deadlocked"][k], f"{name} t={t} deadlocked")
-            _assert_same(pr[:, 2], fx["o_p_ready"][k], f"{name} t={t} ready")
+            util.same(pr[:, 0], fx["o_p_dist_target"][k], f"{name} t={t} dist_target")
+            util.same(pr[:, 1], fx["o_p_deadlocked"][k], f"{name} t={t} deadlocked")
+            util.same(pr[:, 2], fx["o_p_ready"][k], f"{name} t={t} ready")
         if t in py_steps:
             k = py_steps[t]
             for pk in pykeys:
                 depth, pdepth = int(pk.split("_")[1][1:]), int(pk.split("_")[2][1:])
                 got = env.obs_tree(depth, pdepth).cpu().numpy()[0]
-                _assert_same(got, fx[pk][k], f"{name} t={t} {pk}")
+                util.same(got, fx[pk][k], f"{name} t={t} {pk}")
 
     check(0)
     for t, a in enumerate(util.actions_of(fx)):
@@ -80,7 +67,7 @@ def test_batched_obs_match_oracle(bases, B, steps, malf_rate, tree):
             st["malf_rate"] = malf_rate
         envs.append(st)
         oracles.append(orc.OracleEnv(st))
-    env = _env(envs)
+    env = util.batched(envs)
     A = env.A
     seed = 5
     tcount = np.zeros(B, dtype=np.int64)
@@ -105,7 +92,7 @@ def test_batched_obs_match_oracle(bases, B, steps, malf_rate, tree):
             for got, key in (("agent_attr", "attr"), ("forest", "forest"), ("adjacency", "adjacency"),
                              ("node_order", "node_order"), ("edge_order", "edge_order"), ("valid_actions", "valid"),
                              ("props", "props")):
-                _assert_same(o[got][b], exp[key], f"replica {b} iter {it} {got}")
+                util.same(o[got][b], exp[key], f"replica {b} iter {it} {got}")
             if tr is not None:
-                _assert_same(tr[b], orc_env.obs_pytree(*tree), f"replica {b} iter {it} tree{tree}")
+                util.same(tr[b], orc_env.obs_pytree(*tree), f"replica {b} iter {it} tree{tree}")
     env.check()

@@ -21,23 +21,19 @@ Each case asserts its edge on the CPU before anything runs on the GPU: the per-a
 lp2 = min(min(n, 30) - 1, 30 // tpc)).  Each switch set runs in ONE fresh child process under a time limit; after a child that ends on a
 signal or at its limit no other is started."""
 import functools
-import json
-import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
-from tests import handmaps, util
 from tests import obs_state_cases as oc
+from tests import obs_switch_runs as sw
+from tests import util
 from tests.handmaps import CURVE_NE, CURVE_NW, CURVE_SE, CURVE_SW, DEAD_E, DEAD_W, HORZ, VERT
 
 pytestmark = pytest.mark.gpu
 N, E, S, W = 0, 1, 2, 3
 M, DONE, WAITING = oc.MOVING, oc.DONE, oc.WAITING
-CUTILS = (("agent_attr", "attr"), ("forest", "forest"), ("adjacency", "adjacency"), ("node_order", "node_order"), ("edge_order", "edge_order"),
-          ("valid_actions", "valid"), ("props", "props"))
 CHILD_TIMEOUT = 90      # a guard, not a measurement (a child takes a few seconds)
 MAX_NODES, CU_PRED, PY_PRED, NT = 31, 500, 30, 1024
 H, WD, TOP, BOTTOM, LEFT, RIGHT = 12, 30, 1, 10, 1, 28
@@ -108,36 +104,13 @@ BATCHES = (("o3", O3), ("o32", O32))
 SWITCH_SETS = (("default", {}), ("nofix", {"FL_OBS_NO_FIX": "1"}))
 
 
-def _static(spec, speed):
-    a = np.array(spec, dtype=np.int32)
-    A = len(a)
-    return dict(grid=long_oval(), init_pos=a[:, 0:2].copy(), init_dir=a[:, 2].copy(), target=a[:, 3:5].copy(), speed=np.array(speed, dtype=np.float64),
-                earliest=np.zeros(A, dtype=np.int32), latest=np.full(A, 200, dtype=np.int32), T=400, malf_rate=0.0, malf_min=0, malf_max=0,
-                mt_key=np.arange(624, dtype=np.uint32), mt_pos=624)
-
-
-def _rows(spec, agents):
-    grid = long_oval()
-    st, aux = np.zeros((len(spec), 12), dtype=np.int32), np.zeros((len(spec), 4), dtype=np.int32)
-    for i, a in enumerate(agents):
-        d = spec[i][2] if a["d"] is None else a["d"]
-        if a["r"] >= 0:
-            assert handmaps.nibble(grid[a["r"], a["c"]], d) != 0, (i, a)
-        st[i] = (a["r"], a["c"], d, a["state"], a["malf"], 0, 0, 0, 1 if a["state"] == DONE else -1, a["r"], a["c"], d if a["r"] >= 0 else -1)
-        aux[i] = (-1, 0, 0, int(a["state"] == DONE))
-    return st, aux
-
-
 @functools.lru_cache(maxsize=None)
 def _oracle(batch, name):
     """(flatland_cutils tensors at depth 500, upstream depth-2 tree at depth 30, per-agent (n, lp, lp2)) of the oracle set to the case's
     state; computed once"""
     from oracle import orc
     spec, speed, agents = dict(BATCHES)[batch][name]
-    o = orc.OracleEnv(_static(spec, speed))
-    st, aux = _rows(spec, agents)
-    o.set_state(st, aux, 0, False)
-    dm, slot = o.distance_map()
+    dm, slot = orc.OracleEnv(util.plain_static(long_oval(), spec, speed)).distance_map()      # (of the map and the targets alone)
     pieces = []
     for i, a in enumerate(agents):
         if a["state"] == DONE:
@@ -150,9 +123,7 @@ def _oracle(batch, name):
         lp = max(0, min(n - 1, (CU_PRED - 1) // tpc + 1))
         lp2 = max(0, min(min(n, PY_PRED) - 1, PY_PRED // tpc))
         pieces.append((n, lp, lp2))
-    tree = o.obs_pytree(2, PY_PRED)
-    o.set_state(st, aux, 0, False)      # (a flatland_cutils call leaves its deadlock flags in the env)
-    return o.obs_cutils(MAX_NODES, CU_PRED), tree, tuple(pieces)
+    return sw.oracle_case(long_oval(), (spec, speed, agents), max_nodes=MAX_NODES, cu_pred=CU_PRED, py_pred=PY_PRED) + (tuple(pieces),)
 
 
 def _items(batch, name):
@@ -183,104 +154,18 @@ def _reached():
             assert any(lp >= 1 for _, lp, _ in _oracle(batch, k)[2])
 
 
-def _same(got, exp, msg):
-    got, exp = np.asarray(got), np.asarray(exp)
-    assert got.shape == exp.shape, f"{msg}: shape {got.shape} vs {exp.shape}"
-    if not np.array_equal(got, exp):
-        bad = np.argwhere(got != exp)
-        raise AssertionError(f"{msg}: {len(bad)} mismatches, first {bad[0].tolist()}: {got[tuple(bad[0])]} vs {exp[tuple(bad[0])]}")
-
-
-def _policy_form(cu, b, A):
-    """the three index tensors of one env as the policy takes them: int64, parent / child offset by tree * max_nodes, every negative entry -2"""
-    adj = cu["adjacency"].astype(np.int64)
-    neg = adj < 0
-    adj[:, :, 0:2] += ((b * A + np.arange(A, dtype=np.int64)) * MAX_NODES)[:, None, None]
-    adj[neg] = -2
-    no, eo = cu["node_order"].astype(np.int64), cu["edge_order"].astype(np.int64)
-    no[no < 0] = -2
-    eo[eo < 0] = -2
-    return adj, no, eo
-
-
-def _run(out_path):
-    """child: the three launches on every batch against the oracle; every tensor goes to out_path for the parent's byte comparison"""
-    from flatland_marl_amd.hip_backend import BatchedRailEnv
-    keep = {}
-    for batch, cases in BATCHES:
-        names = list(cases)
-        env = BatchedRailEnv([_static(cases[k][0], cases[k][1]) for k in names])
-        assert env.max_nodes == MAX_NODES and env.pred_depth == CU_PRED
-        pairs = [_rows(cases[k][0], cases[k][2]) for k in names]
-        states, aux = np.stack([p[0] for p in pairs]), np.stack([p[1] for p in pairs])
-        B, A = len(names), env.A
-
-        def inject():
-            env.set_state(states, aux, np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.uint8))
-
-        for call in ("both", "alone", "policy"):
-            inject()
-            tree = None
-            if call == "both":
-                got, tree = env.obs_both(2, PY_PRED)
-                tree = tree.cpu().numpy()
-            elif call == "alone":
-                got = env.obs_cutils()
-            else:
-                pol = env.obs_policy()
-                got = dict(env.obs_outputs(), agent_attr=pol[0], forest=pol[1], adjacency=pol[2], node_order=pol[3], edge_order=pol[4])
-            print("RECORD", batch, call, json.dumps(env.last_obs_launch()), flush=True)
-            got = {k: v.cpu().numpy() for k, v in got.items()}
-            for b, k in enumerate(names):
-                exp_cu, exp_tree, _ = _oracle(batch, k)
-                exp_cu = dict(exp_cu)
-                if call == "policy":
-                    exp_cu["adjacency"], exp_cu["node_order"], exp_cu["edge_order"] = _policy_form(exp_cu, b, A)
-                for g, e in CUTILS:
-                    assert got[g][b].dtype == exp_cu[e].dtype, (g, got[g].dtype)
-                    _same(got[g][b], exp_cu[e], f"{batch}/{k} {call} {g}")
-                if tree is not None:
-                    _same(tree[b], exp_tree, f"{batch}/{k} {call} depth-2 tree")
-            for g, _ in CUTILS:
-                keep[f"{batch}/{call}/{g}"] = got[g]
-            if tree is not None:
-                keep[f"{batch}/{call}/tree"] = tree
-        env.check()
-        env.close()
-    np.savez(out_path, **keep)
-    print("DONE", len(keep), "tensors")
-
-
 def test_flat_item_space_changes_no_byte_and_equals_the_oracle(tmp_path):
     _reached()
-    env = {k: v for k, v in os.environ.items() if not k.startswith("FL_OBS_")}
-    outs, records = {}, {}
-    for tag, switches in SWITCH_SETS:
-        path = str(tmp_path / (tag + ".npz"))
-        try:
-            child = subprocess.run([sys.executable, os.path.abspath(__file__), path], env=dict(env, PYTHONPATH=util.ROOT, **switches),
-                                   capture_output=True, text=True, timeout=CHILD_TIMEOUT)
-        except subprocess.TimeoutExpired as e:      # nothing more is started on the card
-            err = e.stderr or ""
-            pytest.fail("%s: no end after %d s\n%s" % (tag, CHILD_TIMEOUT, (err if isinstance(err, str) else err.decode(errors="replace"))[-3000:]))
-        assert child.returncode == 0, "%s: exit status %d\n%s" % (tag, child.returncode, child.stderr[-3000:])      # (a failed assert ends the test: no further child)
-        lines = child.stdout.splitlines()
-        assert any(ln.startswith("DONE ") for ln in lines), tag
-        records[tag] = {tuple(ln.split()[1:3]): json.loads(ln.split(None, 3)[3]) for ln in lines if ln.startswith("RECORD ")}
-        outs[tag] = np.load(path)
+    outs, records = sw.run_switch_sets(__file__, SWITCH_SETS, tmp_path, CHILD_TIMEOUT)
     # every batch runs the one-round kernels: both builders MODE 3, the builder alone (int32 and the policy's int64 form) MODE 6
     for tag, rec in records.items():
         assert len(rec) == 3 * len(BATCHES)
         for (batch, call), r in rec.items():
             assert r["mode"] == (3 if call == "both" else 6) and r["nt"] == NT and r["split"] == 0, (tag, batch, call, r)
             assert (r["fix"] == 0) == (tag == "nofix"), (tag, batch, call, r)
-    a = outs["default"]
-    assert len(a.files) == len(BATCHES) * (3 * len(CUTILS) + 1)
-    for tag, b in outs.items():
-        assert sorted(a.files) == sorted(b.files), tag
-        for k in a.files:
-            assert a[k].dtype == b[k].dtype and a[k].tobytes() == b[k].tobytes(), (tag, k)
+    sw.assert_same_bytes(outs, len(BATCHES) * (3 * len(sw.CUTILS) + 1))
 
 
 if __name__ == "__main__":
-    _run(sys.argv[1])
+    sw.run_batches([(b, long_oval(), c) for b, c in BATCHES], ("both", "alone", "policy"), sys.argv[1], oracle=_oracle,
+                   max_nodes=MAX_NODES, cu_pred=CU_PRED, py_pred=PY_PRED)

@@ -6,8 +6,6 @@ row's maps, steps it with the device-side action streams and shadows EVERY env b
 observation (the seven flatland_cutils tensors and / or the upstream tree) and what the launch ran (BatchedRailEnv.last_obs_launch()) must be
 the oracle's resp. the row's.  A child that fails is not run again; its stderr is the case's failure."""
 import json
-import os
-import subprocess
 import sys
 import time
 
@@ -15,10 +13,10 @@ import numpy as np
 import pytest
 
 from tests import obs_kernel_cases as cases
+from tests import obs_switch_runs as sw
 from tests import util
 
-CUTILS = (("agent_attr", "attr"), ("forest", "forest"), ("adjacency", "adjacency"), ("node_order", "node_order"),
-          ("edge_order", "edge_order"), ("valid_actions", "valid"), ("props", "props"))
+CUTILS = sw.CUTILS
 SEED = 9
 # a guard, not a measurement: five times the slowest child of the first full run on an MI355X (split-cfg5x2-d3: two 400-agent envs)
 CHILD_TIMEOUT = 60
@@ -100,13 +98,10 @@ def _run(row):
 @pytest.mark.parametrize("row_id", [r.id for r in cases.ROWS])
 def test_row_matches_the_oracle_and_runs_the_kernel_it_names(row_id):
     row = cases.BY_ID[row_id]
-    env = {k: v for k, v in os.environ.items() if not k.startswith("FL_OBS_")}
     t0 = time.time()
-    child = subprocess.run([sys.executable, os.path.abspath(__file__), row_id], env=dict(env, PYTHONPATH=util.ROOT, **row.switches),
-                           capture_output=True, text=True, timeout=CHILD_TIMEOUT)
-    print("%s: %.1f s  %s" % (row_id, time.time() - t0, "".join(ln for ln in child.stdout.splitlines() if ln.startswith("RECORD "))))
-    assert child.returncode == 0, child.stderr[-3000:]
-    assert ("DONE %s" % row_id) in child.stdout.splitlines()
+    lines = sw.fresh_child(__file__, [row_id], row.switches, CHILD_TIMEOUT)
+    print("%s: %.1f s  %s" % (row_id, time.time() - t0, "".join(ln for ln in lines if ln.startswith("RECORD "))))
+    assert ("DONE %s" % row_id) in lines
 
 
 @pytest.mark.gpu

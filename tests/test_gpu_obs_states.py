@@ -12,8 +12,6 @@ asserts from last_obs_launch() that the option it exists for took effect on thes
 cells), so no set had to be replaced.  A child that fails is not run again; one that ends with a signal or at its time limit fails the test with
 its stderr, and the children after it are not started (they fail, saying so)."""
 import json
-import os
-import subprocess
 import sys
 import time
 
@@ -21,6 +19,7 @@ import numpy as np
 import pytest
 
 from tests import obs_state_cases as oc
+from tests import obs_switch_runs as sw
 from tests import util
 
 pytestmark = pytest.mark.gpu
@@ -44,14 +43,6 @@ SWITCH_SETS = {
     "tshift3": ({"FL_OBS_TSHIFT": "3"}, {"tshift": 3, "tmask": 1}),
     "round16": ({"FL_OBS_ROUND16": "2"}, {"nt": 512, "mode": ("ge", 3)}),                   # rounds of 16 agents, two workgroups a CU
 }
-
-
-def _same(got, exp, msg):
-    got, exp = np.asarray(got), np.asarray(exp)
-    assert got.shape == exp.shape and got.dtype == exp.dtype, f"{msg}: {got.dtype}{got.shape} vs {exp.dtype}{exp.shape}"
-    if not np.array_equal(got, exp):
-        bad = np.argwhere(got != exp)
-        raise AssertionError(f"{msg}: {len(bad)} mismatches, first {bad[0].tolist()}: {got[tuple(bad[0])]} vs {exp[tuple(bad[0])]}")
 
 
 def _matches(record, expect):
@@ -80,7 +71,7 @@ def _run(set_id):
             env.set_state(states, aux, np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.uint8))
 
         inject()
-        _same(env.state()[0], states, f"{m}/{s} rows read back after the injection")
+        util.same(env.state()[0], states, f"{m}/{s} rows read back after the injection", dtype=True)
         tag = f"[{set_id}] {m}/{s}"
 
         def compare_cutils(got, P, how):
@@ -88,15 +79,15 @@ def _run(set_id):
             for b, c in enumerate(cases):
                 if P in c["cu_pred"]:
                     for g, e in CUTILS:
-                        _same(got[g][b], fx["%s/cu_p%d_%s" % (c["name"], P, e)], f"{tag} {c['name']} {how} pred_depth {P} {g}")
+                        util.same(got[g][b], fx["%s/cu_p%d_%s" % (c["name"], P, e)], f"{tag} {c['name']} {how} pred_depth {P} {g}", dtype=True)
                     for col, k in enumerate(PROPS):
-                        _same(got["props"][b][:, col], fx["%s/cu_p%d_%s" % (c["name"], P, k)], f"{tag} {c['name']} {how} pred_depth {P} {k}")
+                        util.same(got["props"][b][:, col], fx["%s/cu_p%d_%s" % (c["name"], P, k)], f"{tag} {c['name']} {how} pred_depth {P} {k}", dtype=True)
 
         def compare_tree(tree, depth, P, how):
             tree = tree.cpu().numpy()
             for b, c in enumerate(cases):
                 if P in c["py_pred"]:
-                    _same(tree[b], fx["%s/py_d%d_p%d" % (c["name"], depth, P)], f"{tag} {c['name']} {how} depth-{depth} tree, predictor depth {P}")
+                    util.same(tree[b], fx["%s/py_d%d_p%d" % (c["name"], depth, P)], f"{tag} {c['name']} {how} depth-{depth} tree, predictor depth {P}", dtype=True)
 
         for P in sorted({P for c in cases for P in c["cu_pred"]}, reverse=True):
             inject()
@@ -125,7 +116,7 @@ def _run(set_id):
                 compare_cutils(got, 500, "obs_both")
                 n_launch += 2
         env.check()
-        _same(env.state()[0], states, f"{tag} rows after the launches")
+        util.same(env.state()[0], states, f"{tag} rows after the launches", dtype=True)
         env.close()
         n_env += B
     print("DONE", set_id, n_env, "envs", n_launch, "launches")
@@ -144,20 +135,10 @@ _GPU_LOST = []      # the child that ended on a signal or at its time limit: not
 def test_kernels_equal_the_reference_on_constructed_states(set_id):
     if _GPU_LOST:
         pytest.fail("%s: not started, the child %s ended %s" % (set_id, _GPU_LOST[0][0], _GPU_LOST[0][1]))
-    env = {k: v for k, v in os.environ.items() if not k.startswith("FL_OBS_")}
     t0 = time.time()
-    try:
-        child = subprocess.run([sys.executable, os.path.abspath(__file__), set_id], env=dict(env, PYTHONPATH=util.ROOT, **SWITCH_SETS[set_id][0]),
-                               capture_output=True, text=True, timeout=CHILD_TIMEOUT)
-    except subprocess.TimeoutExpired as e:
-        _GPU_LOST.append((set_id, "at its time limit of %d s" % CHILD_TIMEOUT))
-        err = e.stderr or ""
-        pytest.fail("%s: no end after %d s\n%s" % (set_id, CHILD_TIMEOUT, (err if isinstance(err, str) else err.decode(errors="replace"))[-3000:]))
-    print("%s: %.1f s\n%s" % (set_id, time.time() - t0, "\n".join(ln for ln in child.stdout.splitlines() if ln.startswith(("RECORD ", "DONE ")))))
-    if child.returncode < 0 or child.returncode in (134, 139):      # a signal (an abort, a segmentation fault): the card may be in a bad state
-        _GPU_LOST.append((set_id, "with exit status %d" % child.returncode))
-    assert child.returncode == 0, "exit status %d\n%s" % (child.returncode, child.stderr[-3000:])
-    assert any(ln.startswith("DONE %s " % set_id) for ln in child.stdout.splitlines())
+    lines = sw.fresh_child(__file__, [set_id], SWITCH_SETS[set_id][0], CHILD_TIMEOUT, lost=_GPU_LOST)
+    print("%s: %.1f s\n%s" % (set_id, time.time() - t0, "\n".join(ln for ln in lines if ln.startswith(("RECORD ", "DONE ")))))
+    assert any(ln.startswith("DONE %s " % set_id) for ln in lines)
 
 
 if __name__ == "__main__":

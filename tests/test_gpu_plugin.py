@@ -13,13 +13,6 @@ pytestmark = pytest.mark.gpu
 CUTILS = (("o_attr", 0, None), ("o_forest", 1, 0), ("o_adjacency", 1, 1), ("o_node_order", 1, 2), ("o_edge_order", 1, 3))
 
 
-def _same(got, exp, msg):
-    got = np.asarray(got)
-    if got.shape != exp.shape or not np.array_equal(got, exp):
-        bad = np.argwhere(got != exp) if got.shape == exp.shape else [["shape", got.shape, exp.shape]]
-        raise AssertionError(f"{msg}: {len(bad)} mismatches, first {bad[0]}")
-
-
 @pytest.mark.parametrize("name,string_states", [("cfg3_spfollow_malf100", False), ("cfg1_sparse", True), ("cfg2_fwd", False),
                                                  ("cfg0_tall_spfollow", True)])
 def test_cutils_plugin_on_a_duck_typed_env_replaying_a_reference_episode(name, string_states):
@@ -42,13 +35,13 @@ def test_cutils_plugin_on_a_duck_typed_env_replaying_a_reference_episode(name, s
         k = obs_steps[T]
         for key, i, j in CUTILS:
             got = out[i] if j is None else out[i][j]
-            _same(np.array(got, dtype=fx[key].dtype), fx[key][k], f"{name} T={T} {key}")
+            util.same(np.array(got, dtype=fx[key].dtype), fx[key][k], f"{name} T={T} {key}")
         cfg, props, valid = b.get_properties()
         assert cfg == dict(curr_step=T, n_agents=A, max_timesteps=int(fx["T"]), height=env.height, width=env.width)
-        _same(np.array(valid, dtype=np.uint8), fx["o_valid"][k], f"{name} T={T} valid_actions")
-        _same(np.array(props["dist_target"]), fx["o_p_dist_target"][k], f"{name} T={T} dist_target")
-        _same(np.array(props["deadlocked"]), fx["o_p_deadlocked"][k], f"{name} T={T} deadlocked")
-        _same(np.array(props["ready_not_depart"]), fx["o_p_ready"][k], f"{name} T={T} ready")
+        util.same(np.array(valid, dtype=np.uint8), fx["o_valid"][k], f"{name} T={T} valid_actions")
+        util.same(np.array(props["dist_target"]), fx["o_p_dist_target"][k], f"{name} T={T} dist_target")
+        util.same(np.array(props["deadlocked"]), fx["o_p_deadlocked"][k], f"{name} T={T} deadlocked")
+        util.same(np.array(props["ready_not_depart"]), fx["o_p_ready"][k], f"{name} T={T} ready")
         assert props["earliest_departure"] == [float(v) for v in fx["earliest"]]
         assert props["speed"] == [float(np.float32(v)) for v in fx["speed"]]
         dead_seen = max(dead_seen, int(fx["o_p_deadlocked"][k].sum()))
@@ -76,17 +69,17 @@ def test_reset_clears_the_sticky_flags_and_follows_a_new_map():
             env.goto(T)
             out = b.get_many(handles)
         k = len(obs_steps) - 1
-        _same(np.array(out[0], dtype=np.float32), fx["o_attr"][k], f"{name} attr")
-        _same(np.array(out[1][0], dtype=np.float32), fx["o_forest"][k], f"{name} forest")
+        util.same(np.array(out[0], dtype=np.float32), fx["o_attr"][k], f"{name} attr")
+        util.same(np.array(out[1][0], dtype=np.float32), fx["o_forest"][k], f"{name} forest")
         assert fx["o_p_deadlocked"][k].sum() > 0
-        _same(np.array(b.get_properties()[1]["deadlocked"]), fx["o_p_deadlocked"][k], f"{name} deadlocked")
+        util.same(np.array(b.get_properties()[1]["deadlocked"]), fx["o_p_deadlocked"][k], f"{name} deadlocked")
         # back to the start of the episode WITHOUT reset(): the flags stay (sticky); after reset() they are gone
         env.goto(obs_steps[1])
         b.get_many(handles)
         assert np.array(b.get_properties()[1]["deadlocked"]).sum() >= fx["o_p_deadlocked"][k].sum()
         b.reset()
         b.get_many(handles)
-        _same(np.array(b.get_properties()[1]["deadlocked"]), fx["o_p_deadlocked"][1], f"{name} deadlocked after reset")
+        util.same(np.array(b.get_properties()[1]["deadlocked"]), fx["o_p_deadlocked"][1], f"{name} deadlocked after reset")
 
 
 @pytest.mark.parametrize("name", ["cfg3_uniform", "cfg2_uniform", "cfg1_uniform"])
@@ -108,7 +101,7 @@ def test_upstream_plugin_on_a_duck_typed_env(name):
             got = b.get_many(list(range(A)))
             assert sorted(got) == list(range(A)) and isinstance(got[0], Node)
             dense = np.stack([dense_from_nodes(got[h], depth) for h in range(A)])
-            _same(dense, fx[pk][k], f"{name} T={T} {pk}")
+            util.same(dense, fx[pk][k], f"{name} T={T} {pk}")
         assert b.get_many(None) == {}             # observations.py:66-67: no handles, no observations
 
 

@@ -12,7 +12,6 @@ agent an env (synth_b1_a1: 2.71 / 3.48 and 2.43 / 2.42, synth_b3_a1: 4.17 in val
 of synth_b1_a1 at the second scale, so the ratios there say little about the kernel's accumulation order; with 7 agents or more
 the kernel's largest ratio is 2.04 and eager torch's 2.45.
 """
-import json
 import os
 
 import numpy as np
@@ -20,6 +19,7 @@ import pytest
 import torch
 
 from tests import policy_head_torch as ph
+from tests import util
 from tests.test_policy_head_golden import NAMES, golden_inputs, golden_params, load
 
 pytestmark = pytest.mark.gpu
@@ -37,14 +37,6 @@ def _net(params):
 def _ratio(err, e32, out):
     floor = ph.tolerance(0.0, out)
     return max(0.0, err - floor) / e32
-
-
-def _record(case, figs):
-    path = os.environ.get("POLICY_HEAD_ERRORS")
-    if path:
-        rec = json.load(open(path)) if os.path.exists(path) else dict(device=torch.cuda.get_device_name(0), cases={})
-        rec["cases"][case] = figs
-        json.dump(rec, open(path, "w"), indent=1, sort_keys=True)
 
 
 @pytest.mark.parametrize("s", [0, 1])
@@ -69,7 +61,7 @@ def test_fixture(name, s):
     figs = dict(err_logits=err_l, e32_logits=e32_l, ratio_logits=_ratio(err_l, e32_l, g["logits"][s]),
                 err_value=err_v, e32_value=e32_v, ratio_value=_ratio(err_v, e32_v, g["value"][s]))
     print(name, "x%d" % s, " ".join("%s %.3g" % kv for kv in figs.items()))
-    _record("%s-x%d" % (name, s), figs)
+    util.record_errors("POLICY_HEAD_ERRORS", "cases", "%s-x%d" % (name, s), figs)
     tol_l, tol_v = ph.tolerance(e32_l, g["logits"][s], R), ph.tolerance(e32_v, g["value"][s], R)
     terr_l, terr_v = float((lt.double() - l64).abs().max()), float((vt.double() - v64).abs().max())
     print(name, "x%d" % s, "head_torch: err_logits %.3g (ratio %.3g) err_value %.3g (ratio %.3g)"

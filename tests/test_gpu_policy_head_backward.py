@@ -111,7 +111,7 @@ def _figures(g, g32, g64, names):
 def _assert_within(g, g32, g64, what, names=tuple(pg.NAMES) + ("tree",), record=False):
     figs = _figures(g, g32, g64, names)
     if record:
-        _record(what, figs)
+        util.record_errors("POLICY_HEAD_GRAD_ERRORS", "cases", what, figs)
     print(what, "largest ratio %.3f" % max(figs["ratio_" + k] for k in names))
     for k in names:
         if float(g64[k].abs().max()) == 0:
@@ -119,14 +119,6 @@ def _assert_within(g, g32, g64, what, names=tuple(pg.NAMES) + ("tree",), record=
         else:
             assert figs["err_" + k] <= R * figs["e32_" + k], (what, k, figs["err_" + k], figs["e32_" + k])
     return figs
-
-
-def _record(case, figs):
-    path = os.environ.get("POLICY_HEAD_GRAD_ERRORS")
-    if path:
-        rec = json.load(open(path)) if os.path.exists(path) else dict(device=torch.cuda.get_device_name(0), cases={})
-        rec["cases"][case] = figs
-        json.dump(rec, open(path, "w"), indent=1, sort_keys=True)
 
 
 def _guarded(nfloats, fill=0xFF):
@@ -164,14 +156,6 @@ def _call(attr, tree, plist, Rl, Rv, value=True):
     return out
 
 
-def _bits(t):
-    return t.contiguous().view(torch.int32)
-
-
-def _same(a, b):
-    return torch.equal(_bits(a), _bits(b))
-
-
 # ---------------------------------------------------------------------------------------------------------------- GPU
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", GRAD_CASES, ids=lambda c: _case_id(*c))
@@ -185,7 +169,7 @@ def test_gradients_match_the_restatement(case):
     g, logits, value = _kernel_grads(net, attr, tree, Rl, Rv)
     with torch.no_grad():
         lg0, v0 = _net(st.params(s), trainable=False).head(attr, tree)
-    assert _same(logits, lg0[0]) and _same(value, v0)
+    assert util.same_bits(logits, lg0[0]) and util.same_bits(value, v0)
     g32, g64 = _reference(B, A, s)
     _assert_within(g, g32, g64, _case_id(*case), record=True)
 
@@ -268,13 +252,13 @@ def test_no_grad_and_the_default_launch_the_inference_path(monkeypatch):
     del calls[:]
     b = net.head(attr, tree)
     assert calls == ["policy_head_forward_saved"]
-    assert _same(a[0][0], b[0][0]) and _same(a[1], b[1]) and b[0][0].requires_grad
+    assert util.same_bits(a[0][0], b[0][0]) and util.same_bits(a[1], b[1]) and b[0][0].requires_grad
     del calls[:]
     c = net.head(attr, tree, valid, "soft")
     assert calls == ["policy_head_forward_saved", "policy_head"]
     with torch.no_grad():
         d = net.head(attr, tree, valid, "soft")
-    assert torch.equal(c[2], d[2]) and _same(c[0][0], a[0][0]) and not c[2].requires_grad
+    assert torch.equal(c[2], d[2]) and util.same_bits(c[0][0], a[0][0]) and not c[2].requires_grad
     del calls[:]
     _net(st.params(0), trainable=False).head(attr, tree)
     assert calls == ["policy_head"]
@@ -290,10 +274,10 @@ def test_same_bits_twice(shape):
     Rl, Rv = (x.to(DEV) for x in pg.upstream(B, A))
     plist = st.device_params(st.params(1), DEV)
     a, b = _call(attr, tree, plist, Rl, Rv), _call(attr, tree, plist, Rl, Rv)
-    assert _same(a.gtree, b.gtree) and _same(a.rows, b.rows) and _same(a.saved, b.saved)
+    assert util.same_bits(a.gtree, b.gtree) and util.same_bits(a.rows, b.rows) and util.same_bits(a.saved, b.saved)
     net = _net(st.params(1))
     g1, g2 = _kernel_grads(net, attr, tree, Rl, Rv)[0], _kernel_grads(net, attr, tree, Rl, Rv)[0]
-    assert all(_same(g1[k], g2[k]) for k in g1)
+    assert all(util.same_bits(g1[k], g2[k]) for k in g1)
 
 
 @pytest.mark.gpu
@@ -309,12 +293,12 @@ def test_envs_are_isolated():
     Rl2[0], Rv2[0] = Rl[0], Rv[0]
     plist = st.device_params(st.params(1), DEV)
     a, b = _call(attr, tree, plist, Rl, Rv), _call(attr2, tree2, plist, Rl2, Rv2)
-    assert _same(a.gtree[0], b.gtree[0]) and not _same(a.gtree[1], b.gtree[1])
+    assert util.same_bits(a.gtree[0], b.gtree[0]) and not util.same_bits(a.gtree[1], b.gtree[1])
     for views in ("rw", "sv"):
         for n, v in getattr(a, views).items():
             w = getattr(b, views)[n]
-            assert _same(v[:A], w[:A]), n
-            assert not _same(v[A:], w[A:]), n
+            assert util.same_bits(v[:A], w[:A]), n
+            assert not util.same_bits(v[A:], w[A:]), n
 
 
 @pytest.mark.gpu
@@ -361,10 +345,10 @@ def test_chunks(monkeypatch):
     net = _net(st.params(s))
     g1, logits, value = _kernel_grads(net, attr, tree, Rl, Rv)
     g2 = _kernel_grads(net, attr, tree, Rl, Rv)[0]
-    assert all(_same(g1[k], g2[k]) for k in g1)
+    assert all(util.same_bits(g1[k], g2[k]) for k in g1)
     with torch.no_grad():
         lg0, v0 = net.head(attr, tree)
-    assert _same(logits, lg0[0]) and _same(value, v0)
+    assert util.same_bits(logits, lg0[0]) and util.same_bits(value, v0)
     _assert_within(g1, *_reference(B, A, s), "chunks")
 
 
@@ -426,4 +410,4 @@ def test_refusals_and_conversions_on_the_device():
     torch.autograd.backward([logits[0], value], [wide[..., ::2], Rv.to(DEV)])
     g2 = {k: v.grad for k, v in net.named_parameters() if k in g1}
     g2["tree"] = t.grad
-    assert all(_same(g1[k], g2[k]) for k in g1)
+    assert all(util.same_bits(g1[k], g2[k]) for k in g1)

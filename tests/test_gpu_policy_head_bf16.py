@@ -12,7 +12,6 @@ the emulation makes already, so the expected ratio is 1 (the encoder measured at
 POLICY_HEAD_BF16_ERRORS=<path> makes the cases write their figures to <path> in the format of
 tests/golden/policy_head_bf16_errors.json."""
 import ctypes as C
-import json
 import os
 import types
 
@@ -43,14 +42,6 @@ PUSH_CASES = [cid for B, A in phs.PUSHED_SHAPES for cid in phs.sharp_cases(B, A)
 FIXTURE_CASES = ["fixture-%s-x%d" % (n, s) for n in NAMES for s in range(2)]
 OBS_CASES = ["obs-%s-x%d" % (n, s) for n in OBS_FIXTURES for s in range(2)]
 IDS = SHAPE_CASES + FIXTURE_CASES + OBS_CASES        # the cases the record holds
-
-
-def _record(case, figs):
-    path = os.environ.get("POLICY_HEAD_BF16_ERRORS")
-    if path:
-        rec = json.load(open(path)) if os.path.exists(path) else dict(device=torch.cuda.get_device_name(0), R16=R16, cases={})
-        rec["cases"][case] = figs
-        json.dump(rec, open(path, "w"), indent=1, sort_keys=True)
 
 
 def run(attr, tree, plist, packed, valid=None, mode=None, u=None, value=True):
@@ -143,7 +134,7 @@ def test_stages(case):
         assert e16 > 0, name
         figs["err_" + name], figs["e16_" + name], figs["ratio_" + name] = err, e16, err / e16
     print(case, " ".join("%s %.3g" % (n, figs["ratio_" + n]) for n in RATIO_STAGES))
-    _record(case, figs)
+    util.record_errors("POLICY_HEAD_BF16_ERRORS", "cases", case, figs, R16=R16)
     for name in RATIO_STAGES:
         assert figs["ratio_" + name] <= R16, (case, name, figs)
     assert phs.worst(st.value.double(), ph.stage_value(st.val.double()), pb.value(st.val.double())) <= 1.0
@@ -200,7 +191,7 @@ def test_reference_fixtures(name, s):
                 err_value=float((st.value.double() - gv).abs().max()), e16_value=float((v16 - gv).abs().max()))
     figs["ratio_logits"], figs["ratio_value"] = figs["err_logits"] / figs["e16_logits"], figs["err_value"] / figs["e16_value"]
     print(name, "x%d" % s, " ".join("%s %.3g" % kv for kv in figs.items()))
-    _record("fixture-%s-x%d" % (name, s), figs)
+    util.record_errors("POLICY_HEAD_BF16_ERRORS", "cases", "fixture-%s-x%d" % (name, s), figs, R16=R16)
     assert figs["ratio_logits"] <= R16 and figs["ratio_value"] <= R16, figs
     other = 0.8125
     for mode in ("soft", "hard"):
@@ -217,7 +208,7 @@ def test_reference_fixtures(name, s):
         obs = dict(agents=int(a16.size), hard_actions_differ=int((a16 != a32).sum()),
                    max_dlogit=float((st.logits - logits32).abs().max()), max_logit=float(logits32.abs().max()))
         print(name, "x%d" % s, obs)
-        _record("obs-%s-x%d" % (name, s), obs)
+        util.record_errors("POLICY_HEAD_BF16_ERRORS", "cases", "obs-%s-x%d" % (name, s), obs, R16=R16)
 
 
 def _pack_values(n, starts):

@@ -14,8 +14,6 @@ torch's eager float32 ops on the same inputs) and max(kernel error / bound) into
 tests/golden/policy_head_stage_errors.json, whose "stages" are the MI355X figures.  Recorded, not asserted: no ratio is fixed here.
 """
 import functools
-import json
-import os
 
 import numpy as np
 import pytest
@@ -24,6 +22,7 @@ import torch
 from tests import policy_head_bounds as pb
 from tests import policy_head_stages as phs
 from tests import policy_head_torch as ph
+from tests import util
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -35,15 +34,6 @@ def _case(case):
     attr, tree, valid, P = phs.CASES[case]()
     return (attr.to(DEV).contiguous(), tree.to(DEV).contiguous(), valid.to(DEV).contiguous(), phs.device_params(P, DEV),
             ph.stage_params(P, DEV), ph.stage_params(P, DEV, torch.float32))
-
-
-def _record(case, figs):
-    path = os.environ.get("POLICY_HEAD_ERRORS")
-    if path:
-        rec = json.load(open(path)) if os.path.exists(path) else {}
-        rec["device"] = torch.cuda.get_device_name(0)
-        rec.setdefault("stages", {})[case] = figs
-        json.dump(rec, open(path, "w"), indent=1, sort_keys=True)
 
 
 def _sound(k):
@@ -88,7 +78,7 @@ def test_stages(case):
             e_k, e_32 = phs.rms(got - ref), phs.rms(eager[n].double() - ref)
             figs[n] = dict(rms_ratio=e_k / e_32 if e_k > 0 else 0.0, max_over_bound=over[n])
     print(case, " ".join("%s %.3g" % kv for kv in over.items()), figs)
-    _record(case, figs)
+    util.record_errors("POLICY_HEAD_ERRORS", "stages", case, figs)
     assert all(w <= 1.0 for w in over.values()), over
     assert (k.actions.cpu().numpy() == ph.choose_actions(k.logits, valid, "soft")).all()
     if case.endswith("flat"):

@@ -17,13 +17,6 @@ pytestmark = pytest.mark.gpu
 DEPTHS = (1, 2, 7, 8, 9, 16, 17, 30, 500)      # the edges of an eight-hop walk and of a 32-lane tile of rows, and the limit
 
 
-def _same(got, exp, msg):
-    got = np.asarray(got)
-    if got.shape != exp.shape or got.dtype != exp.dtype or not np.array_equal(got, exp):
-        bad = np.argwhere(got != exp) if got.shape == exp.shape else [["shape", got.shape, exp.shape]]
-        raise AssertionError(f"{msg}: {len(bad)} mismatches, first {bad[0] if len(bad) else got.dtype}")
-
-
 def _by_shape(groups):
     shapes = {}
     for g in groups:
@@ -46,10 +39,10 @@ def _check_groups(env, gs, pick=None):
                     continue
                 k = min(s, len(g["steps"]) - 1)
                 msg = "%s state %d depth %d" % (g["name"], k, D)
-                _same(pick(pred, b), g[("pred", D)][k], msg + " float64")
-                _same(pick(p32, b), g[("pred", D)][k].astype(np.int32), msg + " int32")
-                _same(pick(wp, b), g[("wp", D)][k], msg + " waypoints")
-                _same(pick(ln, b), g[("len", D)][k], msg + " length")
+                util.same(pick(pred, b), g[("pred", D)][k], msg + " float64", dtype=True)
+                util.same(pick(p32, b), g[("pred", D)][k].astype(np.int32), msg + " int32", dtype=True)
+                util.same(pick(wp, b), g[("wp", D)][k], msg + " waypoints", dtype=True)
+                util.same(pick(ln, b), g[("len", D)][k], msg + " length", dtype=True)
     env.check()
 
 
@@ -91,10 +84,10 @@ def test_handmaps_in_one_mixed_batch():
             for i, g in enumerate(gs):
                 k = min(s, len(g["steps"]) - 1)
                 pred, wp, ln = mb.pick(i, out)
-                _same(pred.cpu().numpy(), g[("pred", D)][k], "mixed %s depth %d" % (g["name"], D))
-                _same(wp.cpu().numpy(), g[("wp", D)][k], "mixed %s waypoints" % g["name"])
-                _same(ln.cpu().numpy(), g[("len", D)][k], "mixed %s length" % g["name"])
-                _same(mb.pick(i, o32).cpu().numpy(), g[("pred", D)][k].astype(np.int32), "mixed %s int32" % g["name"])
+                util.same(pred.cpu().numpy(), g[("pred", D)][k], "mixed %s depth %d" % (g["name"], D), dtype=True)
+                util.same(wp.cpu().numpy(), g[("wp", D)][k], "mixed %s waypoints" % g["name"], dtype=True)
+                util.same(ln.cpu().numpy(), g[("len", D)][k], "mixed %s length" % g["name"], dtype=True)
+                util.same(mb.pick(i, o32).cpu().numpy(), g[("pred", D)][k].astype(np.int32), "mixed %s int32" % g["name"], dtype=True)
     mb.check()
     mb.close()
 
@@ -119,10 +112,10 @@ def _check_against_restatement(env, statics, envs_checked, depths, msg):
         p32 = env.predictions(D, torch.int32).cpu().numpy()
         for b in envs_checked:
             e_pred, e_wp, e_ln = _restated(env, statics, st, b, D, cache)
-            _same(pred[b], e_pred, "%s env %d depth %d float64" % (msg, b, D))
-            _same(p32[b], e_pred.astype(np.int32), "%s env %d depth %d int32" % (msg, b, D))
-            _same(wp[b], e_wp, "%s env %d depth %d waypoints" % (msg, b, D))
-            _same(ln[b], e_ln, "%s env %d depth %d length" % (msg, b, D))
+            util.same(pred[b], e_pred, "%s env %d depth %d float64" % (msg, b, D), dtype=True)
+            util.same(p32[b], e_pred.astype(np.int32), "%s env %d depth %d int32" % (msg, b, D), dtype=True)
+            util.same(wp[b], e_wp, "%s env %d depth %d waypoints" % (msg, b, D), dtype=True)
+            util.same(ln[b], e_ln, "%s env %d depth %d length" % (msg, b, D), dtype=True)
     return st
 
 
@@ -215,9 +208,9 @@ def test_1101_one_agent_envs_in_one_launch():
         p32 = env.predictions(D, torch.int32).cpu().numpy()
         for b in range(1101):
             s = (b // A) % (k + 1)
-            _same(pred[b, 0], g[("pred", D)][s][b % A], "env %d depth %d" % (b, D))
-            _same(p32[b, 0], g[("pred", D)][s][b % A].astype(np.int32), "env %d depth %d int32" % (b, D))
-            _same(wp[b, 0], g[("wp", D)][s][b % A], "env %d waypoints" % b)
+            util.same(pred[b, 0], g[("pred", D)][s][b % A], "env %d depth %d" % (b, D), dtype=True)
+            util.same(p32[b, 0], g[("pred", D)][s][b % A].astype(np.int32), "env %d depth %d int32" % (b, D), dtype=True)
+            util.same(wp[b, 0], g[("wp", D)][s][b % A], "env %d waypoints" % b, dtype=True)
             assert ln[b, 0] == g[("len", D)][s][b % A]
     env.check()
     env.close()
@@ -270,10 +263,10 @@ def test_guarded_buffers_null_outputs_and_a_side_stream(side_stream):
                             assert not (body == 0x7f7f7f7f).any()
                     if exp is not None:
                         if skip != "pred":
-                            _same(pred.cpu().numpy()[G:G + n_pred].reshape(nb, A, D + 1, 5), exp[0][b0:b0 + nb].astype(pred.cpu().numpy().dtype), "pred")
+                            util.same(pred.cpu().numpy()[G:G + n_pred].reshape(nb, A, D + 1, 5), exp[0][b0:b0 + nb].astype(pred.cpu().numpy().dtype), "pred", dtype=True)
                         if skip != "paths":
-                            _same(wp.cpu().numpy()[G:G + n_wp].reshape(nb, A, D, 3), exp[1][b0:b0 + nb], "waypoints")
-                            _same(ln.cpu().numpy()[G:G + n_len].reshape(nb, A), exp[2][b0:b0 + nb], "length")
+                            util.same(wp.cpu().numpy()[G:G + n_wp].reshape(nb, A, D, 3), exp[1][b0:b0 + nb], "waypoints", dtype=True)
+                            util.same(ln.cpu().numpy()[G:G + n_len].reshape(nb, A), exp[2][b0:b0 + nb], "length", dtype=True)
     if side_stream:
         # the same values as on the handle's usual stream
         st, _ = env.state()
@@ -282,7 +275,7 @@ def test_guarded_buffers_null_outputs_and_a_side_stream(side_stream):
         assert L.fl_sync(env.h) == 0
         cache = {}
         for b in range(3):
-            _same(pred[b].cpu().numpy(), _restated(env, envs, st, b, 30, cache)[0], "side stream env %d" % b)
+            util.same(pred[b].cpu().numpy(), _restated(env, envs, st, b, 30, cache)[0], "side stream env %d" % b, dtype=True)
         env.use_torch_stream()
     env.check()
     env.close()
@@ -323,7 +316,7 @@ def _dicts_equal_fixture(p, g, k, D, A, msg):
     got = p.get()
     assert sorted(got) == list(range(A))
     for h in range(A):
-        _same(got[h], g[("pred", D)][k][h], "%s get() handle %d" % (msg, h))
+        util.same(got[h], g[("pred", D)][k][h], "%s get() handle %d" % (msg, h), dtype=True)
         n = int(g[("devlen", D)][k][h])
         assert list(p.env.dev_pred_dict[h]) == [tuple(int(q) for q in x) for x in g[("dev", D)][k][h][:n]], (msg, h)
     paths = p.get_shortest_paths(D)
@@ -350,12 +343,12 @@ def test_rail_env_facade_on_a_hand_made_map():
             env.step({i: int(a) for i, a in enumerate(fx["actions"][t - 1])})
         if t in steps:
             k = steps.index(t)
-            _same(env._batch.state()[0][0], g["state"][k], "%s t=%d state" % (g["name"], t))
+            util.same(env._batch.state()[0][0], g["state"][k], "%s t=%d state" % (g["name"], t), dtype=True)
             _dicts_equal_fixture(p, g, k, 8, A, "%s t=%d" % (g["name"], t))
             if k == int(g["extra"]["get3_step"]):
                 assert sorted(p.get(3)) == g["extra"]["get3"].tolist() == [3]
                 assert sorted(p.get(0)) == g["extra"]["get0"].tolist() and sorted(p.get(None)) == g["extra"]["getnone"].tolist()
-                _same(p.get(3)[3], g[("pred", 8)][k][3], "get(3)")
+                util.same(p.get(3)[3], g[("pred", 8)][k][3], "get(3)", dtype=True)
     q = ShortestPathPredictorForRailEnv(30)
     q.set_env(env)
     _dicts_equal_fixture(q, g, steps.index(max(steps)), 30, A, g["name"] + " depth 30")

@@ -23,8 +23,8 @@ import numpy as np
 import pytest
 
 from tests import obs_state_cases as oc
-from tests import test_gpu_obs_tail_fill as tf
-from tests import test_gpu_passb_slices as ps
+from tests import obs_switch_runs as sw
+from tests import util
 
 pytestmark = pytest.mark.gpu
 N, E, S, W = 0, 1, 2, 3
@@ -32,24 +32,15 @@ M, WAIT = oc.MOVING, oc.off(oc.WAITING)
 
 
 def _y20():
-    spec, speed, _ = ps._crowd(8)
+    spec, speed, _ = sw.crowd(8)
     turn = [oc.on(M, 1, 4, W), oc.on(M, 4, 1, E)] + [oc.GONE, WAIT] * 8 + [oc.on(M, 4, 5, W), oc.on(M, 3, 3, N)]
     return {"turn": (spec, speed, turn)}, {"alldone": (spec, speed, [oc.GONE] * 20), "turn": (spec, speed, turn)}
 
 
 Y20, Y20_OVER = _y20()
 # batch -> (map, cases, steps): the constructed states are stepped with the synthetic uniform actions like the generated envs
-STATE_BATCHES = (("y1", "yard", tf.Y1, 10), ("y20", "yard", Y20, 10), ("y20over", "yard", Y20_OVER, 0), ("y32", "yard", ps.Y32, 10))
+STATE_BATCHES = (("y1", "yard", sw.Y1, 10), ("y20", "yard", Y20, 10), ("y20over", "yard", Y20_OVER, 0), ("y32", "yard", dict(sw.Y32, dense=sw.dense(15)), 10))
 GEN_BATCHES = (("cfg1", 3, 2, 16), ("cfg2", 3, 2, 12), ("cfg3", 2, 3, 6))      # workload, envs, depth of the upstream tree, steps
-
-
-def _same(got, exp, msg):
-    got, exp = np.asarray(got), np.asarray(exp)
-    assert got.shape == exp.shape and got.dtype == exp.dtype, f"{msg}: {got.dtype}{got.shape} vs {exp.dtype}{exp.shape}"
-    if got.tobytes() != exp.tobytes():
-        bad = np.argwhere(got != exp)
-        first = f", first {bad[0].tolist()}: {got[tuple(bad[0])]} vs {exp[tuple(bad[0])]}" if len(bad) else ""
-        raise AssertionError(f"{msg}: {len(bad)} mismatches{first}")
 
 
 def _compare(env, oracles, depth, where, classes):
@@ -66,13 +57,13 @@ def _compare(env, oracles, depth, where, classes):
     pol = {n: t.cpu().numpy() for n, t in zip(names, pol)}
     for b, o in enumerate(oracles):
         exp_tree = o.obs_pytree(depth, 30)
-        exp = o.obs_cutils(tf.MAX_NODES, 500)       # (every step: the deadlock flags are sticky)
-        for g, e in tf.CUTILS:
-            _same(got[g][b], exp[e], f"{where} env {b} both {g}")
-        _same(tree[b], exp_tree, f"{where} env {b} depth-{depth} tree")
-        adj, no, eo = tf._policy_form(exp, b, A)
+        exp = o.obs_cutils(sw.MAX_NODES, 500)       # (every step: the deadlock flags are sticky)
+        for g, e in sw.CUTILS:
+            util.same(got[g][b], exp[e], f"{where} env {b} both {g}", dtype=True, bytes=True)
+        util.same(tree[b], exp_tree, f"{where} env {b} depth-{depth} tree", dtype=True, bytes=True)
+        adj, no, eo = sw.policy_form(exp, b, A)
         for g, e in (("agent_attr", exp["attr"]), ("forest", exp["forest"]), ("adjacency", adj), ("node_order", no), ("edge_order", eo)):
-            _same(pol[g][b], e, f"{where} env {b} policy {g}")
+            util.same(pol[g][b], e, f"{where} env {b} policy {g}", dtype=True, bytes=True)
 
 
 def _episode(env, oracles, statics, seed, steps, depth, name, classes):
@@ -89,9 +80,9 @@ def _episode(env, oracles, statics, seed, steps, depth, name, classes):
             r_o, d_o, da = o.step(synth.uniform_actions(seed, b, tc[b], A))
             tc[b] += 1
             w = f"{name} env {b} step {t}"
-            _same(st[b], o.state(), w + " state")
-            _same(rew[b], np.asarray(r_o, dtype=rew.dtype), w + " rewards")
-            _same(done[b].astype(bool), np.asarray(d_o).astype(bool), w + " dones")
+            util.same(st[b], o.state(), w + " state", dtype=True, bytes=True)
+            util.same(rew[b], np.asarray(r_o, dtype=rew.dtype), w + " rewards", dtype=True, bytes=True)
+            util.same(done[b].astype(bool), np.asarray(d_o).astype(bool), w + " dones", dtype=True, bytes=True)
             assert bool(done_all[b]) == bool(da), w + " done_all"
             if da:
                 ended.append(b)
@@ -109,9 +100,10 @@ def _state_batch(batch):
     from oracle import orc
     _, map_name, cases, steps = next(b for b in STATE_BATCHES if b[0] == batch)
     names = list(cases)
-    statics = [tf._static(map_name, cases[k][0], cases[k][1]) for k in names]
+    grid = sw.grid_of(map_name)
+    statics = [util.plain_static(grid, cases[k][0], cases[k][1]) for k in names]
     env = BatchedRailEnv(statics)
-    pairs = [tf._rows(map_name, cases[k][0], cases[k][2]) for k in names]
+    pairs = [sw.rows(grid, cases[k][0], cases[k][2]) for k in names]
     states, aux = np.stack([p[0] for p in pairs]), np.stack([p[1] for p in pairs])
     env.set_state(states, aux, np.zeros(len(names), dtype=np.int32), np.zeros(len(names), dtype=np.uint8))
     oracles = [orc.OracleEnv(s) for s in statics]

@@ -9,18 +9,6 @@ from tests import util
 pytestmark = pytest.mark.gpu
 
 
-def _env(envs, **kw):
-    from flatland_marl_amd.hip_backend import BatchedRailEnv
-    return BatchedRailEnv(envs, **kw)
-
-
-def _same(got, exp, msg):
-    got = np.asarray(got)
-    if not np.array_equal(got, exp):
-        bad = np.argwhere(got != exp)
-        raise AssertionError(f"{msg}: {len(bad)} mismatches, first {bad[0].tolist()}: {got[tuple(bad[0])]} vs {exp[tuple(bad[0])]}")
-
-
 def _rng(b):
     st = np.random.RandomState([b]).get_state()
     return np.array(st[1], dtype=np.uint32), int(st[2])
@@ -31,12 +19,12 @@ def _compare(env, oracles, tag, tree=(2, 30)):
     tr = env.obs_tree(*tree).cpu().numpy()
     st = env.state()[0]
     for b, oe in enumerate(oracles):
-        _same(st[b], oe.state(), f"{tag} env {b} state")
+        util.same(st[b], oe.state(), f"{tag} env {b} state")
         exp = oe.obs_cutils(31, 500)
         for got, key in (("agent_attr", "attr"), ("forest", "forest"), ("adjacency", "adjacency"), ("node_order", "node_order"),
                          ("edge_order", "edge_order"), ("valid_actions", "valid"), ("props", "props")):
-            _same(o[got][b], exp[key], f"{tag} env {b} {got}")
-        _same(tr[b], oe.obs_pytree(*tree), f"{tag} env {b} tree")
+            util.same(o[got][b], exp[key], f"{tag} env {b} {got}")
+        util.same(tr[b], oe.obs_pytree(*tree), f"{tag} env {b} tree")
 
 
 def test_env_of_a_live_batch_is_replaced_by_another_map_and_matches_the_oracle_from_there():
@@ -50,7 +38,7 @@ def test_env_of_a_live_batch_is_replaced_by_another_map_and_matches_the_oracle_f
     for b in range(4):
         key, pos = _rng(700 + b)
         envs.append(util.static_of(bases[b], key, pos))
-    env = _env(envs, reserve=(U, R))
+    env = util.batched(envs, reserve=(U, R))
     oracles = [orc.OracleEnv(e) for e in envs]
     A = env.A
     tc = [0] * 4
@@ -63,8 +51,8 @@ def test_env_of_a_live_batch_is_replaced_by_another_map_and_matches_the_oracle_f
             for b, oe in enumerate(oracles):
                 r_o, d_o, da = oe.step(synth.forward_biased_actions(seed, 50 + b, tc[b], A))
                 tc[b] += 1
-                _same(rew[b], r_o, f"{tag} it {it} env {b} rewards")
-                _same(done[b], d_o, f"{tag} it {it} env {b} dones")
+                util.same(rew[b], r_o, f"{tag} it {it} env {b} rewards")
+                util.same(done[b], d_o, f"{tag} it {it} env {b} dones")
                 assert bool(done_all[b]) == da
                 if da:
                     key, pos = oe.get_rng()
@@ -83,9 +71,9 @@ def test_env_of_a_live_batch_is_replaced_by_another_map_and_matches_the_oracle_f
         tc[b] = 0
     env.commit()
     dm, slot = env.distance_map(1)
-    _same(dm, bases[5]["dm_u16"], "distance map of the replaced env")
-    _same(slot, bases[5]["target_slot"], "target slots of the replaced env")
-    _same(env.distance_map(0)[0], bases[0]["dm_u16"], "distance map of an untouched env")
+    util.same(dm, bases[5]["dm_u16"], "distance map of the replaced env")
+    util.same(slot, bases[5]["target_slot"], "target slots of the replaced env")
+    util.same(env.distance_map(0)[0], bases[0]["dm_u16"], "distance map of an untouched env")
     assert env.state()[1].tolist()[1] == 0 and env.state()[1].tolist()[0] == 60
     run(120, "after")
     env.check()
@@ -102,7 +90,7 @@ def test_replacement_without_reserve_is_limited_to_the_first_commit_sizes():
     from flatland_marl_amd.hip_backend import FlatlandHipError
     small, large = util.load("cfg1_uniform"), None
     st = util.static_of(small)
-    env = _env([st, st])
+    env = util.batched([st, st])
     env.replace_env(1, st)       # same size: fine
     env.check()
     more = dict(st)
@@ -120,7 +108,7 @@ def test_masked_rebuild_touches_only_the_masked_envs_and_reset_takes_a_device_ma
     from flatland_marl_amd import synth
     fx = util.load("cfg4_fwd_head")
     st = util.static_of(fx)
-    env = _env([st, st, st])
+    env = util.batched([st, st, st])
     oracles = [orc.OracleEnv(st) for _ in range(3)]
     for t in range(30):
         env.step_synth(3, 0, 1, auto_reset=True)
@@ -129,7 +117,7 @@ def test_masked_rebuild_touches_only_the_masked_envs_and_reset_takes_a_device_ma
     mask = torch.tensor([0, 1, 0], dtype=torch.uint8, device="cuda")
     env.rebuild_distance_maps(mask)
     for b in range(3):
-        _same(env.distance_map(b)[0], fx["dm_u16"], f"env {b} distance map")
+        util.same(env.distance_map(b)[0], fx["dm_u16"], f"env {b} distance map")
     # the same map before and after says little about a rebuild: the tables the observations read (segments, next-hop, hop8) are rebuilt with
     # it, and the observations of all three envs are still the oracle's (a rebuild from scratch, at a size where the work is spread over a
     # looping grid: tests/test_gpu_handmaps.py)
@@ -137,9 +125,9 @@ def test_masked_rebuild_touches_only_the_masked_envs_and_reset_takes_a_device_ma
     s0 = env.state()[0].copy()
     env.reset(mask)                               # device mask: only env 1 starts over
     s1, el = env.state()
-    _same(s1[0], s0[0], "env 0 untouched"); _same(s1[2], s0[2], "env 2 untouched")
+    util.same(s1[0], s0[0], "env 0 untouched"); util.same(s1[2], s0[2], "env 2 untouched")
     assert el.tolist() == [30, 0, 30] and (s1[1][:, 3] == 0).all()
-    e2 = _env([st])
+    e2 = util.batched([st])
     for t in range(40):
         env.step_synth(3, 0, 1, auto_reset=True)
     for t in range(40):
@@ -148,7 +136,7 @@ def test_masked_rebuild_touches_only_the_masked_envs_and_reset_takes_a_device_ma
     # with malfunction rate 1/7200 the two runs differ only if a malfunction fired; compare the non-malfunctioning agents
     a, b = env.state()[0][1], e2.state()[0][0]
     same = (a[:, 5] == 0) & (b[:, 5] == 0)
-    _same(a[same][:, :4], b[same][:, :4], "env 1 after the masked reset")
+    util.same(a[same][:, :4], b[same][:, :4], "env 1 after the masked reset")
     env.check()
 
 
@@ -169,7 +157,7 @@ def test_envs_of_one_map_share_their_static_tables_through_replacements():
     for b, m in enumerate(which):
         key, pos = _rng(1700 + b)
         envs.append(util.static_of(bases[m], key, pos))
-    env = _env(envs, reserve=(U, R))
+    env = util.batched(envs, reserve=(U, R))
     oracles = [orc.OracleEnv(e) for e in envs]
     A, seed = env.A, 47
     tc = [0] * len(envs)
@@ -183,7 +171,7 @@ def test_envs_of_one_map_share_their_static_tables_through_replacements():
             for b, oe in enumerate(oracles):
                 r_o, d_o, da = oe.step(synth.forward_biased_actions(seed, 70 + b, tc[b], A))
                 tc[b] += 1
-                _same(rew[b], r_o, f"{tag} it {it} env {b} rewards")
+                util.same(rew[b], r_o, f"{tag} it {it} env {b} rewards")
                 if da:
                     key, pos = oe.get_rng()
                     oracles[b] = orc.OracleEnv(envs[b])
@@ -203,12 +191,12 @@ def test_envs_of_one_map_share_their_static_tables_through_replacements():
     replace(0, 2, 1800)          # the owner of map 0's tables gets map 2: env 2 now owns map 0's (never built so far)
     run(40, "owner replaced")
     for b in (2, 4):
-        _same(env.distance_map(b)[0], bases[0]["dm_u16"], f"distance map of dependent {b}")
+        util.same(env.distance_map(b)[0], bases[0]["dm_u16"], f"distance map of dependent {b}")
     replace(3, 2, 1801)          # env 3 joins map 2 (owner: env 0)
     replace(2, 1, 1802)          # the new owner of map 0 leaves too: env 4 is the last one on it
     run(40, "joined", rebuild=True)
-    _same(env.distance_map(4)[0], bases[0]["dm_u16"], "distance map of the last env on map 0")
-    _same(env.distance_map(3)[0], bases[2]["dm_u16"], "distance map of the env that joined map 2")
+    util.same(env.distance_map(4)[0], bases[0]["dm_u16"], "distance map of the last env on map 0")
+    util.same(env.distance_map(3)[0], bases[2]["dm_u16"], "distance map of the env that joined map 2")
     env.rebuild_distance_maps(torch.tensor([0, 0, 0, 1, 1, 0], dtype=torch.uint8, device="cuda"))
     env.rebuild_distance_maps()
     run(20, "after rebuilds")

@@ -14,11 +14,6 @@ from tests import util
 pytestmark = pytest.mark.gpu
 
 
-def _env(envs, **kw):
-    from flatland_marl_amd.hip_backend import BatchedRailEnv
-    return BatchedRailEnv(envs, **kw)
-
-
 def test_score_sums_equal_the_reference_evaluator_scores():
     """fl_scores = sum over finished episodes of (1 + R / (T * A), arrived / A) (flatland/evaluators/service.py:875-879, 900-913):
     two replicas of the golden `cfg2_filtered` episode, one of them run twice (auto-reset), against the scores the capture
@@ -26,7 +21,7 @@ def test_score_sums_equal_the_reference_evaluator_scores():
     import torch
     fx = util.load("cfg2_filtered")
     st = util.static_of(fx)
-    env = _env([st, dict(st)])
+    env = util.batched([st, dict(st)])
     raw = np.array(fx["actions"], dtype=np.uint8)
     for t in range(len(raw)):
         a = torch.from_numpy(np.stack([raw[t], raw[t]])).cuda()
@@ -54,7 +49,7 @@ def test_score_sums_equal_the_reference_evaluator_scores():
 def test_set_state_refuses_a_position_off_the_rail():
     from flatland_marl_amd.hip_backend import FlatlandHipError
     fx = util.load("cfg1_uniform")
-    env = _env([util.static_of(fx)])
+    env = util.batched([util.static_of(fx)])
     grid = np.asarray(fx["grid"])
     empty = np.argwhere(grid == 0)[0]
     st, _ = env.state()
@@ -80,7 +75,7 @@ def test_shortest_path_following_stream_is_shadowed_by_the_oracle(name, steps):
     st = util.static_of(fx)
     envs = [st, dict(st)]
     envs[1]["mt_key"], envs[1]["mt_pos"] = np.random.RandomState([5]).get_state()[1:3]
-    env = _env(envs)
+    env = util.batched(envs)
     oracles = [orc.OracleEnv(e) for e in envs]
     dm, slot = oracles[0].distance_map()
     seed, arrived, tc = 9, 0, [0, 0]
@@ -116,7 +111,7 @@ def test_distinct_generated_maps_in_one_batch_match_the_oracle():
     from oracle import orc
     envs, seed = wl.make_envs("cfg2", B=10, distinct=10)
     assert len({e["grid"].tobytes() for e in envs}) == 10
-    env = _env(envs)
+    env = util.batched(envs)
     oracles = [orc.OracleEnv(e) for e in envs]
     for t in range(60):
         rew, done, done_all = env.step_synth(seed, 0, 0, auto_reset=False)
@@ -146,7 +141,7 @@ def test_two_hundred_agents_on_a_tall_map_match_the_oracle():
         st = gen.np_random(seed).get_state()
         envs.append(gen.generate_env(40, 76, 200, rg, lg, st[1], st[2], 1.0 / 200, 20, 50))
     assert envs[0]["grid"].shape == (76, 40)
-    env = _env(envs)
+    env = util.batched(envs)
     oracles = [orc.OracleEnv(e) for e in envs]
     keys = (("agent_attr", "attr"), ("forest", "forest"), ("adjacency", "adjacency"), ("node_order", "node_order"),
             ("edge_order", "edge_order"), ("valid_actions", "valid"))
@@ -249,7 +244,7 @@ def test_grid_with_a_three_way_cell_matches_the_reference(name, fused):
     such a batch (max_branch > 2) instead of the compact ones"""
     import torch
     fx = util.load(name)
-    env = _env([util.static_of(fx)])
+    env = util.batched([util.static_of(fx)])
     dm, slot = env.distance_map(0)
     np.testing.assert_array_equal(dm, fx["dm_u16"])
     keys = (("agent_attr", "o_attr"), ("forest", "o_forest"), ("adjacency", "o_adjacency"), ("node_order", "o_node_order"),

@@ -8,16 +8,11 @@ from tests import util
 pytestmark = pytest.mark.gpu
 
 
-def _env(envs, **kw):
-    from flatland_marl_amd.hip_backend import BatchedRailEnv
-    return BatchedRailEnv(envs, **kw)
-
-
 @pytest.mark.parametrize("name", util.episode_fixtures())
 def test_step_matches_reference_golden(name):
     import torch
     fx = util.load(name)
-    env = _env([util.static_of(fx)])
+    env = util.batched([util.static_of(fx)])
     acts = util.actions_of(fx)
     for t in range(len(acts)):
         rew, done, done_all = env.step(torch.from_numpy(acts[t][None, :].copy()).cuda())
@@ -33,7 +28,7 @@ def test_step_matches_reference_golden(name):
 @pytest.mark.parametrize("name", util.episode_fixtures() + util.base_fixtures())
 def test_distance_map_matches_reference_golden(name):
     fx = util.load(name)
-    env = _env([util.static_of(fx)])
+    env = util.batched([util.static_of(fx)])
     dm, slot = env.distance_map(0)
     np.testing.assert_array_equal(slot, fx["target_slot"])
     np.testing.assert_array_equal(dm, fx["dm_u16"])
@@ -43,7 +38,7 @@ def test_step_after_done_raises_like_reference():
     import torch
     from flatland_marl_amd.hip_backend import EpisodeDoneError
     fx = util.load("cfg1_spfollow")
-    env = _env([util.static_of(fx)])
+    env = util.batched([util.static_of(fx)])
     for a in util.actions_of(fx):
         env.step(torch.from_numpy(a[None, :].copy()).cuda())
     env.check()
@@ -78,7 +73,7 @@ def test_batched_step_matches_oracle_with_synth_stream_and_autoreset(bases, B, s
             st["malf_rate"] = malf_rate
         envs.append(st)
         oracles.append(orc.OracleEnv(st))
-    env = _env(envs)
+    env = util.batched(envs)
     A = env.A
     seed = 99
     tcount = np.zeros(B, dtype=np.int64)

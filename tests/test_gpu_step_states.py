@@ -29,14 +29,6 @@ def _fixture(map_name):
     return _FX[map_name]
 
 
-def _same(got, exp, msg):
-    got, exp = np.asarray(got), np.asarray(exp)
-    if got.shape != exp.shape or not np.array_equal(got, exp):
-        bad = np.argwhere(got != exp) if got.shape == exp.shape else []
-        first = "" if not len(bad) else " first %s: %s vs %s" % (bad[0].tolist(), got[tuple(bad[0])], exp[tuple(bad[0])])
-        raise AssertionError("%s: %d mismatches%s\n%s\n%s" % (msg, len(bad), first, got, exp))
-
-
 def _run(cases, how, pad=None, obs=False):
     """the cases (same number of steps, same filter flag) as the envs of one batch; how: "step" | "step_obs"; pad: canvas (H, W)"""
     import torch
@@ -54,8 +46,8 @@ def _run(cases, how, pad=None, obs=False):
     env.set_state(np.stack([c["state"] for c in cases]), np.stack([c["aux"] for c in cases]),
                   np.array([c["elapsed"] for c in cases], dtype=np.int32), np.array([c["done_all"] for c in cases], dtype=np.uint8))
     st, el = env.state()
-    _same(st, np.stack([c["state"] for c in cases]), "rows read back after the injection")
-    _same(env.state_aux(), np.stack([c["aux"] for c in cases]), "aux read back after the injection")
+    util.same(st, np.stack([c["state"] for c in cases]), "rows read back after the injection")
+    util.same(env.state_aux(), np.stack([c["aux"] for c in cases]), "aux read back after the injection")
     oracles = None
     if obs:
         oracles = [orc.OracleEnv(s) for s in statics]
@@ -76,15 +68,15 @@ def _run(cases, how, pad=None, obs=False):
         key, pos = env.rng_state()
         for b, c in enumerate(cases):
             w = "%s (%s, env %d of %d) step %d" % (c["name"], how, b, B, k)
-            _same(st[b], f[b]["state"][k], w + " rows")
-            _same(aux[b][:, AUX_COLS], f[b]["aux"][k][:, AUX_COLS], w + " aux")
-            _same(rew[b], f[b]["reward"][k], w + " rewards")
+            util.same(st[b], f[b]["state"][k], w + " rows")
+            util.same(aux[b][:, AUX_COLS], f[b]["aux"][k][:, AUX_COLS], w + " aux")
+            util.same(rew[b], f[b]["reward"][k], w + " rewards")
             # (a step on a finished env: the reference raises and leaves its dones, all set by the ending step, as they are)
-            _same(done[b], f[b]["done"][k], w + " dones")
+            util.same(done[b], f[b]["done"][k], w + " dones")
             assert bool(done_all[b]) == bool(f[b]["done_all"][k]), w + " done_all"
             assert el[b] == f[b]["elapsed"][k], w + " elapsed %d vs %d" % (el[b], f[b]["elapsed"][k])
             assert pos[b] == f[b]["mt_pos"][k], w + " mt_pos %d vs %d" % (pos[b], f[b]["mt_pos"][k])
-            _same(key[b], fxs[b][0][f[b]["mt_key_id"][k]], w + " mt_key")
+            util.same(key[b], fxs[b][0][f[b]["mt_key_id"][k]], w + " mt_key")
             if not f[b]["raised"][k]:
                 metrics[2] += A
                 if f[b]["done_all"][k]:
@@ -98,8 +90,8 @@ def _run(cases, how, pad=None, obs=False):
                 env.check()
         else:
             env.check()
-        _same(env.metrics().cpu().numpy(), metrics, "%s step %d metrics()" % (how, k))
-        _same(env.info()["scores"].cpu().numpy(), pair, "%s step %d the per-episode pair" % (how, k))
+        util.same(env.metrics().cpu().numpy(), metrics, "%s step %d metrics()" % (how, k))
+        util.same(env.info()["scores"].cpu().numpy(), pair, "%s step %d the per-episode pair" % (how, k))
         # scores() adds the envs' terms up in an order of its own: at most B additions of values in [-|R|, 1] per sum, each within
         # half an ulp of the running sum -- B * 2^-53 relative to the sum of the magnitudes; the episode count is exact
         got = env.scores().cpu().numpy()
@@ -118,9 +110,9 @@ def _run(cases, how, pad=None, obs=False):
                     assert f[b]["raised"][k]
                 exp = o.obs_cutils(31, 500)
                 w = "%s (step_obs) step %d" % (c["name"], k)
-                _same(forest[b], exp["forest"], w + " forest vs oracle")
-                _same(attr[b], exp["attr"], w + " agent_attr vs oracle")
-                _same(adj[b], exp["adjacency"], w + " adjacency vs oracle")
+                util.same(forest[b], exp["forest"], w + " forest vs oracle")
+                util.same(attr[b], exp["attr"], w + " agent_attr vs oracle")
+                util.same(adj[b], exp["adjacency"], w + " adjacency vs oracle")
     env.close()
 
 

@@ -120,14 +120,6 @@ def _assert_within(g, g32, g64, what):
     return figs
 
 
-def _record(case, figs):
-    path = os.environ.get("TREE_LSTM_GRAD_ERRORS")
-    if path:
-        rec = json.load(open(path)) if os.path.exists(path) else dict(device=torch.cuda.get_device_name(0), cases={})
-        rec["cases"][case] = figs
-        json.dump(rec, open(path, "w"), indent=1, sort_keys=True)
-
-
 # ---------------------------------------------------------------------------------------------------------------- CPU
 def test_R_follows_the_recorded_errors():
     rec = json.load(open(ERRORS))
@@ -185,7 +177,7 @@ def test_gradients_match_the_restatement(case):
     g32 = tg.grads(x, params, up, roots, torch.float32)
     figs = _figures(g, g32, g64)
     print(_case_id(*case), "T %d" % T, " ".join("%s %.3g" % (k[6:], v) for k, v in figs.items() if k.startswith("ratio_")))
-    _record(_case_id(*case), figs)
+    util.record_errors("TREE_LSTM_GRAD_ERRORS", "cases", _case_id(*case), figs)
     _assert_within(g, g32, g64, _case_id(*case))
     if kind == "flat":
         for k in ("U_iou.weight", "W_c.weight", "W_c.bias", "W_f.weight", "W_f.bias", "U_f.weight"):

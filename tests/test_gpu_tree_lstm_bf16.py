@@ -14,7 +14,6 @@ to the float32 kernel's bound, R = 3 times e32 (the float32 restatement's error)
 TREE_LSTM_BF16_ERRORS=<path> makes the cases write err, e16 and their ratio to <path> in the format of
 tests/golden/synth_tree_lstm_bf16_errors.json."""
 import glob
-import json
 import os
 
 import numpy as np
@@ -70,14 +69,6 @@ def _launch(x, w, packed, roots_only, with_c, status):
     hb.tree_lstm_bf16(*x, w, packed, roots_only, h, c, status)
     assert torch.isnan(hb_[rows:]).all() and (not with_c or torch.isnan(cb_[rows:]).all()), "a write past the last tree"
     return h, c
-
-
-def _record(case, figs):
-    path = os.environ.get("TREE_LSTM_BF16_ERRORS")
-    if path:
-        rec = json.load(open(path)) if os.path.exists(path) else dict(device=torch.cuda.get_device_name(0), R16=R16, cases={})
-        rec["cases"][case] = figs
-        json.dump(rec, open(path, "w"), indent=1, sort_keys=True)
 
 
 @pytest.mark.gpu
@@ -158,7 +149,7 @@ def test_kernel_matches_the_emulation(case):
     else:
         figs = dict(err_h=err_h, e16_h=e16_h, ratio_h=err_h / e16_h, err_c=err_c, e16_c=e16_c, ratio_c=err_c / e16_c)
     print(_case_id(*case), "T %d" % T, " ".join("%s %.3g" % kv for kv in figs.items()))
-    _record(_case_id(*case), figs)
+    util.record_errors("TREE_LSTM_BF16_ERRORS", "cases", _case_id(*case), figs, R16=R16)
     if int(x[2].max()) > 0:
         assert err_h <= R16 * e16_h, figs
         assert err_c <= R16 * e16_c, figs

@@ -266,14 +266,6 @@ def _errors(h, c, h64, c64):
     return float((h.double() - h64).abs().max()), float(((c.double() - c64).abs() / c64.abs().clamp(min=1)).max())
 
 
-def _record(case, figs):
-    path = os.environ.get("TREE_LSTM_SYNTH_ERRORS")
-    if path:
-        rec = json.load(open(path)) if os.path.exists(path) else dict(device=torch.cuda.get_device_name(0), cases={})
-        rec["cases"][case] = figs
-        json.dump(rec, open(path, "w"), indent=1, sort_keys=True)
-
-
 @pytest.mark.gpu
 def test_sizes_cover_the_groupings():
     """G = 1; G = 2 with a one-tree tail; 2 < G < 16 with 1, 2 and 3 waves in the last set-up pass (tb += 4), in full groups and
@@ -339,7 +331,7 @@ def test_kernel_matches_the_restatement(case):
     err_h, err_c = _errors(h, c, h64, c64)
     figs = dict(err_h=err_h, e32_h=e32_h, ratio_h=err_h / e32_h, err_c=err_c, e32_c=e32_c, ratio_c=err_c / e32_c)
     print(_case_id(*case), "T %d" % T, " ".join("%s %.3g" % kv for kv in figs.items()))
-    _record(_case_id(*case), figs)
+    util.record_errors("TREE_LSTM_SYNTH_ERRORS", "cases", _case_id(*case), figs)
     assert err_h <= R * e32_h, figs
     assert err_c <= R * e32_c, figs
     e_h, e_c = _errors(hn, c, h64, c64)

@@ -1,4 +1,5 @@
 import glob
+import json
 import os
 
 import numpy as np
@@ -33,6 +34,65 @@ def static_of(fx, mt_key=None, mt_pos=None):
     if mt_key is not None:
         d["mt_key"], d["mt_pos"] = mt_key, mt_pos
     return d
+
+
+def same(got, exp, msg, dtype=False, bytes=False):
+    """got equals exp: the shape always, the dtype with dtype=True, the values by np.array_equal or, with bytes=True, by tobytes() (which
+    tells -0.0 from 0.0 and takes equal NaNs for equal).  Raises AssertionError with msg, the number of mismatches and the first of them."""
+    got, exp = np.asarray(got), np.asarray(exp)
+    if got.shape != exp.shape or (dtype and got.dtype != exp.dtype):
+        raise AssertionError(f"{msg}: {got.dtype}{got.shape}, expected {exp.dtype}{exp.shape}")
+    if (got.tobytes() != exp.tobytes()) if bytes else not np.array_equal(got, exp):
+        bad = np.argwhere(got != exp)
+        if not len(bad):      # the same values in other bytes (a zero's sign), or bytes of another type
+            raise AssertionError(f"{msg}: equal values, other bytes ({got.dtype} vs {exp.dtype})")
+        k = tuple(bad[0])
+        raise AssertionError(f"{msg}: {len(bad)} mismatches, first at {bad[0].tolist()}: got {got[k]}, expected {exp[k]}")
+
+
+def same_bits(a, b):
+    """a predicate, not an assertion: two numpy arrays, or two torch tensors, of one dtype and shape hold the same bytes"""
+    if a.dtype != b.dtype or a.shape != b.shape:
+        return False
+    if isinstance(a, np.ndarray):
+        return a.tobytes() == b.tobytes()
+    import torch
+    return torch.equal(a.contiguous().reshape(-1).view(torch.uint8), b.contiguous().reshape(-1).view(torch.uint8))
+
+
+def batched(envs, **kw):
+    from flatland_marl_amd.hip_backend import BatchedRailEnv
+    return BatchedRailEnv(envs, **kw)
+
+
+def plain_static(grid, spec, speed, latest=200, T=400, target=None):
+    """the static description BatchedRailEnv / OracleEnv take, with nothing drawn: spec holds (row, col, direction, target row, target col)
+    per agent (`target` replaces its last two columns), every agent may depart at once, no malfunctions, the RNG at the end of its block"""
+    a = np.array(spec, dtype=np.int32)
+    A = len(a)
+    target = a[:, 3:5].copy() if target is None else np.array(target, dtype=np.int32)
+    return dict(grid=grid, init_pos=a[:, 0:2].copy(), init_dir=a[:, 2].copy(), target=target, speed=np.array(speed, dtype=np.float64),
+                earliest=np.zeros(A, dtype=np.int32), latest=np.full(A, latest, dtype=np.int32), T=T, malf_rate=0.0, malf_min=0, malf_max=0,
+                mt_key=np.arange(624, dtype=np.uint32), mt_pos=624)
+
+
+def group_static(g, agents=None):
+    """plain_static of a fixture group (its map and agents, or the subset `agents` of them) with a long episode; the scalars are numpy's,
+    as the loaders of the action-space and prediction fixtures have always given them"""
+    sel = slice(None) if agents is None else list(agents)
+    spec = np.column_stack([g["init_pos"][sel], g["init_dir"][sel], g["target"][sel]])
+    return dict(plain_static(g["grid"], spec, g["speed"][sel], latest=1000, T=np.int32(2000)),
+                malf_rate=np.float64(0.0), malf_min=np.int32(0), malf_max=np.int32(0), mt_pos=np.int32(624))
+
+
+def record_errors(env_var, section, case, figs, **header):
+    """when env_var names a file: figs goes into it as rec[section][case]; a new file starts with the device's name and `header`"""
+    path = os.environ.get(env_var)
+    if path:
+        import torch
+        rec = json.load(open(path)) if os.path.exists(path) else dict(device=torch.cuda.get_device_name(0), **header)
+        rec.setdefault(section, {})[case] = figs
+        json.dump(rec, open(path, "w"), indent=1, sort_keys=True)
 
 
 def actions_of(fx):
