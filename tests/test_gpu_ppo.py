@@ -7,7 +7,15 @@ of the restatement's value, plus the float64 evaluation's own error: 1e-12 times
 (float64 roundoff is 1.1e-16, the device's exp / log are within a few float64 ulps, the log-softmax is conditioned by the logit
 spread, <= ~100 here: two orders of margin).  The statistics are float64 sums: 1e-12 of the mean of the absolute row terms.  The
 actions are the restatement's except where policy_head_torch.exempt allows the float32 expf of record to differ (at most 1 % of a
-case's rows, counted); fl_gae is bit for bit."""
+case's rows, counted); fl_gae is bit for bit.
+
+The loss at training sizes (LARGE_CASES of tests/test_ppo.py, from the kernel's own constants): three loops of csrc/fl_ppo.h take one
+trip at every row count up to 65 536 -- fpp_counts over the count slots, k_ppo_final over the sum slots, k_ppo_count over the rows --
+so the cases up to 1 025 rows cannot tell a wrong bound, stride or slot index in them.  The same tolerances hold there by derivation,
+not by fit: a float64 sum of n <= 8e5 terms, in the kernel's fixed tree or in numpy's pairwise order, errs by at most about
+log2(n) * 1.1e-16 * sum |t|, that is 2e-15 times the mean absolute term, three orders of magnitude under the 1e-12 the statistics are
+held to; a gradient element is one row's float64 value divided by n and rounded to float32 at any size.  The placement cases count
+one row at a time, so that a dropped, doubled or misplaced slot changes an integer and not a rounding."""
 import ctypes as C
 
 import numpy as np
@@ -20,7 +28,8 @@ from tests import policy_head_torch as pht
 from tests import ppo_np as pn
 from tests import util
 from tests.test_policy_head_golden import NAMES, golden_inputs, golden_params, load
-from tests.test_ppo import loss_inputs, off_the_clip_boundary
+from tests.test_ppo import (E1, E2, FPP_THREADS, LARGE_CASES, PLACE_B, PLACE_R, PLACE_ROWS, large_inputs, loss_inputs,
+                            off_the_clip_boundary)
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -51,7 +60,7 @@ def _intact(*outs):
 
 
 def _dev(a):
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+    return None if a is None else torch.from_numpy(np.require(a, requirements="CW")).to(DEV)     # (a shared, read-only input: a copy)
 
 
 def _ptr(t):
@@ -168,7 +177,7 @@ def check_sample(logits, valid, u, got, cap=0.01):
     some = valid.any(axis=1)
     assert (valid[np.arange(R), actions][some] != 0).all()           # an exempt row's action is a valid one too
     assert (actions[~some] == 0).all() and (logp[~some] == 0).all() and (entropy[~some] == 0).all()
-    single = valid.sum(axis=1) == 1
+    single = (valid != 0).sum(axis=1) == 1
     assert (logp[single] == 0).all() and (entropy[single] == 0).all()
     lp_all, _, _, m = pn.log_softmax(logits, valid)
     ref_lp = np.where(some, lp_all[np.arange(R), actions], 0.0)      # the log-probability of the action the kernel drew
@@ -331,6 +340,108 @@ def test_loss_rows_deep_inside_and_far_outside_the_clip_range():
     assert st[5] == 0.5 and st[6] == R
 
 
+# ---- past the edges of the slot loops (more than 256 workgroups) and of k_ppo_count's stride (more than 1 024 count workgroups)
+@pytest.mark.parametrize("R,B", LARGE_CASES)
+def test_loss_against_the_restatement_past_each_edge(R, B):
+    x = large_inputs(R, B)
+    run = lambda: raw_loss(x)                                       # noqa: E731
+    got = _on_side_stream(run) if (R, B) == (E1 + 1, 257) else run()
+    check_loss(x, got)
+    if R > FPP_THREADS:
+        assert 0 < got[2][6] < R and got[2][7] > 0
+
+
+@pytest.mark.parametrize("kw", (dict(mask=False), dict(critic=False)), ids=("no mask", "no critic"))
+def test_loss_options_where_the_count_kernel_strides(kw):
+    R = E2 + 1
+    x = large_inputs(R, 257)
+    got = raw_loss(x, **kw)
+    check_loss(x, got, **kw)
+    assert 0 < got[2][6] < R and got[2][7] > 0
+
+
+def _counted_only(x, rows):
+    mask = np.zeros(len(x["actions"]), dtype=np.uint8)
+    mask[rows] = 1
+    return dict(x, mask=mask)
+
+
+@pytest.mark.parametrize("k", PLACE_ROWS)
+def test_loss_one_counted_row_wherever_it_lies(k):
+    """every row well formed, the mask 0 except on row k: n = 1, and every other sum slot holds an exact 0.0, every other count slot
+    an integer 0, so the statistics and row k's gradients are, bit for bit, those of a call on that row alone"""
+    x = large_inputs(PLACE_R, PLACE_B, True)
+    y = _counted_only(x, [k])
+    gl, gv, st = got = raw_loss(y)
+    assert st[6] == 1 and st[7] == 0
+    assert (gl[:k] == 0).all() and (gl[k + 1:] == 0).all() and (gl[k] != 0).any()
+    check_loss(y, got)
+    alone = {key: x[key][k:k + 1] for key in ("logits", "valid", "actions", "old_logp", "adv")}
+    gl1, gv1, st1 = raw_loss(dict(alone, mask=np.ones(1, dtype=np.uint8), value=x["value"], returns=x["returns"]))
+    assert st1[6] == 1 and st[1] != 0 and st[2] != 0 and st[4] != 0
+    assert np.array_equal(st.view(np.uint64), st1.view(np.uint64)), (st, st1)
+    assert np.array_equal(gl[k].view(np.uint32), gl1[0].view(np.uint32)) and np.array_equal(gv.view(np.uint32), gv1.view(np.uint32))
+
+
+def test_loss_one_counted_row_in_every_workgroup():
+    """the last row of every 256-row group, and of the ragged last one: a count slot that is dropped or added twice changes n"""
+    x = large_inputs(PLACE_R, PLACE_B, True)
+    rows = np.unique(np.minimum(np.arange(FPP_THREADS - 1, PLACE_R + FPP_THREADS - 1, FPP_THREADS), PLACE_R - 1))
+    assert len(rows) == 2 * (E2 // FPP_THREADS) + 1 == 2049
+    y = _counted_only(x, rows)
+    got = raw_loss(y)
+    assert got[2][6] == len(rows) and got[2][7] == 0
+    check_loss(y, got)
+
+
+def test_loss_rows_with_an_invalid_action_only_where_the_count_kernel_strides():
+    """every row's mask set, the action not a valid one exactly on the rows from E2 on: the rows a workgroup of k_ppo_count reaches
+    on its second and third trip"""
+    x = large_inputs(PLACE_R, PLACE_B, True)
+    actions = x["actions"].copy()
+    late = np.arange(E2, PLACE_R)
+    off = x["valid"][late] == 0
+    actions[late] = np.where(off.any(axis=1) & (late % 2 == 0), off.argmax(axis=1), 5 + late % 250).astype(np.uint8)
+    y = dict(x, actions=actions)
+    got = raw_loss(y)
+    ref = check_loss(y, got)
+    assert got[2][6] == ref["stats"][6] == E2 and got[2][7] == ref["stats"][7] == PLACE_R - E2
+
+
+# ---- valid[j] != 0 and mask_r == 0 are what the header tests: any non-zero byte is a 1
+OTHER_BYTES = np.array([2, 0x80, 0xFF], dtype=np.uint8)
+
+
+def _other_bytes(a):
+    """a's non-zero bytes replaced by 2, 0x80 or 0xFF, by row index"""
+    by_row = OTHER_BYTES[np.arange(len(a)) % 3].reshape((-1,) + (1,) * (a.ndim - 1))
+    out = np.where(a != 0, by_row, 0).astype(np.uint8)
+    assert set(np.unique(out)) == {0, 2, 0x80, 0xFF} and np.array_equal(out != 0, a != 0)
+    return out
+
+
+def test_loss_takes_any_nonzero_byte_of_valid_and_mask_as_set():
+    x = loss_inputs(257, 3, 4)
+    assert set(np.unique(x["valid"])) == {0, 1} and set(np.unique(x["mask"])) == {0, 1}
+    y = dict(x, valid=_other_bytes(x["valid"]), mask=_other_bytes(x["mask"]))
+    for kw in ({}, dict(mask=False)):
+        want, got = raw_loss(x, **kw), raw_loss(y, **kw)
+        for a, b in zip(want, got):
+            assert np.array_equal(a.view(np.uint8), b.view(np.uint8))
+        check_loss(y, got, **kw)
+
+
+def test_sample_takes_any_nonzero_byte_of_valid_as_set():
+    """kernel against kernel on the same logits and u: every bit equal, no row exempt"""
+    logits, valid, u = sample_inputs(257, 1.0, 3)
+    assert set(np.unique(valid)) == {0, 1}
+    other = _other_bytes(valid)
+    want, got = raw_sample(logits, valid, u), raw_sample(logits, other, u)
+    for a, b in zip(want, got):
+        assert np.array_equal(a.view(np.uint8), b.view(np.uint8))
+    check_sample(logits, other, u, got)
+
+
 # ---------------------------------------------------------------------------------------------------------------- GAE
 def _dones(kind, T, N, rng):
     d = np.zeros((T, N), dtype=np.uint8)
@@ -418,6 +529,23 @@ def test_ppo_loss_module_scales_the_kernels_gradients():
         policy.ppo_loss(logits, value, *args, None)
     with pytest.raises(ValueError):
         policy.ppo_loss(logits, None, *args, None, clip=-0.1)
+
+
+def test_ppo_loss_module_at_the_benchmarked_shape():
+    """(256, 400, 5) logits and 256 values, tools/ppo_bench.py's cfg5: 400 workgroups, the slot loops' second trip, through the module"""
+    from flatland_marl_amd import policy
+    shape = (256, 400)
+    x = large_inputs(shape[0] * shape[1], shape[0])
+    gl, gv, st = raw_loss(x)
+    t = {k: _dev(v) for k, v in x.items()}
+    logits = t["logits"].view(*shape, 5).clone().requires_grad_(True)
+    value = t["value"].clone().requires_grad_(True)
+    loss, stats = policy.ppo_loss(logits, value, t["valid"].view(*shape, 5), t["actions"].view(shape), t["old_logp"].view(shape),
+                                  t["adv"].view(shape), t["returns"], mask=t["mask"].view(shape))
+    assert np.array_equal(stats.cpu().numpy().view(np.uint64), st.view(np.uint64)) and float(loss.detach()) == st[3]
+    loss.backward()
+    assert np.array_equal(logits.grad.cpu().numpy().reshape(-1, 5).view(np.uint32), gl.view(np.uint32))
+    assert np.array_equal(value.grad.cpu().numpy().view(np.uint32), gv.view(np.uint32))
 
 
 def test_gae_module():

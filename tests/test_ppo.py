@@ -2,9 +2,11 @@
 through ctypes without a device (the refusals come before any HIP call); the byte function; and the numpy restatements of
 tests/ppo_np.py pinned: the draw to the reference actor's actions of the fixtures, the closed-form gradients to torch's float64
 autograd of the plain formula, GAE to an independent evaluation.  The kernels themselves: tests/test_gpu_ppo.py."""
+import functools
 import glob
 import math
 import os
+import re
 
 import numpy as np
 import pytest
@@ -20,6 +22,36 @@ OK = 0x10000          # a pointer that is there and 16-byte aligned; no refused 
 ODD = OK + 4
 MAX_ROWS = 1 << 28    # FL_PPO_MAX_ROWS
 FIXTURES = sorted(glob.glob(os.path.join(util.ROOT, "tests", "golden", "policy_head_*.npz")))
+
+
+def kernel_constant(name):
+    """the integer of `#define name value` in csrc/fl_ppo.h, comments apart (tests/cabi.py reads the public headers the same way)"""
+    src = open(os.path.join(util.ROOT, "flatland_marl_amd", "csrc", "fl_ppo.h")).read()
+    src = re.sub(r"//[^\n]*", " ", re.sub(r"/\*.*?\*/", " ", src, flags=re.S))
+    found = re.findall(r"^[ \t]*#[ \t]*define[ \t]+%s[ \t]+(\d+)[ \t]*$" % name, src, re.M)
+    assert len(found) == 1, (name, found)
+    return int(found[0])
+
+
+FPP_THREADS = kernel_constant("FPP_THREADS")
+FPP_COUNT_GROUPS = kernel_constant("FPP_COUNT_GROUPS")
+FPP_SUMS = kernel_constant("FPP_SUMS")
+E1 = FPP_THREADS * FPP_THREADS            # the last row count at which fpp_counts and k_ppo_final add their slots in a single trip
+E2 = FPP_COUNT_GROUPS * FPP_THREADS       # the last row count at which k_ppo_count does not stride
+# (R, B) past each edge and what takes its first second trip there; tests/test_gpu_ppo.py runs the kernels on them
+LARGE_CASES = (
+    (E1, 3),                # nothing: the last single-trip size, the control
+    (E1 + 1, 257),          # fpp_counts and k_ppo_final: 257 groups, 257 count groups
+    (102400, 256),          # the shape tools/ppo_bench.py times as cfg5: 400 groups
+    (E2, 1),                # FPP_COUNT_GROUPS groups: four trips of the slot loops, no stride yet
+    (E2 + 1, 257),          # k_ppo_count strides for one row only; one more sum slot than count slots
+    (3 * E2 + 1, 3),        # three full strides and a ragged fourth
+    (1, E1 + 1),            # groups set by the values: 257 sum slots, one count slot, 256 workgroups without a row
+    (300, E1 + 1),          # the same with two row workgroups
+)
+LARGE_SEED = 4
+PLACE_R, PLACE_B = 2 * E2 + 1, 3          # the placement cases: two full strides of k_ppo_count and one row of a third
+PLACE_ROWS = (0, E1 - 1, E1, E2 - 1, E2, PLACE_R - 1)
 
 
 def test_header_binding_and_library_agree():
@@ -143,6 +175,26 @@ def test_workspace_bytes():
     assert fn(1, 1) == 48 and fn(257, 1) == 96 and fn(1, 257) == 96
 
 
+def test_workspace_bytes_at_the_kernels_own_edges():
+    """E1, E2 and the sizes of LARGE_CASES come from FPP_THREADS and FPP_COUNT_GROUPS of csrc/fl_ppo.h; the library's byte function
+    shows the same groups and the same cap.  If a constant moves, the literals here name what moves with it"""
+    assert (FPP_THREADS, FPP_COUNT_GROUPS, FPP_SUMS) == (256, 1024, 5) and (E1, E2) == (65536, 262144)
+    fn = hb._sym("fl_ppo_loss_workspace_bytes")
+    sums, counts = FPP_SUMS * 8, 2 * 4                                  # a workgroup's float64 sums, a count workgroup's two integers
+    assert (sums, counts) == (40, 8)
+    up16 = lambda n: (n + 15) // 16 * 16                                # noqa: E731
+    assert fn(E2, 0) == 1024 * 40 + 1024 * 8 == FPP_COUNT_GROUPS * (sums + counts)
+    assert fn(E2 + 1, 0) == up16(1025 * 40 + 1024 * 8) == up16((FPP_COUNT_GROUPS + 1) * sums + FPP_COUNT_GROUPS * counts)   # the cap holds
+    assert fn(3 * E2 + 1, 0) == up16((3 * FPP_COUNT_GROUPS + 1) * sums + FPP_COUNT_GROUPS * counts)
+    assert fn(1, E1 + 1) == up16(257 * 40 + 8) == up16((FPP_THREADS + 1) * sums + counts)       # 257 groups, one count group
+    assert fn(E1, 0) == FPP_THREADS * (sums + counts) and fn(E1 + 1, 0) == up16((FPP_THREADS + 1) * (sums + counts))
+    for R, B in LARGE_CASES:
+        groups = max(-(-R // FPP_THREADS), -(-B // FPP_THREADS))
+        assert fn(R, B) == up16(groups * sums + min(-(-R // FPP_THREADS), FPP_COUNT_GROUPS) * counts), (R, B)
+    assert any(-(-R // FPP_THREADS) > FPP_COUNT_GROUPS for R, _ in LARGE_CASES)
+    assert any(-(-B // FPP_THREADS) > FPP_THREADS >= -(-R // FPP_THREADS) for R, B in LARGE_CASES)
+
+
 # ---------------------------------------------------------------------------------------------------------------- the restatements
 def loss_inputs(R, B, seed, scale=1.0):
     """seeded inputs of the loss with every kind of row: no valid action, a single one, masked, an action that is not valid (masked
@@ -176,6 +228,102 @@ def off_the_clip_boundary(x, clip):
     rho = pn.ratio(x["logits"], x["valid"], x["actions"], x["old_logp"])
     w, _ = pn.weights(x["valid"], x["actions"], x["mask"])
     return bool((np.minimum(np.abs(rho[w] - (1.0 - clip)), np.abs(rho[w] - (1.0 + clip))) >= 1e-9).all())
+
+
+def loss_inputs_large(R, B, seed, well_formed=False):
+    """loss_inputs's kinds of row (by row index mod 8: no valid action, a single one, an action that is not valid -- masked out or
+    >= 5 --, A = 0; about one row in five masked) without a Python loop over rows, for the sizes of LARGE_CASES.  Its own bits, not
+    loss_inputs's: the action is a uniform draw among the valid ones, not pn.sample's.  well_formed: every row has a valid action
+    and takes one, and mask is 1 everywhere (the single-action rows of kind 1 and the A = 0 rows stay; every other row has two
+    valid actions or more, so its gradient row is not zero)"""
+    rng = np.random.default_rng([seed, R, B, 1])
+    logits = rng.standard_normal((R, 5), dtype=np.float32)
+    valid = rng.integers(0, 2, size=(R, 5), dtype=np.uint8)
+    kind = (np.arange(R) + seed) % 8
+    valid[kind == 1] = 0
+    one = np.flatnonzero(kind == 1)
+    valid[one, rng.integers(0, 5, size=len(one))] = 1
+    valid[(kind != 1) & (valid.sum(axis=1) == 0), 2] = 1
+    if well_formed:                                                  # only the rows of kind 1 have a single action: theirs is a zero gradient
+        few = (kind != 1) & (valid.sum(axis=1) < 2)
+        valid[few, 1] = valid[few, 3] = 1
+    nth =(rng.random(R) * valid.sum(axis=1)).astype(np.int64)       # the nth valid action of the row, n uniform
+    actions = ((valid != 0) & (np.cumsum(valid, axis=1) - 1 == nth[:, None])).argmax(axis=1).astype(np.uint8)
+    logp = pn.log_softmax(logits, valid)[0][np.arange(R), actions]
+    old_logp = (logp + 0.3 * rng.standard_normal(R)).astype(np.float32)
+    adv = rng.standard_normal(R, dtype=np.float32)
+    adv[kind == 3] = 0.0
+    mask = (rng.random(R) < 0.8).astype(np.uint8)
+    value = rng.standard_normal(B, dtype=np.float32)
+    returns = rng.standard_normal(B, dtype=np.float32)
+    if well_formed:
+        mask[:] = 1
+    else:
+        valid[kind == 0] = 0
+        actions[kind == 0] = 0
+        bad = np.flatnonzero(kind == 2)
+        i = np.arange(len(bad))
+        off = valid[bad] == 0
+        actions[bad] = np.where(off.any(axis=1) & (i % 2 == 0), off.argmax(axis=1), 5 + i % 250).astype(np.uint8)
+    return dict(logits=logits, valid=valid, actions=actions, old_logp=old_logp, adv=adv, mask=mask, value=value, returns=returns)
+
+
+@functools.lru_cache(maxsize=2)
+def large_inputs(R, B, well_formed=False):
+    """loss_inputs_large at LARGE_SEED, built once for the tests that share a size, read-only so that it stays as it was built"""
+    x = loss_inputs_large(R, B, LARGE_SEED, well_formed)
+    for a in x.values():
+        a.setflags(write=False)
+    return x
+
+
+def test_large_inputs_hold_every_kind_of_row():
+    R, B = E1 + 1, 257
+    x = large_inputs(R, B)
+    w, bad = pn.weights(x["valid"], x["actions"], x["mask"])
+    nv = (x["valid"] != 0).sum(axis=1)
+    assert (nv == 0).any() and (nv == 1).any() and 0.15 * R < (x["mask"] == 0).sum() < 0.25 * R
+    masked_out = (x["actions"] < 5) & (x["valid"][np.arange(R), np.minimum(x["actions"], 4)] == 0) & (nv > 0)
+    assert (bad & masked_out).any() and (bad & (x["actions"] >= 5)).any() and x["actions"].max() > 250
+    assert (w & (x["adv"] == 0)).any() and (w & (nv == 1)).any() and 0 < w.sum() < R and bad.sum() > 0
+    rho, A = pn.ratio(x["logits"], x["valid"], x["actions"], x["old_logp"])[w], x["adv"][w].astype(np.float64)
+    for sign in (A > 0, A < 0):
+        assert (sign & (rho > 1.2)).any() and (sign & (rho < 0.8)).any() and (sign & (np.abs(rho - 1) < 0.2)).any()
+    # every 256-row group and every lane takes part, so a slot that is dropped changes the sums
+    assert (np.add.reduceat(w, np.arange(0, R, FPP_THREADS)) > 0).all()
+    # well formed: every row counts once the mask says so
+    y = large_inputs(PLACE_R, PLACE_B, True)
+    w, bad = pn.weights(y["valid"], y["actions"], y["mask"])
+    nv = (y["valid"] != 0).sum(axis=1)
+    assert w.all() and not bad.any() and (nv == 1).any() and (y["adv"] == 0).any() and (nv[list(PLACE_ROWS)] >= 2).all()
+    assert off_the_clip_boundary(y, 0.2)
+
+
+@pytest.mark.parametrize("R,B", LARGE_CASES)
+def test_large_inputs_are_off_the_clip_boundary(R, B):
+    """a condition of the GPU comparison (tests/test_gpu_ppo.py asserts it again on what it runs), with the mask on and, as
+    check_loss asks, with every row's mask set; and the row counts the GPU cases rely on"""
+    x = large_inputs(R, B)
+    assert off_the_clip_boundary(x, 0.2) and off_the_clip_boundary(dict(x, mask=np.ones(R, dtype=np.uint8)), 0.2)
+    for mask in (x["mask"], None):
+        w, bad = pn.weights(x["valid"], x["actions"], mask)
+        assert w.sum() >= 1                                            # (the single row of R = 1 counts)
+        if R > FPP_THREADS:
+            assert 0 < w.sum() < R and bad.sum() > 0
+    assert len(x["value"]) == B and x["logits"].shape == (R, 5) and x["logits"].dtype == np.float32
+
+
+def test_closed_form_gradients_are_torch_autograd_past_256_groups():
+    x = large_inputs(E1 + 1, 257)
+    out = pn.ppo_loss(clip=0.2, vf_coef=0.5, ent_coef=0.01, **x)
+    total, leaf, v = pn.plain_loss_torch(clip=0.2, vf_coef=0.5, ent_coef=0.01, **x)
+    total.backward()
+    w, bad = pn.weights(x["valid"], x["actions"], x["mask"])
+    assert np.abs(out["grad_logits"] - leaf.grad.numpy()).max() <= 1e-15
+    assert np.abs(out["grad_value"] - v.grad.numpy()).max() <= 1e-15
+    assert abs(out["stats"][3] - float(total.detach())) <= 1e-13
+    assert out["stats"][6] == w.sum() and out["stats"][7] == bad.sum()
+    assert (out["grad_logits"][x["valid"] == 0] == 0).all() and (out["grad_logits"][~w] == 0).all()
 
 
 @pytest.mark.parametrize("R,B,seed,clip,ent", ((4099, 7, 1, 0.2, 0.01), (257, 3, 2, 0.1, 0.0), (64, 1, 3, 0.3, 0.5), (1025, 257, 4, 0.2, 0.01)))
