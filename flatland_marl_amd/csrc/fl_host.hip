@@ -14,6 +14,7 @@
 #include "fl_policy_layout.h"
 #include "fl_static.h"
 #include "fl_obs.h"
+#include "fl_obs_switches.h"
 #include "fl_global.h"
 #include "fl_predict.h"
 #include "fl_wrappers.h"
@@ -339,7 +340,7 @@ static int obs_check_request(const fl_batch *h, const char *who, const FlObsCuti
     }
     // every argument error is raised BEFORE anything is launched: a depth-4 tree needs compact node tables (fl_launch_obs_tree's own check, which in
     // a call with a step or a cutils launch would fire after the envs have advanced a step and the cutils launch has set its sticky deadlock bits)
-    if (tree && t->max_depth > 3 && (h->d.max_branch > 2 || (t->compact_switch && fl_obs_no_compact()))) {
+    if (tree && t->max_depth > 3 && (h->d.max_branch > 2 || (t->compact_switch && obs_switches().no_compact))) {
         fl_set_error("%s: max_depth 4 needs a grid on which no direction of a cell has more than two transitions (every Flatland rail cell type)%s; this batch has %d "
                 "(nothing was launched: the envs have not advanced)", who, t->compact_switch ? " and the compact node tables" : "", h->d.max_branch);
         return FL_ERR_ARG;
@@ -882,6 +883,18 @@ extern "C" int fl_debug_obs_plan(int kind, int A, int Ucap, int tall, int max_br
     o.pred_cap = FL_OBS_MAX_PRED + 2; o.n_cu = n_cu; o.h_R = R; o.keep_rows = keep_mode;
     *n_fit = 0;
     return fl_obs_plan(kind, o, d, max_nodes, pred_depth, max_depth, tree_pred, label ? &dummy_label : nullptr, record, n_fit);
+}
+
+// diagnostic (not part of the public header), no GPU needed: the launcher's table of environment switches (fl_obs_switches.h), a line a switch --
+// "NAME kind rules-out\n", kind flag / int / bytes / keys, rules-out nothing / bins / classes.  Returns the bytes of it with the final 0
+// (written when they fit `cap`).
+extern "C" int fl_debug_obs_switches(char *out, int cap) {
+    static const char *const kinds[] = {"flag", "int", "bytes", "keys"}, *const outs[] = {"nothing", "bins", "classes", "classes"};
+    int n = 1;
+    for (const ObsSwitchRow &r : OBS_SWITCH_TABLE) n += snprintf(nullptr, 0, "%s %s %s\n", r.name, kinds[r.kind], outs[r.out]);
+    if (!out || n > cap) return n;
+    for (const ObsSwitchRow &r : OBS_SWITCH_TABLE) out += sprintf(out, "%s %s %s\n", r.name, kinds[r.kind], outs[r.out]);
+    return n;
 }
 
 // diagnostic (not part of the public header), no GPU needed: the host half of a handle alone -- an FlStatic (fl_static.h) behind an opaque

@@ -70,4 +70,3 @@ int fl_obs_config_of_fused(const FlDev &d, int pred_depth, int max_depth, int tr
 // diagnostic: the host half of launch `kind` (0 cutils, 1 both, 2 tree) up to the enqueue -- its record and the envs on a launch class's body
 int fl_obs_plan(int kind, const FlObsScratch &o, const FlDev &d, int max_nodes, int pred_depth, int max_depth, int tree_pred, const int16_t *label,
                 int record[FL_OBS_LAUNCH_WORDS], int *n_fit);
-bool fl_obs_no_compact();   // FL_OBS_NO_COMPACT (diagnostic): DFS-slot node tables for the upstream trees of every grid -- no depth 4

@@ -7,11 +7,11 @@
 #include <algorithm>
 #include <utility>
 #include <stdio.h>
-#include <stdlib.h>
 #include <string.h>
 
 #include "../../include/flatland_hip.h"
 #include "fl_obs_layout.h"
+#include "fl_obs_switches.h"
 
 int fl_obs_alloc(FlObsScratch &o, const FlDev &d, hipStream_t s, std::vector<void *> &allocs) {
     o.pred_cap = OBS_PRED_CAP;
@@ -33,17 +33,6 @@ int fl_obs_alloc(FlObsScratch &o, const FlDev &d, hipStream_t s, std::vector<voi
     o.order_age = 0;
     return FL_OK;
 }
-
-// Diagnostic switches that more than one function reads: one accessor each, read once per process.
-bool fl_obs_no_compact() { static const bool v = getenv("FL_OBS_NO_COMPACT") != nullptr; return v; }
-static bool obs_no_fix() { static const bool v = getenv("FL_OBS_NO_FIX") != nullptr; return v; }                    // the runtime carving for every batch
-static bool obs_no_split() { static const bool v = getenv("FL_OBS_NO_SPLIT") != nullptr; return v; }                // no split kernels
-static bool obs_no_cutils_merge() { static const bool v = getenv("FL_OBS_NO_CUTILS_MERGE") != nullptr; return v; }  // the builder alone on the stand-alone kernel, as before round 6
-static bool obs_verbose_on() { static const bool v = getenv("FL_OBS_VERBOSE") != nullptr; return v; }               // print the configuration obs_pick_config chose
-static bool obs_no_cf_dirs() { static const bool v = getenv("FL_OBS_NO_CF_DIRS") != nullptr; return v; }            // classify loop: file every query, whatever the directions of the key's items
-static bool obs_pb_ceil_split() { static const bool v = getenv("FL_OBS_PB_CEIL_SPLIT") != nullptr; return v; }    // pass B: ceil(total / nt) cells a lane until none are left, as before the even slices
-static bool obs_no_early_topo() { static const bool v = getenv("FL_OBS_NO_EARLY_TOPO") != nullptr; return v; }      // one-round kernels: adjacency / padding rows / orders behind pass B, not beside its conflict scan
-static bool obs_no_wl_head() { static const bool v = getenv("FL_OBS_NO_WL_HEAD") != nullptr; return v; }            // HBM work lists without their LDS head (rules out the classes that have one)
 
 // The launch is one workgroup per env and a CU holds one workgroup: with more envs than CUs the launch ends when the last CU has
 // worked through its envs, and the envs differ (agents on the map, traffic around them) -- mean 187 us, slowest 315 us at cfg4.
@@ -97,8 +86,7 @@ __global__ void k_keep_verify(int B, int A, int n_rows, const double *__restrict
     if (real == ninf) atomicCAS(&err[g / A], 0, FL_ERR_ARG);
 }
 static void obs_keep_verify(const FlDev &d, const ObsArgs &P, const uint4 *rowmask, hipStream_t s) {
-    static const bool verify = getenv("FL_OBS_KEEP_VERIFY") != nullptr;
-    if (!verify || !P.keep_rows || !rowmask || P.n_tree_nodes > 96) return;
+    if (!obs_switches().keep_verify ||!P.keep_rows || !rowmask || P.n_tree_nodes > 96) return;
     const long long n = (long long)d.B * d.A * P.n_tree_nodes;
     hipLaunchKernelGGL(k_keep_verify, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d.B, d.A, P.n_tree_nodes, P.tree_out, rowmask, d.err);
 }
@@ -110,9 +98,8 @@ static void obs_keep_verify(const FlDev &d, const ObsArgs &P, const uint4 *rowma
 #define OBS_ORDER_EVERY 4   // what an env takes changes slowly from step to step: the order of every fourth launch serves the next three
 #endif
 FlObsScratch fl_obs_env_order(FlObsScratch &o, const FlDev &d, hipStream_t s) {
-    static const bool off = getenv("FL_OBS_NO_ORDER") != nullptr;   // diagnostic: workgroup k builds env k
     FlObsScratch u = o;
-    if (off || d.B <= o.n_cu) { u.order = nullptr; return u; }
+    if (obs_switches().no_order || d.B <= o.n_cu) { u.order = nullptr; return u; }
     if (o.order_age++ % OBS_ORDER_EVERY == 0) hipLaunchKernelGGL(k_env_order, dim3(1), dim3(1024), 0, s, d.B, o.cost, o.order);
     return u;
 }
@@ -136,7 +123,7 @@ enum ObsFit { OBS_FIT_EXACT, OBS_FIT_BIN, OBS_FIT_SPLIT };
 static int obs_var(const ObsLayout &L) { return L.tab_lds ? 1 : L.wl_bytes == 0 ? 2 : 0; }
 static bool obs_class_holds(const ObsClass &c, ObsFit kind, const FlDev &d, ObsArgs &P, const ObsOptions &own, ObsLayout &L) {
     const ObsLayout &CL = OBS_CLASS_LAYOUTS.L[&c - OBS_CLASSES];
-    if (c.opt.wl_head && obs_no_wl_head()) return false;
+    if (c.opt.wl_head && obs_switches().no_wl_head) return false;
     if (P.label) return false;   // (get_many(handles) with a strict subset: the stand-alone kernel's runtime body)
     if (P.keep_mode && !c.keep_rows) return false;   // (FL_OBS_KEEP_TREE_ROWS: the runtime carving instead)
     if (!P.compact_t || (d.rkey != nullptr) != (c.dims.rkey != 0) || (c.agents != 0 ? d.A != c.agents : d.A > c.dims.A)) return false;
@@ -185,26 +172,19 @@ static bool obs_take_first(const int *ids, ObsFit kind, const FlDev &d, ObsArgs 
         if (obs_class_holds(OBS_CLASSES[obs_class_index(*ids)], kind, d, P, o, L)) { P.fix = *ids; return true; }
     return false;
 }
-static void obs_take_fixed_class(const FlDev &d, ObsArgs &P, const ObsOptions &o, ObsLayout &L, bool allowed) {
-    // diagnostic: exact classes only (the launcher of rounds 4 and 5).  A bin class REPLACES the batch's own options, so the switches that shape those options
-    // (what a same-box experiment wants to measure) rule the bins out as well; an exact class only ever matches options it dominates.
-    static const bool no_bins = [] {
-        for (const char *v : {"FL_OBS_NO_BINS", "FL_OBS_FORCE", "FL_OBS_NO_FB", "FL_OBS_NO_BK", "FL_OBS_NO_OWN_FILTER", "FL_OBS_NO_MERGE", "FL_OBS_NO_TAB", "FL_OBS_ROUND16"})
-            if (getenv(v) != nullptr) return true;
-        return false;
-    }();
+// the launch class of a configuration just accepted (P.fix_allowed: no switch rules the classes out; which switches rule out what: fl_obs_switches.h)
+static void obs_take_fixed_class(const FlDev &d, ObsArgs &P, const ObsOptions &o, ObsLayout &L) {
     P.fix = 0; P.split = 0;
-    if (obs_no_fix() || !allowed) return;
+    if (!P.fix_allowed) return;
     if (P.tw_t == 0) {   // the flatland_cutils builder alone
         // (FL_OBS_NO_CUTILS_MERGE, !P.cutils_alone: no bin -- but the exact classes are tried all the same, so class 9, the stand-alone kernel's, is still taken)
-        if (obs_take_first(OBS_ORDER_ALONE_EXACT, OBS_FIT_EXACT, d, P, o, L) || no_bins || !P.cutils_alone) return;
-        obs_take_first(OBS_ORDER_ALONE_BIN, OBS_FIT_BIN, d, P, o, L);
+        if (!obs_take_first(OBS_ORDER_ALONE_EXACT, OBS_FIT_EXACT, d, P, o, L) && obs_switches().bins_allowed && P.cutils_alone) obs_take_first(OBS_ORDER_ALONE_BIN, OBS_FIT_BIN, d, P, o, L);
         return;
     }
-    if (obs_take_first(OBS_ORDER_BOTH_EXACT, OBS_FIT_EXACT, d, P, o, L) || no_bins) return;
+    if (obs_take_first(OBS_ORDER_BOTH_EXACT, OBS_FIT_EXACT, d, P, o, L) || !obs_switches().bins_allowed) return;
     // an exact class's SPLIT launch (its body for the envs that fit, the runtime carving L for the few larger maps) goes before a bin class for
     // the whole batch when at least half the envs fit the exact class: no class here, obs_take_split_class takes it
-    if (!obs_no_split() && P.h_R)
+    if (!obs_switches().no_split && P.h_R)
         for (const int *k = OBS_ORDER_BOTH_SPLIT_FIRST; *k; k++)
             if (2 * obs_split_count(OBS_CLASSES[obs_class_index(*k)], d, P, L, P.h_R) >= d.B) return;
     obs_take_first(OBS_ORDER_BOTH_BIN, OBS_FIT_BIN, d, P, o, L);
@@ -217,7 +197,7 @@ static void obs_take_fixed_class(const FlDev &d, ObsArgs &P, const ObsOptions &o
 //            one kernel, every env on a compile-time carving
 // Returns the number of envs that fit (0: no split launch).
 static int obs_take_split_class(const FlDev &d, ObsArgs &P, const int *h_R) {
-    if (obs_no_fix() || obs_no_split() || !P.fix_allowed) return 0;
+    if (obs_switches().no_split || !P.fix_allowed) return 0;
     auto take = [&](const ObsClass &c, int split) {
         const int n = obs_split_count(c, d, P, P.L, h_R);
         if (n > 0) {
@@ -236,142 +216,119 @@ static int obs_take_split_class(const FlDev &d, ObsArgs &P, const int *h_R) {
     return 0;
 }
 
-// Choose what lives in LDS so that the workgroup fits 160 KiB.  `accepted`: the options of the configuration chosen (what the launch's
-// record and FL_OBS_VERBOSE report), untouched when nothing fits.
-static bool obs_pick_config(const FlDev &d, ObsArgs &P, ObsOptions &accepted) {
-    // diagnostic overrides (experiments on the LDS / occupancy trade-off): FL_OBS_NT, FL_OBS_LDS_LIMIT (bytes), FL_OBS_NO_TAB
-    static const int force_nt = getenv("FL_OBS_NT") ? atoi(getenv("FL_OBS_NT")) : 0;
-    static const size_t lds_limit = getenv("FL_OBS_LDS_LIMIT") ? (size_t)atol(getenv("FL_OBS_LDS_LIMIT")) : (size_t)160 * 1024;
-    static const bool no_tab = getenv("FL_OBS_NO_TAB") != nullptr;
-    // FL_OBS_FORCE="nt=512,wl=8192,tab=0,nh=1,tmask=1,dual=0,items=0,snext=1": only configurations with these values
-    struct Force { int nt = -1, wl = -1, tab = -1, nh = -1, tmask = -1, dual = -1, items = -1, snext = -1; };
-    static const Force force = [] {
-        Force f;
-        const char *e = getenv("FL_OBS_FORCE");
-        if (!e) return f;
-        const struct { const char *k; int *v; } keys[] = {{"nt=", &f.nt}, {"wl=", &f.wl}, {"tab=", &f.tab}, {"nh=", &f.nh},
-                                                         {"tmask=", &f.tmask}, {"dual=", &f.dual}, {"items=", &f.items}, {"snext=", &f.snext}};
-        for (const auto &kv : keys) {
-            const char *q = strstr(e, kv.k);
-            if (q && (q == e || q[-1] == ',')) *kv.v = atoi(q + strlen(kv.k));
-        }
-        return f;
-    }();
-    auto ok = [](int forced, int v) { return forced < 0 || forced == v; };
-    const int nts[3] = {OBS_NT, 512, 256};
-    const bool nh_fit = (size_t)d.Ucap * d.Rcap * 2 <= 24 * 1024;  // beyond that the next-hop tables stay in HBM / L2
-    const bool dual_ok = P.tw_c != 0 && P.tw_t != 0 && P.tree_pred >= 0 &&
-                         (long long)d.A * (P.pred_depth + 2) < 65536 && (long long)d.A * (P.tree_pred + 2) < 32768;
+// ---- obs_pick_config: choose what lives in LDS so that the workgroup fits 160 KiB.  Two preference walks -- the one-pass kernels' (P.merged
+// 1 / 2 / 3), then the two-stage kernels' -- and one acceptance, obs_accept, of what either of them finds.
+static bool obs_ok(int forced, int v) { return forced < 0 || forced == v; }   // FL_OBS_FORCE (ObsSwitches::force): only configurations with these values
+static bool obs_nh_fit(const FlDev &d) { return (size_t)d.Ucap * d.Rcap * 2 <= 24 * 1024; }  // beyond that the next-hop tables stay in HBM / L2
+static bool obs_dual_ok(const FlDev &d, const ObsArgs &P) { return P.tw_c != 0 && P.tw_t != 0 && P.tree_pred >= 0 && (long long)d.A * (P.pred_depth + 2) < 65536 && (long long)d.A * (P.tree_pred + 2) < 32768; }
+// what the launcher derives from the options of a configuration, where the walks differ (tshift: unless FL_OBS_TSHIFT sets it; tab_of_layout: the
+// static tables joined the carving behind the options' back, so `accepted.tab` is the layout's)
+struct ObsDerived { int bk, bk_nb, bk_shift, wl_occ_div, tshift; bool tab_of_layout; };
+// The configuration (o, L) is chosen.  `accepted`: its options (what the launch's record and FL_OBS_VERBOSE report), untouched when nothing fits;
+// what it sets in P; and the fixed launch class that has exactly these options (or whose bin holds them), if the batch fits one.
+static bool obs_accept(const FlDev &d, ObsArgs &P, ObsOptions &accepted, const ObsOptions &o, ObsLayout L, const ObsDerived &v) {
+    accepted = o; if (v.tab_of_layout) accepted.tab = L.tab_lds;
+    P.use_tmask = o.tmask; P.dual_index = o.dual;
+    P.bk = v.bk; P.bk_nb = v.bk_nb; P.bk_shift = v.bk_shift; P.wl_occ_div = v.wl_occ_div;
+    P.tshift = obs_switches().tshift >= 0 ? (int)obs_switches().tshift : v.tshift;
+    P.fix_allowed = obs_switches().classes_allowed;
+    obs_take_fixed_class(d, P, o, L);
+    P.L = L;
+    return true;
+}
+
+struct ObsPref { int fb, wl, items; };
+// Both builders: ONE pass B per round of 32 agents over the trees of both (trees_merged).  It needs compact upstream
+// trees, sixteen wavefronts, the second index with its items and the time masks in LDS, the successor table and keys =
+// rail indices (the fast classify loop).  Small envs (one round) also get the own-path filter of the classify loop.
+static bool obs_walk_one_pass(const FlDev &d, ObsArgs &P, ObsOptions &accepted) {
+    const ObsSwitches &sw = obs_switches();
+    const bool nh_fit = obs_nh_fit(d), up = P.tw_t != 0;
     // the flatland_cutils builder ALONE on the one-pass kernels (MODE 6 / 7 / 8: no second index, no upstream tables): 32-slot trees,
     // every agent listed (get_many(handles) with a strict subset stays on the stand-alone kernel)
-    const bool up = P.tw_t != 0;
-    const bool merge_ok = up ? dual_ok : (P.cutils_alone && P.tw_c == N_WORDS_C * OBS_CAP_C && P.label == nullptr && (long long)d.A * (P.pred_depth + 2) < 65536);
-    static const int opts[5][3] = {{1, 1, 1}, {1, 0, 1}, {1, 0, 0}, {0, 0, 1}, {0, 0, 0}};  // masks, second index, items
-    // Order of preference, from same-box A/B runs (tools/obs_sweep.py): the most wavefronts; the full work-list space; the LDS
-    // copy of the items, the time masks and the second index; the successor table; the next-hop tables; own scan scratch.
-    // The env's distance / segment / eight-hop tables join them when there is room left (small maps): they make no
-    // difference in time (their gathers hit L2 and hide behind the rest) but replace narrow HBM gathers with one coalesced read.
-    ObsOptions o = {};
-    static const int force_tshift = getenv("FL_OBS_TSHIFT") ? atoi(getenv("FL_OBS_TSHIFT")) : -1;
-    // Both builders: ONE pass B per round of 32 agents over the trees of both (trees_merged).  It needs compact upstream
-    // trees, sixteen wavefronts, the second index with its items and the time masks in LDS, the successor table and keys =
-    // rail indices (the fast classify loop).  Small envs (one round) also get the own-path filter of the classify loop.
-    static const bool no_merge = getenv("FL_OBS_NO_MERGE") != nullptr;
-    P.merged = 0;
-    P.wl_occ_div = OBS_WL_OCC_DIV;
+    const bool merge_ok = up ? obs_dual_ok(d, P) : (P.cutils_alone && P.tw_c == N_WORDS_C * OBS_CAP_C && P.label == nullptr && (long long)d.A * (P.pred_depth + 2) < 65536);
     // Rounds of 16 agents on 512 threads and at most 80 KB of LDS (MODE 5): a CU then holds TWO workgroups, and one env's barriers
     // and L2 round trips are filled by the other's issue.  FL_OBS_ROUND16=0 / 1 overrides the default.
-    static const int round16_env = getenv("FL_OBS_ROUND16") ? atoi(getenv("FL_OBS_ROUND16")) : -1;
     // Envs of at most 32 agents (rounds of 16 instead of the one-round kernel): when the batch has several envs per CU (P.wide) -- same-box
     // sweep at the cfg2 shape, runtime carving on both sides: 512 envs +7 %, 1024 +13 %, 2048 +17 % with two workgroups a CU; at one
     // env per CU the 512-thread workgroup alone takes 75 us against 53 (profiles/r05_cfg2_bsweep.json).  FL_OBS_ROUND16=2 forces it
     // for any batch, =0 rules it out.
-    const bool r16_small = d.A <= 32 && (round16_env >= 0 ? round16_env == 2 : P.wide != 0);
+    const bool r16_small = d.A <= 32 && (sw.round16 >= 0 ? sw.round16 == 2 : P.wide != 0);
     // ... and, round 6, envs of more than 32 agents when the builder runs ALONE on small maps (cfg3's kind) in a wide batch: without the second index
     // and the upstream tables its LDS lists and items fit 80 KB (class 21; same box at 1 024 cfg3 envs, runtime carving: 0.467 -> 0.419 ms)
     // (only where class 21 holds the batch: beyond its capacities the one-a-CU bin classes are the better choice)
     const bool r16_alone = !up && P.cutils_alone && d.A > 32 && P.wide != 0 && d.Rcap <= ObsFixed<21>::dims.Rcap && d.A <= ObsFixed<21>::dims.A;
-    const bool r16 = (r16_small || (d.A > 32 && (round16_env >= 0 ? round16_env != 0 : (OBS_ROUND16_DEFAULT != 0 || r16_alone)))) && (!force_nt || force_nt == 512) && ok(force.nt, 512);
-    const int merged_nt = r16 ? 512 : OBS_NT;
-    const size_t merged_limit = r16 ? std::min(lds_limit, (size_t)80 * 1024) : lds_limit;
-    if (!no_merge && merge_ok && P.compact_t && d.rkey == nullptr && (r16 || ((!force_nt || force_nt == OBS_NT) && ok(force.nt, OBS_NT))) &&
-        ok(force.tmask, 1) && ok(force.dual, up ? 1 : 0) && ok(force.snext, 1) &&
-        (!up || (size_t)d.A * (P.tree_pred + 2) <= OBS_ITEMS2_CAP)) {
-        P.merged = r16 ? 3 : d.A <= 32 ? 1 : 2;
-        o.nt = merged_nt; o.tmask = 1; o.dual = up ? 1 : 0; o.snext = 1; o.partial = 1; o.tab = 0; o.bk_room = 0;
-        // Order of preference, from same-box sweeps (tools/gpu_env_sweep.sh).  One round (at most 32 agents, cfg2): 24 KB of LDS work
-        // lists, the items in LDS, plain lists (the extra counting pass of the bucketed lists costs more than their short scans
-        // save: 57.9 against 51.8 us).  Rounds of 32 agents: a round of 64 trees meets thousands of occupied cells, and a work
-        // list that overflows is handled cell by cell inside the classify loop (cfg3: 1.04 ms with 24 KB, 0.82 ms with 36 KB) -- so
-        // 36 KB of LDS lists, or else the lists in HBM scratch (no cap); the items in LDS before anything else (cfg4: 0.45 against
-        // 0.52 ms); lists grouped by 32-step time buckets where their offsets fit too (cfg4: 0.48 -> 0.45 ms, cfg3 neutral).
-        const bool no_head = obs_no_wl_head();
-        static const bool no_own = getenv("FL_OBS_NO_OWN_FILTER") != nullptr;
-        static const bool no_fb = getenv("FL_OBS_NO_FB") != nullptr;
-        struct Pref { int fb, wl, items; };
-        static const Pref one_round[] = {{0, 24 * 1024, 1}, {0, 16 * 1024, 1}, {0, 0, 1}, {0, 24 * 1024, 0}, {0, 0, 0}, {0, 8 * 1024, 0}};
-        // (round 5) HBM lists without the LDS copy of the items BEFORE the copy: at 80 agents on 60 x 60 every env has more items than the
-        // 4 096 entries that fit beside the rest (the copy is dead weight there), and what it occupied becomes the lists' LDS head
-        static const Pref rounds[] = {{1, 36 * 1024, 1}, {0, 36 * 1024, 1}, {1, 0, 0}, {1, 0, 1}, {0, 0, 1}, {1, 24 * 1024, 1}, {0, 24 * 1024, 1},
-                                      {0, 0, 0}, {0, 24 * 1024, 0}, {0, 8 * 1024, 0}};
-        // rounds of 16 agents in 80 KB: half the trees a round meet half the cells -- 16 KB of LDS lists, else HBM scratch
-        static const Pref rounds16[] = {{1, 16 * 1024, 1}, {0, 16 * 1024, 1}, {1, 0, 1}, {1, 12 * 1024, 1}, {0, 12 * 1024, 1}, {0, 0, 1}, {1, 16 * 1024, 0}, {1, 0, 0}, {0, 16 * 1024, 0},
-                                        {0, 0, 0}, {0, 8 * 1024, 0}};
-        // ... of small envs (17 .. 32 agents, two rounds): plain lists like the one-round kernel, so that the own-path filter fits too
-        static const Pref rounds16_small[] = {{0, 16 * 1024, 1}, {0, 12 * 1024, 1}, {1, 16 * 1024, 1}, {0, 0, 1}, {0, 16 * 1024, 0}, {0, 0, 0}, {0, 8 * 1024, 0}};
-        const Pref *prefs = P.merged == 1 ? one_round : P.merged == 3 ? (d.A <= 32 ? rounds16_small : rounds16) : rounds;
-        const int n_prefs = P.merged == 1 ? (int)(sizeof one_round / sizeof one_round[0]) : P.merged == 3 ? (d.A <= 32 ? (int)(sizeof rounds16_small / sizeof rounds16_small[0]) : (int)(sizeof rounds16 / sizeof rounds16[0])) : (int)(sizeof rounds / sizeof rounds[0]);
-        // what a configuration of this branch sets in P (and the fixed launch class that has exactly these options, if the batch fits one)
-        auto accept = [&](const ObsOptions &oo, ObsLayout L) {
-            accepted = oo;
-            P.use_tmask = 1; P.dual_index = up ? 1 : 0;
-            P.bk = oo.fb ? 2 : 0; P.bk_nb = OBS_FB_NB; P.bk_shift = OBS_FB_SHIFT;
-            P.wl_occ_div = d.A <= 32 ? OBS_WL_OCC_DIV : 3;
-            // small envs: 4-step buckets (same-box A/B on cfg2: 54.8 us against 55.1 with 2-step and 56.9 with 8-step buckets)
-            P.tshift = force_tshift >= 0 ? force_tshift : (d.A <= 31 ? 2 : OBS_TSHIFT);
-            P.fix_allowed = !force_nt && lds_limit == (size_t)160 * 1024 && force_tshift < 0;
-            obs_take_fixed_class(d, P, oo, L, P.fix_allowed != 0);
-            P.L = L;
-        };
-        for (int pk = 0; pk < n_prefs; pk++) {
-            // the builder alone has the room for 36 KB of LDS lists AND the items' copy on maps where both builders never had it -- but there
-            // (cfg4: 649 rail cells) every env has more items than the copy holds and the lists' entries are many: same box, runtime carving,
-            // 0.268 ms with the LDS lists against 0.261 with HBM lists behind a 16 KB LDS head.  Small maps (cfg3) keep the LDS lists.
-            if (!up && P.merged == 2 && prefs[pk].wl >= 36 * 1024 && d.Rcap > OBS_ALONE_LDS_LISTS_RCAP) continue;
-            o.fb = prefs[pk].fb && P.pred_depth + 1 > 64; o.wl_bytes = prefs[pk].wl; o.items = prefs[pk].items;
-            // diagnostic: the env's static tables in LDS too -- but never for both builders in rounds of 16 agents (MODE 5 has no VAR 1 kernel:
-            // fl_obs_unit.hip), where FL_OBS_FORCE=tab=1 leaves the tables in HBM / L2
-            o.tab = force.tab == 1 && o.wl_bytes && nh_fit && !(P.merged == 3 && up);
-            if ((o.fb && no_fb) || !ok(force.wl, o.wl_bytes) || !ok(force.items, o.items) || (o.items && d.A * 32 > OBS_ITEMS_LDS_CAP)) continue;
-            // the own-path filter of the classify loop (a second set of time masks) before the full-size LDS copy of the items: on
-            // sparse maps a third of the conflict entries are the walking agent's own prediction (cfg4: 34 %), and an env whose
-            // items do not fit the smaller copy scans them in HBM scratch at nearly the same speed
-            static const int caps[3] = {OBS_ITEMS_LDS_CAP, 4096, 2048};   // (2048: cfg3 0.86 against 0.77 ms -- most envs' items then sit in HBM; only in 80 KB)
-            for (o.own_filter = no_own ? 0 : 1; o.own_filter >= 0; o.own_filter--)
-                for (int ck = 0; ck < (o.items ? (P.merged == 3 ? 3 : 2) : 1); ck++)
-                    for (o.raw = o.own_filter; o.raw >= 0; o.raw--)
-                        for (o.nh = nh_fit ? 1 : 0; o.nh >= 0; o.nh--) {
-                            if (!ok(force.nh, o.nh)) continue;
-                            o.items_cap = caps[ck];
-                            o.wl_head = 0;
-                            ObsLayout L = obs_layout(d, P, o);
-                            if (L.total > merged_limit) continue;
-                            if (o.wl_bytes == 0 && !no_head) {   // lists in HBM scratch: an LDS head of what the carving leaves
-                                const size_t room = (merged_limit - L.total) & ~(size_t)1023;
-                                o.wl_head = (int)std::min(room, (size_t)OBS_WL_HEAD_MAX);
-                                if (o.wl_head < OBS_WL_HEAD_MIN) o.wl_head = 0;
-                                if (o.wl_head) L = obs_layout(d, P, o);
-                            }
-                            accept(o, L);
-                            return true;
+    const bool r16 = (r16_small || (d.A > 32 && (sw.round16 >= 0 ? sw.round16 != 0 : (OBS_ROUND16_DEFAULT != 0 || r16_alone)))) && (!sw.nt || sw.nt == 512) && obs_ok(sw.force.nt, 512);
+    const size_t merged_limit = r16 ? std::min((size_t)sw.lds_limit, (size_t)80 * 1024) : (size_t)sw.lds_limit;
+    if (!(!sw.no_merge && merge_ok && P.compact_t && d.rkey == nullptr && (r16 || ((!sw.nt || sw.nt == OBS_NT) && obs_ok(sw.force.nt, OBS_NT))) &&
+          obs_ok(sw.force.tmask, 1) && obs_ok(sw.force.dual, up ? 1 : 0) && obs_ok(sw.force.snext, 1) &&
+          (!up || (size_t)d.A * (P.tree_pred + 2) <= OBS_ITEMS2_CAP))) { P.merged = 0; return false; }
+    P.merged = r16 ? 3 : d.A <= 32 ? 1 : 2;
+    ObsOptions o = {};
+    o.nt = r16 ? 512 : OBS_NT; o.tmask = 1; o.dual = up ? 1 : 0; o.snext = 1; o.partial = 1; o.tab = 0; o.bk_room = 0;
+    // Order of preference, from same-box sweeps (tools/gpu_env_sweep.sh).  One round (at most 32 agents, cfg2): 24 KB of LDS work
+    // lists, the items in LDS, plain lists (the extra counting pass of the bucketed lists costs more than their short scans
+    // save: 57.9 against 51.8 us).  Rounds of 32 agents: a round of 64 trees meets thousands of occupied cells, and a work
+    // list that overflows is handled cell by cell inside the classify loop (cfg3: 1.04 ms with 24 KB, 0.82 ms with 36 KB) -- so
+    // 36 KB of LDS lists, or else the lists in HBM scratch (no cap); the items in LDS before anything else (cfg4: 0.45 against
+    // 0.52 ms); lists grouped by 32-step time buckets where their offsets fit too (cfg4: 0.48 -> 0.45 ms, cfg3 neutral).
+    static const std::initializer_list<ObsPref> one_round = {{0, 24 * 1024, 1}, {0, 16 * 1024, 1}, {0, 0, 1}, {0, 24 * 1024, 0}, {0, 0, 0}, {0, 8 * 1024, 0}};
+    // (round 5) HBM lists without the LDS copy of the items BEFORE the copy: at 80 agents on 60 x 60 every env has more items than the
+    // 4 096 entries that fit beside the rest (the copy is dead weight there), and what it occupied becomes the lists' LDS head
+    static const std::initializer_list<ObsPref> rounds = {{1, 36 * 1024, 1}, {0, 36 * 1024, 1}, {1, 0, 0}, {1, 0, 1}, {0, 0, 1}, {1, 24 * 1024, 1}, {0, 24 * 1024, 1},
+                                     {0, 0, 0}, {0, 24 * 1024, 0}, {0, 8 * 1024, 0}};
+    // rounds of 16 agents in 80 KB: half the trees a round meet half the cells -- 16 KB of LDS lists, else HBM scratch
+    static const std::initializer_list<ObsPref> rounds16 = {{1, 16 * 1024, 1}, {0, 16 * 1024, 1}, {1, 0, 1}, {1, 12 * 1024, 1}, {0, 12 * 1024, 1}, {0, 0, 1}, {1, 16 * 1024, 0}, {1, 0, 0}, {0, 16 * 1024, 0},
+                                       {0, 0, 0}, {0, 8 * 1024, 0}};
+    // ... of small envs (17 .. 32 agents, two rounds): plain lists like the one-round kernel, so that the own-path filter fits too
+    static const std::initializer_list<ObsPref> rounds16_small = {{0, 16 * 1024, 1}, {0, 12 * 1024, 1}, {1, 16 * 1024, 1}, {0, 0, 1}, {0, 16 * 1024, 0}, {0, 0, 0}, {0, 8 * 1024, 0}};
+    for (const ObsPref &pref : P.merged == 1 ? one_round : P.merged == 2 ? rounds : d.A <= 32 ? rounds16_small : rounds16) {
+        // the builder alone has the room for 36 KB of LDS lists AND the items' copy on maps where both builders never had it -- but there
+        // (cfg4: 649 rail cells) every env has more items than the copy holds and the lists' entries are many: same box, runtime carving,
+        // 0.268 ms with the LDS lists against 0.261 with HBM lists behind a 16 KB LDS head.  Small maps (cfg3) keep the LDS lists.
+        if (!up && P.merged == 2 && pref.wl >= 36 * 1024 && d.Rcap > OBS_ALONE_LDS_LISTS_RCAP) continue;
+        o.fb = pref.fb && P.pred_depth + 1 > 64; o.wl_bytes = pref.wl; o.items = pref.items;
+        // diagnostic: the env's static tables in LDS too -- but never for both builders in rounds of 16 agents (MODE 5 has no VAR 1 kernel:
+        // fl_obs_unit.hip), where FL_OBS_FORCE=tab=1 leaves the tables in HBM / L2
+        o.tab = sw.force.tab == 1 && o.wl_bytes && nh_fit && !(P.merged == 3 && up);
+        if ((o.fb && sw.no_fb) || !obs_ok(sw.force.wl, o.wl_bytes) || !obs_ok(sw.force.items, o.items) || (o.items && d.A * 32 > OBS_ITEMS_LDS_CAP)) continue;
+        // the own-path filter of the classify loop (a second set of time masks) before the full-size LDS copy of the items: on
+        // sparse maps a third of the conflict entries are the walking agent's own prediction (cfg4: 34 %), and an env whose
+        // items do not fit the smaller copy scans them in HBM scratch at nearly the same speed
+        static const int caps[3] = {OBS_ITEMS_LDS_CAP, 4096, 2048};   // (2048: cfg3 0.86 against 0.77 ms -- most envs' items then sit in HBM; only in 80 KB)
+        for (o.own_filter = sw.no_own_filter ? 0 : 1; o.own_filter >= 0; o.own_filter--)
+            for (int ck = 0; ck < (o.items ? (P.merged == 3 ? 3 : 2) : 1); ck++)
+                for (o.raw = o.own_filter; o.raw >= 0; o.raw--)
+                    for (o.nh = nh_fit ? 1 : 0; o.nh >= 0; o.nh--) {
+                        if (!obs_ok(sw.force.nh, o.nh)) continue;
+                        o.items_cap = caps[ck]; o.wl_head = 0;
+                        ObsLayout L = obs_layout(d, P, o);
+                        if (L.total > merged_limit) continue;
+                        if (o.wl_bytes == 0 && !sw.no_wl_head) {   // lists in HBM scratch: an LDS head of what the carving leaves
+                            const size_t room = (merged_limit - L.total) & ~(size_t)1023;
+                            o.wl_head = (int)std::min(room, (size_t)OBS_WL_HEAD_MAX); if (o.wl_head < OBS_WL_HEAD_MIN) o.wl_head = 0;
+                            if (o.wl_head) L = obs_layout(d, P, o);
                         }
-        }
-        P.merged = 0;
+                        // small envs: 4-step buckets (same-box A/B on cfg2: 54.8 us against 55.1 with 2-step and 56.9 with 8-step buckets)
+                        return obs_accept(d, P, accepted, o, L, {o.fb ? 2 : 0, OBS_FB_NB, OBS_FB_SHIFT, d.A <= 32 ? OBS_WL_OCC_DIV : 3, d.A <= 31 ? 2 : OBS_TSHIFT, false});
+                    }
     }
-    o = ObsOptions();
-    for (int k = 0; k < 3; k++) {
-        o.nt = nts[k];
-        if ((force_nt && o.nt != force_nt) || !ok(force.nt, o.nt)) continue;
+    P.merged = 0;
+    return false;
+}
+// The two-stage kernels.  Order of preference, from same-box A/B runs (tools/obs_sweep.py): the most wavefronts; the full work-list space; the LDS
+// copy of the items, the time masks and the second index; the successor table; the next-hop tables; own scan scratch.
+// The env's distance / segment / eight-hop tables join them when there is room left (small maps): they make no
+// difference in time (their gathers hit L2 and hide behind the rest) but replace narrow HBM gathers with one coalesced read.
+static bool obs_walk_two_stage(const FlDev &d, ObsArgs &P, ObsOptions &accepted) {
+    const ObsSwitches &sw = obs_switches();
+    static const int opts[5][3] = {{1, 1, 1}, {1, 0, 1}, {1, 0, 0}, {0, 0, 1}, {0, 0, 0}};  // masks, second index, items
+    const size_t lds_limit = (size_t)sw.lds_limit;
+    const bool nh_fit = obs_nh_fit(d), dual_ok = obs_dual_ok(d, P);
+    ObsOptions o = {};
+    for (const int nt : {OBS_NT, 512, 256}) {
+        o.nt = nt;
+        if ((sw.nt && o.nt != sw.nt) || !obs_ok(sw.force.nt, o.nt)) continue;
         // work lists: in LDS when everything else fits beside them (small maps), else in HBM scratch (the LDS goes to the time
         // masks, the items and the second index; no cap on the entries), else LDS lists with whatever still fits
         for (int wk = 0; wk < 4; wk++) {
@@ -380,47 +337,38 @@ static bool obs_pick_config(const FlDev &d, ObsArgs &P, ObsOptions &accepted) {
                 o.tmask = opts[opt][0]; o.dual = opts[opt][1]; o.items = opts[opt][2];
                 if (o.dual && !dual_ok) continue;
                 if (o.items && d.A * 32 > OBS_ITEMS_LDS_CAP) continue;  // hundreds of agents: their items never fit the LDS copy
-                if (!ok(force.wl, o.wl_bytes) || !ok(force.tmask, o.tmask) || !ok(force.dual, o.dual) || !ok(force.items, o.items)) continue;
+                if (!obs_ok(sw.force.wl, o.wl_bytes) || !obs_ok(sw.force.tmask, o.tmask) || !obs_ok(sw.force.dual, o.dual) || !obs_ok(sw.force.items, o.items)) continue;
                 // large maps: the cutils index grouped by time bucket, counted in the node tables' LDS (room for the counters)
-                static const bool no_bk = getenv("FL_OBS_NO_BK") != nullptr;
-                const bool want_bk = !no_bk && o.wl_bytes == 0 && !o.items && o.tmask && !o.dual && P.tw_c != 0 && P.pred_depth + 1 > 64 &&
+                const bool want_bk = !sw.no_bk && o.wl_bytes == 0 && !o.items && o.tmask && !o.dual && P.tw_c != 0 && P.pred_depth + 1 > 64 &&
                                      d.A * ((1 << OBS_BK_SHIFT) + 2) <= 65535;   // (offsets inside a bucket are 16 bits)
                 for (o.bk_room = want_bk ? 1 : 0; o.bk_room >= 0; o.bk_room--)
                 for (o.snext = 1; o.snext >= 0; o.snext--)
                     for (o.nh = nh_fit ? 1 : 0; o.nh >= 0; o.nh--)
                         for (o.partial = 1; o.partial >= 0; o.partial--) {  // 4 KB of scan scratch: borrowed when tight
-                            if (!ok(force.snext, o.snext) || !ok(force.nh, o.nh)) continue;
+                            if (!obs_ok(sw.force.snext, o.snext) || !obs_ok(sw.force.nh, o.nh)) continue;
                             ObsLayout L = obs_layout(d, P, o);
                             if (L.total > lds_limit) continue;
-                            if (!no_tab && force.tab != 0 && nh_fit && o.wl_bytes) {
-                                ObsOptions ot = o;
-                                ot.tab = 1;
+                            if (sw.force.tab != 0 && nh_fit && o.wl_bytes) {   // the static tables join the carving where they fit beside it
+                                ObsOptions ot = o; ot.tab = 1;
                                 const ObsLayout Lt = obs_layout(d, P, ot);
                                 if (Lt.total <= lds_limit) L = Lt;
-                                else if (force.tab == 1) continue;
-                            } else if (force.tab == 1) continue;
-                            accepted = o;
-                            accepted.tab = L.tab_lds;   // (the tables joined the carving above)
-                            P.use_tmask = o.tmask; P.dual_index = o.dual;
-                            P.bk = o.bk_room; P.bk_nb = OBS_BK_NB; P.bk_shift = OBS_BK_SHIFT;
+                                else if (sw.force.tab == 1) continue;
+                            } else if (sw.force.tab == 1) continue;
                             // 2-step buckets where the traffic is and one catch-all bucket for late times (8-step buckets over the
                             // whole horizon measured slower on every map size)
-                            P.tshift = force_tshift >= 0 ? force_tshift : OBS_TSHIFT;
-                            P.fix_allowed = !force_nt && lds_limit == (size_t)160 * 1024 && force_tshift < 0;
-                            obs_take_fixed_class(d, P, o, L, P.fix_allowed != 0);
-                            P.L = L;
-                            return true;
+                            return obs_accept(d, P, accepted, o, L, {o.bk_room, OBS_BK_NB, OBS_BK_SHIFT, OBS_WL_OCC_DIV, OBS_TSHIFT, true});
                         }
             }
         }
     }
     return false;
 }
+static bool obs_pick_config(const FlDev &d, ObsArgs &P, ObsOptions &accepted) { return obs_walk_one_pass(d, P, accepted) || obs_walk_two_stage(d, P, accepted); }
 
 static void obs_verbose(const ObsArgs &P) {
     static int printed = 0;
     const ObsLayout &L = P.L;
-    if (obs_verbose_on() && printed < 4) {
+    if (obs_switches().verbose && printed < 4) {
         printed++;
         fprintf(stderr, "[fl_obs] fixed launch class %d%s, %d threads, %u B LDS: static tables in LDS %d, next-hop in LDS %d, successor table %d, work lists %d B, time masks %d, second index %d, items in LDS %d, one pass B for both builders %d, compact upstream trees %d, bucketed index %d\n",
                 P.fix, P.split ? " (split: the envs that fit it)" : "", L.nt, L.total, L.tab_lds, L.off[L_NH] != L_ABSENT, L.off[L_SNEXT] != L_ABSENT, L.wl_bytes, P.use_tmask, P.dual_index, L.off[L_ITEMS] != L_ABSENT, P.merged, P.compact_t, P.bk);
@@ -472,8 +420,8 @@ static void obs_cutils_args(ObsArgs &P, int max_nodes, int pred_depth, int wide)
 // (MODE 6 / 7 / 8 = MODE 3 / 4 / 5 without the upstream builder; classes 6 .. 10) wherever those apply: 16-lane pass A teams need grids
 // whose cells have at most two transitions a direction (every Flatland rail cell type).  FL_OBS_NO_CUTILS_MERGE: the stand-alone kernel.
 static void obs_alone_args(const FlDev &d, ObsArgs &P) {
-    P.compact_t = d.max_branch <= 2 && !fl_obs_no_compact();
-    P.cutils_alone = !obs_no_cutils_merge();
+    P.compact_t = d.max_branch <= 2 && !obs_switches().no_compact;
+    P.cutils_alone = !obs_switches().no_cutils_merge;
 }
 // node tables of the upstream builder: compact slots when no direction of a cell of the batch has more than two transitions
 static void obs_tree_args(const FlDev &d, ObsArgs &P, int max_depth, int tree_pred, double *tree_out) {
@@ -481,7 +429,7 @@ static void obs_tree_args(const FlDev &d, ObsArgs &P, int max_depth, int tree_pr
     int n = 0, p = 1;
     for (int k = 0; k <= max_depth; k++) { n += p; p *= 4; }
     P.n_tree_nodes = n;
-    P.compact_t = d.max_branch <= 2 && !fl_obs_no_compact();
+    P.compact_t = d.max_branch <= 2 && !obs_switches().no_compact;
     if (P.compact_t && max_depth >= 4) { P.tw_t = N_WORDS_T * 32; P.tpw_t = 2; }   // depth 4: 30 compact slots on a 32-lane team (the stand-alone tree launch)
     else if (P.compact_t) { P.tw_t = N_WORDS_T * OBS_CAP_T_COMPACT; P.tpw_t = 4; }
     else { P.tw_t = max_depth <= 2 ? N_WORDS_T * 32 : N_WORDS_T * 88; P.tpw_t = max_depth <= 2 ? 2 : 1; }
@@ -560,9 +508,7 @@ static int obs_enqueue(FlObsScratch &o, const FlDev &d, ObsPlan &pl, hipStream_t
         // mode off, or more rows than the masks' 96 bits (the tree launch alone goes beyond depth 3): the kernels keep no row masks (restored on return -- `u` is a copy of o)
         if (!o.keep_rows || P.max_depth > 3) { o.rowmask = nullptr; P.keep_rows = 0; o.rows_out = nullptr; }
     }
-    P.no_cf_dirs = obs_no_cf_dirs();
-    P.pb_ceil_split = obs_pb_ceil_split();
-    P.no_early_topo = obs_no_early_topo();
+    P.no_cf_dirs = obs_switches().no_cf_dirs; P.pb_ceil_split = obs_switches().pb_ceil_split; P.no_early_topo = obs_switches().no_early_topo;   // (what the kernels see of the switches)
     obs_verbose(P);
     obs_keep_verify(d, P, rowmask, s);
     FlObsScratch u = o;
@@ -625,7 +571,7 @@ int fl_obs_config_of_fused(const FlDev &d, int pred_depth, int max_depth, int tr
     else obs_alone_args(d, P);   // max_depth 0: the flatland_cutils builder alone (fl_launch_obs_cutils)
     ObsOptions q = {};
     if (obs_configure(d, P, q, nullptr) < 0) return FL_ERR_ARG;
-    if (obs_verbose_on()) {   // diagnostic: the carving of the LDS, array by array (enum L_* of fl_obs_layout.h)
+    if (obs_switches().verbose) {   // diagnostic: the carving of the LDS, array by array (enum L_* of fl_obs_layout.h)
         fprintf(stderr, "  options {nt %d, wl_bytes %d, tab %d, nh %d, tmask %d, dual %d, items %d, snext %d, partial %d, bk_room %d, own_filter %d, fb %d, raw %d, items_cap %d, wl_head %d}; "
                         "shape {merged %d, tw_c %d, tw_t %d, tpw_t %d, tree_pred %d}; bk %d tshift %d wl_occ_div %d\n",
                 q.nt, q.wl_bytes, q.tab, q.nh, q.tmask, q.dual, q.items, q.snext, q.partial, q.bk_room, q.own_filter, q.fb, q.raw, q.items_cap, q.wl_head,

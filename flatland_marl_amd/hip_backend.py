@@ -144,6 +144,8 @@ DEBUG_ABI = {
     # the library's copy of POLICY_SAVED_LAYOUT (table 0), POLICY_ROWS_LAYOUT (1) and POLICY_HEAD_PARAM_SHAPES (2), csrc/fl_policy_layout.h:
     # (table, entry or -1 for the count, name out, its capacity, a out, b out)
     "fl_debug_policy_layout": ([i32, i32, C.c_char_p, i32, C.POINTER(i32), C.POINTER(i32)], i32),
+    # the launcher's table of environment switches (csrc/fl_obs_switches.h) as text, no GPU needed: (out, its capacity) -> bytes
+    "fl_debug_obs_switches": ([C.c_char_p, i32], i32),
 }
 _lib = None
 
@@ -202,6 +204,15 @@ def _sym(name):
     if fn is None:
         raise FlatlandHipError(1, "the loaded library has no %s (an older build loaded through --lib?)" % name)
     return fn
+
+
+def obs_switches():
+    """the observation launcher's diagnostic environment switches, from the library's own table: {name: (kind, what it rules out)} with kind
+    "flag" / "int" / "bytes" / "keys" and "nothing" / "bins" / "classes".  No GPU."""
+    fn = _sym("fl_debug_obs_switches")
+    buf = C.create_string_buffer(fn(None, 0))
+    assert fn(buf, len(buf)) == len(buf)
+    return {name: (kind, out) for name, kind, out in (ln.split() for ln in buf.value.decode().splitlines())}
 
 
 def _chk(rc):

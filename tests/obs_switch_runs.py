@@ -174,8 +174,13 @@ def fresh_child(script, args, switches, timeout, tag=None, lost=None):
     """`script args` in ONE fresh python process (the launcher reads its switches once per process) whose environment holds `switches` and no
     other FL_OBS_* variable, under a time limit.  Returns the lines of its stdout.  A child that ends at its limit or with another status
     than 0 fails the calling test with the end of its output -- an exception, so a caller's loop starts nothing more on the card; one
-    that ended at its limit or on a signal is also appended to `lost`, for a caller that is entered again (a parametrised test)."""
+    that ended at its limit or on a signal is also appended to `lost`, for a caller that is entered again (a parametrised test).
+    An FL_OBS_* key of `switches` that the library's table (csrc/fl_obs_switches.h) does not have is refused before any child starts: the
+    launcher would ignore it, and the child would run the default."""
+    from flatland_marl_amd.hip_backend import obs_switches
     tag = " ".join(args) if tag is None else tag
+    unknown = sorted(k for k in switches if k.startswith("FL_OBS_") and k not in obs_switches())
+    assert not unknown, "%s: no such switch of the launcher: %s" % (tag, ", ".join(unknown))
     env = {k: v for k, v in os.environ.items() if not k.startswith("FL_OBS_")}
     try:
         child = subprocess.run([sys.executable, os.path.abspath(script)] + list(args), env=dict(env, PYTHONPATH=util.ROOT, **switches),

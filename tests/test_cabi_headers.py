@@ -63,7 +63,7 @@ def test_the_type_check_tells_types_apart():
 def test_no_name_is_in_two_groups():
     groups = list(TABLES.values()) + [hb.DEBUG_ABI]
     names = [name for g in groups for name in g]
-    assert len(names) == len(set(names)) == 69 + 5 + 9
+    assert len(names) == len(set(names)) == 69 + 5 + 10
     assert hb.symbols() == tuple(name for h in hb.ABI for name in hb.ABI[h]) and len(hb.symbols()) == 69
     assert gen.SYMBOLS == tuple(gen.ABI["flatland_gen.h"])
 

@@ -141,13 +141,14 @@ def test_every_option_appears_with_both_of_its_values():
 
 
 def test_rows_are_well_formed():
-    from flatland_marl_amd.hip_backend import BatchedRailEnv
+    from flatland_marl_amd.hip_backend import BatchedRailEnv, obs_switches
     assert 45 <= len(cases.ROWS) <= 80
     lists = cases.handle_lists()
+    names = set(obs_switches())      # the library's table (csrc/fl_obs_switches.h): a misspelt switch would be a row that tests the default
     for r in cases.ROWS:
         assert r.recipe in cases.RECIPES and r.call[0] in ("cutils", "both", "tree"), r.id
         assert set(r.expect) <= set(BatchedRailEnv.LAUNCH_FIELDS) and {"mode", "var", "fix", "split", "nt"} <= set(r.expect), r.id
-        assert all(k.startswith("FL_OBS_") for k in r.switches), r.id
+        assert set(r.switches) <= names, r.id
         if r.handles is not None:
             hs = lists[r.handles]
             assert r.recipe == "subset" and sorted(hs) == list(range(len(hs))) and 1 < len(hs) < 20, r.id     # a strict subset

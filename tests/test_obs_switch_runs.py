@@ -200,6 +200,18 @@ def test_a_child_without_DONE_fails(script, tmp_path, monkeypatch):
     assert _started(tmp_path) == ["default", "second"]
 
 
+def test_a_misspelt_switch_is_refused_before_any_child_starts(script, tmp_path):
+    """the launcher ignores a name its table does not have: the child would run the default, and a "this switch changes no byte" test pass"""
+    with pytest.raises(AssertionError, match="no such switch of the launcher: FL_OBS_NOFIX"):
+        sw.run_switch_sets(script, (("typo", {"FL_OBS_NOFIX": "1"}),) + SETS, tmp_path, 30)
+    assert _started(tmp_path) == []
+    with pytest.raises(AssertionError, match="alone: no such switch of the launcher: FL_OBS_NOFIX, FL_OBS_NO_TAB"):
+        sw.fresh_child(script, [str(tmp_path / "alone.npz")], {"FL_OBS_NO_FIX": "1", "FL_OBS_NO_TAB": "1", "FL_OBS_NOFIX": "1"}, 30, tag="alone")
+    assert _started(tmp_path) == []
+    sw.fresh_child(script, [str(tmp_path / "other.npz")], {"STANDIN_OTHER": "", "FL_OBS_NO_FIX": "1"}, 30)      # (another prefix is the caller's business)
+    assert _started(tmp_path) == ["other"]
+
+
 def test_the_child_sees_its_switches_and_no_others(script, tmp_path, monkeypatch):
     monkeypatch.setenv("FL_OBS_FOO", "1")
     monkeypatch.setenv("FL_OBS_NO_CF_DIRS", "1")
